@@ -28,6 +28,16 @@ Workloads
           data path.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration).  --full
+adds everything else the line can carry: the self-check against the oracle, four more K-step blocks,
+per-kernel HIP-event timing and the rooflines, the cold single steps, the physical-order rerun, the
+CPU baselines and, with N > 1, the multi-GPU diagnostics.  An option given explicitly (--check,
+--blocks, --profile, ...) holds in either mode.
+
+--dump-outputs DIR writes what the timed path computed in its last step, as its caller receives it,
+to DIR/<name>.npy in float64 (complex arrays as <name>_re / <name>_im), at most 64 MB in all.
 """
 import argparse
 import json
@@ -217,6 +227,45 @@ def cpu_reference_route(lens, x, wavelength, side, source):
                       % (side, side, t_nf, t_fft, t_pr)}
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: every numeric array (or number) of ``outs`` as PATH/<name>.npy in float64, complex ones as
+    <name>_re / <name>_im.  Past DUMP_LIMIT_BYTES in all, every array larger than its share keeps a fixed, seeded
+    sample of its flat indices, and the indices go beside it as <name>_index.npy"""
+    arrays = {}
+    for k, v in outs.items():
+        a = np.asarray(v) if v is not None and not isinstance(v, str) else None
+        if a is None or a.dtype.kind not in 'biufc':
+            continue
+        if a.dtype.kind == 'c':
+            arrays[k + '_re'], arrays[k + '_im'] = a.real.astype(np.float64), a.imag.astype(np.float64)
+        else:
+            arrays[k] = a.astype(np.float64)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        # (room for an index array beside each, and for the files' headers)
+        keep = DUMP_LIMIT_BYTES * 15 // 16 // 8 // (2 * len(arrays))
+        for k, a in list(arrays.items()):
+            if a.size > keep:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                arrays[k], arrays[k + '_index'] = a.ravel()[idx], idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+
+
+def sweep_sums(ctx, n_sources, shape):
+    """what a queued SourceSweep pass leaves on the GPU for its caller: the incoherent sum of the power maps
+    and the radiated power per source (SourceSweep.run's P_sum / total_P)"""
+    from metalens_amd import _lib
+    P_sum = np.empty(shape)
+    total_P, cone_P = np.zeros(n_sources), np.zeros(n_sources)
+    _lib.check(ctx.lib.ml_farfield_sums(ctx.handle, _lib.dptr(P_sum), _lib.dptr(total_P), _lib.dptr(cone_P),
+                                        n_sources))
+    return {'P_sum': P_sum, 'total_P': total_P}
+
+
 def self_launch(n):
     """``python bench.py --gpus N`` without a launcher (no WORLD_SIZE in the environment): this process
     starts the N ranks itself - one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set the way
@@ -278,22 +327,24 @@ def main():
     ap.add_argument('--positions', type=int, default=1,
                     help='> 1: that many source POSITIONS per step (1 um apart along x, polarisation --pols[0]): a '
                          'position batch - synthesised back to back, then a transform and projection per member')
-    ap.add_argument('--blocks', type=int, default=5,
+    ap.add_argument('--blocks', type=int, default=None,
                     help='K-step blocks run back to back; the FIRST is the timed region `value` '
-                         'comes from, the median block is reported beside it')
-    ap.add_argument('--cpu-rows', type=int, default=2048,
-                    help='aperture rows of the CPU-baseline sample (0 = skip)')
-    ap.add_argument('--cpu-fft-side', type=int, default=1024,
-                    help="side of the window the reference's FFT route is timed on (0 = skip)")
-    ap.add_argument('--check', type=int, default=1, help='verify a sample against the oracle')
+                         'comes from, the median block is reported beside it (default 5 with --full, else 1)')
+    ap.add_argument('--cpu-rows', type=int, default=None,
+                    help='aperture rows of the CPU-baseline sample (0 = skip; default 2048 with --full, else 0)')
+    ap.add_argument('--cpu-fft-side', type=int, default=None,
+                    help="side of the window the reference's FFT route is timed on (0 = skip; default 1024 with "
+                         "--full, else 0)")
+    ap.add_argument('--check', type=int, default=None,
+                    help='verify a sample against the oracle (default 1 with --full, else 0)')
     ap.add_argument('--fuse-modulation', type=int, default=1,
                     help='1: the stage-1 input modulation rides in the synthesis kernel (default)')
     ap.add_argument('--dump', default=None,
                     help='rank 0 saves the far field it ends with (P, a_theta, a_phi) to this .npz')
-    ap.add_argument('--profile', choices=('main', 'all', 'none'), default='main',
+    ap.add_argument('--profile', choices=('main', 'all', 'none'), default=None,
                     help='kernels timed with HIP events inside the timed region: the two that '
-                         'carry the rooflines (default), all of them, or none; every timed launch '
-                         'serialises the stream for a few microseconds')
+                         'carry the rooflines (default with --full), all of them, or none (default '
+                         'without); every timed launch serialises the stream for a few microseconds')
     ap.add_argument('--profile-every', type=int, default=4,
                     help="with --profile main: time every n-th step's two kernels (a sample of the "
                          'timed region at 1/n of the instrumentation cost); --profile all times '
@@ -318,13 +369,26 @@ def main():
                     help="diffraction orders in the synthetic tables: survey = (0,0), (-1,0), (+1,0) everywhere "
                          "(SURVEY.md 8(d)); physical = what characterize() would record, per collection and "
                          "direction (7 to 11 orders per ring collection of the default lens)")
-    ap.add_argument('--also-physical', type=int, default=1,
-                    help='1 (default, N = 1, --orders survey): after the timed region run the same workload with the '
-                         'physical order lists too and report it as `physical_orders`')
-    ap.add_argument('--cold', type=int, default=1,
-                    help='1: also time single steps on a sample grid the context has not seen '
+    ap.add_argument('--also-physical', type=int, default=None,
+                    help='1 (default with --full; N = 1, --orders survey): after the timed region run the same workload '
+                         'with the physical order lists too and report it as `physical_orders`')
+    ap.add_argument('--cold', type=int, default=None,
+                    help='1 (default with --full): also time single steps on a sample grid the context has not seen '
                          '(ms_first_step_new_geometry); N = 1 only')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure as well: the oracle self-check, more blocks, '
+                         'per-kernel timing and rooflines, cold steps, the physical-order rerun, the CPU baselines '
+                         'and the multi-GPU diagnostics (a plain run does only set-up, warm-up and the K timed steps)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write what the timed path computed in its last step, as its caller receives it, to "
+                         "DIR/<name>.npy (float64, complex as <name>_re / <name>_im; at most 64 MB, past that a "
+                         "fixed, seeded sample); rank 0")
     args = ap.parse_args()
+    # what a plain run leaves out; --full restores the measurements beyond the headline, an explicit option wins
+    for k, (full, plain) in {'blocks': (5, 1), 'cpu_rows': (2048, 0), 'cpu_fft_side': (1024, 0), 'check': (1, 0),
+                             'profile': ('main', 'none'), 'also_physical': (1, 0), 'cold': (1, 0)}.items():
+        if getattr(args, k) is None:
+            setattr(args, k, full if args.full else plain)
 
     from metalens_amd import _lib, dist
     from metalens_amd.pipeline import HotPath
@@ -401,16 +465,18 @@ def main():
     for _ in range(prime):
         hp.step()
     hp.sync()
-    # ... and then until two consecutive K-step blocks agree to 3 % (at most eight more): `value` comes
-    # from the FIRST timed block, which must not be the one that is still warming up
+    # ... and then until two consecutive blocks of K steps agree to 3 % (at most eight more): `value` comes
+    # from the FIRST timed block, which must not be the one that is still warming up.  A block here is
+    # capped at ~0.2 s of steps, so that a large K does not make the warm-up cost several timed regions
+    settle = max(1, min(args.steps, int(0.2 / max(t_one, 1e-5))))
     last = None
     for _ in range(8):
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(settle):
             hp.step()
         hp.sync()
         dt = float(dist.allreduce_host(ctx, [time.perf_counter() - t0], 'max')[0])
-        prime += args.steps
+        prime += settle
         settled = last is not None and abs(dt - last) <= 0.03 * last
         last = dt
         if settled:
@@ -442,6 +508,12 @@ def main():
             elapsed = dt
             prof = ctx.profile_get()
             ctx.profile(False)
+    # ---- what the timed path computed in its last step, as its caller receives it (every rank takes part:
+    # results() settles and gathers collectively)
+    if args.dump_outputs:
+        outs = sweep_sums(ctx, len(batch), (ux.size, uy.size)) if n_pols > 1 else hp.results()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
     if n_pols > 1:
         hp.step = one_step
         hp.step()
@@ -449,7 +521,7 @@ def main():
     # ---- multi-GPU diagnostics: the same shards WITHOUT the collective (what the decomposition alone
     # costs), every rank's kernel sums, what the main stream waited for the collective
     no_coll_ms = None
-    if world > 1 and not replicas and args.reduce != 'none':
+    if args.full and world > 1 and not replicas and args.reduce != 'none':
         hp_nc = HotPath(source, wavelength, lens['lens_periphery_summary'], lens['lens_center_summary'],
                         lens['hexgridset'], x, x, ux, uy, ctx=ctx, pair_list=bool(args.pair_list), rank=rank,
                         world=world, precision=args.precision, reduce='none',
@@ -470,7 +542,7 @@ def main():
     # that value(N) / one_gpu_same_workload.value is a strong-scaling ratio of ONE problem whatever the driver
     # ran at --gpus 1
     one_gpu = None
-    if world > 1 and not replicas and tiled and not args.pair_list:
+    if args.full and world > 1 and not replicas and tiled and not args.pair_list:
         if rank == 0:
             hp_1 = HotPath(source, wavelength, lens['lens_periphery_summary'], lens['lens_center_summary'],
                            lens['hexgridset'], x, x, ux, uy, ctx=ctx, rank=0, world=1, precision=args.precision,
@@ -491,7 +563,7 @@ def main():
         hp.step()      # (the far field fetched below is the sharded, reduced one again)
         hp.sync()
     per_rank = None
-    if world > 1 and not replicas:
+    if args.full and world > 1 and not replicas:
         names = ('nearfield', 'zgemm_stage1', 'zgemm_stage2', 'project', 'comm_wait', 'collective')
         mine = np.zeros((world, len(names)))
         mine[rank] = [prof[k]['total_ms'] / prof[k]['launches'] if prof[k]['launches'] else -1.0 for k in names]

@@ -22,7 +22,7 @@ def test_rccl_path_single_rank(reduce):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--aperture', '512', '--farfield', '64',
            '--diameter', '3e-4', '--steps', '2', '--warmup', '1', '--blocks', '1',
-           '--cpu-rows', '0', '--cpu-fft-side', '0', '--reduce', reduce]
+           '--cpu-rows', '0', '--cpu-fft-side', '0', '--reduce', reduce, '--full']
     env = dict(os.environ, ML_FORCE_RCCL='1', RANK='0', LOCAL_RANK='0', WORLD_SIZE='1',
                MASTER_ADDR='127.0.0.1', MASTER_PORT='29511' if reduce == 'vectors' else '29512')
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -44,7 +44,7 @@ def _run_bench(extra, env, timeout=600, aperture=512, farfield=64, diameter='3e-
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--aperture', str(aperture),
            '--farfield', str(farfield),
            '--diameter', diameter, '--na', '0.5', '--steps', '2', '--warmup', '1', '--blocks', '1',
-           '--cpu-rows', '0', '--cpu-fft-side', '0', '--scaling', 'strong'] + extra
+           '--cpu-rows', '0', '--cpu-fft-side', '0', '--scaling', 'strong', '--full'] + extra
     return subprocess.Popen(cmd, env=dict(os.environ, **env), stdout=subprocess.PIPE,
                             stderr=subprocess.PIPE, text=True)
 
@@ -120,7 +120,7 @@ def test_plain_bench_gpus_n_starts_its_own_ranks(tmp_path, world):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(world), '--aperture', '2048', '--farfield', '64',
            '--diameter', '3e-4', '--na', '0.5', '--steps', '2', '--warmup', '1', '--blocks', '1', '--cpu-rows', '0',
-           '--cpu-fft-side', '0', '--scaling', 'strong', '--dump', many]
+           '--cpu-fft-side', '0', '--scaling', 'strong', '--full', '--dump', many]
     q = subprocess.run(cmd, env=dict(env, ML_COMM_BACKEND='file'), capture_output=True, text=True, timeout=900)
     assert q.returncode == 0, q.stderr[-2000:]
     lines = [l for l in q.stdout.splitlines() if l.strip()]
@@ -188,7 +188,7 @@ def test_bench_line_contract():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--aperture', '512', '--farfield', '64',
            '--diameter', '1.2e-4', '--steps', '3', '--warmup', '1', '--blocks', '2', '--cpu-rows', '32',
-           '--cpu-fft-side', '128']
+           '--cpu-fft-side', '128', '--full']
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -230,6 +230,51 @@ def test_bench_line_contract():
     assert c['kind'] == 'port' and c['cores'] == 1 and c['value'] > 0 and 'sample' in c
     assert d['cpu_baseline_reference_route']['value'] > 0
     assert d['rel_err']['nearfield_vs_oracle'] < 1e-12 and d['rel_err']['farfield_E_vs_oracle'] < 1e-12
+
+
+def test_plain_bench_line_and_dump_outputs(tmp_path):
+    """a plain bench.py run (no --full) times exactly K steps and carries the headline and nothing that takes a
+    measurement of its own; --dump-outputs writes what the timed path's caller receives: HotPath.results()
+    for one source (equal to the --dump file of the same run), SourceSweep's sums for a --pols batch (the
+    sum of the single-polarisation maps)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--aperture', '512', '--farfield', '64',
+               '--diameter', '1.2e-4', '--steps', '3', '--warmup', '1'] + list(extra)
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout
+        return json.loads(lines[0])
+
+    dx, dy, dxy = (str(tmp_path / k) for k in ('x', 'y', 'xy'))
+    npz = str(tmp_path / 'x.npz')
+    d = run('--dump-outputs', dx, '--dump', npz)
+    assert d['metric'] == 'aperture x far-field pair-evals/sec' and d['unit'] == 'pair-evals/s'
+    assert d['steps'] == 3 and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert abs(d['value'] - 512.0 ** 2 * 64 ** 2 * 3 / (d['ms_per_step'] * 3e-3)) < 1e-6 * d['value']
+    assert len(d['ms_per_step_blocks']) == 1 and d['kernel_timing']['mode'] == 'none'
+    for key in ('rel_err', 'cpu_baseline', 'cpu_baseline_reference_route', 'physical_orders', 'cold_step', 'roofline'):
+        assert key not in d, key
+    ref = np.load(npz)
+    assert np.array_equal(np.load(os.path.join(dx, 'P.npy')), ref['P'], equal_nan=True)
+    for key in ('a_theta', 'a_phi'):
+        re, im = (np.load(os.path.join(dx, '%s_%s.npy' % (key, part))) for part in ('re', 'im'))
+        assert re.dtype == np.float64 and np.array_equal(re + 1j * im, ref[key])
+    for key in ('Nx', 'Ny', 'Lx', 'Ly'):
+        assert np.load(os.path.join(dx, key + '_re.npy')).shape == (64, 64)
+    run('--dump-outputs', dy, '--pols', 'y')
+    run('--dump-outputs', dxy, '--pols', 'xy')
+    p_sum = np.load(os.path.join(dxy, 'P_sum.npy'))
+    want = np.load(os.path.join(dx, 'P.npy')) + np.load(os.path.join(dy, 'P.npy'))
+    ok = ~np.isnan(want)
+    assert ok.any() and np.array_equal(np.isnan(p_sum), ~ok)
+    assert np.abs(p_sum[ok] - want[ok]).max() <= 1e-11 * want[ok].max()
+    assert np.load(os.path.join(dxy, 'total_P.npy')).shape == (2,)
 
 
 def test_two_gpus_real_rccl(tmp_path):

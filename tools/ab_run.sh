@@ -11,7 +11,7 @@ for r in $(seq 1 $ROUNDS); do
     # variant = LIB[:NAME=VALUE[,NAME=VALUE...]] - environment for a -DML_DIAG build's knobs (common.h diag_int)
     lib=${v%%:*}; envs=""; [ "$lib" != "$v" ] && envs=$(echo "${v#*:}" | tr ',' ' ')
     if [ "$lib" = product ]; then unset METALENS_HIP_LIB; else export METALENS_HIP_LIB=$R/$lib; fi
-    env $envs timeout 300 python $R/bench.py --profile all --steps 20 --blocks 4 --cpu-rows 0 --cpu-fft-side 0 --cold 0 --also-physical 0 $ARGS 2>>$OUT.err | python -c "
+    env $envs timeout 300 python $R/bench.py --full --profile all --steps 20 --blocks 4 --cpu-rows 0 --cpu-fft-side 0 --cold 0 --also-physical 0 $ARGS 2>>$OUT.err | python -c "
 import json,sys
 v=sys.argv[1]
 for line in sys.stdin:

@@ -5,8 +5,8 @@
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=$1
 mkdir -p $O
-B="python bench.py --cpu-rows 0 --cpu-fft-side 0"
-timeout 600 python bench.py 2>/dev/null | tail -1 > $O/bench.json
+B="python bench.py --full --cpu-rows 0 --cpu-fft-side 0"
+timeout 600 python bench.py --full 2>/dev/null | tail -1 > $O/bench.json
 timeout 300 $B --profile all 2>/dev/null | tail -1 > $O/bench_profile_all.json
 timeout 300 $B --profile none 2>/dev/null | tail -1 > $O/bench_profile_none.json
 timeout 300 $B --method gemm --profile all 2>/dev/null | tail -1 > $O/bench_gemm_profile_all.json
@@ -27,5 +27,5 @@ timeout 300 $B --pair-list 4096 --profile all 2>/dev/null | tail -1 > $O/bench_p
 timeout 600 $B --aperture 16384 --farfield 1024 --diameter 4e-3 --steps 5 --warmup 1 --blocks 2 --cold 0 --profile all 2>/dev/null | tail -1 > $O/bench_16384x1024_f64.json
 # the multi-rank path on this one GPU: plain `bench.py --gpus N` starts its own ranks (file communicator)
 for n in 2 4 8; do
-  ML_COMM_BACKEND=file timeout 600 python bench.py --gpus $n --cpu-rows 0 --cpu-fft-side 0 --aperture 8192 --farfield 512 --diameter 2e-3 --na 0.94 --scaling strong 2>$O/bench_gpus$n.err | tail -1 > $O/bench_gpus${n}_8192_file_comm.json
+  ML_COMM_BACKEND=file timeout 600 python bench.py --gpus $n --full --cpu-rows 0 --cpu-fft-side 0 --aperture 8192 --farfield 512 --diameter 2e-3 --na 0.94 --scaling strong 2>$O/bench_gpus$n.err | tail -1 > $O/bench_gpus${n}_8192_file_comm.json
 done

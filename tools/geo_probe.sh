@@ -7,7 +7,7 @@ cd /tmp; export TMPDIR=/tmp
 for v in "$@"; do
   if [ "$v" = product ]; then unset METALENS_HIP_LIB; else export METALENS_HIP_LIB=$R/$v; fi
   d=/tmp/geo_$(basename $v .so); rm -rf $d
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python $R/bench.py --steps 10 --blocks 1 --cpu-rows 0 --cpu-fft-side 0 --also-physical 0 --check 0 > $R/$OUT.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $d -- python $R/bench.py --full --steps 10 --blocks 1 --cpu-rows 0 --cpu-fft-side 0 --also-physical 0 --check 0 > $R/$OUT.log 2>&1
   echo "== $v" >> $R/$OUT
   python - $d >> $R/$OUT <<'PY'
 import csv,glob,sys

@@ -1,6 +1,6 @@
 #!/bin/bash
-# One round's evidence in one GPU call: rocprofv3 kernel trace + stats of EXACTLY the default
-# bench command (what the driver runs at N = 1), the counter passes (each in its own run,
+# One round's evidence in one GPU call: rocprofv3 kernel trace + stats of the default bench
+# command with --full (the line DESIGN.md quotes), the counter passes (each in its own run,
 # kernel-trace only, as MI355X_MICROARCH.md prescribes) for the configurations DESIGN.md quotes,
 # and their bench lines.  Run on the GPU box:
 #     tools/profile_round.sh TAG        -> gpurun_out/TAG/...
@@ -13,7 +13,7 @@ O=$R/gpurun_out/$1
 mkdir -p $O
 T="timeout -k 5 ${PMC_TIMEOUT:-240}"
 cd /tmp && export TMPDIR=/tmp
-$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --cpu-rows 0 --cpu-fft-side 0 > $O/stats.log 2>&1
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --cpu-rows 0 --cpu-fft-side 0 > $O/stats.log 2>&1
 pmc() {   # KEY=<config.pmc_key> pmc NAME <bench args>: the counter passes of one configuration
   name=$1; shift
   SHORT="python $R/bench.py --steps ${PMC_STEPS:-7} --warmup 2 --blocks 1 --cpu-rows 0 --cpu-fft-side 0 --check 0 --cold 0 --also-physical 0 $@"
