@@ -56,30 +56,18 @@ inline int diag_int(const char *name, int dflt) {
 constexpr int diag_int(const char *, int dflt) { return dflt; }
 #endif
 
-// A device allocation that only grows.
-// `piece` > 0: the allocation is made of PHYSICAL pieces of that many bytes, each an allocation of its own
-// (hipMemCreate), mapped side by side into one reserved address range (hipMemMap).  What that is for: how fast
-// 16-byte stores a fixed large stride apart go (the row transform's transposed result, farfield.hip) depends on the
-// physical layout behind the buffer, which hipMalloc leaves to the driver's free lists - measured at 4096^2 -> 512^2,
-// stage 1 (profiles/r06_ab_runs.txt): one physically contiguous allocation 0.33 ms, pieces of 16 KB 1.28, 512 KB 0.8-1.0,
-// 1 MB 0.51 (address translation: the 2 MB fragment is lost), 2 / 4 / 8 MB 0.178-0.190 in three processes of four (else
-// 0.195-0.20), 32 MB 0.186; plain hipMalloc 0.183 or 0.200, one of two each, depending on what the process was handed.  Falls back to hipMalloc where the virtual-memory
-// API is not available.  (The two-pass kernel of rows beyond 8192 samples is the other way round and keeps hipMalloc.)
+// A device allocation (hipMalloc) that only grows and is freed with its owner.  Not copyable: a copy would free the
+// same memory twice.  None may have static storage duration: its destructor would run after the HIP runtime's.
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
-    size_t piece = 0;                                      // 0: one hipMalloc
-    std::vector<hipMemGenericAllocationHandle_t> handles;  // the pieces behind p
-    bool reserved = false;                                 // p is a reserved address range with the pieces mapped into it
-    size_t va_bytes = 0;                                   // ... of this many bytes (the buffer grows inside it)
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t want) {
         if (want <= bytes) return ML_OK;
-        if (piece > 0) {
-            if (p && !reserved) release();
-            if (grow_pieces(want)) return ML_OK;
-        } else {
-            release();
-        }
+        release();
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) {
             set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
@@ -89,90 +77,114 @@ struct DevBuf {
         bytes = want;
         return ML_OK;
     }
-    // ADDRESS RANGES ARE NEVER GIVEN BACK.  On this runtime (ROCm 7.2) an address range that has been unmapped, freed
-    // (hipMemAddressFree) and handed out again by a later hipMemAddressReserve reads back wrong data: a stand-alone
-    // program that fills and checks a freshly mapped buffer fails from the first round whose range overlaps an earlier
-    // one (19 008 ... 644 992 mismatching words; none when the old ranges stay reserved) - translations of the old
-    // mapping survive.  So a buffer reserves four times what it needs and GROWS by mapping more pieces behind the ones
-    // it has; a buffer that outgrows its range, or is released, unmaps and releases its physical pieces and leaves the
-    // range reserved for the life of the process (address space, not memory: 128 TB of it).
-    bool grow_pieces(size_t want) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return false;
-        hipMemAllocationProp prop = {};
-        prop.type = hipMemAllocationTypePinned;
-        prop.location.type = hipMemLocationTypeDevice;
-        prop.location.id = dev;
-        size_t gran = 0;
-        if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran ||
-            piece % gran) {
-            (void)hipGetLastError();
-            return false;
-        }
-        const size_t total = (want + piece - 1) / piece * piece;
-        if (!reserved || total > va_bytes) {
-            drop_pieces();
-            const size_t va = std::max(4 * total, (size_t)256 << 20);
-            void *base = nullptr;
-            if (hipMemAddressReserve(&base, va, piece, nullptr, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            p = base;
-            va_bytes = va;
-            reserved = true;
-        }
-        hipMemAccessDesc acc = {};
-        acc.location = prop.location;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        while (bytes < total) {
-            hipMemGenericAllocationHandle_t h;
-            if (hipMemCreate(&h, piece, &prop, 0) != hipSuccess) break;
-            void *at = static_cast<char *>(p) + bytes;
-            if (hipMemMap(at, piece, 0, h, 0) != hipSuccess) {
-                (void)hipMemRelease(h);
-                break;
-            }
-            handles.push_back(h);
-            bytes += piece;
-            if (hipMemSetAccess(at, piece, &acc, 1) != hipSuccess) break;
-        }
-        if (bytes < total) {   // (out of memory or an API that is not there: the caller falls back to hipMalloc)
-            (void)hipGetLastError();
-            drop_pieces();
-            return false;
-        }
-        return true;
-    }
-    // unmap and release the physical pieces; the address range stays reserved (see above)
-    void drop_pieces() {
-        if (p && reserved) {
-            (void)hipDeviceSynchronize();   // (as hipFree would: launches still in flight may use the range)
-            for (size_t k = 0; k < handles.size(); ++k) {
-                (void)hipMemUnmap(static_cast<char *>(p) + k * piece, piece);
-                (void)hipMemRelease(handles[k]);
-            }
-            (void)hipGetLastError();
-        }
-        handles.clear();
-        if (reserved) {
-            reserved = false;
-            p = nullptr;
-            bytes = 0;
-            va_bytes = 0;
-        }
-    }
     void release() {
-        if (reserved) {
-            drop_pieces();
-            return;
-        }
         if (p) (void)hipFree(p);
         p = nullptr;
         bytes = 0;
     }
     template <typename T>
     T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// A device allocation that only grows, made of PHYSICAL pieces of `piece` bytes, each an allocation of its own
+// (hipMemCreate), mapped side by side into one reserved address range (hipMemMap).  What that is for: how fast 16-byte
+// stores a fixed large stride apart go (the row transform's transposed result, farfield.hip) depends on the physical
+// layout behind the buffer, which hipMalloc leaves to the driver's free lists - measured at 4096^2 -> 512^2, stage 1
+// (profiles/r06_ab_runs.txt): one physically contiguous allocation 0.33 ms, pieces of 16 KB 1.28, 512 KB 0.8-1.0, 1 MB
+// 0.51 (address translation: the 2 MB fragment is lost), 2 / 4 / 8 MB 0.178-0.190 in three processes of four (else
+// 0.195-0.20), 32 MB 0.186; plain hipMalloc 0.183 or 0.200, one of two each, depending on what the process was handed.
+// reserve() either succeeds or leaves the buffer empty and returns an error; after the first failure (out of memory,
+// or a driver without the virtual-memory API) the buffer stays unavailable and reserve() fails at once - the caller
+// falls back to a DevBuf.
+// ADDRESS RANGES ARE NEVER GIVEN BACK.  On this runtime (ROCm 7.2) an address range that has been unmapped, freed
+// (hipMemAddressFree) and handed out again by a later hipMemAddressReserve reads back wrong data: a stand-alone program
+// that fills and checks a freshly mapped buffer fails from the first round whose range overlaps an earlier one (19 008
+// ... 644 992 mismatching words; none when the old ranges stay reserved, tools/vmm_reuse.hip) - translations of the old
+// mapping survive.  So a buffer reserves four times what it needs (at least 256 MB) and GROWS by mapping more pieces
+// behind the ones it has; a buffer that outgrows its range, fails or is destroyed unmaps and releases its physical
+// pieces and leaves the range reserved for the life of the process.  That holds memory too, not only address space:
+// this runtime returns unmapped, released pieces only with their range (free device memory stays down by the pieces
+// until hipMemAddressFree), so each abandoned range keeps the pieces that were last mapped into it.
+struct PieceBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    const size_t piece;
+    explicit PieceBuf(size_t piece_bytes) : piece(piece_bytes) {}
+    PieceBuf(const PieceBuf &) = delete;
+    PieceBuf &operator=(const PieceBuf &) = delete;
+    ~PieceBuf() { drop(); }
+    int reserve(size_t want) {
+        if (want <= bytes) return ML_OK;
+        if (failed != ML_OK) return failed;
+        const int rc = grow(want);
+        if (rc != ML_OK) {
+            (void)hipGetLastError();
+            drop();
+            failed = rc;
+        }
+        return rc;
+    }
+    template <typename T>
+    T *as() const { return reinterpret_cast<T *>(p); }
+
+  private:
+    std::vector<hipMemGenericAllocationHandle_t> handles;   // the pieces behind p
+    void *base = nullptr;    // the reserved range (p, once a piece is mapped) ...
+    size_t va_bytes = 0;     // ... of this many bytes
+    int failed = ML_OK;      // the error of the first failed reserve(): never tried again
+
+    int grow(size_t want) {
+        int dev = 0;
+        ML_HIP(hipGetDevice(&dev));
+        hipMemAllocationProp prop = {};
+        prop.type = hipMemAllocationTypePinned;
+        prop.location.type = hipMemLocationTypeDevice;
+        prop.location.id = dev;
+        size_t gran = 0;
+        ML_HIP(hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended));
+        ML_REQUIRE(gran && piece % gran == 0, "pieces of %zu bytes are not a multiple of the granularity %zu", piece,
+                   gran);
+        const size_t total = (want + piece - 1) / piece * piece;
+        if (total > va_bytes) {   // a new range; the old one (if any) stays reserved
+            drop();
+            const size_t va = std::max(4 * total, (size_t)256 << 20);
+            ML_HIP(hipMemAddressReserve(&base, va, piece, nullptr, 0));
+            va_bytes = va;
+        }
+        hipMemAccessDesc acc = {};
+        acc.location = prop.location;
+        acc.flags = hipMemAccessFlagsProtReadWrite;
+        while (bytes < total) {
+            hipMemGenericAllocationHandle_t h;
+            ML_HIP(hipMemCreate(&h, piece, &prop, 0));
+            void *at = static_cast<char *>(base) + bytes;
+            const hipError_t e = hipMemMap(at, piece, 0, h, 0);
+            if (e != hipSuccess) {
+                (void)hipMemRelease(h);
+                set_error("hipMemMap failed: %s", hipGetErrorString(e));
+                return ML_EHIP;
+            }
+            handles.push_back(h);
+            p = base;
+            bytes += piece;
+            ML_HIP(hipMemSetAccess(at, piece, &acc, 1));
+        }
+        return ML_OK;
+    }
+    // unmap and release the physical pieces; the address range stays reserved (see above)
+    void drop() {
+        if (!handles.empty()) {
+            (void)hipDeviceSynchronize();   // (as hipFree would: launches still in flight may use the range)
+            for (size_t k = 0; k < handles.size(); ++k) {
+                (void)hipMemUnmap(static_cast<char *>(base) + k * piece, piece);
+                (void)hipMemRelease(handles[k]);
+            }
+            (void)hipGetLastError();
+            handles.clear();
+        }
+        p = nullptr;
+        bytes = 0;
+    }
 };
 
 constexpr int MAX_SLOTS = 32;      // grating collections per lens (+1 centre)
@@ -328,7 +340,8 @@ struct FarfieldPlan {
     DevBuf ux, uy;       // direction cosines
     DevBuf tw_x;         // complex [mx][nx_total]   exp(-i k x' ux)   (A operand of stage 2)
     DevBuf tw_y;         // complex [ny][my]         exp(-i k y' uy)   (B operand of stage 1)
-    DevBuf stage1;       // complex [4][nx_local][my]
+    DevBuf stage1;       // complex [4][nx_local][my], or transposed (farfield.hip transform_impl) ...
+    PieceBuf stage1_pieces{(size_t)4 << 20};   // ... the transposed one of rows up to 8192 samples
     DevBuf vectors;      // complex [4][mx][my]  (Nx, Ny, Lx, Ly)  or [4][mx] for a pair list
     DevBuf power;        // double  [mx][my]
     // complex [2 slots][2][mx][my]  (a_theta, a_phi).  Two slots: with a communicator the

@@ -649,40 +649,13 @@ void ml_ctx_destroy(ml_ctx *ctx) {
         }
         (void)hipStreamDestroy(ctx->comm_stream);
     }
-    for (auto &s : ctx->slots) {
-        s.axis0.release();
-        s.axis1.release();
-        s.values.release();
-        s.order_k.release();
-    }
-    ctx->center.axis0.release();
-    ctx->center.axis1.release();
-    ctx->center.values.release();
-    ctx->center.order_k.release();
-    DevBuf *bufs[] = {&ctx->table_desc, &ctx->ring_boundaries, &ctx->ring_r_center,
-                      &ctx->ring_period, &ctx->ring_dphi, &ctx->ring_lateral, &ctx->ring_gc,
-                      &ctx->ring_rec, &ctx->ring_coll, &ctx->ring_tab, &ctx->ring_ok,
-                      &ctx->ring_ok_off, &ctx->center_qmajor, &ctx->rot_table, &ctx->tie_table, &ctx->ring_rot_center,
-                      &ctx->ring_rot_half, &ctx->ring_lut, &ctx->ring_lutrec, &ctx->cell_x, &ctx->cell_y,
-                      &ctx->cell_xy, &ctx->cell_which, &ctx->cell_index, &ctx->bin_start,
-                      &ctx->cell_lattice_map, &ctx->cell_lattice_rec, &ctx->tie_count, &ctx->tie_list,
-                      &ctx->ovr_key, &ctx->ovr_slot, &ctx->geo_ix, &ctx->active_list, &ctx->active_count, &ctx->active_flag, &ctx->fields,
-                      &ctx->x_pts, &ctx->y_pts, &ctx->partial_power, &ctx->power,
-                      &ctx->violations, &ctx->row_first, &ctx->acc_P, &ctx->acc_partials, &ctx->acc_sums, &ctx->plan.ux, &ctx->plan.uy, &ctx->plan.tw_x,
-                      &ctx->plan.tw_y, &ctx->plan.stage1, &ctx->plan.vectors, &ctx->plan.power,
-                      &ctx->plan.amplitudes, &ctx->comm_scratch, &ctx->lattice_in,
-                      &ctx->plan.fold_cm, &ctx->plan.fold_sm, &ctx->plan.fold_E, &ctx->plan.fold_D,
-                      &ctx->plan.fold_v, &ctx->plan.fold_r4, &ctx->plan.fold2_v, &ctx->plan.fold2_cm,
-                      &ctx->plan.fold2_sm, &ctx->plan.fold2_r4, &ctx->plan.fold2_E, &ctx->plan.fold2_D,
-                      &ctx->plan.fold2_gt, &ctx->plan.fold2_ot};
-    for (DevBuf *b : bufs) b->release();
     for (auto &pd : ctx->prof.pending) {
         (void)hipEventDestroy(pd.a);
         (void)hipEventDestroy(pd.b);
     }
     for (auto e : ctx->prof.pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // (the device buffers free themselves, on the device set above)
 }
 
 int ml_device_info(ml_ctx *ctx, char *name, int name_len, int *cu_count, int64_t *hbm_bytes) {
@@ -983,33 +956,6 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
     ML_TRY(grid_axis(ctx->x_pts, ctx->h_x_pts, x_pts, nx));
     ML_TRY(grid_axis(ctx->y_pts, ctx->h_y_pts, y_pts, ny));
     const size_t plane = (size_t)nx * ny;
-#ifdef ML_DIAG
-    {   // (tools/ab_goffset.sh: the field planes in physical pieces, as the row transform's result is - common.h DevBuf::piece)
-        static const size_t f_piece = (size_t)diag_int("ML_F_PIECE_KB", 0) << 10;
-        if (f_piece && ctx->fields.piece != f_piece) {
-            ctx->fields.release();
-            ctx->fields.piece = f_piece;
-        }
-    }
-#endif
-#ifdef ML_DIAG
-    {   // (... or as ONE physically contiguous allocation)
-        static const int f_contig = diag_int("ML_F_CONTIGUOUS", 0);
-        const size_t want = (size_t)n * 4 * plane * 2 * sizeof(double);
-        if (f_contig && ctx->fields.bytes < want) {
-            ctx->fields.release();
-            void *q = nullptr;
-            const hipError_t e = hipExtMallocWithFlags(&q, want, hipDeviceMallocContiguous);
-            fprintf(stderr, "ML_F_CONTIGUOUS %zu bytes: %s\n", want, hipGetErrorString(e));
-            if (e == hipSuccess) {
-                ctx->fields.p = q;
-                ctx->fields.bytes = want;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    }
-#endif
     ML_TRY(ctx->fields.reserve((size_t)n * 4 * plane * 2 * sizeof(double)));
     ctx->nx = nx;
     ctx->ny = ny;
@@ -1038,15 +984,6 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
         ctx->n_ovr = 0;
         ++ctx->ovr_serial;
     }
-#ifdef ML_DIAG
-    {   // (... and the geometry records)
-        static const size_t r_piece = (size_t)diag_int("ML_R_PIECE_KB", 0) << 10;
-        if (r_piece && ctx->geo_ix.piece != r_piece) {
-            ctx->geo_ix.release();
-            ctx->geo_ix.piece = r_piece;
-        }
-    }
-#endif
     ML_TRY(ctx->geo_ix.reserve((size_t)blocks * 64 * 2 * sizeof(int)));   // patch-major, 64 per patch
     ML_TRY(ctx->active_list.reserve((size_t)4 * blocks * 2 * sizeof(int)));           // four lists (NfArgs::active_list)
     ML_TRY(ctx->active_count.reserve((size_t)4 * (blocks / 1024 + 4) * sizeof(int)));   // each: total + one per chunk of 1024 patches

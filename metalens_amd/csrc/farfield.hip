@@ -907,49 +907,24 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     // 72 0.206, 4 0.190, 8 0.194-0.196, 40 0.196, 136 0.192: anything but a multiple of 256 bytes)
     static const int g_skew = diag_int("ML_G_SKEW", 8);   // (diagnostic builds: the pitch's skew in elements)
     const int64_t g_ld = nxl + g_skew;
-    // The TRANSPOSED result lies in physical pieces of 4 MB, each an allocation of its own, mapped side by side
-    // (common.h DevBuf::piece).  Stage 1 stores it in 16-byte pieces one pitch (65 KB at 4096 samples) apart, and how
-    // fast those go is decided by the physical layout behind the buffer: 0.33 ms over one physically contiguous
-    // allocation (whatever the pitch), 0.5-1.3 ms in pieces below the 2 MB translation fragment, 0.178-0.190 in pieces
-    // of 2 to 8 MB in three processes of four (8192 samples, pitch 131 KB: 0.75 in 2 MB pieces, 0.70 in 4 MB, 0.72 in 8 MB)
-    // - and 0.183 or 0.200, one of two each, from hipMalloc, whose layout is whatever the driver's free lists hold: the
-    // two 'modes' of rounds 4-6 (profiles/r06_ab_runs.txt)
-    // ... for rows of up to 8192 samples.  The two-pass kernel of longer rows (one 152 KB workgroup per CU, whole lines
-    // stored) is the other way round: 16384^2 -> 1024^2 stage 1 4.01-4.16 ms over hipMalloc, 4.95 in 4 MB pieces, 4.32
-    // in 8, 4.45 in 16, 4.13 in 32, 4.03 in 64 - it keeps hipMalloc
-#ifdef ML_DIAG
-    static const long g_piece_kb = diag_int("ML_G_PIECE_KB", -1);                   // (0: hipMalloc; -1: the rule)
-    const size_t g_piece = g_piece_kb >= 0 ? (size_t)g_piece_kb << 10 : nxl <= 8192 ? (size_t)4 << 20 : 0;
-    static const size_t g_shift = (size_t)diag_int("ML_G_OFFSET_KB", 0) << 10;     // (G that far into a larger buffer)
-#else
-    const size_t g_piece = nxl <= 8192 ? (size_t)4 << 20 : 0;
-    constexpr size_t g_shift = 0;
-#endif
-    // (METALENS_HIP_PIECES=0 in the environment: plain hipMalloc - the way out should a driver's virtual-memory API misbehave)
+    // The TRANSPOSED result of rows up to 8192 samples lies in physical pieces of 4 MB, each an allocation of its own,
+    // mapped side by side (common.h PieceBuf).  Stage 1 stores it in 16-byte pieces one pitch (65 KB at 4096 samples)
+    // apart, and how fast those go is decided by the physical layout behind the buffer: 0.33 ms over one physically
+    // contiguous allocation (whatever the pitch), 0.5-1.3 ms in pieces below the 2 MB translation fragment, 0.178-0.190
+    // in pieces of 2 to 8 MB in three processes of four (8192 samples, pitch 131 KB: 0.75 in 2 MB pieces, 0.70 in 4 MB,
+    // 0.72 in 8 MB) - and 0.183 or 0.200, one of two each, from hipMalloc, whose layout is whatever the driver's free
+    // lists hold: the two 'modes' of rounds 4-6 (profiles/r06_ab_runs.txt).  The two-pass kernel of
+    // longer rows (one 152 KB workgroup per CU, whole lines stored) is the other way round: 16384^2 -> 1024^2 stage 1
+    // 4.01-4.16 ms over hipMalloc, 4.95 in 4 MB pieces, 4.32 in 8, 4.45 in 16, 4.13 in 32, 4.03 in 64 - it keeps
+    // hipMalloc, as does every other layout.  A context that runs both kinds holds both buffers.
+    // (METALENS_HIP_PIECES=0 in the environment: plain hipMalloc - the way out should a driver's virtual-memory API
+    // misbehave; so is a PieceBuf that has failed once: it is not tried again)
     static const bool pieces_off = [] { const char *e = getenv("METALENS_HIP_PIECES"); return e && e[0] == '0'; }();
-    const size_t g_need = (size_t)4 * my * g_ld * 2 * sizeof(double) + g_shift;
-    const size_t g_piece_now = pieces_off ? 0 : g_piece;
-    if (g_transposed && pl.stage1.piece != g_piece_now) {
-        pl.stage1.release();
-        pl.stage1.piece = g_piece_now;
-    }
-    ML_TRY(pl.stage1.reserve(g_transposed ? g_need : (size_t)pl.stage1_splits * 4 * nxl * my * 2 * sizeof(double)));
-    void *g_at = pl.stage1.p;     // G of this call
-#ifdef ML_DIAG
-    {   // (tools/ab_goffset.sh: ONE physically contiguous allocation behind the result)
-        static const int contiguous = diag_int("ML_G_CONTIGUOUS", 0);
-        static void *c_ptr = nullptr;
-        static size_t c_bytes = 0;
-        if (contiguous && g_transposed && c_bytes < g_need) {
-            const hipError_t e = hipExtMallocWithFlags(&c_ptr, g_need, hipDeviceMallocContiguous);
-            fprintf(stderr, "ML_G_CONTIGUOUS %zu bytes: %s at %p\n", g_need, hipGetErrorString(e), c_ptr);
-            if (e == hipSuccess) c_bytes = g_need;
-            else (void)hipGetLastError();
-        }
-        if (contiguous && g_transposed && c_bytes >= g_need) g_at = c_ptr;
-    }
-#endif
-    double *const g_buf = reinterpret_cast<double *>(static_cast<char *>(g_at) + (g_transposed ? g_shift : 0));
+    const size_t g_bytes = g_transposed ? (size_t)4 * my * g_ld * 2 * sizeof(double)
+                                        : (size_t)pl.stage1_splits * 4 * nxl * my * 2 * sizeof(double);
+    const bool pieced = g_transposed && nxl <= 8192 && !pieces_off && pl.stage1_pieces.reserve(g_bytes) == ML_OK;
+    if (!pieced) ML_TRY(pl.stage1.reserve(g_bytes));
+    double *const g_buf = pieced ? pl.stage1_pieces.as<double>() : pl.stage1.as<double>();   // G of this call
     // the folded stage 2 pays once its grid (32-row x 64-half-direction tiles over the 4*my
     // transposed rows) fills the chip; below that the generic GEMM with 32 x 32 tiles is faster
     static const long fold2_min_tiles = diag_int("ML_FOLD2_MIN_TILES", 32);
@@ -990,17 +965,6 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         }
     }
     const int nxt = trim_hi - trim_lo;   // rows per field plane the FFT stages work on
-#ifdef ML_DIAG
-    {   // (tools/mode_contexts.py: where this context's buffers lie, once per stage-1 buffer)
-        static const bool print_ptrs = diag_int("ML_PRINT_PTRS", 0) != 0;
-        static const void *seen = nullptr;
-        if (print_ptrs && seen != pl.stage1.p) {
-            seen = pl.stage1.p;
-            fprintf(stderr, "ML_PTRS fields %p stage1 %p vectors %p geo %p\n", (void *)ctx->set_ptr(), pl.stage1.p,
-                    pl.vectors.p, ctx->geo_ix.p);
-        }
-    }
-#endif
     const bool use_fold2 = !fft2 && !pl.pair_list && pl.fold2 && fold2_pays && (mirrored || whole) && sh.kind != 2;
     // both stages folded: stage 1 writes its result already transposed for stage 2
     static const bool no_direct = diag_int("ML_NO_GT_DIRECT", 0) != 0;
@@ -1049,7 +1013,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         c.a1 = c.h1 = 0;
         c.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() + trim_lo : nullptr;
         c.rf_mod = nxt;
-        c.out = pl.stage1.as<double>() + (size_t)trim_lo * my * 2;
+        c.out = g_buf + (size_t)trim_lo * my * 2;
         c.out_rb = nxt;
         c.out_s1 = (int64_t)nxl * my;
         c.out_s2 = my;
@@ -1093,12 +1057,12 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
                                 pl.fold_r4.as<double>(), pl.fold_T,
                                 pl.fold_S,
                                 pl.fold_has_E && !fields_premodulated ? pl.fold_E.as<double>() : nullptr,
-                                pl.fold_D.as<double>(), pl.stage1.as<double>(), my, my,
+                                pl.fold_D.as<double>(), g_buf, my, my,
                                 ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr, nxl,
                                 want_split1, (int64_t)4 * nxl * my, ctx->gemm_f32 != 0, io1));
         else
             ML_TRY(zgemm(ctx->stream, 4 * nxl, my, ny, one, ctx->set_ptr(), ny, 0,
-                         pl.tw_y.as<double>(), my, 0, pl.stage1.as<double>(), my, 0, 1, 0));
+                         pl.tw_y.as<double>(), my, 0, g_buf, my, 0, 1, 0));
     }
     const double dA = pl.dxp * pl.dyp;
     // fields are stored Ex,Ey,Hx,Hy; radiation vectors Nx,Ny,Lx,Ly = -Hy, Hx, Ey, -Ex (x dA)
@@ -1107,7 +1071,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         if (pl.stage1_splits > 1) {
             const size_t n = (size_t)4 * nxl * my;
             hipLaunchKernelGGL(zsum_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                               ctx->stream, pl.stage1.as<double2>(), n, pl.stage1_splits);
+                               ctx->stream, reinterpret_cast<double2 *>(g_buf), n, pl.stage1_splits);
             ML_HIP(hipGetLastError());
             pl.stage1_splits = 1;
         }
@@ -1142,7 +1106,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
             c.jstep = pl.fft_x.jstep;
             c.pad1 = pl.il_pad1;
             c.pad2 = pl.il_pad2;
-            c.in = pl.stage1.as<double>();
+            c.in = g_buf;
             c.rows = 4 * my;
             c.in_rb = my;
             c.in_s1 = (int64_t)nxl * my;
@@ -1241,7 +1205,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         for (int run = 0; run < 2; ++run) {
             const int first = run == 0 ? row0 : pl.nx_total - row0 - h;
             ML_TRY(zgemm(ctx->stream, mx, my, h, alpha, pl.tw_x.as<double>() + (size_t)first * 2,
-                         pl.nx_total, 0, pl.stage1.as<double>() + (size_t)run * h * my * 2, my,
+                         pl.nx_total, 0, g_buf + (size_t)run * h * my * 2, my,
                          (int64_t)nxl * my, slot3, my, -(int64_t)mx * my, 4,
                          run == 0 ? accumulate : 1));
         }
@@ -1253,14 +1217,14 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         ML_TRY(collapse_stage1());
         double *slot3 = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
         ML_TRY(zgemm(ctx->stream, mx, my, nxl, alpha, pl.tw_x.as<double>() + (size_t)row0 * 2,
-                     pl.nx_total, 0, pl.stage1.as<double>(), my, (int64_t)nxl * my, slot3, my,
+                     pl.nx_total, 0, g_buf, my, (int64_t)nxl * my, slot3, my,
                      -(int64_t)mx * my, 4, accumulate));
     } else {
         ML_TRY(need_tw_x(ctx));
         ProfScope scope(ctx, ML_K_COLDOT);
         ML_TRY(collapse_stage1());
         ML_TRY(zcoldot(ctx->stream, 4, nxl, mx, alpha, pl.tw_x.as<double>(), mx, row0,
-                       pl.stage1.as<double>(), pl.vectors.as<double>(), accumulate));
+                       g_buf, pl.vectors.as<double>(), accumulate));
     }
     pl.have_vectors = true;
     pl.amplitudes_reduced = false;

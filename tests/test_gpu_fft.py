@@ -183,7 +183,7 @@ def test_hot_path_fft_equals_gemm(ma, ctx):
 
 def test_transposed_result_buffer_grows_and_moves_without_changing_results(ma):
     """the transposed stage-1 result lives in physical pieces mapped into a reserved address range (common.h
-    DevBuf::piece): it GROWS inside the range, and a result that outgrows the range moves to a new one (the old
+    PieceBuf): it GROWS inside the range, and a result that outgrows the range moves to a new one (the old
     range is never handed back: on this runtime a re-used range reads stale data).  Sizes chosen to walk that path -
     16, 67 and 269 MB of result, then small again - each against the GEMMs on the same fields"""
     from metalens_amd import _lib

@@ -1,8 +1,9 @@
-"""The whole-flow tests of the HIP path: every test here starts `bench.py` (or ranks of it) as a
-SUBPROCESS on the GPU - real RCCL with one rank, 2 / 4 / 8 ranks sharing one GPU through the file
-communicator, the wavelength replicas, the bench-line contract, real RCCL with two ranks where two
-devices exist.  Kept apart from tests/test_gpu_parity.py and named to run LAST: under `pytest -x` a
-flaky subprocess must not hide the kernel-parity tests from the record.  Needs an MI355X: ``-m gpu``."""
+"""The whole-flow tests of the HIP path: every test here starts `bench.py` (or ranks of it, or a short
+script of its own) as a SUBPROCESS on the GPU - real RCCL with one rank, 2 / 4 / 8 ranks sharing one GPU
+through the file communicator, the wavelength replicas, the bench-line contract, real RCCL with two ranks
+where two devices exist, the stage-1 result in pieces or not, contexts created and destroyed over and
+over.  Kept apart from tests/test_gpu_parity.py and named to run LAST: under `pytest -x` a flaky
+subprocess must not hide the kernel-parity tests from the record.  Needs an MI355X: ``-m gpu``."""
 import os
 
 import numpy as np
@@ -312,3 +313,103 @@ def test_two_gpus_real_rccl(tmp_path):
         ok = ~np.isnan(a['P'])
         assert np.array_equal(np.isnan(b['P']), ~ok)
         assert np.abs(a['P'][ok] - b['P'][ok]).max() <= 1e-12 * a['P'][ok].max()
+
+
+def test_pieces_and_hipmalloc_give_the_same_bits(tmp_path):
+    """the transposed stage-1 result in 4 MB physical pieces (the default, csrc/common.h PieceBuf) or from hipMalloc
+    (METALENS_HIP_PIECES=0, which the library reads once per process: hence two processes) - the same radiation
+    vectors, amplitudes and power, bit for bit.  --method fft-streamed takes the transposed layout at any aperture
+    size (csrc/farfield.hip g_transposed), so a small one does"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = {k: v for k, v in os.environ.items() if k != 'METALENS_HIP_PIECES'}
+    dirs = {}
+    for name, extra in (('pieces', {}), ('hipmalloc', {'METALENS_HIP_PIECES': '0'})):
+        dirs[name] = str(tmp_path / name)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--aperture', '512', '--farfield', '64',
+               '--diameter', '1.2e-4', '--steps', '2', '--warmup', '1', '--method', 'fft-streamed',
+               '--dump-outputs', dirs[name]]
+        p = subprocess.run(cmd, env=dict(base, **extra), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+    names = sorted(os.listdir(dirs['pieces']))
+    assert names == sorted(os.listdir(dirs['hipmalloc']))
+    for key in ('Nx', 'Ny', 'Lx', 'Ly', 'a_theta', 'a_phi'):
+        assert key + '_re.npy' in names and key + '_im.npy' in names, key
+    assert 'P.npy' in names
+    for name in names:
+        a, b = (np.load(os.path.join(dirs[k], name)) for k in ('pieces', 'hipmalloc'))
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), name
+
+
+_CONTEXT_CYCLES = r'''
+import ctypes, json, sys
+sys.path.insert(0, sys.argv[1])
+import bench
+from metalens_amd import _lib
+from metalens_amd.pipeline import HotPath
+wl = 580e-9
+lens, x, u = bench.build_workload(4096, 512, 1e-3, 0.5, wl, 1.0)
+src = (0.0, 0.0, -lens['source_distance'], 'x')
+
+
+def cycle():
+    ctx = _lib.Context()
+    hp = HotPath(src, wl, lens['lens_periphery_summary'], lens['lens_center_summary'], lens['hexgridset'],
+                 x, x, u, u, ctx=ctx)
+    hp.step()
+    hp.sync()
+    kernels = ctx.plan_kernels()
+    ctx.close()
+    return kernels
+
+
+def free_bytes():
+    # hipMemGetInfo of the HIP runtime the library has loaded
+    hip = ctypes.CDLL(next(l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l))
+    free, total = ctypes.c_size_t(), ctypes.c_size_t()
+    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+    return free.value
+
+
+kernels = cycle()
+after = [free_bytes()]
+for _ in range(5):
+    cycle()
+    after.append(free_bytes())
+print(json.dumps({'kernels': list(kernels), 'free': after}))
+'''
+
+
+def _context_cycles(pieces):
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != 'METALENS_HIP_PIECES'}
+    if not pieces:
+        env['METALENS_HIP_PIECES'] = '0'
+    p = subprocess.run([sys.executable, '-c', _CONTEXT_CYCLES, root], env=env, capture_output=True, text=True,
+                       timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith('{')][-1])
+    assert d['kernels'] == ['fft', 'fft']
+    return d['free']
+
+
+def test_destroyed_contexts_return_their_memory():
+    """create -> plan -> synthesis -> transform -> projection -> destroy on the benchmark's 4096^2 -> 512^2
+    workload (more than 1 GB per context), once to warm up and five more times in one child process: free device
+    memory after the last cycle is within 64 MB of what it was after the first.  This guards the large buffers; leaks
+    of a few kB (the FFT tables) are below what it can see - those are members with destructors, freed by
+    construction.
+    The stage-1 result in 4 MB pieces (csrc/common.h PieceBuf) is the exception: the runtime (ROCm 7.2) gives unmapped,
+    released pieces back only with their address range, which the library never frees (a re-used range reads stale
+    data) - measured: 132 MiB per context at this size.  So that run may lose those pieces per cycle and nothing
+    more; the run with METALENS_HIP_PIECES=0 must lose nothing."""
+    free = _context_cycles(pieces=False)
+    assert free[0] - free[-1] < 64 << 20, free
+    piece = 4 << 20
+    held = -(-4 * 512 * (4096 + 8) * 16 // piece) * piece   # the transposed result [4][512][4096 + 8] complex128
+    free = _context_cycles(pieces=True)
+    assert free[0] - free[-1] < 5 * held + (64 << 20), free
