@@ -4,6 +4,7 @@ There is no CPU fallback: if the shared library is missing or no MI355X is
 visible, every entry point of the package raises ``MetalensHipError``.
 """
 import ctypes
+import itertools
 import os
 from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32, c_int64,
                     c_uint8, c_void_p)
@@ -265,6 +266,16 @@ class Context:
         self.lib = lib
         self.layout_token = None
         self.tables_token = None
+        # the context-wide settings as the library has them (ml_ctx_create's defaults): an object that
+        # re-asserts its own settings before every pass pays an attribute compare when they still hold
+        self.precision = 'f64'
+        self.method = 'auto'
+        self.comm_reduce = 0
+        # which API object made the active far-field plan / left the resident field set (a serial from
+        # new_owner(); None: a drop-in call or nobody): results downloaded later are refused by an
+        # object that is no longer the owner - the plan's size and content are another object's
+        self.plan_owner = None
+        self.fields_owner = None
 
     def close(self):
         if getattr(self, '_h', None):
@@ -296,6 +307,8 @@ class Context:
     def set_precision(self, precision):
         """'f64' (default) or 'f32': arithmetic of the folded aperture -> direction GEMMs
         (include/metalens_hip.h, ml_farfield_set_precision); everything else stays fp64"""
+        if precision == self.precision:
+            return
         check(self.lib.ml_farfield_set_precision(self.handle, {'f64': 0, 'f32': 1}[precision]))
         self.precision = precision
 
@@ -304,7 +317,18 @@ class Context:
         output-pruned FFTs, the others as GEMMs; 'gemm': GEMMs everywhere; 'fft-streamed': as
         'auto' with the stage-1 result transposed for a streaming stage 2 at every size (auto:
         from 96 MiB of records + stage-1 result on).  Applies to the next plan."""
+        if method == self.method:
+            return
         check(self.lib.ml_farfield_set_method(self.handle, {'auto': 0, 'gemm': 1, 'fft-streamed': 2}[method]))
+        self.method = method
+
+    def set_comm_reduce(self, allreduce):
+        """multi-GPU amplitude reduction: 0 reduce-scatter (default), 1 all-reduce (ml_comm_set_reduce)"""
+        allreduce = int(allreduce)
+        if allreduce == self.comm_reduce or not hasattr(self.lib, 'ml_comm_set_reduce'):
+            return
+        check(self.lib.ml_comm_set_reduce(self.handle, allreduce))
+        self.comm_reduce = allreduce
 
     def plan_kernels(self):
         """(stage 1, stage 2) of the active plan: 'gemm', 'folded' or 'fft'"""
@@ -344,6 +368,14 @@ class Context:
             check(self.lib.ml_profile_get(self.handle, k, byref(n), byref(ms)))
             out[name] = {'launches': n.value, 'total_ms': ms.value}
         return out
+
+
+_owner_serial = itertools.count(1)
+
+
+def new_owner():
+    """a fresh serial for an API object that plans / synthesises on a context (Context.plan_owner)"""
+    return next(_owner_serial)
 
 
 _default = None

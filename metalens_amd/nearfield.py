@@ -155,6 +155,7 @@ def build_nearfield(source_x, source_y, source_z, source_pol, wavelength,
     # the drop-in hands back (or leaves resident) the PLAIN fields: a HotPath that shared this
     # context may have left the synthesis writing exp(-i pi (i+j)) modulated ones
     _lib.check(ctx.lib.ml_nearfield_premodulate(ctx.handle, 0))
+    ctx.fields_owner = None   # the resident near field is this call's now (HotPath.results)
     p = nearfield_params(source_x, source_y, source_z, source_pol, wavelength, n_glass,
                          dipole_moment, c0, Z0)
     power = _lib.c_double(0)

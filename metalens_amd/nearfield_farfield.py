@@ -148,31 +148,61 @@ class FarfieldTransform:
     def __init__(self, num_x_total, num_y, dxp, dyp, wavelength, n_glass, ux, uy,
                  pair_list=False, ctx=None, precision=None):
         self.ctx = ctx or _lib.default_context()
-        # 'f64' | 'f32': arithmetic of the GEMMs.  A property of the CONTEXT that plans inherit, so
-        # it is set on every construction: an earlier HotPath(precision='f32') on the same context
-        # must not leak into a transform that documents 1e-12
-        self.ctx.set_precision(precision or 'f64')
+        # 'f64' | 'f32': arithmetic of the GEMMs, and the method: properties of the CONTEXT that
+        # plans and transforms inherit.  This object keeps its precision (default fp64: a later
+        # HotPath(precision='f32') on the same context must not leak into a transform that documents
+        # 1e-12) and the method the context had when it was built, and re-asserts both whenever it
+        # plans or transforms
+        self.precision = precision or 'f64'
+        self.method = self.ctx.method
+        self.owner = _lib.new_owner()
         self.ux = _lib.f64(np.ravel(ux))
         self.uy = _lib.f64(np.ravel(uy))
         self.pair_list = bool(pair_list)
         self.shape = (self.ux.size,) if pair_list else (self.ux.size, self.uy.size)
         self.wavelength, self.n_glass = wavelength, n_glass
-        _lib.check(self.ctx.lib.ml_farfield_plan(
-            self.ctx.handle, num_x_total, num_y, dxp, dyp, wavelength, n_glass,
-            _lib.dptr(self.ux), self.ux.size, _lib.dptr(self.uy), self.uy.size, int(pair_list)))
+        self._geometry = (num_x_total, num_y, dxp, dyp)
+        self._plan()
+
+    def _plan(self):
+        ctx = self.ctx
+        ctx.set_precision(self.precision)
+        ctx.set_method(self.method)
+        num_x_total, num_y, dxp, dyp = self._geometry
+        _lib.check(ctx.lib.ml_farfield_plan(
+            ctx.handle, num_x_total, num_y, dxp, dyp, self.wavelength, self.n_glass,
+            _lib.dptr(self.ux), self.ux.size, _lib.dptr(self.uy), self.uy.size, int(self.pair_list)))
+        ctx.plan_owner = self.owner
+
+    def _check_owner(self):
+        """the context's plan and radiation vectors are this object's: the copies below are sized by its
+        directions, and the library copies as many as the ACTIVE plan has"""
+        if self.ctx.plan_owner != self.owner:
+            raise RuntimeError('the far-field plan on this context is no longer this FarfieldTransform\'s '
+                               '(another object has planned since): call transform() again')
 
     def transform(self, row0=0, accumulate=False, mirrored=False):
         """radiation vectors of the resident field rows (a partial sum if sharded).
         ``mirrored``: the resident rows are the pairs [row0, row0+h) + [N-row0-h, N-row0)
-        (see dist.mirrored_rows) instead of the contiguous block [row0, row0+rows)."""
-        fn = (self.ctx.lib.ml_farfield_transform_mirrored if mirrored
-              else self.ctx.lib.ml_farfield_transform)
-        _lib.check(fn(self.ctx.handle, row0, int(accumulate)))
+        (see dist.mirrored_rows) instead of the contiguous block [row0, row0+rows).
+        Plans again if another object has planned on the context since (``accumulate`` onto another
+        object's radiation vectors is refused)."""
+        ctx = self.ctx
+        if ctx.plan_owner != self.owner:
+            if accumulate:
+                self._check_owner()
+            self._plan()
+        ctx.set_precision(self.precision)
+        fn = (ctx.lib.ml_farfield_transform_mirrored if mirrored
+              else ctx.lib.ml_farfield_transform)
+        _lib.check(fn(ctx.handle, row0, int(accumulate)))
 
     def allreduce(self):
+        self._check_owner()
         _lib.check(self.ctx.lib.ml_farfield_allreduce(self.ctx.handle))
 
     def radiation_vectors(self):
+        self._check_owner()
         out = [np.empty(self.shape, dtype=np.complex128) for _ in range(4)]
         _lib.check(self.ctx.lib.ml_farfield_download(self.ctx.handle, *[_lib.dptr(a) for a in out]))
         return dict(zip(('Nx', 'Ny', 'Lx', 'Ly'), out))
@@ -182,6 +212,7 @@ class FarfieldTransform:
         two complex far-field amplitudes ``L_phi + Z N_theta`` (prop. to E_theta) and
         ``L_theta - Z N_phi`` (prop. to -E_phi) of nearfield_farfield.py:184-185."""
         Z0 = constants.as_units(units).Z0 if Z0 is None else Z0
+        self._check_owner()
         P = np.empty(self.shape, dtype=np.float64)
         a_theta = np.empty(self.shape, dtype=np.complex128)
         a_phi = np.empty(self.shape, dtype=np.complex128)
@@ -207,6 +238,7 @@ def farfield_direct(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, ux, u
         assert arrs[0].shape == arrs[1].shape == arrs[2].shape == arrs[3].shape == (len(xp_list), len(yp_list))
         _lib.check(ctx.lib.ml_fields_upload(ctx.handle, len(xp_list), len(yp_list),
                                             *[_lib.dptr(a) for a in arrs]))
+        ctx.fields_owner = None
     t = FarfieldTransform(len(xp_list), len(yp_list), dxp, dyp, wavelength, n_glass, ux, uy,
                           pair_list=pair_list, ctx=ctx, precision=precision)
     t.transform()

@@ -33,8 +33,12 @@ class SourceSweep:
                  x_pts, y_pts, ux, uy, dipole_moment=None, c0=None, Z0=None, ctx=None,
                  precision=None, method=None, units=None):
         self.ctx = ctx or _lib.default_context()
-        self.ctx.set_precision(precision or 'f64')
-        self.ctx.set_method(method or 'auto')
+        # context-wide settings, re-asserted by every prepare() (other objects share the context)
+        self.precision = precision or 'f64'
+        self.method = method or 'auto'
+        self.owner = _lib.new_owner()
+        self.ctx.set_precision(self.precision)
+        self.ctx.set_method(self.method)
         self.units = constants.as_units(units)   # the caller's unit system (nearfield.build_nearfield); default SI
         self.c0 = self.units.c0 if c0 is None else c0
         self.Z0 = self.units.Z0 if Z0 is None else Z0
@@ -67,10 +71,13 @@ class SourceSweep:
             packing.upload_tables(ctx, *self._tables)
             packing.upload_layout(ctx, *self._layout)
             self._resident = (ctx.tables_token, ctx.layout_token)
+        ctx.set_precision(self.precision)
+        ctx.set_method(self.method)
         _lib.check(lib.ml_nearfield_premodulate(ctx.handle, 0))
         _lib.check(lib.ml_farfield_plan(ctx.handle, self.x.size, self.y.size, self.dxp, self.dyp,
                                         self.wavelength, self.n_glass, _lib.dptr(self.ux),
                                         self.ux.size, _lib.dptr(self.uy), self.uy.size, 0))
+        ctx.plan_owner = ctx.fields_owner = self.owner
 
     def queue(self, sources):
         """queue the whole sweep on the GPU and return without synchronising (benchmarks);
