@@ -565,7 +565,10 @@ struct ZfftCall {
     int alpha_rb, rows, accumulate;
     int passes = 0;                  // > 1: the pass-split kernel (0: the library's default)
     int second = 0;                  // contiguous rows that are the SECOND stage (of a transposed stage-1 result)
+    int tiled_out = 0;               // bins stored in tiles of 8 (zfft_core.h tile_off; out_es = the tile's stride)
 };
+// the column pass over a tiled stage-1 result (zfft.hip zfft_tiles_kernel)
+int zfft_run_tiles(hipStream_t stream, const ZfftCall &c);
 int zfft_split(int N_eff);   // sub-sequences a lattice of N_eff samples is transformed in (0: none)
 bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
                        long double tol, int *N_eff, int *j0, int *jstep);

@@ -16,6 +16,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "zfft_core.h"
 
 namespace ml {
 
@@ -826,6 +827,9 @@ struct Shard {
     int block = 0, n_ranks = 1, rank = 0;   // kind 2
 };
 
+// layout of stage 1's result G for stage 2: row-major G[f][n1][b], transposed G[f][b][n1], or tiled G[f][b / 8][n1][b % 8]
+enum class GLayout { row_major, transposed, tiled };
+
 static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     ML_REQUIRE(ctx, "ctx is NULL");
     const int row0 = sh.row0, mirrored = sh.kind == 1;
@@ -907,6 +911,18 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     // 72 0.206, 4 0.190, 8 0.194-0.196, 40 0.196, 136 0.192: anything but a multiple of 256 bytes)
     static const int g_skew = diag_int("ML_G_SKEW", 8);   // (diagnostic builds: the pitch's skew in elements)
     const int64_t g_ld = nxl + g_skew;
+    // Where both transforms take the one-level kernels, the transposed G is stored TILED instead: G[f][b / 8][n1][b % 8],
+    // the 8 bins of a 128-byte line side by side, tiles 8 g_ld elements long (zfft_core.h tile_off) - the same bytes.
+    // Stage 1 then stores whole lines (8 lanes = one line, a 64-lane store 8 lines in 8 tiles, 8 x 65 KB apart, instead
+    // of 64 16-byte pieces one pitch apart), and stage 2 (zfft.hip zfft_tiles_kernel) reads whole lines once, the 8
+    // columns of a tile together.  (Measured at 4096^2 -> 512^2: DESIGN.md 4.2.)
+    static const bool tiles_off = diag_int("ML_G_TILED", 1) == 0;   // (diagnostic builds: the plain transposed G)
+    const int r3y = pl.fft_y.N_eff / 256;
+    const GLayout g_layout = !g_transposed ? GLayout::row_major
+                             : (!tiles_off && my % 8 == 0 && mx <= zf::TL_NT && r3y >= 3 && r3y <= 16 &&
+                                pl.fft_y.passes <= 1 && pl.fft_x.passes <= 1)
+                                 ? GLayout::tiled
+                                 : GLayout::transposed;
     // The TRANSPOSED result of rows up to 8192 samples lies in physical pieces of 4 MB, each an allocation of its own,
     // mapped side by side (common.h PieceBuf).  Stage 1 stores it in 16-byte pieces one pitch (65 KB at 4096 samples)
     // apart, and how fast those go is decided by the physical layout behind the buffer: 0.33 ms over one physically
@@ -1018,12 +1034,19 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         c.out_s1 = (int64_t)nxl * my;
         c.out_s2 = my;
         c.out_es = 1;
-        if (g_transposed) {   // row (f, n1), bin b -> G[f][b][n1]
+        if (g_layout == GLayout::transposed) {   // row (f, n1), bin b -> G[f][b][n1]
             c.out = g_buf + (size_t)trim_lo * 2;
             c.out_rb = nxt;
             c.out_s1 = (int64_t)my * g_ld;
             c.out_s2 = 1;
             c.out_es = g_ld;
+        } else if (g_layout == GLayout::tiled) {   // row (f, n1), bin b -> G[f][b / 8][n1][b % 8]
+            c.out = g_buf + (size_t)trim_lo * 8 * 2;
+            c.out_rb = nxt;
+            c.out_s1 = (int64_t)my * g_ld;
+            c.out_s2 = 8;
+            c.out_es = 8 * g_ld;
+            c.tiled_out = 1;
         }
         c.tw1 = pl.fft_tw1.as<double>();
         c.wk = pl.fft_y.wk.as<double>();
@@ -1153,11 +1176,16 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         c.in_s1 = (int64_t)nxl * my;
         c.in_s2 = 1;
         c.in_es = my;
-        if (g_transposed) {
+        if (g_layout == GLayout::transposed) {
             c.in_s1 = (int64_t)my * g_ld;
             c.in_s2 = g_ld;
             c.in_es = 1;
             c.second = 1;
+        } else if (g_layout == GLayout::tiled) {   // tile (f, t) at f in_s1 + t in_s2, my / 8 tiles per plane
+            c.in_s1 = (int64_t)my * g_ld;
+            c.in_s2 = 8 * g_ld;
+            c.in_rb = my / 8;
+            c.in_es = 8;
         }
         if (mirrored) {
             c.a0 = row0;
@@ -1184,7 +1212,10 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         c.kbin = pl.fft_x.kbin.as<int>();
         for (int k = 0; k < 4; ++k) c.alpha[k] = alpha[k];
         c.alpha_rb = my;
-        for (int i = 0; i < split2; ++i) {
+        if (g_layout == GLayout::tiled) {
+            c.accumulate = accumulate;
+            ML_TRY(zfft_run_tiles(ctx->stream, c));
+        } else for (int i = 0; i < split2; ++i) {
             c.sub_s = split2;
             c.sub_i = i;
             c.pj = pl.fft_x.pj.as<double>() + (size_t)i * mx * 2;

@@ -24,6 +24,8 @@
 //   zfft_pass_kernel           the same row in two passes over groups of R3 / 2 residues, half the LDS:
 //                              8192-sample lattices (two workgroups per CU instead of one) and 16384-
 //                              sample lattices with <= 1024 wanted bins (one launch, rows read once)
+//   zfft_tiles_kernel          the column pass over a stage-1 result stored in tiles of 8 bins: one workgroup per
+//                              tile, whole lines read once, four residues at a time
 //   zfft_multi_kernel          256- and 512-sample transforms, four / two rows per 64-thread workgroup
 //   zfft_interleaved_kernel    the column pass of an interleaved multi-GPU row shard: the s short
 //                              transforms of a column in one workgroup, one store per bin
@@ -105,12 +107,20 @@ __device__ __forceinline__ void load_row(const FftArgs &a, const zf::Geo &g, int
     }
 }
 
+// element offset of output bin j in its row: out_es apart, or (PASS 4: rows of the aperture into a TILED G,
+// zfft_core.h tile_off) in tiles of 8 bins, out_es = the tile's stride
+template <int PASS>
+__device__ __forceinline__ int64_t out_off(const FftArgs &a, int j) {
+    return PASS == 4 ? zf::tile_off(j, a.out_es) : (int64_t)j * a.out_es;
+}
+
 // R3T > 0: residues known at compile time (the div / mod by R3 become shifts), R3T == 0: any R3.
 // The next row's loads are issued before the current row's arithmetic (its 16 values wait in a
 // second register set), so a workgroup always has a row in flight; the stage-1 twiddles live in
 // LDS ([k2][n1]: the lanes of a 16-lane group read neighbouring or equal slots) to pay for it.
-// PASS (1: rows of the aperture, 2: columns of stage 1's result) only names the instantiation, so
-// that a profile lists the two passes separately.
+// PASS (1: rows of the aperture, 2: columns of stage 1's result, 3: contiguous rows of a transposed one,
+// 4: rows of the aperture stored as tiles) names the instantiation, so that a profile lists the passes
+// separately; 4 also picks the tiled store (out_off).
 // IP: exchange 2 in place (zfft_core.h Geo::ip): one barrier fewer per row.
 // row of the idx-th turn of the workgroups on XCD `xcd` (-1: past the end).  (Visiting the four field
 // planes newest rows first - the tail of the synthesis might still be in the memory-side cache - measured
@@ -194,7 +204,7 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
             xa.y *= al;
             xb.x *= al;
             xb.y *= al;
-            cd *da = dst + bin0 * a.out_es, *db = dst + bin1 * a.out_es;
+            cd *da = dst + out_off<PASS>(a, bin0), *db = dst + out_off<PASS>(a, bin1);
             if (a.accumulate) {
                 xa = zf::cadd(xa, *da);
                 xb = zf::cadd(xb, *db);
@@ -206,7 +216,7 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
                 cd x = zf::cmul(IP ? zf::stage3_ip(g, k0, w0, lds) : zf::stage3(g, k0, w0, lds), p0);
                 x.x *= al;
                 x.y *= al;
-                cd *d = dst + bin0 * a.out_es;
+                cd *d = dst + out_off<PASS>(a, bin0);
                 if (a.accumulate) x = zf::cadd(x, *d);
                 *d = x;
             }
@@ -214,7 +224,7 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
                 cd x = zf::cmul(IP ? zf::stage3_ip(g, k1, w1, lds) : zf::stage3(g, k1, w1, lds), p1);
                 x.x *= al;
                 x.y *= al;
-                cd *d = dst + bin1 * a.out_es;
+                cd *d = dst + out_off<PASS>(a, bin1);
                 if (a.accumulate) x = zf::cadd(x, *d);
                 *d = x;
             }
@@ -224,7 +234,7 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
                 cd x = zf::cmul(IP ? zf::stage3_ip(g, a.kbin[o], w, lds) : zf::stage3(g, a.kbin[o], w, lds), p);
                 x.x *= al;
                 x.y *= al;
-                cd *d = dst + o * a.out_es;
+                cd *d = dst + out_off<PASS>(a, o);
                 if (a.accumulate) x = zf::cadd(x, *d);
                 *d = x;
             }
@@ -234,6 +244,104 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
         for (int n2 = 0; n2 < 16; ++n2) v[n2] = nx[n2];
         idx = idx_n;
         row = row_n;
+    }
+}
+
+// The column pass over a TILED stage-1 result (farfield.hip GLayout::tiled; zfft_core.h tl_*): one workgroup per
+// tile, i.e. the 8 neighbouring columns (f, 8 t .. 8 t + 7) whose samples n1 lie in whole 128-byte lines, one line
+// per n1.  TL_SLOTS residues n0 of the lattice at a time, highest first: slot s loads the rows n1 = n0 + R3 m
+// (m < 256, 8 lanes = one line) with non-temporal loads - G is read once and must not push the next synthesis'
+// geometry records out of the memory-side cache -, the 8 columns' 256-point DFTs run in LDS (phases A and B), and
+// the thread of each wanted bin Horner-adds B_n0[k mod 256] of the 8 columns into registers.  The next round's
+// samples are loaded while this round's phase B and Horner sums run.  Input: tile T = (f, t) starts at in + f in_s1 + t in_s2
+// (in_rb tiles per plane), sample q of column c at + 8 q + c, with the resident samples of load_row (a0 / h0,
+// a1 / h1: anything else reads as zero); output row (f, b) = 8 T + c as in zfft_kernel.
+__device__ __forceinline__ void load_tile(const FftArgs &a, const cd *src, int n0, int m1, cd *v) {
+#pragma unroll
+    for (int m2 = 0; m2 < 16; ++m2) {
+        const int n = n0 + a.g.R3 * (m1 + 16 * m2);   // sample of the axis (n0 < 0: a residue past the lattice)
+        int q = -1;
+        if (n0 >= 0 && n >= a.a0 && n < a.a0 + a.h0) q = n - a.a0;
+        if (n0 >= 0 && n >= a.a1 && n < a.a1 + a.h1) q = a.h0 + n - a.a1;
+        if (q >= 0) {
+            typedef double double2v __attribute__((ext_vector_type(2)));
+            const double2v t = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(src + 8 * (int64_t)q));
+            v[m2] = zf::mk(t.x, t.y);
+        } else {
+            v[m2] = zf::mk(0.0, 0.0);
+        }
+    }
+}
+
+__global__ __launch_bounds__(zf::TL_NT, 1) void zfft_tiles_kernel(const FftArgs a) {
+    extern __shared__ __align__(16) unsigned char zfft_lds_raw[];
+    cd *lds = reinterpret_cast<cd *>(zfft_lds_raw);
+    constexpr int S = zf::TL_SLOTS;
+    const int R3 = a.g.R3, tid = threadIdx.x;
+    cd *s_tw = lds + S * zf::TL_SS;   // [16][16] behind the exchange buffers
+    for (int e = tid; e < 256; e += zf::TL_NT) s_tw[(e & 15) * 16 + (e >> 4)] = a.tw1[e];   // e = m1 * 16 + k2
+    const int m1 = zf::tl_sub(tid), col = zf::tl_col(tid), slot = zf::tl_slot(tid);
+    // this thread's wanted bin (the same for every tile; its phasor pj is read at the store)
+    const bool own = tid < a.g.M;
+    cd w = zf::mk(0.0, 0.0);
+    int k = 0;
+    if (own) {
+        w = a.wk[tid];
+        k = a.kbin[tid];
+    }
+    __syncthreads();
+    const int tiles = a.rows >> 3, rounds = (R3 + S - 1) / S;
+    for (int T = blockIdx.x; T < tiles; T += gridDim.x) {   // block-uniform
+        const cd *src = a.in + (T / a.in_rb) * a.in_s1 + (T % a.in_rb) * a.in_s2 + col;
+        cd acc[8], v[16];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[c] = zf::mk(0.0, 0.0);
+        load_tile(a, src, R3 - 1 - slot, m1, v);
+        for (int i = 0; i < rounds; ++i) {
+            {
+                // W^(4 a) and W^b of W = W_256^(m1) from LDS (no registers to spare for them across the loop)
+                cd ta[4], tb[4];
+                ta[0] = tb[0] = zf::mk(1.0, 0.0);
+#pragma unroll
+                for (int q = 1; q < 4; ++q) {
+                    ta[q] = s_tw[(4 * q) * 16 + m1];
+                    tb[q] = s_tw[q * 16 + m1];
+                }
+                zf::tl_phaseA(tid, v, ta, tb, lds);
+            }
+            // v is free once phase A has stored it: the next round's loads fly during phase B and the Horner sums
+            // (a second register set loaded a whole round ahead, as zfft_kernel does, spills at 512 threads)
+            if (i + 1 < rounds) load_tile(a, src, R3 - 1 - S * (i + 1) - slot, m1, v);
+            __syncthreads();
+            {
+                cd u[16];
+                zf::tl_phaseB(tid, u, lds);
+            }
+            __syncthreads();
+            if (own) {
+#pragma unroll 1   // (unrolled, the compiler hoists all 32 LDS reads and spills)
+                for (int s = 0; s < S; ++s) {
+                    if (R3 - 1 - S * i - s < 0) break;   // (R3 not a multiple of S: no such residue)
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) acc[c] = zf::cmac(acc[c], w, zf::tl_bin(s, c, k, lds));
+                }
+            }
+            __syncthreads();   // the next round's phase A overwrites the buffers
+        }
+        if (own) {
+            const cd p = a.pj[tid];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int row = 8 * T + c;
+                cd x = zf::cmul(acc[c], p);
+                const double al = a.alpha[row / a.alpha_rb];
+                x.x *= al;
+                x.y *= al;
+                cd *d = a.out + (row / a.out_rb) * a.out_s1 + (row % a.out_rb) * a.out_s2 + tid * a.out_es;
+                if (a.accumulate) x = zf::cadd(x, *d);
+                *d = x;
+            }
+        }
     }
 }
 
@@ -761,7 +869,7 @@ static int launch_one(hipStream_t stream, const FftArgs &a, int grid, size_t lds
     return ML_OK;
 }
 
-int zfft_run(hipStream_t stream, const ZfftCall &c) {
+static FftArgs args_of(const ZfftCall &c) {
     FftArgs a;
     a.g.R3 = c.N_eff / 256;
     a.g.n_valid = c.n_valid;
@@ -798,6 +906,33 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
     a.rows = c.rows;
     a.accumulate = c.accumulate;
     a.chunk = (c.rows + 7) / 8;
+    return a;
+}
+
+// the column pass over a tiled stage-1 result (zfft_tiles_kernel): c.in = tile 0 of plane 0, c.in_s1 / c.in_s2 the
+// strides of planes / tiles (c.in_rb tiles per plane), sample q of a column 8 q elements on
+int zfft_run_tiles(hipStream_t stream, const ZfftCall &c) {
+    ML_REQUIRE(c.N_eff % 256 == 0 && c.M <= zf::TL_NT && c.rows % 8 == 0 && (c.sub_s <= 1) && c.in_es == 8,
+               "tiled column pass: %d samples, %d bins, %d rows", c.N_eff, c.M, c.rows);
+    const FftArgs a = args_of(c);
+    const size_t bytes = ((size_t)zf::TL_SLOTS * zf::TL_SS + 256) * sizeof(cd);
+    static bool attr_done = false;
+    if (!attr_done) {
+        ML_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(zfft_tiles_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_done = true;
+    }
+    const int tiles = c.rows / 8, grid = std::min(tiles, 256);   // (one 149 KB workgroup per CU)
+    hipLaunchKernelGGL(zfft_tiles_kernel, dim3(grid), dim3(zf::TL_NT), bytes, stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+int zfft_run(hipStream_t stream, const ZfftCall &c) {
+    FftArgs a = args_of(c);
+    // a tiled result (PASS 4) is stored by the one-level kernel only
+    ML_REQUIRE(!c.tiled_out || (a.g.R3 >= 3 && a.g.R3 <= 16 && c.passes <= 1 && c.in_es == 1 && !c.second),
+               "tiled row pass: %d samples", c.N_eff);
     if (a.g.R3 <= 2) {
         // short transforms: 64 threads = 4 or 2 rows per workgroup (zfft_multi_kernel)
         const int cpw = 4 / a.g.R3;
@@ -859,12 +994,19 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
         lds_bytes = ((size_t)zf::lds_elems(a.g) + 256) * sizeof(cd);
     }
     // PASS (a template argument so that profiles can tell the launches apart): 1 rows of the aperture,
-    // 2 strided columns of a row-major stage-1 result, 3 contiguous rows of a transposed one
+    // 2 strided columns of a row-major stage-1 result, 3 contiguous rows of a transposed one, 4 rows of the
+    // aperture into a tiled one
     if (c.in_es == 1 && c.second) switch (a.g.R3) {
             case 8: return launch_one<8, 128, 2, 3>(stream, a, grid, lds_bytes);
             case 16: return launch_one<16, 256, 2, 3>(stream, a, grid, lds_bytes);
             case 32: return launch_one<32, 512, 2, 3>(stream, a, grid, lds_bytes);
             default: break;
+        }
+    if (c.tiled_out) switch (a.g.R3) {   // pass 1 into a tiled G (out_es: the tile's stride)
+            case 4: return launch_one<4, 64, 2, 4>(stream, a, grid, lds_bytes);
+            case 8: return launch_one<8, 128, 2, 4>(stream, a, grid, lds_bytes);
+            case 16: return launch_one<16, 256, 2, 4>(stream, a, grid, lds_bytes);
+            default: return launch_one<0, 512, 1, 4>(stream, a, grid, lds_bytes);
         }
     if (c.in_es == 1) switch (a.g.R3) {   // pass 1: contiguous rows
             case 4: return launch_one<4, 64, 2, 1>(stream, a, grid, lds_bytes);

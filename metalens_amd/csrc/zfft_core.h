@@ -245,6 +245,51 @@ ZF_HD void stage3_pair(const Geo &g, int k, cd wa, cd wb, const cd *lds, cd &xa,
     }
 }
 
+// ---- the column pass over a TILED stage-1 result (zfft.hip zfft_tiles_kernel) ---------------------
+// Tiled G: bin j of row n1 sits at (j / 8) * tile + n1 * 8 + j % 8 (tile = 8 x the pitch along n1), so a
+// 128-byte line holds 8 consecutive bins of one row and 8 consecutive lanes of the row pass store a whole line.
+ZF_HD long long tile_off(int j, long long tile) { return (long long)(j >> 3) * tile + (j & 7); }
+// One workgroup of TL_NT threads transforms the 8 columns of one tile, TL_SLOTS residues n0 of the N = 256 R3
+// lattice at a time: slot s holds the sub-sequence n = n0 + R3 m, m = m1 + 16 m2 < 256, of all 8 columns, whose
+// 256-point DFT B_n0[k mod 256] is what Horner sums over n0 (X[k] = sum_n0 (W_N^k)^n0 B_n0[k mod 256]).
+//   phase A  thread (s, m1, c): DFT16 over m2 of its 16 loaded samples, times W_256^(m1 k2)  -> LDS (s, c, k2, m1)
+//   phase B  thread (s, k2, c): DFT16 over m1, result IN PLACE                              -> LDS (s, c, k2, k1)
+//   Horner   thread = bin: 8 columns x TL_SLOTS residues
+// Strides from the LDS conflict model below (tools/zfft_tiles_emul.cpp reports the cycles).
+constexpr int TL_NT = 512, TL_SLOTS = 4, TL_KS = 18, TL_CS = 289, TL_SS = 8 * TL_CS;
+ZF_HD int tl_addr(int s, int c, int k2, int m1) { return s * TL_SS + c * TL_CS + k2 * TL_KS + m1; }
+ZF_HD int tl_slot(int tid) { return tid >> 7; }
+ZF_HD int tl_col(int tid) { return tid & 7; }
+ZF_HD int tl_sub(int tid) { return (tid >> 3) & 15; }   // m1 in phase A, k2 in phase B
+// phase A; ta / tb: W^(4 a) and W^b of the thread's W = W_256^(m1) (stage1_regs)
+ZF_HD void tl_phaseA(int tid, cd *v, const cd *ta, const cd *tb, cd *lds) {
+    const int s = tl_slot(tid), c = tl_col(tid), m1 = tl_sub(tid);
+    dft16(v);
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        const int hi = k2 >> 2, lo = k2 & 3;
+        cd a = v[bin16(k2)];
+        if (hi && lo)
+            a = cmul(a, cmul(ta[hi], tb[lo]));
+        else if (hi)
+            a = cmul(a, ta[hi]);
+        else if (lo)
+            a = cmul(a, tb[lo]);
+        lds[tl_addr(s, c, k2, m1)] = a;
+    }
+}
+// phase B: a thread overwrites only the sixteen slots it has just read (no barrier in between)
+ZF_HD void tl_phaseB(int tid, cd *v, cd *lds) {
+    const int s = tl_slot(tid), c = tl_col(tid), k2 = tl_sub(tid);
+#pragma unroll
+    for (int m1 = 0; m1 < 16; ++m1) v[m1] = lds[tl_addr(s, c, k2, m1)];
+    dft16(v);
+#pragma unroll
+    for (int k1 = 0; k1 < 16; ++k1) lds[tl_addr(s, c, k2, k1)] = v[bin16(k1)];
+}
+// B_n0[k mod 256] of slot s, column c
+ZF_HD cd tl_bin(int s, int c, int k, const cd *lds) { return lds[tl_addr(s, c, k & 15, (k >> 4) & 15)]; }
+
 }  // namespace zf
 
 // ---- host side: LDS bank-conflict model and the choice of the two paddings ---------------------
@@ -354,6 +399,37 @@ inline void choose_pads(Geo &g) {
     }
     g.pad1 = b1;
     g.pad2 = b2;
+}
+
+// LDS cycles of the tile column pass for one round (TL_SLOTS residues) of one workgroup, and the conflict-free
+// count: phase A writes, phase B reads and in-place writes, and the Horner reads of bins j0 .. j0 + M
+struct TileCost {
+    long a_write = 0, b_read = 0, b_write = 0, horner = 0, ideal = 0;
+};
+inline TileCost tile_cost(int M, int j0) {
+    TileCost c;
+    int addr[64];
+    for (int w0 = 0; w0 < TL_NT; w0 += 64) {
+        for (int q = 0; q < 16; ++q) {
+            for (int l = 0; l < 64; ++l) addr[l] = tl_addr(tl_slot(w0 + l), tl_col(w0 + l), q, tl_sub(w0 + l));
+            c.a_write += lds_cycles(addr, false);
+            for (int l = 0; l < 64; ++l) addr[l] = tl_addr(tl_slot(w0 + l), tl_col(w0 + l), tl_sub(w0 + l), q);
+            c.b_read += lds_cycles(addr, true);
+            c.b_write += lds_cycles(addr, false);
+            c.ideal += 8 + 4 + 8;
+        }
+    }
+    for (int o0 = 0; o0 < M; o0 += 64)
+        for (int s = 0; s < TL_SLOTS; ++s)
+            for (int col = 0; col < 8; ++col) {
+                for (int l = 0; l < 64; ++l) {
+                    const int k = ((o0 + l + j0) % 256 + 256) % 256;
+                    addr[l] = o0 + l < M ? tl_addr(s, col, k & 15, k >> 4) : -1;
+                }
+                c.horner += lds_cycles(addr, true);
+                c.ideal += 4;
+            }
+    return c;
 }
 
 }  // namespace zf
