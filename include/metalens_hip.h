@@ -210,7 +210,8 @@ int ml_farfield_plan_info(ml_ctx *ctx, int *stage1_kernel);
  * the reference's default grids are 2^a 3^b 5^c long, nearfield.py:30-36 - 400, 1920, 2000 ... -
  * and run on the 256 / gcd(N, 256) times finer lattice, the aperture zero-padded, of which every
  * such bin is wanted; lattices of up to 16 x 8192 samples, in interleaved sub-sequences beyond
- * 8192; the GEMMs take over where the odd part of N has no divisor that brings it to <= 32).    */
+ * 8192; the GEMMs take over where the odd part of N has no divisor that brings it to <= 32),
+ * 3 output-pruned FFT on a mixed-radix lattice (ML_METHOD_FFT_MIXED).                            */
 int ml_farfield_plan_kernels(ml_ctx *ctx, int *stage1_kernel, int *stage2_kernel);
 /* How ml_farfield_plan chooses: ML_METHOD_AUTO (default) takes the FFT on every axis whose grid
  * sits on a lattice that is a multiple of 64 samples long (padded at most 4-fold) and the GEMMs
@@ -226,6 +227,14 @@ int ml_farfield_plan_kernels(ml_ctx *ctx, int *stage1_kernel, int *stage2_kernel
  * whatever the aperture's size (AUTO does so from 96 MiB of geometry records + stage-1 result on:
  * DESIGN.md 4.2)                                                                                  */
 #define ML_METHOD_FFT_STREAMED 2
+/* ML_METHOD_FFT_MIXED: as ML_METHOD_FFT_STREAMED, except that an axis whose lattice of N samples is NOT
+ * a multiple of 256 long runs on that lattice itself, or the twice finer one, factored N s = A x B x R
+ * with two legs A, B from {9, 10, 12, 15, 16}, s <= 2 and R <= 32 residues (plan kernel 3), instead of on
+ * the 256 / gcd(N, 256) times finer one: the method for the reference's default grids (the smallest
+ * 2^a 3^b 5^c at or above a goal, nearfield.py:30-36: 400, 1000, 1440, 2000, 3000, 3600 ...).  A lattice
+ * with no such factorisation (4374 = 2 3^7, 6561 = 3^8), one beyond 8192 samples, a multiple of 256 and
+ * any axis of a context with more than one rank take exactly what ML_METHOD_FFT_STREAMED takes.        */
+#define ML_METHOD_FFT_MIXED 3
 int ml_farfield_set_method(ml_ctx *ctx, int method);
 /* Arithmetic of the aperture -> direction GEMMs (BASELINE.json: "1e-12 (fp64) / 1e-4 (fp32)",
  * configs[4] "fp32 GEMM-cast MFMA path").  ML_PRECISION_F64 (default): fp64 matrix cores.

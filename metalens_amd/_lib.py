@@ -316,10 +316,12 @@ class Context:
         """'auto' (default): axes whose direction grid sits on the aperture's FFT lattice run as
         output-pruned FFTs, the others as GEMMs; 'gemm': GEMMs everywhere; 'fft-streamed': as
         'auto' with the stage-1 result transposed for a streaming stage 2 at every size (auto:
-        from 96 MiB of records + stage-1 result on).  Applies to the next plan."""
+        from 96 MiB of records + stage-1 result on); 'fft-mixed': as 'fft-streamed', with lattices that
+        are not a multiple of 256 long - the reference's default grids, 2^a 3^b 5^c samples - on their own
+        lattice through the mixed-radix kernels.  Applies to the next plan."""
         if method == self.method:
             return
-        check(self.lib.ml_farfield_set_method(self.handle, {'auto': 0, 'gemm': 1, 'fft-streamed': 2}[method]))
+        check(self.lib.ml_farfield_set_method(self.handle, {'auto': 0, 'gemm': 1, 'fft-streamed': 2, 'fft-mixed': 3}[method]))
         self.method = method
 
     def set_comm_reduce(self, allreduce):
@@ -331,10 +333,10 @@ class Context:
         self.comm_reduce = allreduce
 
     def plan_kernels(self):
-        """(stage 1, stage 2) of the active plan: 'gemm', 'folded' or 'fft'"""
+        """(stage 1, stage 2) of the active plan: 'gemm', 'folded', 'fft' or 'fft-mixed'"""
         s1, s2 = c_int(0), c_int(0)
         check(self.lib.ml_farfield_plan_kernels(self.handle, byref(s1), byref(s2)))
-        names = ('gemm', 'folded', 'fft')
+        names = ('gemm', 'folded', 'fft', 'fft-mixed')
         return names[s1.value], names[s2.value]
 
     def nearfield_kernels(self):

@@ -315,6 +315,11 @@ struct ZfftAxis {
     // (a quarter) of the LDS (zfft_pass_kernel); lattices of 8192 < N_eff <= 16384 samples with at
     // most 1024 wanted bins run this way instead of split in two
     int passes = 0;
+    // method 'fft-mixed' on a lattice that is not a multiple of 256 long: N_eff = A B R samples (the lattice itself
+    // or the twice finer one: jstep = 1 or 2) through zfft_mixed_kernel<A, B>; pad1 is its one padding and tw its
+    // [B][A] twiddle table (zfft_core.h mixed_choose).  A = 0: the 256 R3 scheme
+    int A = 0, B = 0, R = 0;
+    DevBuf tw;
     DevBuf wk, pj, kbin;   // per-bin Horner ratio, origin phasor, reduced bin (zfft.hip FftArgs)
 };
 
@@ -566,14 +571,20 @@ struct ZfftCall {
     int passes = 0;                  // > 1: the pass-split kernel (0: the library's default)
     int second = 0;                  // contiguous rows that are the SECOND stage (of a transposed stage-1 result)
     int tiled_out = 0;               // bins stored in tiles of 8 (zfft_core.h tile_off; out_es = the tile's stride)
+    int mixA = 0, mixB = 0;          // > 0: N_eff = mixA mixB R through zfft_mixed_kernel, tw1 = the axis' [B][A] table
 };
 // the column pass over a tiled stage-1 result (zfft.hip zfft_tiles_kernel)
 int zfft_run_tiles(hipStream_t stream, const ZfftCall &c);
 int zfft_split(int N_eff);   // sub-sequences a lattice of N_eff samples is transformed in (0: none)
+// (N_plain, if given: the lattice the grid sits on, 0 if none, and *j0 its first bin - also where the function
+// returns false because the 256 R3 scheme has no place for that lattice)
 bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
-                       long double tol, int *N_eff, int *j0, int *jstep);
+                       long double tol, int *N_eff, int *j0, int *jstep, int *N_plain = nullptr);
+// tw1: [B][A] W_AB^(n1 k2) - 16 x 16 for the 256 R3 scheme, the legs of a mixed-radix axis otherwise
 int zfft_build_tables(hipStream_t stream, double *tw1, double *wk, double *pj, int *kbin, int M,
-                      int j0, int N_eff, int c, int jstep = 1);
+                      int j0, int N_eff, int c, int jstep = 1, int A = 16, int B = 16);
+// the padding of a mixed-radix axis' exchange layout with the fewest LDS conflict cycles
+int zfft_choose_pad_mixed(int A, int B, int R, int M, int j0, int jstep);
 void zfft_choose_pads(int N_eff, int M, int j0, int *pad1, int *pad2, int jstep = 1);
 // the column pass of an interleaved shard: s short transforms per column in one workgroup; c.pj holds
 // [s][M] phasors, sub-sequence i starts sub_off elements behind sub-sequence i - 1

@@ -495,8 +495,40 @@ static int plan_fft_axis(ml_ctx *ctx, ZfftAxis &ax, int n, double step, const do
     const long double kappa = (long double)pl.n_glass / (long double)pl.wavelength;
     const long double p_max = 0.5L * (n + 1) * fabsl((long double)step);
     int N_eff = 0, j0 = 0, jstep = 1;
-    if (!zfft_commensurate(n, step, kappa, u, m, symmetry_tolerance(kappa, p_max, u, m), &N_eff, &j0, &jstep))
-        return ML_OK;
+    int N_plain = 0;
+    const bool fits256 = zfft_commensurate(n, step, kappa, u, m, symmetry_tolerance(kappa, p_max, u, m), &N_eff, &j0,
+                                           &jstep, &N_plain);
+    ax.A = ax.B = ax.R = 0;
+    // 'fft-mixed': a lattice that is not a multiple of 256 long runs unpadded or padded 2-fold as A x B x R samples
+    // where the factor chooser finds legs for it (zfft_core.h mixed_choose; up to 8192 samples, one rank) - 729 =
+    // 9 x 9 x 9 too, which the 256 R3 scheme has no place for; where it finds none, what follows is what
+    // 'fft-streamed' does
+    if (pl.method == ML_METHOD_FFT_MIXED && N_plain > 0 && N_plain % 256 != 0 && ctx->n_ranks == 1) {
+        const int N = N_plain;
+        const zf::MixChoice ch = zf::mixed_choose(N, m);
+        if (ch.s) {
+            ML_TRY(ax.tw.reserve((size_t)ch.A * ch.B * 2 * sizeof(double)));
+            ML_TRY(ax.wk.reserve((size_t)m * 2 * sizeof(double)));
+            ML_TRY(ax.pj.reserve((size_t)m * 2 * sizeof(double)));
+            ML_TRY(ax.kbin.reserve((size_t)m * sizeof(int)));
+            ProfScope scope(ctx, ML_K_TWIDDLE);
+            ML_TRY(zfft_build_tables(ctx->stream, ax.tw.as<double>(), ax.wk.as<double>(), ax.pj.as<double>(),
+                                     ax.kbin.as<int>(), m, j0, N * ch.s, n - n / 2, ch.s, ch.A, ch.B));
+            ax.pad1 = zfft_choose_pad_mixed(ch.A, ch.B, ch.R, m, j0, ch.s);
+            ax.pad2 = 0;
+            ax.A = ch.A;
+            ax.B = ch.B;
+            ax.R = ch.R;
+            ax.split = 1;
+            ax.passes = 0;
+            ax.N_eff = N * ch.s;
+            ax.j0 = j0;
+            ax.jstep = ch.s;
+            ax.ok = true;
+            return ML_OK;
+        }
+    }
+    if (!fits256) return ML_OK;
     // A lattice that is not a multiple of 256 long runs jstep-fold padded, at jstep times the arithmetic and (beyond
     // 8192 padded samples) as many passes over the rows.  Measured against the folded GEMMs on square apertures
     // (tools/padded_fft_sweep.py, profiles/r06_padded_fft_sweep.txt; M = 64, 256, N directions): jstep 2 (1920, 3200
@@ -805,7 +837,7 @@ static int interleave_stuff(int n_sub) {
 }
 
 static int interleave_block(const FarfieldPlan &pl, int n_ranks) {
-    if (!pl.ready || pl.pair_list || !pl.fft_x.ok || n_ranks < 2) return 0;
+    if (!pl.ready || pl.pair_list || !pl.fft_x.ok || pl.fft_x.A || n_ranks < 2) return 0;
     // N = the x axis' lattice (longer than the aperture when the direction grid is finer than the
     // aperture's own: the rows beyond nx_total are zeros nobody holds); the rows that exist must
     // deal out evenly
@@ -905,7 +937,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     // transposed one is 1-1.5 % ahead: 0.282 against 0.287 ms, 3072^2 0.368 / 0.372, 3584^2 0.458 / 0.463).
     const bool g_transposed = ML_STAGE1_TRANSPOSED && pl.fft_y.ok && pl.fft_x.ok && !pl.pair_list &&
                               pl.fft_y.split == 1 && pl.fft_x.split == 1 && sh.kind != 2 &&
-                              (pl.method == ML_METHOD_FFT_STREAMED ||
+                              (pl.method == ML_METHOD_FFT_STREAMED || pl.method == ML_METHOD_FFT_MIXED ||
                                (size_t)nxl * ny * 8 + (size_t)4 * nxl * my * 16 > (size_t)96 << 20);
     // (skew sweep at 4096^2 -> 512^2, stage 1: 0 elements 0.220 ms, 16 0.222, 1 0.204, 2 0.212, 24 0.208,
     // 72 0.206, 4 0.190, 8 0.194-0.196, 40 0.196, 136 0.192: anything but a multiple of 256 bytes)
@@ -920,7 +952,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     const int r3y = pl.fft_y.N_eff / 256;
     const GLayout g_layout = !g_transposed ? GLayout::row_major
                              : (!tiles_off && my % 8 == 0 && mx <= zf::TL_NT && r3y >= 3 && r3y <= 16 &&
-                                pl.fft_y.passes <= 1 && pl.fft_x.passes <= 1)
+                                pl.fft_y.passes <= 1 && pl.fft_x.passes <= 1 && !pl.fft_y.A && !pl.fft_x.A)
                                  ? GLayout::tiled
                                  : GLayout::transposed;
     // The TRANSPOSED result of rows up to 8192 samples lies in physical pieces of 4 MB, each an allocation of its own,
@@ -1048,7 +1080,9 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
             c.out_es = 8 * g_ld;
             c.tiled_out = 1;
         }
-        c.tw1 = pl.fft_tw1.as<double>();
+        c.tw1 = pl.fft_y.A ? pl.fft_y.tw.as<double>() : pl.fft_tw1.as<double>();
+        c.mixA = pl.fft_y.A;
+        c.mixB = pl.fft_y.B;
         c.wk = pl.fft_y.wk.as<double>();
         c.pj = pl.fft_y.pj.as<double>();
         c.kbin = pl.fft_y.kbin.as<int>();
@@ -1206,7 +1240,9 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         c.out_s1 = -(int64_t)mx * my;
         c.out_s2 = 1;
         c.out_es = my;
-        c.tw1 = pl.fft_tw1.as<double>();
+        c.tw1 = pl.fft_x.A ? pl.fft_x.tw.as<double>() : pl.fft_tw1.as<double>();
+        c.mixA = pl.fft_x.A;
+        c.mixB = pl.fft_x.B;
         c.wk = pl.fft_x.wk.as<double>();
         c.pj = pl.fft_x.pj.as<double>();
         c.kbin = pl.fft_x.kbin.as<int>();
@@ -1654,13 +1690,15 @@ int ml_farfield_plan_kernels(ml_ctx *ctx, int *stage1_kernel, int *stage2_kernel
     ML_REQUIRE(ctx && stage1_kernel && stage2_kernel, "NULL argument");
     ML_TRY(ml_farfield_plan_info(ctx, stage1_kernel));
     const FarfieldPlan &pl = ctx->plan;
-    *stage2_kernel = (pl.fft_x.ok && !pl.pair_list) ? 2 : pl.fold2 ? 1 : 0;
+    if (pl.fft_y.ok && pl.fft_y.A) *stage1_kernel = 3;
+    *stage2_kernel = (pl.fft_x.ok && !pl.pair_list) ? (pl.fft_x.A ? 3 : 2) : pl.fold2 ? 1 : 0;
     return ML_OK;
 }
 
 int ml_farfield_set_method(ml_ctx *ctx, int method) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    ML_REQUIRE(method == ML_METHOD_AUTO || method == ML_METHOD_GEMM || method == ML_METHOD_FFT_STREAMED,
+    ML_REQUIRE(method == ML_METHOD_AUTO || method == ML_METHOD_GEMM || method == ML_METHOD_FFT_STREAMED ||
+                   method == ML_METHOD_FFT_MIXED,
                "unknown method %d", method);
     ctx->ff_method = method;
     return ML_OK;

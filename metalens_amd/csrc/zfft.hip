@@ -26,6 +26,8 @@
 //                              sample lattices with <= 1024 wanted bins (one launch, rows read once)
 //   zfft_tiles_kernel          the column pass over a stage-1 result stored in tiles of 8 bins: one workgroup per
 //                              tile, whole lines read once, four residues at a time
+//   zfft_mixed_kernel<A, B>    lattices of A x B x R samples (2^a 3^b 5^c: the reference's default grids) under the
+//                              method 'fft-mixed': two legs from {9, 10, 12, 15, 16} and R <= 32 residues
 //   zfft_multi_kernel          256- and 512-sample transforms, four / two rows per 64-thread workgroup
 //   zfft_interleaved_kernel    the column pass of an interleaved multi-GPU row shard: the s short
 //                              transforms of a column in one workgroup, one store per bin
@@ -245,6 +247,89 @@ __global__ __launch_bounds__(NTMAX, MINW) void zfft_kernel(const FftArgs a) {
         idx = idx_n;
         row = row_n;
     }
+}
+
+// Mixed-radix lattices (zfft_core.h mx_*): N_eff = A x B x R with compile-time legs and R = a.g.R3 residues at run
+// time, for the reference's default grids (2^a 3^b 5^c samples: 400, 1000, 1440, 2000, 3000, 3600 ...) on their own
+// lattice or the twice finer one instead of the 256 / gcd(N, 256) times finer one of zfft_kernel.  max(A, B) R
+// threads: the first B R hold A samples each in stage 1, the first A R gather B values each in stage 2, whose result
+// goes back IN PLACE; the last stage is the same Horner sum over the wanted bins.  Rows, residency (a0 / h0, a1 / h1),
+// row_first, strides, alpha and accumulate as in zfft_kernel, and the same register prefetch of the next row.
+// a.tw1: this axis' [B][A] table of W_AB^(n1 k2).  STREAM: contiguous rows read once (load_row).
+template <int A, bool STREAM>
+__device__ __forceinline__ void load_row_mixed(const FftArgs &a, const zf::Geo &g, int row, int tid, int stride, cd *v) {
+    const cd *src = a.in + (row / a.in_rb) * a.in_s1 + (row % a.in_rb) * a.in_s2;
+    const int first = a.row_first ? a.row_first[row % a.rf_mod] : 0;
+#pragma unroll
+    for (int n2 = 0; n2 < A; ++n2) {
+        const int n = tid + stride * n2;   // sample of the axis
+        int q = -1;
+        if (n >= a.a0 && n < a.a0 + a.h0) q = n - a.a0;
+        if (n >= a.a1 && n < a.a1 + a.h1) q = a.h0 + n - a.a1;
+        if (min(n, g.n_valid - 1 - n) < first) q = -1;
+        if (STREAM && q >= 0) {
+            typedef double double2v __attribute__((ext_vector_type(2)));
+            const double2v t = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(src + q * a.in_es));
+            v[n2] = zf::mk(t.x, t.y);
+        } else {
+            v[n2] = q >= 0 ? src[q * a.in_es] : zf::mk(0.0, 0.0);
+        }
+    }
+}
+
+template <int A, int B, bool STREAM>
+__global__ __launch_bounds__(512) void zfft_mixed_kernel(const FftArgs a) {
+    extern __shared__ __align__(16) unsigned char zfft_lds_raw[];
+    cd *lds = reinterpret_cast<cd *>(zfft_lds_raw);
+    const zf::Geo g = a.g;
+    constexpr int LMAX = A > B ? A : B;
+    const int R = g.R3, NT = LMAX * R, tid = threadIdx.x;
+    cd *s_tw = lds + zf::mx_lds_elems<A, B>(g);   // [k2][n1] behind the exchange buffer
+    for (int e = tid; e < A * B; e += NT) s_tw[(e % A) * B + e / A] = a.tw1[e];   // e = n1 * A + k2
+    const bool act1 = tid < B * R, act2 = tid < A * R;
+    __syncthreads();
+    const int xcd = blockIdx.x & 7, step = gridDim.x >> 3;
+    int idx = blockIdx.x >> 3;
+    int row = row_of_turn(a, xcd, idx);   // block-uniform
+    cd v[LMAX], nx[A];
+    if (row >= 0 && act1) load_row_mixed<A, STREAM>(a, g, row, tid, B * R, v);
+    while (row >= 0) {
+        const int idx_n = idx + step, row_n = row_of_turn(a, xcd, idx_n);
+        if (row_n >= 0 && act1) load_row_mixed<A, STREAM>(a, g, row_n, tid, B * R, nx);
+        if (act1) zf::mx_stage1<A, B>(g, tid, v, s_tw, lds);
+        __syncthreads();
+        if (act2) zf::mx_stage2<A, B>(g, tid, v, lds);   // (a thread overwrites only the slots it has just read)
+        __syncthreads();
+        cd *dst = a.out + (row / a.out_rb) * a.out_s1 + (row % a.out_rb) * a.out_s2;
+        const double al = a.alpha[row / a.alpha_rb];
+        for (int o = tid; o < g.M; o += NT) {
+            cd x = zf::cmul(zf::mx_stage3<A, B>(g, a.kbin[o], a.wk[o], lds), a.pj[o]);
+            x.x *= al;
+            x.y *= al;
+            cd *d = dst + (int64_t)o * a.out_es;
+            if (a.accumulate) x = zf::cadd(x, *d);
+            *d = x;
+        }
+        __syncthreads();   // the next row's stage 1 overwrites the buffer
+#pragma unroll
+        for (int n2 = 0; n2 < A; ++n2) v[n2] = nx[n2];
+        idx = idx_n;
+        row = row_n;
+    }
+}
+
+template <int A, int B, bool STREAM>
+static int launch_mixed(hipStream_t stream, const FftArgs &a, int threads, int grid, size_t lds_bytes) {
+    auto kern = zfft_mixed_kernel<A, B, STREAM>;
+    static bool attr_done = false;   // per instantiation
+    if (!attr_done) {
+        ML_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds_bytes, stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
 }
 
 // The column pass over a TILED stage-1 result (farfield.hip GLayout::tiled; zfft_core.h tl_*): one workgroup per
@@ -756,12 +841,12 @@ int zfft_build_interleave_tables(hipStream_t stream, double *wk, double *pj, int
 
 // tables of one axis: tw1 (shared by all axes), wk / pj / kbin per plan axis
 __global__ __launch_bounds__(256) void zfft_tables_kernel(cd *tw1, cd *wk, cd *pj, int *kbin, int M,
-                                                          int j0, int N, int c, int jstep) {
+                                                          int j0, int N, int c, int jstep, int A, int B) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < 256) {
-        const int n1 = e >> 4, k2 = e & 15;
+    if (e < A * B) {   // [B][A]: W_AB^(n1 k2)  (16 x 16 for the 256 R3 scheme)
+        const int n1 = e / A, k2 = e % A;
         double s, co;
-        sincospi(-2.0 * ((n1 * k2) & 255) / 256.0, &s, &co);
+        sincospi(-2.0 * ((n1 * k2) % (A * B)) / (double)(A * B), &s, &co);
         tw1[e] = zf::mk(co, s);
     }
     if (e < M) {
@@ -796,7 +881,8 @@ int zfft_split(int N_eff) {
 }
 
 bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
-                       long double tol, int *N_eff, int *j0, int *jstep) {
+                       long double tol, int *N_eff, int *j0, int *jstep, int *N_plain) {
+    if (N_plain) *N_plain = 0;
     if (M < 2 || n < 2) return false;
     const long double du = ((long double)u[M - 1] - (long double)u[0]) / (M - 1);
     const long double turns = kappa * fabsl((long double)step) * du;   // per (sample, bin)
@@ -806,6 +892,20 @@ bool zfft_commensurate(int n, double step, long double kappa, const double *u, i
     if (!(inv < 1e7L)) return false;
     const long N = lrintl(inv);                        // the lattice the directions sit on
     if (N < n || N < M) return false;
+    const long double du_exact = 1.0L / (kappa * fabsl((long double)step) * N);
+    const long jj = lrintl((long double)u[0] / du_exact);
+    // worst phase error over the grid at the outermost sample
+    const long double p_max = 0.5L * n * fabsl((long double)step) + fabsl((long double)step);
+    long double worst = 0;
+    for (int j = 0; j < M; ++j)
+        worst = fmaxl(worst, fabsl((long double)u[j] - (jj + j) * du_exact));
+    const bool on_lattice = !(2 * M_PIl * kappa * p_max * worst > tol);
+    // (N_plain: the lattice itself and its first bin, for the mixed-radix kernels - whether or not the 256 R3
+    // scheme below has a place for it)
+    if (on_lattice && N_plain && labs(jj) <= (1L << 29)) {
+        *N_plain = (int)N;
+        *j0 = (int)jj;
+    }
     // The kernels transform 256 R3 samples.  A lattice that is not a multiple of 256 long - the
     // reference's default grids are the smallest 2^a 3^b 5^c above a goal (nearfield.py:30-36: 400, 1920,
     // 2000 ...) - runs on the s-times finer lattice of N s samples, s = 256 / gcd(N, 256), the aperture
@@ -822,15 +922,8 @@ bool zfft_commensurate(int n, double step, long double kappa, const double *u, i
     // one workgroup holds 8192 samples in LDS (257 * R3 * 16 bytes, R3 <= 32); longer lattices are
     // split into up to 16 interleaved sub-sequences, one launch each (zfft_split)
     if (R3 < 1 || zfft_split((int)Ne) == 0) return false;
-    const long double du_exact = 1.0L / (kappa * fabsl((long double)step) * N);
-    const long jj = lrintl((long double)u[0] / du_exact);
     if (labs(jj) > (1L << 30) / s) return false;
-    // worst phase error over the grid at the outermost sample
-    const long double p_max = 0.5L * n * fabsl((long double)step) + fabsl((long double)step);
-    long double worst = 0;
-    for (int j = 0; j < M; ++j)
-        worst = fmaxl(worst, fabsl((long double)u[j] - (jj + j) * du_exact));
-    if (2 * M_PIl * kappa * p_max * worst > tol) return false;
+    if (!on_lattice) return false;
     *N_eff = (int)Ne;
     *j0 = (int)jj;
     *jstep = (int)s;
@@ -838,11 +931,11 @@ bool zfft_commensurate(int n, double step, long double kappa, const double *u, i
 }
 
 int zfft_build_tables(hipStream_t stream, double *tw1, double *wk, double *pj, int *kbin, int M, int j0,
-                      int N_eff, int c, int jstep) {
+                      int N_eff, int c, int jstep, int A, int B) {
     const int n = M > 256 ? M : 256;
     hipLaunchKernelGGL(zfft_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, stream,
                        reinterpret_cast<cd *>(tw1), reinterpret_cast<cd *>(wk),
-                       reinterpret_cast<cd *>(pj), kbin, M, j0, N_eff, c, jstep);
+                       reinterpret_cast<cd *>(pj), kbin, M, j0, N_eff, c, jstep, A, B);
     ML_HIP(hipGetLastError());
     return ML_OK;
 }
@@ -928,7 +1021,34 @@ int zfft_run_tiles(hipStream_t stream, const ZfftCall &c) {
     return ML_OK;
 }
 
+// one axis on a mixed-radix lattice (zfft_mixed_kernel): c.N_eff = c.mixA c.mixB R, c.tw1 the axis' own table
+static int zfft_run_mixed(hipStream_t stream, const ZfftCall &c) {
+    FftArgs a = args_of(c);
+    const int A = c.mixA, B = c.mixB, R = c.N_eff / (A * B), threads = std::max(A, B) * R;
+    ML_REQUIRE(A * B * R == c.N_eff && R >= 1 && R <= 32 && threads <= 512 && c.sub_s <= 1 && !c.tiled_out &&
+                   c.passes <= 1 && c.pad1 >= 0 && c.pad1 <= 16,
+               "mixed-radix transform: %d samples as %d x %d x %d", c.N_eff, A, B, R);
+    a.g.R3 = R;
+    a.g.pad2 = 0;
+    const size_t lds_bytes = ((size_t)(B * R + c.pad1) * A + A * B) * sizeof(cd);   // exchange buffer + twiddles
+    ML_REQUIRE(lds_bytes <= 160 * 1024, "mixed-radix transform: %d samples do not fit one workgroup", c.N_eff);
+    // workgroups resident per CU: LDS, and 2048 threads at up to 256 registers each = 1024
+    const int per_cu = (int)std::min<size_t>({(size_t)8, std::max<size_t>(1, (160 * 1024) / lds_bytes),
+                                              (size_t)std::max(1, 1024 / ((threads + 63) / 64 * 64))});
+    int grid = std::min(256 * per_cu, a.chunk * 8);
+    grid = (grid + 7) / 8 * 8;
+#define ML_MIXED(AA, BB)                                                                            \
+    if (A == AA && B == BB)                                                                         \
+        return c.in_es == 1 ? launch_mixed<AA, BB, true>(stream, a, threads, grid, lds_bytes)       \
+                            : launch_mixed<AA, BB, false>(stream, a, threads, grid, lds_bytes);
+    ZF_MX_PAIRS(ML_MIXED)
+#undef ML_MIXED
+    set_error("mixed-radix transform: no kernel for legs %d x %d", A, B);
+    return ML_EINVAL;
+}
+
 int zfft_run(hipStream_t stream, const ZfftCall &c) {
+    if (c.mixA) return zfft_run_mixed(stream, c);
     FftArgs a = args_of(c);
     // a tiled result (PASS 4) is stored by the one-level kernel only
     ML_REQUIRE(!c.tiled_out || (a.g.R3 >= 3 && a.g.R3 <= 16 && c.passes <= 1 && c.in_es == 1 && !c.second),
@@ -1022,6 +1142,22 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
         case 32: return launch_one<32, 512, 2, 2>(stream, a, grid, lds_bytes);
         default: return launch_one<0, 512, 1, 2>(stream, a, grid, lds_bytes);
     }
+}
+
+int zfft_choose_pad_mixed(int A, int B, int R, int M, int j0, int jstep) {
+    static std::map<std::tuple<int, int, int, int, int, int>, int> memo;
+    const auto key = std::make_tuple(A, B, R, M, j0, jstep);
+    auto hit = memo.find(key);
+    if (hit == memo.end()) {
+        zf::Geo g{R, A * B * R, M, j0, 0, 0, 0, jstep};
+#define ML_MIXED(AA, BB) \
+    if (A == AA && B == BB) zf::mixed_choose_pad<AA, BB>(g);
+        ZF_MX_PAIRS(ML_MIXED)
+#undef ML_MIXED
+        if (memo.size() > 4096) memo.clear();
+        hit = memo.emplace(key, g.pad1).first;
+    }
+    return hit->second;
 }
 
 void zfft_choose_pads(int N_eff, int M, int j0, int *pad1, int *pad2, int jstep) {

@@ -290,6 +290,217 @@ ZF_HD void tl_phaseB(int tid, cd *v, cd *lds) {
 // B_n0[k mod 256] of slot s, column c
 ZF_HD cd tl_bin(int s, int c, int k, const cd *lds) { return lds[tl_addr(s, c, k & 15, (k >> 4) & 15)]; }
 
+
+// ---- mixed-radix lattices: N = A x B x R (zfft.hip zfft_mixed_kernel) ------------------------------
+// The reference's default grids are the smallest 2^a 3^b 5^c at or above a goal (nearfield.py:30-36): 400, 1000,
+// 1440, 2000, 3000, 3600 ... samples, which the 16 x 16 x R3 scheme above only reaches on a 16- or 32-fold padded
+// lattice.  The same three stages with two legs A, B from {9, 10, 12, 15, 16} run on the lattice itself:
+//
+//     n = n0 + R n1 + B R n2      (n0 < R, n1 < B, n2 < A)
+//     k = k2 + A k1 + A B k0      (k2 < A, k1 < B, k0 < R)
+//     n k = B R n2 k2  +  R n1 k2 + A R n1 k1  +  n0 k      (mod N)
+//
+//   stage 1  (thread t = n0 + R n1 holds its A samples n2)   A-point DFT over n2, times W_AB^(n1 k2)
+//   stage 2  (thread u = n0 + R k2 gathers n1 = 0..B-1)      B-point DFT over n1, result IN PLACE (k1 takes n1's slot)
+//   stage 3  (wanted bins only)                              Horner over the R consecutive residues
+//
+// The legs are compile-time (template arguments), R is Geo::R3 at run time; max(A, B) R threads per workgroup, of
+// which B R work in stage 1 and A R in stage 2.  One exchange layout, one padding (Geo::pad1).
+
+// W_L^m = exp(-2 pi i m / L) for the odd legs, correctly rounded
+template <int L>
+ZF_HD cd wroot(int m) {
+    if constexpr (L == 9) {
+        constexpr double C[9] = {1.0, 0.766044443118978, 0.17364817766693036, -0.5, -0.9396926207859084,
+                                 -0.9396926207859084, -0.5, 0.17364817766693036, 0.766044443118978};
+        constexpr double S[9] = {0.0, -0.6427876096865394, -0.984807753012208, -0.8660254037844386, -0.3420201433256687,
+                                 0.3420201433256687, 0.8660254037844386, 0.984807753012208, 0.6427876096865394};
+        return mk(C[m], S[m]);
+    } else if constexpr (L == 10) {
+        constexpr double C[10] = {1.0, 0.8090169943749475, 0.30901699437494745, -0.30901699437494745, -0.8090169943749475,
+                                  -1.0, -0.8090169943749475, -0.30901699437494745, 0.30901699437494745, 0.8090169943749475};
+        constexpr double S[10] = {0.0, -0.5877852522924731, -0.9510565162951535, -0.9510565162951535, -0.5877852522924731,
+                                  0.0, 0.5877852522924731, 0.9510565162951535, 0.9510565162951535, 0.5877852522924731};
+        return mk(C[m], S[m]);
+    } else if constexpr (L == 12) {
+        constexpr double C[12] = {1.0, 0.8660254037844386, 0.5, 0.0, -0.5, -0.8660254037844386,
+                                  -1.0, -0.8660254037844386, -0.5, 0.0, 0.5, 0.8660254037844386};
+        constexpr double S[12] = {0.0, -0.5, -0.8660254037844386, -1.0, -0.8660254037844386, -0.5,
+                                  0.0, 0.5, 0.8660254037844386, 1.0, 0.8660254037844386, 0.5};
+        return mk(C[m], S[m]);
+    } else {
+        static_assert(L == 15, "no twiddle table for this leg");
+        constexpr double C[15] = {1.0, 0.9135454576426009, 0.6691306063588582, 0.30901699437494745, -0.10452846326765347,
+                                  -0.5, -0.8090169943749475, -0.9781476007338057, -0.9781476007338057, -0.8090169943749475,
+                                  -0.5, -0.10452846326765347, 0.30901699437494745, 0.6691306063588582, 0.9135454576426009};
+        constexpr double S[15] = {0.0, -0.4067366430758002, -0.7431448254773942, -0.9510565162951535, -0.9945218953682733,
+                                  -0.8660254037844386, -0.5877852522924731, -0.20791169081775934, 0.20791169081775934,
+                                  0.5877852522924731, 0.8660254037844386, 0.9945218953682733, 0.9510565162951535,
+                                  0.7431448254773942, 0.4067366430758002};
+        return mk(C[m], S[m]);
+    }
+}
+// a * W_L^m (m is a compile-time value once the callers' loops are unrolled: the trivial factors cost nothing)
+template <int L>
+ZF_HD cd mul_w(cd a, int m) {
+    m %= L;
+    if (m == 0) return a;
+    if (2 * m == L) return mk(-a.x, -a.y);
+    if (4 * m == L) return mul_mi(a);
+    if (4 * m == 3 * L) return mk(-a.y, a.x);
+    return cmul(a, wroot<L>(m));
+}
+// forward P-point DFT in place, natural order, P = 2, 3, 4, 5
+template <int P>
+ZF_HD void dft_small(cd *x) {
+    if constexpr (P == 2) {
+        const cd t = x[0];
+        x[0] = cadd(t, x[1]);
+        x[1] = csub(t, x[1]);
+    } else if constexpr (P == 3) {
+        constexpr double H3 = 0.8660254037844386;   // sin(2 pi / 3)
+        const cd t = cadd(x[1], x[2]), d = csub(x[1], x[2]);
+        const cd m1 = mk(fma(-0.5, t.x, x[0].x), fma(-0.5, t.y, x[0].y));
+        const cd e = mul_mi(mk(d.x * H3, d.y * H3));
+        x[0] = cadd(x[0], t);
+        x[1] = cadd(m1, e);
+        x[2] = csub(m1, e);
+    } else if constexpr (P == 4) {
+        dft4(x[0], x[1], x[2], x[3]);
+    } else {
+        static_assert(P == 5, "no butterfly of this radix");
+        constexpr double C1_5 = 0.30901699437494745, C2_5 = -0.8090169943749475;   // cos(2 pi / 5), cos(4 pi / 5)
+        constexpr double S1_5 = 0.9510565162951535, S2_5 = 0.5877852522924731;     // sin(2 pi / 5), sin(4 pi / 5)
+        const cd t1 = cadd(x[1], x[4]), t2 = cadd(x[2], x[3]), t3 = csub(x[1], x[4]), t4 = csub(x[2], x[3]);
+        const cd m1 = mk(fma(C1_5, t1.x, fma(C2_5, t2.x, x[0].x)), fma(C1_5, t1.y, fma(C2_5, t2.y, x[0].y)));
+        const cd m2 = mk(fma(C2_5, t1.x, fma(C1_5, t2.x, x[0].x)), fma(C2_5, t1.y, fma(C1_5, t2.y, x[0].y)));
+        const cd n1 = mul_mi(mk(fma(S1_5, t3.x, S2_5 * t4.x), fma(S1_5, t3.y, S2_5 * t4.y)));
+        const cd n2 = mul_mi(mk(fma(S2_5, t3.x, -(S1_5 * t4.x)), fma(S2_5, t3.y, -(S1_5 * t4.y))));
+        x[0] = cadd(x[0], cadd(t1, t2));
+        x[1] = cadd(m1, n1);
+        x[4] = csub(m1, n1);
+        x[2] = cadd(m2, n2);
+        x[3] = csub(m2, n2);
+    }
+}
+// forward (P Q)-point DFT in place, natural order in and out: n = Q n_p + n_q, k = k_p + P k_q
+template <int P, int Q>
+ZF_HD void dft_ct(cd *v) {
+    cd y[P * Q];
+#pragma unroll
+    for (int nq = 0; nq < Q; ++nq) {
+        cd x[P];
+#pragma unroll
+        for (int np = 0; np < P; ++np) x[np] = v[np * Q + nq];
+        dft_small<P>(x);
+#pragma unroll
+        for (int kp = 0; kp < P; ++kp) y[kp * Q + nq] = mul_w<P * Q>(x[kp], nq * kp);
+    }
+#pragma unroll
+    for (int kp = 0; kp < P; ++kp) {
+        cd x[Q];
+#pragma unroll
+        for (int nq = 0; nq < Q; ++nq) x[nq] = y[kp * Q + nq];
+        dft_small<Q>(x);
+#pragma unroll
+        for (int kq = 0; kq < Q; ++kq) v[kp + P * kq] = x[kq];
+    }
+}
+// one leg: forward L-point DFT in place, natural order in and out
+template <int L>
+ZF_HD void dft_leg(cd *v) {
+    if constexpr (L == 16) {
+        dft16(v);
+        cd t[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t[k] = v[bin16(k)];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = t[k];
+    } else if constexpr (L == 9) {
+        dft_ct<3, 3>(v);
+    } else if constexpr (L == 10) {
+        dft_ct<5, 2>(v);
+    } else if constexpr (L == 12) {
+        dft_ct<4, 3>(v);
+    } else {
+        static_assert(L == 15, "no leg of this size");
+        dft_ct<5, 3>(v);
+    }
+}
+
+// Geometry: Geo with R3 = R (N_eff = A B R), pad1 = the padding of the one exchange layout, jstep = s in {1, 2}
+// (the lattice of the aperture, or the twice finer one); pad2 and ip are not used.
+template <int A, int B>
+ZF_HD int mx_threads(const Geo &g) { return (A > B ? A : B) * g.R3; }
+// exchange element (t, k2), t = n0 + R n1 < B R; after stage 2 the same slot holds (n0, k1 = n1's place, k2)
+template <int A, int B>
+ZF_HD int mx_addr(const Geo &g, int t, int k2) { return t + (B * g.R3 + g.pad1) * k2; }
+template <int A, int B>
+ZF_HD int mx_lds_elems(const Geo &g) { return (B * g.R3 + g.pad1) * A; }
+// wanted bin of output j, reduced to [0, N_eff)
+template <int A, int B>
+ZF_HD int mx_bin_of(const Geo &g, int j) {
+    const int N = A * B * g.R3;
+    long long k = ((long long)(j + g.j0) * g.jstep) % N;
+    return (int)(k < 0 ? k + N : k);
+}
+// stage 1 on the A samples v[n2] of thread t < B R; tw: the [k2][n1] table of W_AB^(n1 k2)
+template <int A, int B>
+ZF_HD void mx_stage1(const Geo &g, int t, cd *v, const cd *tw, cd *lds) {
+    const int n1 = t / g.R3;
+    dft_leg<A>(v);
+    lds[mx_addr<A, B>(g, t, 0)] = v[0];
+#pragma unroll
+    for (int k2 = 1; k2 < A; ++k2) lds[mx_addr<A, B>(g, t, k2)] = cmul(v[k2], tw[k2 * B + n1]);
+}
+// stage 2 for thread u = n0 + R k2 < A R: a thread overwrites only the B slots it has just read (no barrier between)
+template <int A, int B>
+ZF_HD void mx_stage2(const Geo &g, int u, cd *v, cd *lds) {
+    const int k2 = u / g.R3, n0 = u - k2 * g.R3;
+#pragma unroll
+    for (int n1 = 0; n1 < B; ++n1) v[n1] = lds[mx_addr<A, B>(g, n0 + g.R3 * n1, k2)];
+    dft_leg<B>(v);
+#pragma unroll
+    for (int k1 = 0; k1 < B; ++k1) lds[mx_addr<A, B>(g, n0 + g.R3 * k1, k2)] = v[k1];
+}
+// stage 3 for ONE wanted bin k: Horner over its R consecutive residues with ratio w = W_N^k
+template <int A, int B>
+ZF_HD cd mx_stage3(const Geo &g, int k, cd w, const cd *lds) {
+    const cd *b = lds + mx_addr<A, B>(g, g.R3 * ((k / A) % B), k % A);
+    cd x = b[g.R3 - 1];
+    for (int n0 = g.R3 - 2; n0 >= 0; --n0) x = cmac(x, w, b[n0]);
+    return x;
+}
+
+// The (A, B) pairs that exist as kernels, and the factorisation of one axis: N s = A B R with s in {1, 2} and
+// R <= 32, the one with the least estimated work - waves x (3 LDS accesses per sample of both legs + the Horner steps
+// of a thread's share of the M wanted bins) - or s = 0: none (the caller keeps the 256 R3 scheme or the GEMMs).
+// With these pairs every 2^a 3^b 5^c in [256, 8192] that is not a multiple of 256 has one except those with a prime
+// power too large for two legs and 32 residues (4374 = 2 3^7, 6561 = 3^8, 3125 = 5^5 ...).
+#define ZF_MX_PAIRS(X) X(16, 15) X(15, 15) X(16, 10) X(15, 10) X(10, 10) X(12, 9) X(9, 9) X(16, 9)
+struct MixChoice {
+    int s = 0, A = 0, B = 0, R = 0;
+};
+ZF_HD MixChoice mixed_choose(int N, int M) {
+    MixChoice best;
+    long long best_cost = -1;
+#define ZF_MX_TRY(AA, BB)                                                                              \
+    for (int s = 1; s <= 2; ++s) {                                                                     \
+        const long long Ne = (long long)N * s;                                                         \
+        if (N < 1 || Ne > 8192 || Ne % (AA * BB)) continue;                                            \
+        const int R = (int)(Ne / (AA * BB)), NT = (AA > BB ? AA : BB) * R;                             \
+        if (R < 1 || R > 32) continue;                                                                 \
+        const long long waves = (NT + 63) / 64, cost = waves * (3 * (AA + BB) + (long long)((M + NT - 1) / NT) * R); \
+        if (best_cost < 0 || cost < best_cost) {                                                       \
+            best_cost = cost;                                                                          \
+            best.s = s, best.A = AA, best.B = BB, best.R = R;                                          \
+        }                                                                                              \
+    }
+    ZF_MX_PAIRS(ZF_MX_TRY)
+#undef ZF_MX_TRY
+    return best;
+}
+
 }  // namespace zf
 
 // ---- host side: LDS bank-conflict model and the choice of the two paddings ---------------------
@@ -399,6 +610,55 @@ inline void choose_pads(Geo &g) {
     }
     g.pad1 = b1;
     g.pad2 = b2;
+}
+
+// LDS cycles of the mixed-radix transform's four access patterns (all waves, all steps) and the conflict-free count
+struct MixCost {
+    long s1_write = 0, s2_read = 0, s2_write = 0, horner = 0, ideal = 0;
+    long total() const { return s1_write + s2_read + s2_write + horner; }
+};
+template <int A, int B>
+inline MixCost mixed_cost(const Geo &g) {
+    MixCost c;
+    const int R = g.R3, NT = mx_threads<A, B>(g);
+    int addr[64];
+    for (int w0 = 0; w0 < NT; w0 += 64) {
+        for (int k2 = 0; k2 < A; ++k2) {
+            bool any = false;
+            for (int l = 0; l < 64; ++l) any |= (addr[l] = w0 + l < B * R ? mx_addr<A, B>(g, w0 + l, k2) : -1) >= 0;
+            if (any) c.s1_write += lds_cycles(addr, false), c.ideal += 8;
+        }
+        for (int n1 = 0; n1 < B; ++n1) {
+            bool any = false;
+            for (int l = 0; l < 64; ++l) {
+                const int u = w0 + l;
+                any |= (addr[l] = u < A * R ? mx_addr<A, B>(g, u % R + R * n1, u / R) : -1) >= 0;
+            }
+            if (any) c.s2_read += lds_cycles(addr, true), c.s2_write += lds_cycles(addr, false), c.ideal += 4 + 8;
+        }
+    }
+    for (int o0 = 0; o0 < g.M; o0 += 64)
+        for (int n0 = 0; n0 < R; ++n0) {
+            for (int l = 0; l < 64; ++l) {
+                const int k = o0 + l < g.M ? mx_bin_of<A, B>(g, o0 + l) : -1;
+                addr[l] = k < 0 ? -1 : mx_addr<A, B>(g, n0 + R * ((k / A) % B), k % A);
+            }
+            c.horner += lds_cycles(addr, true);
+            c.ideal += 4;
+        }
+    return c;
+}
+// the padding with the fewest conflict cycles (smaller paddings win ties)
+template <int A, int B>
+inline void mixed_choose_pad(Geo &g) {
+    long best = -1;
+    int bp = 0;
+    for (int p = 0; p <= 16; ++p) {
+        g.pad1 = p;
+        const long cost = mixed_cost<A, B>(g).total();
+        if (best < 0 || cost < best) best = cost, bp = p;
+    }
+    g.pad1 = bp;
 }
 
 // LDS cycles of the tile column pass for one round (TL_SLOTS residues) of one workgroup, and the conflict-free

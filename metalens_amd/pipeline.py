@@ -47,7 +47,7 @@ class HotPath:
         # transforms inherit, and other objects on the same context set their own: this object
         # re-asserts them before every pass (_assert_state), an attribute compare while they hold
         self.precision = precision or 'f64'   # 'f64' | 'f32': arithmetic of the GEMMs
-        self.method = method or 'auto'        # 'auto' | 'gemm' | 'fft-streamed': _lib.Context.set_method
+        self.method = method or 'auto'        # 'auto' | 'gemm' | 'fft-streamed' | 'fft-mixed': _lib.Context.set_method
         self.allreduce = int(allreduce)
         self.owner = _lib.new_owner()
         self._assert_settings()
