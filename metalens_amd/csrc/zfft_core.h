@@ -475,8 +475,10 @@ ZF_HD cd mx_stage3(const Geo &g, int k, cd w, const cd *lds) {
 // The (A, B) pairs that exist as kernels, and the factorisation of one axis: N s = A B R with s in {1, 2} and
 // R <= 32, the one with the least estimated work - waves x (3 LDS accesses per sample of both legs + the Horner steps
 // of a thread's share of the M wanted bins) - or s = 0: none (the caller keeps the 256 R3 scheme or the GEMMs).
-// With these pairs every 2^a 3^b 5^c in [256, 8192] that is not a multiple of 256 has one except those with a prime
-// power too large for two legs and 32 residues (4374 = 2 3^7, 6561 = 3^8, 3125 = 5^5 ...).
+// With these pairs 81 of the 97 lattices 2^a 3^b 5^c in [256, 8192] that are not multiples of 256 have one.  The 16
+// without - no pair divides N or 2 N <= 8192 and leaves 32 residues or fewer: 384 (2^7 3) and 625 (5^4), which no
+// pair divides at all, and 3125, 3645, 4374, 4860, 5000, 5184, 5832, 6250, 6561, 7290, 7500, 7776, 8000, 8100, whose
+// powers of 2, 3 or 5 are too large for two legs (tests/test_zfft_mixed_emul.py pins the list).
 #define ZF_MX_PAIRS(X) X(16, 15) X(15, 15) X(16, 10) X(15, 10) X(10, 10) X(12, 9) X(9, 9) X(16, 9)
 struct MixChoice {
     int s = 0, A = 0, B = 0, R = 0;

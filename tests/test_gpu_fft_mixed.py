@@ -3,10 +3,13 @@ N = 2^a 3^b 5^c samples that is not a multiple of 256 long - what the reference'
 caller passes no grid (nearfield.py:30-36, 95-102) - runs as an output-pruned FFT on that lattice itself, factored
 A x B x R, instead of on the 256 / gcd(N, 256) times finer one.  Checked against the CPU oracle's direct sum and its
 restatement of the reference flow, against 'fft-streamed' where no factorisation exists, and for the state the API
-objects keep.  Needs an MI355X."""
+objects keep.  The table of tests/mixed_cases.py takes every leg pair through its three roles (stage 1, stage 2
+streaming and strided: the 16 instantiations of the kernel), the twice finer lattice, R = 1 ... 32 and lattices
+below 256 samples; test_zfft_mixed_emul.py ties the table to the production chooser.  Needs an MI355X."""
 import numpy as np
 import pytest
 
+import mixed_cases
 from test_gpu_fft import N_GLASS, TOL, WL, fields, lattice
 
 pytestmark = pytest.mark.gpu
@@ -76,6 +79,30 @@ def test_mixed_lattices_match_the_oracle(ma, ctx, nx, ny, nex, ney, mx, my, jx, 
     _check_against_oracle(got, farfield_oracle.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy))
 
 
+def _worst(got, want):
+    """largest error of the radiation vectors relative to each one's largest component (what TOL bounds)"""
+    return max(np.abs(got[key] - want[key]).max() / np.abs(want[key]).max() for key in ('Nx', 'Ny', 'Lx', 'Ly'))
+
+
+@pytest.mark.parametrize('xr,yr', mixed_cases.GPU_CASES, ids=['%s-%s' % (a, b or 'off') for a, b in mixed_cases.GPU_CASES])
+def test_every_pair_in_every_role_matches_the_oracle(ma, ctx, xr, yr):
+    """one table row per axis: the x row is stage 2 - streaming over a transposed stage-1 result where y is an FFT
+    axis, strided over a row-major one where uy sits on no lattice -, the y row stage 1"""
+    from oracle import farfield_oracle
+    X, Y = mixed_cases.ROWS[xr], mixed_cases.ROWS[yr] if yr else None
+    nx, ny = X.n_samples, Y.n_samples if Y else mixed_cases.OFF_NY
+    x, y = _axes(nx, ny)
+    ux = lattice(X.n_lattice, x[1] - x[0], X.m_bins, X.j0)
+    uy = lattice(Y.n_lattice, y[1] - y[0], Y.m_bins, Y.j0) if Y else np.linspace(-0.2, 0.22, mixed_cases.OFF_MY)
+    F = fields(nx, ny, nx + ny)
+    got = ma.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy, ctx=ctx)
+    assert ctx.plan_kernels() == ('fft-mixed' if Y else 'folded', 'fft-mixed')
+    want = farfield_oracle.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy)
+    print('mixed-case x %s %s y %s %s: worst rel err %.3e' % (xr, X.expect, yr, Y.expect if Y else None,
+                                                             _worst(got, want)))
+    _check_against_oracle(got, want)
+
+
 def test_one_axis_mixed_the_other_off_the_lattice(ma, ctx):
     """each axis decides for itself: the mixed-radix FFT where the grid sits on such a lattice, the folded GEMM
     on a uniform grid that sits on none"""
@@ -91,7 +118,134 @@ def test_one_axis_mixed_the_other_off_the_lattice(ma, ctx):
         _check_against_oracle(got, farfield_oracle.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy))
 
 
-@pytest.mark.parametrize('N', [400, 1000, 1440, 2000])
+@pytest.mark.parametrize('nx,ny,mx,my,jx,jy', [
+    (540, 320, 96, 64, -48, -32),     # 12 x 9 x 5 and 16 x 10 x 2
+    (360, 450, 96, 64, -48, -32),     # 720 = 16 x 15 x 3: the twice finer lattice along x; 15 x 10 x 3
+])
+@pytest.mark.parametrize('mirrored', [False, True])
+def test_sharded_rows_through_the_mixed_fft(ma, ctx, mirrored, nx, ny, mx, my, jx, jy):
+    """test_gpu_fft.py test_sharded_rows_through_the_fft on mixed lattices: row shards (contiguous blocks or mirrored
+    pairs: two resident runs a0 / h0 + a1 / h1 of stage 2) accumulate to the whole aperture - and to the oracle's
+    sum: two runs of one kernel agreeing says nothing about the kernel"""
+    from metalens_amd import _lib, dist
+    from oracle import farfield_oracle
+    x, y = _axes(nx, ny)
+    ux, uy = lattice(nx, x[1] - x[0], mx, jx), lattice(ny, y[1] - y[0], my, jy)
+    F = fields(nx, ny, 9)
+    whole = ma.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy, ctx=ctx)
+    t = ma.FarfieldTransform(nx, ny, x[1] - x[0], y[1] - y[0], WL, N_GLASS, ux, uy, ctx=ctx)
+    assert ctx.plan_kernels() == ('fft-mixed', 'fft-mixed')
+    world = 3
+    for rank in range(world):
+        if mirrored:
+            q0, q1 = dist.mirrored_block(nx, world, rank, align=2)
+            rows = dist.mirrored_rows(nx, q0, q1)
+        else:
+            q0, q1 = dist.row_block(nx, world, rank)
+            rows = np.arange(q0, q1)
+        part = [np.ascontiguousarray(f[rows]) for f in F]
+        _lib.check(ctx.lib.ml_fields_upload(ctx.handle, len(rows), ny, *[_lib.dptr(a) for a in part]))
+        t.transform(row0=q0, accumulate=rank > 0, mirrored=mirrored)
+    got = t.radiation_vectors()
+    assert ctx.plan_kernels() == ('fft-mixed', 'fft-mixed')
+    want = farfield_oracle.farfield_direct(*F, x, y, WL, N_GLASS, ux, uy)
+    print('mixed-shards %d x %d mirrored %s: worst rel err %.3e (whole aperture %.3e)'
+          % (nx, ny, mirrored, _worst(got, want), _worst(whole, want)))
+    for key in ('Nx', 'Ny', 'Lx', 'Ly'):
+        assert np.abs(got[key] - whole[key]).max() <= 1e-13 * np.abs(whole[key]).max(), key
+        assert np.abs(got[key] - want[key]).max() <= TOL * np.abs(want[key]).max(), key
+    _check_against_oracle(whole, want)
+
+
+def _hot_path_lens(ma):
+    import math
+    from metalens_amd import layout, synthetic
+    return synthetic.make_lens((ma.Grating, ma.GratingCollection, ma.HexGridSet), layout.make_design,
+                               radius=0.14e-3, numerical_aperture=0.5, wavelength=WL,
+                               switch_angle=12 * math.pi / 180, num_gratings=20, num_entries=12)
+
+
+@pytest.mark.parametrize('n,m', [(1000, 100), (360, 90)])   # 10 x 10 x 10; 720 = 16 x 15 x 3 (the twice finer lattice)
+def test_hot_path_mixed_equals_gemm_and_the_oracle(ma, ctx, n, m):
+    """test_gpu_fft.py test_hot_path_fft_equals_gemm under 'fft-mixed': the resident pipeline (synthesis -> transform
+    -> projection) agrees with the GEMM formulation and with the oracle's flow (its near field, its direct sum)"""
+    from metalens_amd.pipeline import HotPath
+    from oracle import farfield_oracle, nearfield_oracle
+    lens = _hot_path_lens(ma)
+    x = (np.arange(n) - (n - 1) / 2) * (WL / 2.2)
+    u = lattice(n, x[1] - x[0], m, -(m // 2))
+    src = (0.4e-6, -0.3e-6, -lens['source_distance'], 'y')
+    out = {}
+    for method in ('fft-mixed', 'gemm'):
+        hp = HotPath(src, WL, lens['lens_periphery_summary'], lens['lens_center_summary'],
+                     lens['hexgridset'], x, x, u, u, ctx=ctx, method=method)
+        hp.step()
+        hp.sync()
+        out[method] = hp.results()
+        assert ctx.plan_kernels() == (('fft-mixed', 'fft-mixed') if method == 'fft-mixed' else ('folded', 'folded'))
+    for key in ('Nx', 'Ny', 'Lx', 'Ly', 'a_theta', 'a_phi', 'P'):
+        a, b = out['fft-mixed'][key], out['gemm'][key]
+        assert np.abs(a - b).max() <= 1e-13 * np.abs(b).max(), key
+    assert out['fft-mixed']['power_local_rows'] == out['gemm']['power_local_rows']
+    nf = nearfield_oracle.build_nearfield(*src, WL, lens['lens_periphery_summary'], lens['lens_center_summary'],
+                                          lens['hexgridset'], x_pts=x, y_pts=x)
+    want = farfield_oracle.farfield_direct(*nf[:4], x, x, WL, nf[7], u, u)
+    print('mixed-hot-path %d -> %d: worst rel err %.3e' % (n, m, _worst(out['fft-mixed'], want)))
+    _check_against_oracle(out['fft-mixed'], want)
+
+
+def test_source_sweep_mixed_incoherent_sum_vs_oracle(ma):
+    """test_gpu_parity.py test_source_sweep_incoherent_sum_vs_oracle with SourceSweep(method='fft-mixed') on a grid
+    of 150 samples (300 = 10 x 10 x 3, the twice finer lattice): a polarisation batch of three field sets in one
+    pass (alpha_rb, in_rb of the kernel's rows), a single source, a batch of two and a position batch"""
+    from metalens_amd import _lib, postprocess
+    from oracle import farfield_oracle, nearfield_oracle
+    from test_gpu_parity import _synthetic_lens
+    wl = 580e-9
+    lens = _synthetic_lens(18e-6, 0.35, wl, switch_deg=9.0)
+    n, m = 150, 36
+    x = (np.arange(n) - (n - 1) / 2) * (wl / 2.2)
+    assert x[-1] >= lens['lens_periphery_summary']['r_max_list'][-1]      # the window holds the lens
+    f = lens['source_distance']
+    sources = [(0.2e-6, 0.1e-6, -f, 'x'), (0.2e-6, 0.1e-6, -f, 'y'), (0.2e-6, 0.1e-6, -f, 'z'),
+               (-1.0e-6, 0.5e-6, -1.05 * f, 'x'),
+               (0.0, 0.0, -0.97 * f, 'y'), (0.0, 0.0, -0.97 * f, 'z'),
+               (0.5e-6, 0.0, -f, 'x'), (-0.5e-6, 0.3e-6, -1.02 * f, 'y')]
+    weights = np.array([1.0, 1.0, 1.0, 0.5, 2.0, 2.0, 1.5, 0.7])
+    cone, center = 0.08, (0.01, -0.005)
+    near = [nearfield_oracle.build_nearfield(sx, sy, sz, pol, wl, lens['lens_periphery_summary'],
+                                             lens['lens_center_summary'], lens['hexgridset'], x_pts=x, y_pts=x)
+            for sx, sy, sz, pol in sources]
+    u = (np.arange(m) - m // 2) * ((wl / near[0][7]) / ((x[1] - x[0]) * n))
+    du = u[1] - u[0]
+    ctx = _lib.default_context()
+    try:
+        sw = ma.SourceSweep(wl, lens['lens_periphery_summary'], lens['lens_center_summary'],
+                            lens['hexgridset'], x, x, u, u, method='fft-mixed')
+        assert sw.n_glass == near[0][7]
+        assert [len(g['members']) for g in sw._group(sources)] == [3, 1, 2, 2]
+        got = sw.run(sources, weights=weights, cone=cone, cone_center=center, keep_each=True)
+        assert ctx.plan_kernels() == ('fft-mixed', 'fft-mixed')
+    finally:
+        ctx.set_method('auto')
+    P_ref, pin_ref = 0, []
+    for k, nf in enumerate(near):
+        ff = farfield_oracle.farfield_direct(*nf[:4], x, x, wl, nf[7], u, u)
+        print('mixed-sweep source %d: P rel err %.3e' % (k, np.nanmax(np.abs(got['P_each'][k] - ff['P'])) / np.nanmax(ff['P'])))
+        assert np.nanmax(np.abs(got['P_each'][k] - ff['P'])) <= 1e-11 * np.nanmax(ff['P'])
+        P_ref = P_ref + weights[k] * ff['P']
+        pin_ref.append(nf[6])
+        want_total = postprocess.total_power(ff['P'], du, du)
+        want_cone = postprocess.encircled_power(ff['P'], u, u, du, du, sin_max=cone, center=center)
+        assert abs(got['total_P'][k] - want_total) <= 1e-11 * want_total, k
+        assert abs(got['cone_P'][k] - want_cone) <= 1e-11 * want_total, k
+        assert 0 < want_cone < want_total          # the cone really cuts the map
+    assert np.nanmax(np.abs(got['P_sum'] - P_ref)) <= 1e-11 * np.nanmax(P_ref)
+    np.testing.assert_allclose(got['power_in'], pin_ref, rtol=1e-12)
+    assert abs(got['efficiency'] - got['total_P'].sum() / np.sum(pin_ref)) < 1e-12
+
+
+@pytest.mark.parametrize('N', [400, 1000, 1440, 2000, 288, 320, 360, 750, 900, 1080])
 def test_whole_default_grids_vs_oracle_flow(N):
     """the reference flow on the grids it picks itself: a lens window of N x N samples synthesised resident, every
     lattice direction against the oracle's restatement of the flow (numpy.fft on the host) - ALL N^2 directions with

@@ -3,10 +3,13 @@
 // the lattice asked for, in long double.  Prints per case the relative error and the LDS cycles of the chosen
 // padding next to the conflict-free count, the error of the 16 x 16 x R3 programme on the same kind of input (the
 // yardstick for the mixed cases), and the chooser's answer for every 2^a 3^b 5^c in [256, 8192].
+// With arguments it runs the cases named there instead and prints their `mixed:` lines only:
+//     --case N valid M j0 a0 h0 a1 h1     (repeatable; tests/mixed_cases.py holds the table the suite passes)
 // Build + run:  make -C tools zfft_mixed_emul && tools/zfft_mixed_emul
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../metalens_amd/csrc/zfft_core.h"
@@ -126,7 +129,28 @@ static double run_base(int R3, int M, int j0) {
     return rel;
 }
 
-int main() {
+// the cases of the command line; 0 when every one ran, 2 on a malformed argument or a lattice without factorisation
+static int run_cases(int argc, char **argv) {
+    int status = 0;
+    for (int i = 1; i < argc; i += 9) {
+        if (strcmp(argv[i], "--case") || i + 8 >= argc) {
+            fprintf(stderr, "usage: %s [--case N valid M j0 a0 h0 a1 h1]...\n", argv[0]);
+            return 2;
+        }
+        int v[8];
+        for (int k = 0; k < 8; ++k) v[k] = atoi(argv[i + 1 + k]);
+        if (v[0] < 1 || v[1] < 1 || v[1] > v[0] || v[2] < 1 || v[2] > v[0]) {
+            fprintf(stderr, "--case %d %d %d ...: need 1 <= valid <= N and 1 <= M <= N\n", v[0], v[1], v[2]);
+            return 2;
+        }
+        if (!zf::mixed_choose(v[0], v[2]).s) status = 2;
+        run_mixed(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+    }
+    return status;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) return run_cases(argc, argv);
     const double base = fmax(run_base(16, 512, -256), run_base(32, 1024, -512));
     double worst = 0;
     worst = fmax(worst, run_mixed(400, 400, 400, -200, 0, 400, 0, 0));
