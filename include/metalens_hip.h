@@ -416,6 +416,39 @@ int ml_nearfield_result(ml_ctx *ctx, double *power, ml_bound_violation *violatio
  * Any pointer may be NULL.                                                                       */
 int ml_nearfield_kernel_info(ml_ctx *ctx, int *family, int *ring_orders_max, int *centre_orders);
 
+/* ---- propagation to points at finite distance ---------------------------------------------
+ * The field at targets r = (x, y, z), z > 0, behind the aperture plane z = 0: the Stratton-Chu / Franz
+ * sum over the equivalent currents of the SELECTED resident field set (ml_fields_select),
+ *   E(r) = dx'dy' sum g { i k Z   [a J - b Rhat (Rhat.J)] - c Rhat x M }
+ *   H(r) = dx'dy' sum g { i (k/Z) [a M - b Rhat (Rhat.M)] + c Rhat x J }
+ *   R = |r - r'|, g = exp(ikR) / (4 pi R), a = 1 + i/(kR) - 1/(kR)^2, b = 1 + 3i/(kR) - 3/(kR)^2, c = ik - 1/R,
+ * a direct fp64 pair sum, valid at any distance (the far field of the entries above needs 2 D^2 / lambda,
+ * metres for a millimetre lens).  Samples outside the row extents of a synthesised field are skipped;
+ * uploaded fields are summed whole.  Bit-for-bit repeatable.  Refused on a context with more than one rank.
+ * The propagator owns its targets and result: the far-field plan, the radiation vectors, the sweep sums,
+ * the method and the precision of the context are not touched.
+ *
+ * ml_propagate_plan replaces no reference lines: the reference ends in direction space.  Its
+ * convention is the reference's far field's (nearfield_farfield.py:94-101, 183-185): J = (-Hy, Hx),
+ * M = (Ey, -Ex), k = 2 pi n_glass / wavelength, Z = Z0 / n_glass, exp(-i omega t).
+ *   x0, y0, dxp, dyp : aperture sample [i][j] of the resident field set sits at (x0 + i dxp, y0 + j dyp);
+ *                      the shape is the resident set's when ml_propagate runs (ml_fields_shape)
+ *   point_list == 0  : targets on the tensor grid x[nx_t] x y[ny_t] in the plane z[0] (nz == 1), C-ordered
+ *   point_list != 0  : the nx_t points (x[d], y[d], z[d]) (ny_t == nz == nx_t), e.g. a cut through a focus
+ *   want_h == 0      : E only (about 40 % less arithmetic)
+ * Every z must be > 0 (ML_EINVAL otherwise); |k R| must stay below 1e9.                              */
+int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                      double wavelength, double n_glass,
+                      const double *x, int nx_t, const double *y, int ny_t, const double *z, int nz,
+                      int point_list, int want_h);
+/* Queue the sum for the active propagation plan on the context's stream (asynchronous).  Replaces no
+ * reference lines; Z0 enters as in nearfield_farfield.py:183-185 (Z = Z0 / n_glass).     */
+int ml_propagate(ml_ctx *ctx, double Z0);
+/* The result of the last ml_propagate: E, H complex128 [3][targets] (x, y, z components; targets in the
+ * plan's order).  H may be NULL, and must be for a plan with want_h == 0.  Synchronises.  Replaces no
+ * reference lines (convention: nearfield_farfield.py:94-101, 183-185).                    */
+int ml_propagate_download(ml_ctx *ctx, double *E, double *H);
+
 #ifdef __cplusplus
 }
 #endif

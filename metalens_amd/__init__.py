@@ -14,3 +14,4 @@ from .sweep import SourceSweep, WavelengthSweep  # noqa: F401
 from .nearfield_farfield import (FarfieldTransform, farfield_direct,  # noqa: F401
                                  farfield_from_nearfield, farfield_from_resident_nearfield,
                                  fft_direction_cosines)
+from .propagate import PlanePropagator, field_at_plane  # noqa: F401

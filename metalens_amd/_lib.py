@@ -46,7 +46,7 @@ SYMBOLS = (
     'ml_nearfield_batch_async', 'ml_fields_select', 'ml_nearfield_powers',
     'ml_farfield_accumulate', 'ml_farfield_sums', 'ml_farfield_total_power', 'ml_host_alloc', 'ml_host_free',
     'ml_comm_info', 'ml_comm_set_reduce', 'ml_farfield_gather', 'ml_nearfield_kernel_info',
-    'ml_comm_set_max_channels',
+    'ml_comm_set_max_channels', 'ml_propagate_plan', 'ml_propagate', 'ml_propagate_download',
 )
 
 
@@ -151,6 +151,10 @@ def load():
         lib.ml_comm_set_max_channels.argtypes = [c_void_p, c_int]
     if hasattr(lib, 'ml_nearfield_kernel_info'):
         lib.ml_nearfield_kernel_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
+    lib.ml_propagate_plan.argtypes = [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double,
+                                      _dp, c_int, _dp, c_int, _dp, c_int, c_int, c_int]
+    lib.ml_propagate.argtypes = [c_void_p, c_double]
+    lib.ml_propagate_download.argtypes = [c_void_p, _dp, _dp]
     lib.ml_profile_enable.argtypes = [c_void_p, c_int]
     lib.ml_profile_reset.argtypes = [c_void_p]
     lib.ml_profile_get.argtypes = [c_void_p, c_int, POINTER(c_int64), _dp]
@@ -276,6 +280,8 @@ class Context:
         # object that is no longer the owner - the plan's size and content are another object's
         self.plan_owner = None
         self.fields_owner = None
+        # ... and which PlanePropagator made the active propagation plan (its targets and result)
+        self.propagate_owner = None
 
     def close(self):
         if getattr(self, '_h', None):

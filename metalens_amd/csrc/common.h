@@ -379,6 +379,17 @@ struct FarfieldPlan {
     double unfold_alpha[4] = {0, 0, 0, 0};
 };
 
+// Targets and buffers of the finite-distance propagator (propagate.hip).  Its own: nothing here is shared with the
+// far-field plan, the radiation vectors or the sweep sums.
+struct PropagatePlan {
+    bool ready = false, have_result = false;
+    int T = 0, want_h = 1;
+    double x0 = 0, y0 = 0, dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
+    DevBuf targets;   // double [3][T]: x - x0, y - y0, z of every target
+    DevBuf partial;   // double [splits][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
+    DevBuf result;    // complex [6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz)
+};
+
 }  // namespace ml
 
 struct ml_ctx {
@@ -490,6 +501,7 @@ struct ml_ctx {
     int nf_blocks = 0;
 
     ml::FarfieldPlan plan;
+    ml::PropagatePlan prop;
     ml::Profile prof;
 
     // RCCL.  comm_stream carries the all-reduce of the projected amplitudes and the power kernel
