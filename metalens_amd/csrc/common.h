@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "metalens_hip.h"
+#include "transform_route.h"
 
 namespace ml {
 
@@ -304,31 +305,16 @@ struct CellRec {
 
 // One axis of a plan whose direction grid sits on the aperture's FFT lattice (zfft.hip): the
 // transform along that axis runs as an output-pruned FFT instead of a GEMM.
-struct ZfftAxis {
-    bool ok = false;
-    int N_eff = 0, j0 = 0, pad1 = 0, pad2 = 0;
-    int jstep = 1;   // output j is bin (j + j0) jstep of the N_eff-sample lattice (zfft_core.h Geo::jstep)
-    // split > 1 (lattices beyond 8192 samples): `split` launches over interleaved sub-sequences of
-    // N_eff / split samples; wk / kbin then belong to the SHORT lattice and pj holds [split][M]
-    int split = 1;
-    // passes > 1: ONE launch per row set, the residues of a row in that many groups through half
-    // (a quarter) of the LDS (zfft_pass_kernel); lattices of 8192 < N_eff <= 16384 samples with at
-    // most 1024 wanted bins run this way instead of split in two
-    int passes = 0;
-    // method 'fft-mixed' on a lattice that is not a multiple of 256 long: N_eff = A B R samples (the lattice itself
-    // or the twice finer one: jstep = 1 or 2) through zfft_mixed_kernel<A, B>; pad1 is its one padding and tw its
-    // [B][A] twiddle table (zfft_core.h mixed_choose).  A = 0: the 256 R3 scheme
-    int A = 0, B = 0, R = 0;
+struct ZfftAxis : ZfftAxisGeo {   // (transform_route.h: the axis' facts)
     DevBuf tw;
     DevBuf wk, pj, kbin;   // per-bin Horner ratio, origin phasor, reduced bin (zfft.hip FftArgs)
 };
 
-struct FarfieldPlan {
+struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's route is decided from)
     bool ready = false;
-    int method = 0;    // ml_farfield_set_method value the plan was made under
     ZfftAxis fft_y, fft_x;
     DevBuf fft_tw1;
-    // column pass of an interleaved row shard (transform_impl): tables of its `block` short
+    // column pass of an interleaved row shard (farfield.hip stage2_interleaved): tables of its `block` short
     // transforms and what they were built for (plan serial, block, ranks, rank)
     DevBuf il_wk, il_pj, il_kbin;
     long il_key[4] = {-1, -1, -1, -1};
@@ -340,12 +326,11 @@ struct FarfieldPlan {
     // amp_gathered: every rank holds every block's sum (and the whole power map), not only its own
     int amp_rows = 0;
     bool amp_gathered = true;
-    int nx_total = 0, ny = 0, mx = 0, my = 0, pair_list = 0;
     double dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
     DevBuf ux, uy;       // direction cosines
     DevBuf tw_x;         // complex [mx][nx_total]   exp(-i k x' ux)   (A operand of stage 2)
     DevBuf tw_y;         // complex [ny][my]         exp(-i k y' uy)   (B operand of stage 1)
-    DevBuf stage1;       // complex [4][nx_local][my], or transposed (farfield.hip transform_impl) ...
+    DevBuf stage1;       // complex [4][nx_local][my], or transposed (transform_route.h GLayout) ...
     PieceBuf stage1_pieces{(size_t)4 << 20};   // ... the transposed one of rows up to 8192 samples
     DevBuf vectors;      // complex [4][mx][my]  (Nx, Ny, Lx, Ly)  or [4][mx] for a pair list
     DevBuf power;        // double  [mx][my]
@@ -359,13 +344,12 @@ struct FarfieldPlan {
     bool tw_x_ready = false;  // complex x twiddles built for the current plan
     int stage1_splits = 1;   // split-K slabs currently held in `stage1`
     // folded (even/odd) stage 1, see zfold.hip; used when uy is centre-symmetric
-    bool fold = false, fold_has_E = false;
-    int fold_T = 0, fold_S = 0;
+    bool fold_has_E = false;
+    int fold_T = 0;
     DevBuf fold_cm, fold_sm, fold_E, fold_D, fold_v, fold_r4;
     std::vector<double> h_ux, h_uy, h_fold_v, h_fold2_v;   // host copies of the plan's inputs
     // folded stage 2 (needs centre-symmetric ux and a mirror-symmetric set of resident rows)
-    bool fold2 = false, fold2_has_E = false;
-    int fold2_S = 0;
+    bool fold2_has_E = false;
     DevBuf fold2_v, fold2_cm, fold2_sm, fold2_r4, fold2_E, fold2_D, fold2_gt, fold2_ot;
     // the stage-2 tables depend on the plan and on which rows are resident: rebuilt only when
     // that changes (serial, row0, resident rows, mirrored)

@@ -853,18 +853,9 @@ static int interleave_block(const FarfieldPlan &pl, int n_ranks) {
     return 0;
 }
 
-struct Shard {
-    int kind = 0;          // 0: rows [row0, row0 + nx), 1: mirrored pairs from row0, 2: interleaved
-    int row0 = 0;
-    int block = 0, n_ranks = 1, rank = 0;   // kind 2
-};
-
-// layout of stage 1's result G for stage 2: row-major G[f][n1][b], transposed G[f][b][n1], or tiled G[f][b / 8][n1][b % 8]
-enum class GLayout { row_major, transposed, tiled };
-
-static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
+static int validate_shard(ml_ctx *ctx, const Shard &sh, int accumulate) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    const int row0 = sh.row0, mirrored = sh.kind == 1;
+    const int row0 = sh.row0;
     FarfieldPlan &pl = ctx->plan;
     if (!pl.ready) {
         set_error("ml_farfield_plan has not been called");
@@ -876,14 +867,14 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     }
     ML_REQUIRE(ctx->ny == pl.ny, "resident fields have ny=%d but the plan has ny=%d", ctx->ny,
                pl.ny);
-    if (sh.kind == 2) {
+    if (sh.kind == ShardKind::interleaved) {
         ML_REQUIRE(sh.block >= 1 && sh.block == interleave_block(pl, sh.n_ranks),
                    "interleaved shard: block %d is not what ml_farfield_interleave_block gives for %d ranks "
                    "on this plan (%d)", sh.block, sh.n_ranks, interleave_block(pl, sh.n_ranks));
         ML_REQUIRE(sh.rank >= 0 && sh.rank < sh.n_ranks && ctx->nx == pl.nx_total / sh.n_ranks,
                    "interleaved shard: rank %d of %d with %d resident rows of %d", sh.rank, sh.n_ranks,
                    ctx->nx, pl.nx_total);
-    } else if (mirrored) {
+    } else if (sh.kind == ShardKind::mirrored) {
         ML_REQUIRE(ctx->nx % 2 == 0 && row0 >= 0 && 2 * row0 + ctx->nx <= pl.nx_total,
                    "mirrored shard: %d resident rows starting at %d do not form row pairs of a "
                    "%d-row aperture", ctx->nx, row0, pl.nx_total);
@@ -894,137 +885,136 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
                    row0 + ctx->nx, pl.nx_total);
     }
     ML_REQUIRE(!accumulate || pl.have_vectors, "accumulate requested but nothing to add to");
-    ML_HIP(hipSetDevice(ctx->device));
-    // a deferred unfold of the previous transform: needed if this one adds to it, moot otherwise
-    if (accumulate)
-        ML_TRY(flush_unfold(ctx));
-    else
-        pl.unfold_pending = false;
-    const int nxl = ctx->nx, ny = pl.ny, mx = pl.mx, my = pl.my;
-    // few resident rows (multi-GPU shards) and a long reduction: split the pairs of stage 1 over
-    // several workgroups per tile; the slabs are summed by the next kernel
-    pl.stage1_splits = 1;
-    int want_split1 = 1;
-    if (pl.fold) {
-        // Measured (tools/zfold_shape_sweep.py): tiles of 128 half-directions read the aperture
-        // fewer times and win when at most a 2-way split fills the chip; otherwise 64-wide
-        // tiles with as many splits as it takes to reach ~2.5 workgroups per CU.
-        const long t128 = (long)((4 * nxl + 31) / 32) * ((pl.fold_S + 127) / 128);
-        const long t64 = (long)((4 * nxl + 31) / 32) * ((pl.fold_S + 63) / 64);
-        if (t128 >= 480)
-            want_split1 = 1;
-        else if (2 * t128 >= 480)
-            want_split1 = 2;
-        else
-            want_split1 = (int)std::min<long>(8, std::max<long>(1, (640 + t64 - 1) / std::max<long>(t64, 1)));
-        static const int forced_split = diag_int("ML_STAGE1_SPLIT", 0);
-        if (forced_split > 0) want_split1 = forced_split;
-        pl.stage1_splits = zfold_splits(pl.fold_T, want_split1);
-    }
-#ifndef ML_STAGE1_TRANSPOSED
-#define ML_STAGE1_TRANSPOSED 1
-#endif
-    // Both axes one-level FFTs on a large aperture: stage 1 writes its result TRANSPOSED, G[f][b][n1]
-    // with rows of nxl + 8 (a 128-byte skew: consecutive bins of a row transform land in different
-    // L2 channels), and stage 2 streams contiguous rows with non-temporal loads like stage 1 does,
-    // instead of gathering 16-byte pieces 8 KB apart with loads that keep G in the caches.  What this
-    // buys is mostly NOT in the transform (4096^2 -> 512^2: stage 1 0.179 -> 0.207 ms for its 16-byte
-    // scattered stores - neighbouring rows meet in the XCD's L2 -, stage 2 0.057 -> 0.037) but in the
-    // NEXT synthesis, 0.265 -> 0.229 ms: a G that is read once and dropped no longer pushes the
-    // geometry records (134 MB at 4096^2, + 134 MB of G > the 256 MB memory-side cache) out between
-    // steps.  Small apertures, where everything fits anyway, keep the row-major G (2048^2 -> 256^2,
-    // 67 MB of records + G: 0.167 against 0.178 ms per step; from 2560^2 -> 320^2, 105 MB, on the
-    // transposed one is 1-1.5 % ahead: 0.282 against 0.287 ms, 3072^2 0.368 / 0.372, 3584^2 0.458 / 0.463).
-    const bool g_transposed = ML_STAGE1_TRANSPOSED && pl.fft_y.ok && pl.fft_x.ok && !pl.pair_list &&
-                              pl.fft_y.split == 1 && pl.fft_x.split == 1 && sh.kind != 2 &&
-                              (pl.method == ML_METHOD_FFT_STREAMED || pl.method == ML_METHOD_FFT_MIXED ||
-                               (size_t)nxl * ny * 8 + (size_t)4 * nxl * my * 16 > (size_t)96 << 20);
-    // (skew sweep at 4096^2 -> 512^2, stage 1: 0 elements 0.220 ms, 16 0.222, 1 0.204, 2 0.212, 24 0.208,
-    // 72 0.206, 4 0.190, 8 0.194-0.196, 40 0.196, 136 0.192: anything but a multiple of 256 bytes)
-    static const int g_skew = diag_int("ML_G_SKEW", 8);   // (diagnostic builds: the pitch's skew in elements)
-    const int64_t g_ld = nxl + g_skew;
-    // Where both transforms take the one-level kernels, the transposed G is stored TILED instead: G[f][b / 8][n1][b % 8],
-    // the 8 bins of a 128-byte line side by side, tiles 8 g_ld elements long (zfft_core.h tile_off) - the same bytes.
-    // Stage 1 then stores whole lines (8 lanes = one line, a 64-lane store 8 lines in 8 tiles, 8 x 65 KB apart, instead
-    // of 64 16-byte pieces one pitch apart), and stage 2 (zfft.hip zfft_tiles_kernel) reads whole lines once, the 8
-    // columns of a tile together.  (Measured at 4096^2 -> 512^2: DESIGN.md 4.2.)
-    static const bool tiles_off = diag_int("ML_G_TILED", 1) == 0;   // (diagnostic builds: the plain transposed G)
-    const int r3y = pl.fft_y.N_eff / 256;
-    const GLayout g_layout = !g_transposed ? GLayout::row_major
-                             : (!tiles_off && my % 8 == 0 && mx <= zf::TL_NT && r3y >= 3 && r3y <= 16 &&
-                                pl.fft_y.passes <= 1 && pl.fft_x.passes <= 1 && !pl.fft_y.A && !pl.fft_x.A)
-                                 ? GLayout::tiled
-                                 : GLayout::transposed;
-    // The TRANSPOSED result of rows up to 8192 samples lies in physical pieces of 4 MB, each an allocation of its own,
-    // mapped side by side (common.h PieceBuf).  Stage 1 stores it in 16-byte pieces one pitch (65 KB at 4096 samples)
-    // apart, and how fast those go is decided by the physical layout behind the buffer: 0.33 ms over one physically
-    // contiguous allocation (whatever the pitch), 0.5-1.3 ms in pieces below the 2 MB translation fragment, 0.178-0.190
-    // in pieces of 2 to 8 MB in three processes of four (8192 samples, pitch 131 KB: 0.75 in 2 MB pieces, 0.70 in 4 MB,
-    // 0.72 in 8 MB) - and 0.183 or 0.200, one of two each, from hipMalloc, whose layout is whatever the driver's free
-    // lists hold: the two 'modes' of rounds 4-6 (profiles/r06_ab_runs.txt).  The two-pass kernel of
-    // longer rows (one 152 KB workgroup per CU, whole lines stored) is the other way round: 16384^2 -> 1024^2 stage 1
-    // 4.01-4.16 ms over hipMalloc, 4.95 in 4 MB pieces, 4.32 in 8, 4.45 in 16, 4.13 in 32, 4.03 in 64 - it keeps
-    // hipMalloc, as does every other layout.  A context that runs both kinds holds both buffers.
-    // (METALENS_HIP_PIECES=0 in the environment: plain hipMalloc - the way out should a driver's virtual-memory API
-    // misbehave; so is a PieceBuf that has failed once: it is not tried again)
-    static const bool pieces_off = [] { const char *e = getenv("METALENS_HIP_PIECES"); return e && e[0] == '0'; }();
-    const size_t g_bytes = g_transposed ? (size_t)4 * my * g_ld * 2 * sizeof(double)
-                                        : (size_t)pl.stage1_splits * 4 * nxl * my * 2 * sizeof(double);
-    const bool pieced = g_transposed && nxl <= 8192 && !pieces_off && pl.stage1_pieces.reserve(g_bytes) == ML_OK;
-    if (!pieced) ML_TRY(pl.stage1.reserve(g_bytes));
-    double *const g_buf = pieced ? pl.stage1_pieces.as<double>() : pl.stage1.as<double>();   // G of this call
-    // the folded stage 2 pays once its grid (32-row x 64-half-direction tiles over the 4*my
-    // transposed rows) fills the chip; below that the generic GEMM with 32 x 32 tiles is faster
-    static const long fold2_min_tiles = diag_int("ML_FOLD2_MIN_TILES", 32);
-    const bool whole = (row0 == 0 && nxl == pl.nx_total);
-    const bool fold2_pays = (long)((4 * my + 31) / 32) * ((pl.fold2_S + 63) / 64) >= fold2_min_tiles;
-    const bool fft1 = pl.fft_y.ok, fft2 = pl.fft_x.ok && !pl.pair_list;
-    // Rows of a synthesised field that lie wholly outside the lens circle are zeros, and so are their row transforms:
-    // both FFT stages run on the resident rows [trim_lo, trim_hi) only (7 % fewer of each in a window of the size
-    // good_fft_number hands out, nearfield.py:30-36, 95-97).  Stage 1 neither reads those rows nor writes their part
-    // of G; stage 2 takes them as rows the rank does not hold (FftArgs::a0 / h0: read as zero without a load; the short
-    // transforms of an interleaved shard likewise, by LOCAL row).
-    // Which rows: the kernels' own inside-the-lens test at the sample nearest y = 0 (row_extent_kernel), on the host's
-    // copies of the axes.
-    int trim_lo = 0, trim_hi = nxl;
-    if (fft1 && fft2 && !mirrored && ctx->row_first_valid && (int)ctx->h_x_pts.size() == nxl &&
-        (int)ctx->h_y_pts.size() == ny && ctx->r_outer > 0) {
-        if (ctx->trim_key[0] != ctx->grid_serial || ctx->trim_key[1] != ctx->layout_serial) {
-            double ymin = INFINITY;
-            for (double y : ctx->h_y_pts) ymin = std::min(ymin, std::fabs(y));
-            int lo = nxl, hi = 0;
-            for (int i = 0; i < nxl; ++i) {
-                const double x = ctx->h_x_pts[i];
-                if (!(std::sqrt(x * x + ymin * ymin) > ctx->r_outer)) {
-                    lo = std::min(lo, i);
-                    hi = i + 1;
-                }
+    return ML_OK;
+}
+
+// (diagnostic builds: the route's knobs from the environment, read once)
+static const RouteKnobs &route_knobs() {
+    static const RouteKnobs knobs = [] {
+        RouteKnobs k;
+        k.stage1_split = diag_int("ML_STAGE1_SPLIT", k.stage1_split);
+        k.g_skew = diag_int("ML_G_SKEW", k.g_skew);
+        k.g_tiled = diag_int("ML_G_TILED", k.g_tiled);
+        k.fold2_min_tiles = diag_int("ML_FOLD2_MIN_TILES", (int)k.fold2_min_tiles);
+        k.no_row_trim = diag_int("ML_NO_ROW_TRIM", k.no_row_trim);
+        k.no_gt_direct = diag_int("ML_NO_GT_DIRECT", k.no_gt_direct);
+        return k;
+    }();
+    return knobs;
+}
+
+// The resident rows that meet the lens circle (transform_route.h), into ctx->trim_rows, found once per (grid, layout).
+// false: the resident fields carry no row_first for their grid (uploaded fields) - nothing is known about their rows.
+static bool trim_rows_of(ml_ctx *ctx) {
+    const int nxl = ctx->nx;
+    if (!ctx->row_first_valid || (int)ctx->h_x_pts.size() != nxl || (int)ctx->h_y_pts.size() != ctx->ny ||
+        !(ctx->r_outer > 0))
+        return false;
+    if (ctx->trim_key[0] != ctx->grid_serial || ctx->trim_key[1] != ctx->layout_serial) {
+        double ymin = INFINITY;
+        for (double y : ctx->h_y_pts) ymin = std::min(ymin, std::fabs(y));
+        int lo = nxl, hi = 0;
+        for (int i = 0; i < nxl; ++i) {
+            const double x = ctx->h_x_pts[i];
+            if (!(std::sqrt(x * x + ymin * ymin) > ctx->r_outer)) {
+                lo = std::min(lo, i);
+                hi = i + 1;
             }
-            if (lo >= hi) lo = 0, hi = std::min(nxl, 1);   // (an empty window keeps one row: nothing to gain)
-            ctx->trim_rows[0] = lo;
-            ctx->trim_rows[1] = hi;
-            ctx->trim_key[0] = ctx->grid_serial;
-            ctx->trim_key[1] = ctx->layout_serial;
         }
-        static const bool no_trim = diag_int("ML_NO_ROW_TRIM", 0) != 0;
-        if (!no_trim) {
-            trim_lo = ctx->trim_rows[0];
-            trim_hi = ctx->trim_rows[1];
-        }
+        if (lo >= hi) lo = 0, hi = std::min(nxl, 1);   // (an empty window keeps one row: nothing to gain)
+        ctx->trim_rows[0] = lo;
+        ctx->trim_rows[1] = hi;
+        ctx->trim_key[0] = ctx->grid_serial;
+        ctx->trim_key[1] = ctx->layout_serial;
     }
-    const int nxt = trim_hi - trim_lo;   // rows per field plane the FFT stages work on
-    const bool use_fold2 = !fft2 && !pl.pair_list && pl.fold2 && fold2_pays && (mirrored || whole) && sh.kind != 2;
-    // both stages folded: stage 1 writes its result already transposed for stage 2
-    static const bool no_direct = diag_int("ML_NO_GT_DIRECT", 0) != 0;
-    const bool gt_direct = pl.fold && use_fold2 && !no_direct;
-    FoldIO io1;
-    int want_split2 = 1;
-    if (gt_direct) {
-        // stage 2's tables first: stage 1's epilogue applies stage 2's input modulation
-        ML_TRY(stage2_tables(ctx, row0, mirrored, &want_split2));
-        io1.out_t_rows = nxl;
-        io1.out_E = pl.fold2_has_E ? pl.fold2_E.as<double>() : nullptr;
+    return true;
+}
+
+// G of this call: in physical pieces where the route wants them and they can be had (transform_route.h), else hipMalloc
+static int reserve_g(FarfieldPlan &pl, const TransformRoute &rt, double **g) {
+    static const bool pieces_off = [] { const char *e = getenv("METALENS_HIP_PIECES"); return e && e[0] == '0'; }();
+    const size_t bytes = (size_t)pl.stage1_splits * rt.g_bytes;
+    const bool pieced = rt.pieces_wanted && !pieces_off && pl.stage1_pieces.reserve(bytes) == ML_OK;
+    if (!pieced) ML_TRY(pl.stage1.reserve(bytes));
+    *g = pieced ? pl.stage1_pieces.as<double>() : pl.stage1.as<double>();
+    return ML_OK;
+}
+
+// the axis part of a call: the lattice of (a sub-sequence of) the axis, its M wanted bins and its tables
+static void call_axis(ZfftCall &c, const FarfieldPlan &pl, const ZfftAxis &ax, int M) {
+    c.passes = ax.passes;
+    c.N_eff = ax.N_eff / ax.split;
+    c.M = M;
+    c.j0 = ax.j0;
+    c.jstep = ax.jstep;
+    c.pad1 = ax.pad1;
+    c.pad2 = ax.pad2;
+    c.tw1 = ax.A ? ax.tw.as<double>() : pl.fft_tw1.as<double>();
+    c.mixA = ax.A;
+    c.mixB = ax.B;
+    c.wk = ax.wk.as<double>();
+    c.pj = ax.pj.as<double>();
+    c.kbin = ax.kbin.as<int>();
+}
+
+// the output part of a column pass: row (f, b) of the call, bin a -> V[3 - f][a][b] * alpha_f
+static void call_into_vectors(ZfftCall &c, const FarfieldPlan &pl, const double *alpha) {
+    c.out = pl.vectors.as<double>() + (size_t)3 * pl.mx * pl.my * 2;
+    c.out_rb = pl.my;
+    c.out_s1 = -(int64_t)pl.mx * pl.my;
+    c.out_s2 = 1;
+    c.out_es = pl.my;
+    for (int k = 0; k < 4; ++k) c.alpha[k] = alpha[k];
+    c.alpha_rb = pl.my;
+}
+
+// one launch per sub-sequence of the axis (two-level: sub-sequence i of every row adds its bins, zfft.hip zfft_split)
+static int run_subsequences(hipStream_t stream, ZfftCall &c, const ZfftAxis &ax, int accumulate) {
+    for (int i = 0; i < ax.split; ++i) {
+        c.sub_s = ax.split;
+        c.sub_i = i;
+        c.pj = ax.pj.as<double>() + (size_t)i * c.M * 2;
+        c.accumulate = i > 0 ? 1 : accumulate;
+        ML_TRY(zfft_run(stream, c));
     }
+    return ML_OK;
+}
+
+// stage 1 as a pruned FFT along y
+static int stage1_fft(ml_ctx *ctx, const TransformRoute &rt, double *g) {
+    FarfieldPlan &pl = ctx->plan;
+    const int nxl = ctx->nx, ny = pl.ny, my = pl.my, trim_lo = rt.trim_lo, nxt = rt.trim_hi - rt.trim_lo;
+    const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, trim_lo);
+    ZfftCall c;
+    call_axis(c, pl, pl.fft_y, my);
+    c.n_valid = ny;
+    // row (f, n1') of the launch = row n1 = trim_lo + n1' of field plane f
+    c.in = ctx->set_ptr() + (size_t)trim_lo * ny * 2;
+    c.rows = 4 * nxt;
+    c.in_rb = nxt;
+    c.in_s1 = (int64_t)nxl * ny;
+    c.in_s2 = ny;
+    c.in_es = 1;
+    c.a0 = 0;
+    c.h0 = ny;
+    c.a1 = c.h1 = 0;
+    c.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() + trim_lo : nullptr;
+    c.rf_mod = nxt;
+    c.out = g + (size_t)v.off * 2;
+    c.out_rb = nxt;
+    c.out_s1 = v.s_f;
+    c.out_s2 = v.s_row;
+    c.out_es = v.s_bin;
+    c.tiled_out = rt.g_layout == GLayout::tiled;
+    for (int k = 0; k < 4; ++k) c.alpha[k] = 1.0;
+    c.alpha_rb = c.rows;   // (every row: alpha[0])
+    return run_subsequences(ctx->stream, c, pl.fft_y, 0);
+}
+
+// stage 1: G[(f, n1)][b] = sum_n2 F_f[n1][n2] * exp(-i k y'_n2 uy_b)
+static int stage1(ml_ctx *ctx, const TransformRoute &rt, double *g) {
+    FarfieldPlan &pl = ctx->plan;
+    const int nxl = ctx->nx, ny = pl.ny, my = pl.my;
     // resident fields that the synthesis already multiplied by this plan's input modulation
     // (ml_nearfield_premodulate): stage 1 then runs without it
     bool fields_premodulated = false;
@@ -1036,263 +1026,190 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
         }
         fields_premodulated = true;
     }
-    const double one[4] = {1.0, 1.0, 1.0, 1.0};
-    // stage 1 as a pruned FFT along y
-    auto launch_fft1 = [&]() -> int {
-        ZfftCall c;
-        const int split1 = pl.fft_y.split;
-        c.passes = pl.fft_y.passes;
-        c.N_eff = pl.fft_y.N_eff / split1;
-        c.n_valid = ny;
-        c.M = my;
-        c.j0 = pl.fft_y.j0;
-        c.jstep = pl.fft_y.jstep;
-        c.pad1 = pl.fft_y.pad1;
-        c.pad2 = pl.fft_y.pad2;
-        // row (f, n1') of the launch = row n1 = trim_lo + n1' of field plane f
-        c.in = ctx->set_ptr() + (size_t)trim_lo * ny * 2;
-        c.rows = 4 * nxt;
-        c.in_rb = nxt;
-        c.in_s1 = (int64_t)nxl * ny;
-        c.in_s2 = ny;
-        c.in_es = 1;
-        c.a0 = 0;
-        c.h0 = ny;
-        c.a1 = c.h1 = 0;
-        c.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() + trim_lo : nullptr;
-        c.rf_mod = nxt;
-        c.out = g_buf + (size_t)trim_lo * my * 2;
-        c.out_rb = nxt;
-        c.out_s1 = (int64_t)nxl * my;
-        c.out_s2 = my;
-        c.out_es = 1;
-        if (g_layout == GLayout::transposed) {   // row (f, n1), bin b -> G[f][b][n1]
-            c.out = g_buf + (size_t)trim_lo * 2;
-            c.out_rb = nxt;
-            c.out_s1 = (int64_t)my * g_ld;
-            c.out_s2 = 1;
-            c.out_es = g_ld;
-        } else if (g_layout == GLayout::tiled) {   // row (f, n1), bin b -> G[f][b / 8][n1][b % 8]
-            c.out = g_buf + (size_t)trim_lo * 8 * 2;
-            c.out_rb = nxt;
-            c.out_s1 = (int64_t)my * g_ld;
-            c.out_s2 = 8;
-            c.out_es = 8 * g_ld;
-            c.tiled_out = 1;
+    ProfScope scope(ctx, ML_K_ZGEMM_STAGE1);
+    if (rt.stage1 == Stage1Kind::fft) return stage1_fft(ctx, rt, g);
+    if (rt.stage1 == Stage1Kind::folded) {
+        FoldIO io;
+        if (rt.gt_direct) {   // (stage2_tables has run: fold2_E is stage 2's input modulation)
+            io.out_t_rows = nxl;
+            io.out_E = pl.fold2_has_E ? pl.fold2_E.as<double>() : nullptr;
         }
-        c.tw1 = pl.fft_y.A ? pl.fft_y.tw.as<double>() : pl.fft_tw1.as<double>();
-        c.mixA = pl.fft_y.A;
-        c.mixB = pl.fft_y.B;
-        c.wk = pl.fft_y.wk.as<double>();
-        c.pj = pl.fft_y.pj.as<double>();
-        c.kbin = pl.fft_y.kbin.as<int>();
-        for (int k = 0; k < 4; ++k) c.alpha[k] = 1.0;
-        c.alpha_rb = c.rows;   // (every row: alpha[0])
-        c.accumulate = 0;
-        if (split1 > 1) {
-            // two-level: sub-sequence i of every row adds its bins (zfft.hip zfft_split)
-            for (int i = 0; i < split1; ++i) {
-                c.sub_s = split1;
-                c.sub_i = i;
-                c.pj = pl.fft_y.pj.as<double>() + (size_t)i * my * 2;
-                c.accumulate = i > 0;
-                ML_TRY(zfft_run(ctx->stream, c));
-            }
-        } else {
-            ML_TRY(zfft_run(ctx->stream, c));
-        }
-        return ML_OK;
-    };
-    {
-        // stage 1: G[(f, n1)][b] = sum_n2 F_f[n1][n2] * exp(-i k y'_n2 uy_b)
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE1);
-        if (fft1) {
-            ML_TRY(launch_fft1());
-        } else if (pl.fold)
-            ML_TRY(zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->set_ptr(), ny,
-                                pl.fold_cm.as<double>(), pl.fold_sm.as<double>(),
-                                pl.fold_r4.as<double>(), pl.fold_T,
-                                pl.fold_S,
-                                pl.fold_has_E && !fields_premodulated ? pl.fold_E.as<double>() : nullptr,
-                                pl.fold_D.as<double>(), g_buf, my, my,
-                                ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr, nxl,
-                                want_split1, (int64_t)4 * nxl * my, ctx->gemm_f32 != 0, io1));
-        else
-            ML_TRY(zgemm(ctx->stream, 4 * nxl, my, ny, one, ctx->set_ptr(), ny, 0,
-                         pl.tw_y.as<double>(), my, 0, g_buf, my, 0, 1, 0));
+        return zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->set_ptr(), ny, pl.fold_cm.as<double>(),
+                            pl.fold_sm.as<double>(), pl.fold_r4.as<double>(), pl.fold_T, pl.fold_S,
+                            pl.fold_has_E && !fields_premodulated ? pl.fold_E.as<double>() : nullptr,
+                            pl.fold_D.as<double>(), g, my, my,
+                            ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr, nxl, rt.want_split1,
+                            (int64_t)4 * nxl * my, ctx->gemm_f32 != 0, io);
     }
+    const double one[4] = {1.0, 1.0, 1.0, 1.0};
+    return zgemm(ctx->stream, 4 * nxl, my, ny, one, ctx->set_ptr(), ny, 0, pl.tw_y.as<double>(), my, 0, g, my, 0, 1,
+                 0);
+}
+
+// the split-K slabs of a folded stage 1 summed into the first, for a stage 2 that reads one array
+static int collapse_stage1(ml_ctx *ctx, double *g) {
+    FarfieldPlan &pl = ctx->plan;
+    if (pl.stage1_splits > 1) {
+        const size_t n = (size_t)4 * ctx->nx * pl.my;
+        hipLaunchKernelGGL(zsum_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                           ctx->stream, reinterpret_cast<double2 *>(g), n, pl.stage1_splits);
+        ML_HIP(hipGetLastError());
+        pl.stage1_splits = 1;
+    }
+    return ML_OK;
+}
+
+// stage 2 of an interleaved shard: `block` short transforms per column (see interleave_block).
+// Transform i reads the local rows i, i + s, i + 2 s, ... of column (f, b) and adds its M
+// bins, carried to the full lattice by pj[i][.], into V[3 - f][.][b]
+static int stage2_interleaved(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, const double *g,
+                              const double *alpha, int accumulate) {
+    FarfieldPlan &pl = ctx->plan;
+    const int nxl = ctx->nx, mx = pl.mx, my = pl.my;
+    const int s = sh.block, G = sh.n_ranks, N = pl.fft_x.N_eff;
+    const int stuff = interleave_stuff(N / (s * G)), Nsub = N / (s * G) * stuff;   // the lattice it runs on
+    const int n_have = pl.nx_total / (s * G);   // samples of each short transform that exist
+    const long key[4] = {pl.serial, s, G, sh.rank};
+    if (memcmp(key, pl.il_key, sizeof key) != 0) {
+        ML_TRY(pl.il_wk.reserve((size_t)mx * 2 * sizeof(double)));
+        ML_TRY(pl.il_kbin.reserve((size_t)mx * sizeof(int)));
+        ML_TRY(pl.il_pj.reserve((size_t)s * mx * 2 * sizeof(double)));
+        ML_TRY(zfft_build_interleave_tables(ctx->stream, pl.il_wk.as<double>(), pl.il_pj.as<double>(),
+                                            pl.il_kbin.as<int>(), mx, pl.fft_x.j0, Nsub, N,
+                                            pl.nx_total - pl.nx_total / 2, s * sh.rank, s, pl.fft_x.jstep));
+        zfft_choose_pads(Nsub, mx, pl.fft_x.j0, &pl.il_pad1, &pl.il_pad2, pl.fft_x.jstep);
+        memcpy(pl.il_key, key, sizeof key);
+    }
+    // (the row-major G from its first local row: the rows stage 1 left out are told by a0 / h0)
+    const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, 0);
+    ZfftCall c;
+    c.N_eff = Nsub;
+    c.n_valid = n_have;
+    c.M = mx;
+    c.j0 = pl.fft_x.j0;
+    c.jstep = pl.fft_x.jstep;
+    c.pad1 = pl.il_pad1;
+    c.pad2 = pl.il_pad2;
+    c.in = g;
+    c.rows = 4 * my;
+    c.in_rb = v.cols;
+    c.in_s1 = v.s_f;
+    c.in_s2 = v.s_bin;
+    c.in_es = (int64_t)s * v.s_row;
+    // (local rows [a0, a0 + h0) exist in G: stage 1 left out the rows outside the lens circle)
+    c.a0 = rt.trim_lo;
+    c.h0 = rt.trim_hi - rt.trim_lo;
+    c.a1 = c.h1 = 0;
+    c.row_first = nullptr;
+    c.rf_mod = 1;
+    call_into_vectors(c, pl, alpha);
+    c.tw1 = pl.fft_tw1.as<double>();
+    c.wk = pl.il_wk.as<double>();
+    c.pj = pl.il_pj.as<double>();
+    c.kbin = pl.il_kbin.as<int>();
+    c.accumulate = accumulate;
+    return zfft_run_interleaved(ctx->stream, c, s, my, stuff);
+}
+
+// stage 2 along x as a pruned FFT over the columns of stage 1's result: row (f, b) reads
+// G[f][n1][b] for the resident n1 (zero elsewhere) and writes V[3 - f][a][b] * alpha_f
+static int stage2_fft(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, const double *g, const double *alpha,
+                      int accumulate) {
+    FarfieldPlan &pl = ctx->plan;
+    const int nxl = ctx->nx, mx = pl.mx, my = pl.my;
+    const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, rt.trim_lo);
+    ZfftCall c;
+    call_axis(c, pl, pl.fft_x, mx);
+    c.n_valid = pl.nx_total;
+    c.in = g + (size_t)v.off * 2;
+    c.rows = 4 * my;
+    c.in_rb = v.cols;   // (tiled: tile (f, t) at f in_s1 + t in_s2, my / 8 tiles per plane)
+    c.in_s1 = v.s_f;
+    c.in_s2 = v.s_bin;
+    c.in_es = v.s_row;
+    c.second = rt.g_layout == GLayout::transposed;
+    if (sh.kind == ShardKind::mirrored) {
+        c.a0 = sh.row0;
+        c.h0 = nxl / 2;
+        c.a1 = pl.nx_total - sh.row0 - nxl / 2;
+        c.h1 = nxl / 2;
+    } else {
+        // (resident rows = the rows stage 1 transformed: those outside the lens circle were never written)
+        c.a0 = sh.row0 + rt.trim_lo;
+        c.h0 = rt.trim_hi - rt.trim_lo;
+        c.a1 = c.h1 = 0;
+    }
+    c.row_first = nullptr;
+    c.rf_mod = 1;
+    call_into_vectors(c, pl, alpha);
+    if (rt.stage2 == Stage2Kind::fft_tiles) {
+        c.accumulate = accumulate;
+        return zfft_run_tiles(ctx->stream, c);
+    }
+    return run_subsequences(ctx->stream, c, pl.fft_x, accumulate);
+}
+
+// stage 2: V_f[a][b] = alpha_f * sum_n1 exp(-i k x'_n1 ux_a) * G[(f, n1)][b];
+// batch entry f writes radiation-vector slot 3 - f.  One GEMM per run of resident rows: two on a mirrored shard
+static int stage2_generic(ml_ctx *ctx, const Shard &sh, const double *g, const double *alpha, int accumulate) {
+    FarfieldPlan &pl = ctx->plan;
+    const int nxl = ctx->nx, mx = pl.mx, my = pl.my, row0 = sh.row0;
+    const int runs = sh.kind == ShardKind::mirrored ? 2 : 1, h = nxl / runs;
+    double *slot3 = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
+    for (int run = 0; run < runs; ++run) {
+        const int first = run == 0 ? row0 : pl.nx_total - row0 - h;
+        ML_TRY(zgemm(ctx->stream, mx, my, h, alpha, pl.tw_x.as<double>() + (size_t)first * 2, pl.nx_total, 0,
+                     g + (size_t)run * h * my * 2, my, (int64_t)nxl * my, slot3, my, -(int64_t)mx * my, 4,
+                     run == 0 ? accumulate : 1));
+    }
+    return ML_OK;
+}
+
+static int stage2(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, double *g, int want_split2,
+                  int accumulate) {
+    FarfieldPlan &pl = ctx->plan;
+    const int mirrored = sh.kind == ShardKind::mirrored;
     const double dA = pl.dxp * pl.dyp;
     // fields are stored Ex,Ey,Hx,Hy; radiation vectors Nx,Ny,Lx,Ly = -Hy, Hx, Ey, -Ex (x dA)
     const double alpha[4] = {-dA, dA, dA, -dA};
-    auto collapse_stage1 = [&]() -> int {
-        if (pl.stage1_splits > 1) {
-            const size_t n = (size_t)4 * nxl * my;
-            hipLaunchKernelGGL(zsum_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                               ctx->stream, reinterpret_cast<double2 *>(g_buf), n, pl.stage1_splits);
-            ML_HIP(hipGetLastError());
-            pl.stage1_splits = 1;
-        }
-        return ML_OK;
-    };
-    if (sh.kind == 2) {
-        // stage 2 of an interleaved shard: `block` short transforms per column (see interleave_block).
-        // Transform i reads the local rows i, i + s, i + 2 s, ... of column (f, b) and adds its M
-        // bins, carried to the full lattice by pj[i][.], into V[3 - f][.][b]
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE2);
-        ML_TRY(collapse_stage1());
-        const int s = sh.block, G = sh.n_ranks, N = pl.fft_x.N_eff;
-        const int stuff = interleave_stuff(N / (s * G)), Nsub = N / (s * G) * stuff;   // the lattice it runs on
-        const int n_have = pl.nx_total / (s * G);   // samples of each short transform that exist
-        const long key[4] = {pl.serial, s, G, sh.rank};
-        if (memcmp(key, pl.il_key, sizeof key) != 0) {
-            ML_TRY(pl.il_wk.reserve((size_t)mx * 2 * sizeof(double)));
-            ML_TRY(pl.il_kbin.reserve((size_t)mx * sizeof(int)));
-            ML_TRY(pl.il_pj.reserve((size_t)s * mx * 2 * sizeof(double)));
-            ML_TRY(zfft_build_interleave_tables(ctx->stream, pl.il_wk.as<double>(), pl.il_pj.as<double>(),
-                                                pl.il_kbin.as<int>(), mx, pl.fft_x.j0, Nsub, N,
-                                                pl.nx_total - pl.nx_total / 2, s * sh.rank, s, pl.fft_x.jstep));
-            zfft_choose_pads(Nsub, mx, pl.fft_x.j0, &pl.il_pad1, &pl.il_pad2, pl.fft_x.jstep);
-            memcpy(pl.il_key, key, sizeof key);
-        }
-        {
-            ZfftCall c;
-            c.N_eff = Nsub;
-            c.n_valid = n_have;
-            c.M = mx;
-            c.j0 = pl.fft_x.j0;
-            c.jstep = pl.fft_x.jstep;
-            c.pad1 = pl.il_pad1;
-            c.pad2 = pl.il_pad2;
-            c.in = g_buf;
-            c.rows = 4 * my;
-            c.in_rb = my;
-            c.in_s1 = (int64_t)nxl * my;
-            c.in_s2 = 1;
-            c.in_es = (int64_t)s * my;
-            // (local rows [a0, a0 + h0) exist in G: stage 1 left out the rows outside the lens circle)
-            c.a0 = trim_lo;
-            c.h0 = nxt;
-            c.a1 = c.h1 = 0;
-            c.row_first = nullptr;
-            c.rf_mod = 1;
-            c.out = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
-            c.out_rb = my;
-            c.out_s1 = -(int64_t)mx * my;
-            c.out_s2 = 1;
-            c.out_es = my;
-            c.tw1 = pl.fft_tw1.as<double>();
-            c.wk = pl.il_wk.as<double>();
-            c.pj = pl.il_pj.as<double>();
-            c.kbin = pl.il_kbin.as<int>();
-            for (int k = 0; k < 4; ++k) c.alpha[k] = alpha[k];
-            c.alpha_rb = my;
-            c.accumulate = accumulate;
-            ML_TRY(zfft_run_interleaved(ctx->stream, c, s, my, stuff));
-        }
-    } else if (fft2) {
-        // stage 2 along x as a pruned FFT over the columns of stage 1's result: row (f, b) reads
-        // G[f][n1][b] for the resident n1 (zero elsewhere) and writes V[3 - f][a][b] * alpha_f
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE2);
-        ML_TRY(collapse_stage1());
-        ZfftCall c;
-        const int split2 = pl.fft_x.split;
-        c.passes = pl.fft_x.passes;
-        c.N_eff = pl.fft_x.N_eff / split2;
-        c.n_valid = pl.nx_total;
-        c.M = mx;
-        c.j0 = pl.fft_x.j0;
-        c.jstep = pl.fft_x.jstep;
-        c.pad1 = pl.fft_x.pad1;
-        c.pad2 = pl.fft_x.pad2;
-        c.in = g_buf;
-        c.rows = 4 * my;
-        c.in_rb = my;
-        c.in_s1 = (int64_t)nxl * my;
-        c.in_s2 = 1;
-        c.in_es = my;
-        if (g_layout == GLayout::transposed) {
-            c.in_s1 = (int64_t)my * g_ld;
-            c.in_s2 = g_ld;
-            c.in_es = 1;
-            c.second = 1;
-        } else if (g_layout == GLayout::tiled) {   // tile (f, t) at f in_s1 + t in_s2, my / 8 tiles per plane
-            c.in_s1 = (int64_t)my * g_ld;
-            c.in_s2 = 8 * g_ld;
-            c.in_rb = my / 8;
-            c.in_es = 8;
-        }
-        if (mirrored) {
-            c.a0 = row0;
-            c.h0 = nxl / 2;
-            c.a1 = pl.nx_total - row0 - nxl / 2;
-            c.h1 = nxl / 2;
-        } else {
-            // (resident rows = the rows stage 1 transformed: those outside the lens circle were never written)
-            c.a0 = row0 + trim_lo;
-            c.h0 = nxt;
-            c.a1 = c.h1 = 0;
-            c.in = g_buf + (size_t)trim_lo * c.in_es * 2;
-        }
-        c.row_first = nullptr;
-        c.rf_mod = 1;
-        c.out = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
-        c.out_rb = my;
-        c.out_s1 = -(int64_t)mx * my;
-        c.out_s2 = 1;
-        c.out_es = my;
-        c.tw1 = pl.fft_x.A ? pl.fft_x.tw.as<double>() : pl.fft_tw1.as<double>();
-        c.mixA = pl.fft_x.A;
-        c.mixB = pl.fft_x.B;
-        c.wk = pl.fft_x.wk.as<double>();
-        c.pj = pl.fft_x.pj.as<double>();
-        c.kbin = pl.fft_x.kbin.as<int>();
-        for (int k = 0; k < 4; ++k) c.alpha[k] = alpha[k];
-        c.alpha_rb = my;
-        if (g_layout == GLayout::tiled) {
-            c.accumulate = accumulate;
-            ML_TRY(zfft_run_tiles(ctx->stream, c));
-        } else for (int i = 0; i < split2; ++i) {
-            c.sub_s = split2;
-            c.sub_i = i;
-            c.pj = pl.fft_x.pj.as<double>() + (size_t)i * mx * 2;
-            c.accumulate = i > 0 ? 1 : accumulate;
-            ML_TRY(zfft_run(ctx->stream, c));
-        }
-    } else if (use_fold2) {
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE2);
-        ML_TRY(stage2_folded(ctx, row0, mirrored, accumulate, alpha, gt_direct, gt_direct,
-                             want_split2));
-    } else if (!pl.pair_list && mirrored) {
-        // generic stage 2 on the two runs of a mirrored shard
-        ML_TRY(need_tw_x(ctx));
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE2);
-        ML_TRY(collapse_stage1());
-        const int h = nxl / 2;
-        double *slot3 = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
-        for (int run = 0; run < 2; ++run) {
-            const int first = run == 0 ? row0 : pl.nx_total - row0 - h;
-            ML_TRY(zgemm(ctx->stream, mx, my, h, alpha, pl.tw_x.as<double>() + (size_t)first * 2,
-                         pl.nx_total, 0, g_buf + (size_t)run * h * my * 2, my,
-                         (int64_t)nxl * my, slot3, my, -(int64_t)mx * my, 4,
-                         run == 0 ? accumulate : 1));
-        }
-    } else if (!pl.pair_list) {
-        // stage 2: V_f[a][b] = alpha_f * sum_n1 exp(-i k x'_n1 ux_a) * G[(f, n1)][b];
-        // batch entry f writes radiation-vector slot 3 - f
-        ML_TRY(need_tw_x(ctx));
-        ProfScope scope(ctx, ML_K_ZGEMM_STAGE2);
-        ML_TRY(collapse_stage1());
-        double *slot3 = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
-        ML_TRY(zgemm(ctx->stream, mx, my, nxl, alpha, pl.tw_x.as<double>() + (size_t)row0 * 2,
-                     pl.nx_total, 0, g_buf, my, (int64_t)nxl * my, slot3, my,
-                     -(int64_t)mx * my, 4, accumulate));
-    } else {
-        ML_TRY(need_tw_x(ctx));
-        ProfScope scope(ctx, ML_K_COLDOT);
-        ML_TRY(collapse_stage1());
-        ML_TRY(zcoldot(ctx->stream, 4, nxl, mx, alpha, pl.tw_x.as<double>(), mx, row0,
-                       g_buf, pl.vectors.as<double>(), accumulate));
+    const bool needs_tw_x = rt.stage2 == Stage2Kind::generic || rt.stage2 == Stage2Kind::generic_mirrored ||
+                            rt.stage2 == Stage2Kind::coldot;
+    if (needs_tw_x) ML_TRY(need_tw_x(ctx));
+    ProfScope scope(ctx, rt.stage2 == Stage2Kind::coldot ? ML_K_COLDOT : ML_K_ZGEMM_STAGE2);
+    if (rt.stage2 == Stage2Kind::folded)   // (sums stage 1's slabs itself)
+        return stage2_folded(ctx, sh.row0, mirrored, accumulate, alpha, rt.gt_direct, rt.gt_direct, want_split2);
+    ML_TRY(collapse_stage1(ctx, g));
+    switch (rt.stage2) {
+    case Stage2Kind::interleaved: return stage2_interleaved(ctx, rt, sh, g, alpha, accumulate);
+    case Stage2Kind::fft:
+    case Stage2Kind::fft_tiles: return stage2_fft(ctx, rt, sh, g, alpha, accumulate);
+    case Stage2Kind::coldot:
+        return zcoldot(ctx->stream, 4, ctx->nx, pl.mx, alpha, pl.tw_x.as<double>(), pl.mx, sh.row0, g,
+                       pl.vectors.as<double>(), accumulate);
+    default: return stage2_generic(ctx, sh, g, alpha, accumulate);
     }
+}
+
+// One far-field step: validate -> route (transform_route.h) -> reserve G -> stage 1 -> stage 2
+static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
+    ML_TRY(validate_shard(ctx, sh, accumulate));
+    FarfieldPlan &pl = ctx->plan;
+    ML_HIP(hipSetDevice(ctx->device));
+    // a deferred unfold of the previous transform: needed if this one adds to it, moot otherwise
+    if (accumulate)
+        ML_TRY(flush_unfold(ctx));
+    else
+        pl.unfold_pending = false;
+    const TransformRoute rt =
+        transform_route(pl, pl.fft_y, pl.fft_x, sh, ctx->nx, trim_rows_of(ctx), ctx->trim_rows, route_knobs());
+    pl.stage1_splits = pl.fold ? zfold_splits(pl.fold_T, rt.want_split1) : 1;
+    double *g = nullptr;
+    ML_TRY(reserve_g(pl, rt, &g));
+    int want_split2 = 1;
+    // both stages folded: stage 2's tables first, stage 1's epilogue applies stage 2's input modulation
+    if (rt.gt_direct) ML_TRY(stage2_tables(ctx, sh.row0, sh.kind == ShardKind::mirrored, &want_split2));
+    ML_TRY(stage1(ctx, rt, g));
+    ML_TRY(stage2(ctx, rt, sh, g, want_split2, accumulate));
     pl.have_vectors = true;
     pl.amplitudes_reduced = false;
     return ML_OK;
@@ -1300,7 +1217,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
 
 static Shard block_shard(int row0, int mirrored) {
     Shard sh;
-    sh.kind = mirrored ? 1 : 0;
+    sh.kind = mirrored ? ShardKind::mirrored : ShardKind::block;
     sh.row0 = row0;
     return sh;
 }
@@ -1337,7 +1254,7 @@ int ml_farfield_interleave_block(ml_ctx *ctx, int n_ranks, int *block) {
 
 int ml_farfield_transform_interleaved_async(ml_ctx *ctx, int block, int n_ranks, int rank, int accumulate) {
     Shard sh;
-    sh.kind = 2;
+    sh.kind = ShardKind::interleaved;
     sh.block = block;
     sh.n_ranks = n_ranks;
     sh.rank = rank;

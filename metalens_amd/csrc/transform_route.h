@@ -1,0 +1,212 @@
+// Which way a far-field transform call goes (farfield.hip transform_impl): the kind of each stage, the layout of
+// stage 1's result G, the allocator that backs it and the rows both stages work on - decided here, as a value, from
+// plain facts; farfield.hip's stage functions consume it.
+//
+// Host code without HIP types: compiled by hipcc into farfield.hip and by the host compiler into
+// tools/transform_route.cpp, which prints the route of given plan facts (tests/test_transform_route.py).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "metalens_hip.h"
+#include "zfft_core.h"
+
+#ifndef ML_STAGE1_TRANSPOSED
+#define ML_STAGE1_TRANSPOSED 1   // 0: stage 1's result stays row-major whatever the aperture
+#endif
+
+namespace ml {
+
+// The facts of one FFT axis of a plan (common.h ZfftAxis adds the axis' device tables).
+struct ZfftAxisGeo {
+    bool ok = false;
+    int N_eff = 0, j0 = 0, pad1 = 0, pad2 = 0;
+    int jstep = 1;   // output j is bin (j + j0) jstep of the N_eff-sample lattice (zfft_core.h Geo::jstep)
+    // split > 1 (lattices beyond 8192 samples): `split` launches over interleaved sub-sequences of
+    // N_eff / split samples; wk / kbin then belong to the SHORT lattice and pj holds [split][M]
+    int split = 1;
+    // passes > 1: ONE launch per row set, the residues of a row in that many groups through half
+    // (a quarter) of the LDS (zfft_pass_kernel); lattices of 8192 < N_eff <= 16384 samples with at
+    // most 1024 wanted bins run this way instead of split in two
+    int passes = 0;
+    // method 'fft-mixed' on a lattice that is not a multiple of 256 long: N_eff = A B R samples (the lattice itself
+    // or the twice finer one: jstep = 1 or 2) through zfft_mixed_kernel<A, B>; pad1 is its one padding and tw its
+    // [B][A] twiddle table (zfft_core.h mixed_choose).  A = 0: the 256 R3 scheme
+    int A = 0, B = 0, R = 0;
+};
+
+// the facts of a FarfieldPlan (common.h adds its tables and buffers).  Set in farfield.hip: method and the sizes by
+// ml_farfield_plan, fold / fold_S by plan_fold, fold2 / fold2_S by plan_fold2 (ZfftAxisGeo: plan_fft_axis)
+struct PlanFacts {
+    int method = 0;    // ml_farfield_set_method value the plan was made under
+    int nx_total = 0, ny = 0, mx = 0, my = 0, pair_list = 0;
+    // centre-symmetric uy / ux: the folded (even/odd) GEMM exists for stage 1 / stage 2, over S half-directions
+    bool fold = false, fold2 = false;
+    int fold_S = 0, fold2_S = 0;
+};
+
+enum class ShardKind { block, mirrored, interleaved };
+
+// the resident rows of a call: rows [row0, row0 + nx), mirrored pairs from row0, or interleaved blocks
+struct Shard {
+    ShardKind kind = ShardKind::block;
+    int row0 = 0;
+    int block = 0, n_ranks = 1, rank = 0;   // interleaved
+};
+
+// The tuning and ablation knobs of the route, by the names diag_int() reads them under in a diagnostic build
+// (common.h); the product library runs on these defaults.
+struct RouteKnobs {
+    int stage1_split = 0;       // ML_STAGE1_SPLIT > 0: the folded stage 1's split, whatever the tile count
+    int g_skew = 8;             // ML_G_SKEW: the transposed G's pitch is the resident rows + this many elements
+    int g_tiled = 1;            // ML_G_TILED=0: the plain transposed G where the tiled one would be taken
+    long fold2_min_tiles = 32;  // ML_FOLD2_MIN_TILES: the folded stage 2 from this many tiles on
+    int no_row_trim = 0;        // ML_NO_ROW_TRIM=1: both FFT stages on every resident row
+    int no_gt_direct = 0;       // ML_NO_GT_DIRECT=1: folded + folded through the transposer
+};
+
+// layout of stage 1's result G for stage 2: row-major G[f][n1][b], transposed G[f][b][n1], or tiled G[f][b / 8][n1][b % 8]
+enum class GLayout { row_major, transposed, tiled };
+
+// Where "row (f, n1), bin b" of G lies, for stage 1's writer and stage 2's reader alike: element
+// off + f s_f + (n1 - trim_lo) s_row + b s_bin for the row-major and the transposed G; in the tiled one bin b is
+// element b % 8 of tile b / 8, s_bin the stride of the tiles.  off is where row trim_lo begins: stage 1 writes rows
+// [trim_lo, trim_hi) only and stage 2 reads those.  Stage 1 takes (s_f, s_row, s_bin) as its output strides, stage 2
+// walks the same array by columns: its rows are G's bins (tiles), its elements G's rows.
+struct GView {
+    int64_t off, s_f, s_row, s_bin;
+    int cols;   // columns (tiles) per field plane: the rows of stage 2
+};
+
+inline GView g_view(GLayout layout, int nxl, int my, int64_t g_ld, int trim_lo) {
+    GView v;
+    v.s_f = layout == GLayout::row_major ? (int64_t)nxl * my : (int64_t)my * g_ld;
+    v.s_row = layout == GLayout::row_major ? my : layout == GLayout::transposed ? 1 : 8;
+    v.s_bin = layout == GLayout::row_major ? 1 : layout == GLayout::transposed ? g_ld : 8 * g_ld;
+    v.cols = layout == GLayout::tiled ? my / 8 : my;
+    v.off = (int64_t)trim_lo * v.s_row;
+    return v;
+}
+
+enum class Stage1Kind { fft, folded, generic };
+enum class Stage2Kind { interleaved, fft, fft_tiles, folded, generic_mirrored, generic, coldot };
+
+struct TransformRoute {
+    Stage1Kind stage1;
+    // the folded stage 1's wanted split (the slabs it writes: zfold_splits of it, applied by the caller)
+    int want_split1;
+    GLayout g_layout;
+    bool g_transposed() const { return g_layout != GLayout::row_major; }
+    int64_t g_ld;          // pitch of the transposed / tiled G in elements
+    size_t g_bytes;        // of G; per split-K slab of a folded stage 1
+    bool pieces_wanted;    // G in 4 MB physical pieces (common.h PieceBuf) if they can be had, else hipMalloc
+    int trim_lo, trim_hi;  // resident rows both FFT stages work on
+    bool gt_direct;        // folded + folded: stage 1 writes its result transposed and modulated for stage 2
+    Stage2Kind stage2;
+};
+
+// nxl: resident rows.  trim_rows: the resident rows that meet the lens circle, [trim_rows[0], trim_rows[1]), where
+// the fields carry a row_first (have_row_first: synthesised fields on the grid the rows were found for).
+inline TransformRoute transform_route(const PlanFacts &pl, const ZfftAxisGeo &fft_y, const ZfftAxisGeo &fft_x,
+                                      const Shard &sh, int nxl, bool have_row_first, const int trim_rows[2],
+                                      const RouteKnobs &knobs = RouteKnobs()) {
+    TransformRoute rt;
+    const int ny = pl.ny, mx = pl.mx, my = pl.my;
+    const bool mirrored = sh.kind == ShardKind::mirrored, interleaved = sh.kind == ShardKind::interleaved;
+    const bool fft1 = fft_y.ok, fft2 = fft_x.ok && !pl.pair_list;
+    rt.stage1 = fft1 ? Stage1Kind::fft : pl.fold ? Stage1Kind::folded : Stage1Kind::generic;
+    // few resident rows (multi-GPU shards) and a long reduction: split the pairs of stage 1 over
+    // several workgroups per tile; the slabs are summed by the next kernel
+    rt.want_split1 = 1;
+    if (pl.fold) {
+        // Measured (tools/zfold_shape_sweep.py): tiles of 128 half-directions read the aperture
+        // fewer times and win when at most a 2-way split fills the chip; otherwise 64-wide
+        // tiles with as many splits as it takes to reach ~2.5 workgroups per CU.
+        const long t128 = (long)((4 * nxl + 31) / 32) * ((pl.fold_S + 127) / 128);
+        const long t64 = (long)((4 * nxl + 31) / 32) * ((pl.fold_S + 63) / 64);
+        if (t128 >= 480)
+            rt.want_split1 = 1;
+        else if (2 * t128 >= 480)
+            rt.want_split1 = 2;
+        else
+            rt.want_split1 = (int)std::min<long>(8, std::max<long>(1, (640 + t64 - 1) / std::max<long>(t64, 1)));
+        if (knobs.stage1_split > 0) rt.want_split1 = knobs.stage1_split;
+    }
+    // Both axes one-level FFTs on a large aperture: stage 1 writes its result TRANSPOSED, G[f][b][n1]
+    // with rows of nxl + 8 (a 128-byte skew: consecutive bins of a row transform land in different
+    // L2 channels), and stage 2 streams contiguous rows with non-temporal loads like stage 1 does,
+    // instead of gathering 16-byte pieces 8 KB apart with loads that keep G in the caches.  What this
+    // buys is mostly NOT in the transform (4096^2 -> 512^2: stage 1 0.179 -> 0.207 ms for its 16-byte
+    // scattered stores - neighbouring rows meet in the XCD's L2 -, stage 2 0.057 -> 0.037) but in the
+    // NEXT synthesis, 0.265 -> 0.229 ms: a G that is read once and dropped no longer pushes the
+    // geometry records (134 MB at 4096^2, + 134 MB of G > the 256 MB memory-side cache) out between
+    // steps.  Small apertures, where everything fits anyway, keep the row-major G (2048^2 -> 256^2,
+    // 67 MB of records + G: 0.167 against 0.178 ms per step; from 2560^2 -> 320^2, 105 MB, on the
+    // transposed one is 1-1.5 % ahead: 0.282 against 0.287 ms, 3072^2 0.368 / 0.372, 3584^2 0.458 / 0.463).
+    const bool transposed = ML_STAGE1_TRANSPOSED && fft_y.ok && fft_x.ok && !pl.pair_list &&
+                            fft_y.split == 1 && fft_x.split == 1 && !interleaved &&
+                            (pl.method == ML_METHOD_FFT_STREAMED || pl.method == ML_METHOD_FFT_MIXED ||
+                             (size_t)nxl * ny * 8 + (size_t)4 * nxl * my * 16 > (size_t)96 << 20);
+    // (skew sweep at 4096^2 -> 512^2, stage 1: 0 elements 0.220 ms, 16 0.222, 1 0.204, 2 0.212, 24 0.208,
+    // 72 0.206, 4 0.190, 8 0.194-0.196, 40 0.196, 136 0.192: anything but a multiple of 256 bytes)
+    rt.g_ld = nxl + knobs.g_skew;
+    // Where both transforms take the one-level kernels, the transposed G is stored TILED instead: G[f][b / 8][n1][b % 8],
+    // the 8 bins of a 128-byte line side by side, tiles 8 g_ld elements long (zfft_core.h tile_off) - the same bytes.
+    // Stage 1 then stores whole lines (8 lanes = one line, a 64-lane store 8 lines in 8 tiles, 8 x 65 KB apart, instead
+    // of 64 16-byte pieces one pitch apart), and stage 2 (zfft.hip zfft_tiles_kernel) reads whole lines once, the 8
+    // columns of a tile together.  (Measured at 4096^2 -> 512^2: DESIGN.md 4.2.)
+    const int r3y = fft_y.N_eff / 256;
+    rt.g_layout = !transposed ? GLayout::row_major
+                  : (knobs.g_tiled != 0 && my % 8 == 0 && mx <= zf::TL_NT && r3y >= 3 && r3y <= 16 &&
+                     fft_y.passes <= 1 && fft_x.passes <= 1 && !fft_y.A && !fft_x.A)
+                      ? GLayout::tiled
+                      : GLayout::transposed;
+    // The TRANSPOSED result of rows up to 8192 samples lies in physical pieces of 4 MB, each an allocation of its own,
+    // mapped side by side (common.h PieceBuf).  Stage 1 stores it in 16-byte pieces one pitch (65 KB at 4096 samples)
+    // apart, and how fast those go is decided by the physical layout behind the buffer: 0.33 ms over one physically
+    // contiguous allocation (whatever the pitch), 0.5-1.3 ms in pieces below the 2 MB translation fragment, 0.178-0.190
+    // in pieces of 2 to 8 MB in three processes of four (8192 samples, pitch 131 KB: 0.75 in 2 MB pieces, 0.70 in 4 MB,
+    // 0.72 in 8 MB) - and 0.183 or 0.200, one of two each, from hipMalloc, whose layout is whatever the driver's free
+    // lists hold: the two 'modes' of rounds 4-6 (profiles/r06_ab_runs.txt).  The two-pass kernel of
+    // longer rows (one 152 KB workgroup per CU, whole lines stored) is the other way round: 16384^2 -> 1024^2 stage 1
+    // 4.01-4.16 ms over hipMalloc, 4.95 in 4 MB pieces, 4.32 in 8, 4.45 in 16, 4.13 in 32, 4.03 in 64 - it keeps
+    // hipMalloc, as does every other layout.  A context that runs both kinds holds both buffers.
+    // (METALENS_HIP_PIECES=0 in the environment: plain hipMalloc - the way out should a driver's virtual-memory API
+    // misbehave; so is a PieceBuf that has failed once: it is not tried again.  Both are the allocation's business:
+    // farfield.hip reserve_g)
+    rt.g_bytes = transposed ? (size_t)4 * my * rt.g_ld * 2 * sizeof(double)
+                            : (size_t)4 * nxl * my * 2 * sizeof(double);
+    rt.pieces_wanted = transposed && nxl <= 8192;
+    // Rows of a synthesised field that lie wholly outside the lens circle are zeros, and so are their row transforms:
+    // both FFT stages run on the resident rows [trim_lo, trim_hi) only (7 % fewer of each in a window of the size
+    // good_fft_number hands out, nearfield.py:30-36, 95-97).  Stage 1 neither reads those rows nor writes their part
+    // of G; stage 2 takes them as rows the rank does not hold (FftArgs::a0 / h0: read as zero without a load; the short
+    // transforms of an interleaved shard likewise, by LOCAL row).
+    // Which rows: the kernels' own inside-the-lens test at the sample nearest y = 0 (row_extent_kernel), on the host's
+    // copies of the axes (farfield.hip trim_rows_of).
+    rt.trim_lo = 0;
+    rt.trim_hi = nxl;
+    if (fft1 && fft2 && !mirrored && have_row_first && !knobs.no_row_trim) {
+        rt.trim_lo = trim_rows[0];
+        rt.trim_hi = trim_rows[1];
+    }
+    // the folded stage 2 pays once its grid (32-row x 64-half-direction tiles over the 4*my
+    // transposed rows) fills the chip; below that the generic GEMM with 32 x 32 tiles is faster
+    const bool whole = (sh.row0 == 0 && nxl == pl.nx_total);
+    const bool fold2_pays = (long)((4 * my + 31) / 32) * ((pl.fold2_S + 63) / 64) >= knobs.fold2_min_tiles;
+    const bool use_fold2 = !fft2 && !pl.pair_list && pl.fold2 && fold2_pays && (mirrored || whole) && !interleaved;
+    // both stages folded: stage 1 writes its result already transposed for stage 2
+    rt.gt_direct = pl.fold && use_fold2 && !knobs.no_gt_direct;
+    rt.stage2 = interleaved                            ? Stage2Kind::interleaved
+                : fft2 && rt.g_layout == GLayout::tiled ? Stage2Kind::fft_tiles
+                : fft2                                 ? Stage2Kind::fft
+                : use_fold2                            ? Stage2Kind::folded
+                : pl.pair_list                         ? Stage2Kind::coldot
+                : mirrored                             ? Stage2Kind::generic_mirrored
+                                                       : Stage2Kind::generic;
+    return rt;
+}
+
+}  // namespace ml

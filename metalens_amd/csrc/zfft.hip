@@ -332,7 +332,7 @@ static int launch_mixed(hipStream_t stream, const FftArgs &a, int threads, int g
     return ML_OK;
 }
 
-// The column pass over a TILED stage-1 result (farfield.hip GLayout::tiled; zfft_core.h tl_*): one workgroup per
+// The column pass over a TILED stage-1 result (transform_route.h GLayout::tiled; zfft_core.h tl_*): one workgroup per
 // tile, i.e. the 8 neighbouring columns (f, 8 t .. 8 t + 7) whose samples n1 lie in whole 128-byte lines, one line
 // per n1.  TL_SLOTS residues n0 of the lattice at a time, highest first: slot s loads the rows n1 = n0 + R3 m
 // (m < 256, 8 lanes = one line) with non-temporal loads - G is read once and must not push the next synthesis'
@@ -563,7 +563,7 @@ static int launch_pass(hipStream_t stream, const FftArgs &a, int grid, size_t ld
 }
 
 // Short transforms (N_eff = 256 or 512: R3 = 1, 2), several rows per workgroup.  The column pass of
-// an INTERLEAVED row shard (farfield.hip transform_impl: rank r of G holds the rows n = s (G m + r)
+// an INTERLEAVED row shard (farfield.hip stage2_interleaved: rank r of G holds the rows n = s (G m + r)
 // + i) is s transforms of N / (s G) points per column instead of one of N points, and sixteen or
 // thirty-two threads are no workgroup: `cpw` rows share one, each with its own exchange buffer,
 // all in step.  Plain form of the kernel above: no prefetch, twiddles applied in place.

@@ -319,7 +319,7 @@ def test_pieces_and_hipmalloc_give_the_same_bits(tmp_path):
     """the transposed stage-1 result in 4 MB physical pieces (the default, csrc/common.h PieceBuf) or from hipMalloc
     (METALENS_HIP_PIECES=0, which the library reads once per process: hence two processes) - the same radiation
     vectors, amplitudes and power, bit for bit.  --method fft-streamed takes the transposed layout at any aperture
-    size (csrc/farfield.hip g_transposed), so a small one does"""
+    size (csrc/transform_route.h transform_route: g_transposed), so a small one does"""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
