@@ -606,11 +606,8 @@ static int stage2_tables(ml_ctx *ctx, int row0, int mirrored, int *want_split_ou
     FarfieldPlan &pl = ctx->plan;
     const int nxl = ctx->nx, mx = pl.mx, my = pl.my, S = pl.fold2_S, T = (nxl + 1) / 2;
     // few rows (4*my) and a long reduction: split the pairs over several workgroups per tile
-    const long tiles = (long)((4 * my + 31) / 32) * ((S + 63) / 64);
     static const int forced_split2 = diag_int("ML_STAGE2_SPLIT", 0);
-    const int want_split = forced_split2 > 0
-                               ? forced_split2
-                               : (int)std::min<long>(8, std::max<long>(1, 1024 / std::max<long>(tiles, 1)));
+    const int want_split = forced_split2 > 0 ? forced_split2 : fold2_want_split(my, S);
     *want_split_out = want_split;
     const long key[4] = {pl.serial, row0, nxl, mirrored};
     if (!plan_cache_disabled() && memcmp(key, pl.fold2_key, sizeof key) == 0) return ML_OK;

@@ -209,4 +209,43 @@ inline TransformRoute transform_route(const PlanFacts &pl, const ZfftAxisGeo &ff
     return rt;
 }
 
+// ---- The launch shapes of the GEMM-path stage kernels: which tile and how many split-K slabs a stage takes for its
+// sizes, as the launchers apply them (zfold.hip zfold_stage1, farfield.hip stage2_tables, zgemm.hip pick_tile; the
+// reasons and measurements stand there).  Pure arithmetic, so that tools/transform_route.cpp can name the kernel of
+// each stage (tests/gemm_cases.py).  The forcing knobs of a diagnostic build (ML_ZFOLD_TILE, ML_STAGE2_SPLIT,
+// ML_ZGEMM_TILE) stay with the launchers.
+
+// pairs per split-K slab of zfold_kernel: a multiple of 64, so that every K tile and re-seed point stays aligned
+inline int zfold_t_chunk(int T, int ksplit) {
+    ksplit = ksplit < 1 ? 1 : ksplit;
+    return ((T + ksplit - 1) / ksplit + 63) / 64 * 64;
+}
+
+// the slabs zfold_kernel writes for a wanted split of ksplit over T pairs
+inline int zfold_eff_splits(int T, int ksplit) {
+    const int chunk = zfold_t_chunk(T, ksplit);
+    return (T + chunk - 1) / chunk;
+}
+
+// 32 x 128 tiles of 8 waves once tiles x slabs give ~2 workgroups per CU, else 32 x 64 tiles
+inline bool zfold_take_wide(int M, int S, int splits) {
+    return (long)((M + 31) / 32) * ((S + 127) / 128) * splits >= 480;
+}
+
+// the folded stage 2's wanted split: few rows (4 my) and a long reduction
+inline int fold2_want_split(int my, int fold2_S) {
+    const long tiles = (long)((4 * my + 31) / 32) * ((fold2_S + 63) / 64);
+    return (int)std::min<long>(8, std::max<long>(1, 1024 / std::max<long>(tiles, 1)));
+}
+
+// zgemm_kernel's tile id: 15 = 128 x 64 with 8 waves as soon as that gives one workgroup per CU, 10 = 64 x 64
+// likewise, else 11 = 32 x 32
+inline int zgemm_tile(int M, int N, int batch) {
+    const long t128 = (long)((M + 127) / 128) * ((N + 63) / 64) * batch;
+    const long t64 = (long)((M + 63) / 64) * ((N + 63) / 64) * batch;
+    if (t128 >= 256) return 15;
+    if (t64 >= 256) return 10;
+    return 11;
+}
+
 }  // namespace ml

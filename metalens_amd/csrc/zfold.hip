@@ -371,8 +371,8 @@ int zfold_stage1(hipStream_t stream, int M, int ny, const double *A, int64_t lda
     a.nxl = nxl;
     ksplit = ksplit < 1 ? 1 : ksplit;
     // chunks are multiples of 64 pairs so that every K tile and re-seed point stays aligned
-    a.t_chunk = ((T + ksplit - 1) / ksplit + 63) / 64 * 64;
-    ksplit = (T + a.t_chunk - 1) / a.t_chunk;
+    a.t_chunk = zfold_t_chunk(T, ksplit);
+    ksplit = zfold_eff_splits(T, ksplit);
     a.split_stride = split_stride;
     // Measured (tools/zfold_shape_sweep.py, bench.py): 128 half-directions per tile read the
     // aperture fewer times (once when S <= 128); 8 waves per workgroup at 4 waves per SIMD beat 4
@@ -382,8 +382,8 @@ int zfold_stage1(hipStream_t stream, int M, int ny, const double *A, int64_t lda
     // slabs give ~2 workgroups per CU, else 64-wide tiles of 4 waves (the folded stage 2: few
     // rows, long reduction).  Tried and slower: cos/sin tables through LDS,
     // 256-wide tiles of 16 waves, 64-row tiles at 2 waves per SIMD, deeper unrolling.
-    const long wide = (long)((M + 31) / 32) * ((S + 127) / 128) * ksplit;
-    const bool take_wide = wide >= 480;
+    // (the rule itself: transform_route.h zfold_take_wide)
+    const bool take_wide = zfold_take_wide(M, S, ksplit);
 #ifdef ML_DIAG   // shape sweeps: ML_ZFOLD_TILE = 31 | 50 | 40 | 51 forces a shape (fp64)
     const int forced = diag_int("ML_ZFOLD_TILE", -1);
     if (!f32 && forced == 40) return launch_fold_io<32, 128, 2, 4, 1, 32, 4, double>(stream, a, ksplit);
@@ -398,10 +398,6 @@ int zfold_stage1(hipStream_t stream, int M, int ny, const double *A, int64_t lda
                      : launch_fold_io<32, 64, 2, 2, 2, 32, 2, double>(stream, a, ksplit);
 }
 
-int zfold_splits(int T, int ksplit) {
-    ksplit = ksplit < 1 ? 1 : ksplit;
-    const int chunk = ((T + ksplit - 1) / ksplit + 63) / 64 * 64;
-    return (T + chunk - 1) / chunk;
-}
+int zfold_splits(int T, int ksplit) { return zfold_eff_splits(T, ksplit); }
 
 }  // namespace ml

@@ -227,11 +227,8 @@ static int pick_tile(int M, int N, int batch) {
     if (forced >= 0) return forced;
     // measured on MI355X (tools/zgemm_sweep.py): the 3M variants win everywhere; 128x64 tiles
     // with 8 waves are best as soon as they give one workgroup per CU
-    const long t128 = (long)((M + 127) / 128) * ((N + 63) / 64) * batch;
-    const long t64 = (long)((M + 63) / 64) * ((N + 63) / 64) * batch;
-    if (t128 >= 256) return 15;
-    if (t64 >= 256) return 10;
-    return 11;
+    // (the rule itself: transform_route.h zgemm_tile)
+    return zgemm_tile(M, N, batch);
 }
 
 int zgemm(hipStream_t stream, int M, int N, int K, const double *alpha, const double *A,
