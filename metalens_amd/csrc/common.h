@@ -571,11 +571,6 @@ struct ZfftCall {
 };
 // the column pass over a tiled stage-1 result (zfft.hip zfft_tiles_kernel)
 int zfft_run_tiles(hipStream_t stream, const ZfftCall &c);
-int zfft_split(int N_eff);   // sub-sequences a lattice of N_eff samples is transformed in (0: none)
-// (N_plain, if given: the lattice the grid sits on, 0 if none, and *j0 its first bin - also where the function
-// returns false because the 256 R3 scheme has no place for that lattice)
-bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
-                       long double tol, int *N_eff, int *j0, int *jstep, int *N_plain = nullptr);
 // tw1: [B][A] W_AB^(n1 k2) - 16 x 16 for the 256 R3 scheme, the legs of a mixed-radix axis otherwise
 int zfft_build_tables(hipStream_t stream, double *tw1, double *wk, double *pj, int *kbin, int M,
                       int j0, int N_eff, int c, int jstep = 1, int A = 16, int B = 16);

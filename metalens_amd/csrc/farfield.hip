@@ -411,20 +411,7 @@ static int upload_if_changed(ml_ctx *ctx, DevBuf &dev, std::vector<double> &host
     return ML_OK;
 }
 
-// How far (in radians of phase at the aperture edge) a direction grid may deviate from exact
-// centre symmetry and still take the folded path: 1e-13 rad, or - for large apertures, where
-// that is less than the grid's own representation error - four times the phase uncertainty that
-// half an ulp of the largest direction cosine already carries (2 pi kappa p_max eps/2 max|u|).
-// A grid computed as centre +/- k*step in floating point is symmetric to about one ulp; without
-// the second term a 16384-sample aperture (4.3 mm at lambda/2.2) falls back to the generic
-// complex GEMM, 5x slower, for an asymmetry of 3e-13 rad that the inputs cannot resolve anyway.
-static long double symmetry_tolerance(long double kappa, long double p_max, const double *u, int n) {
-    long double umax = 0;
-    for (int k = 0; k < n; ++k) umax = fmaxl(umax, fabsl((long double)u[k]));
-    const long double inherent = 2 * M_PIl * kappa * p_max * umax * (long double)DBL_EPSILON * 0.5L;
-    return fmaxl(1e-13L, 4 * inherent);
-}
-
+// (symmetry_tolerance, the phase deviation a direction grid is allowed: transform_route.h)
 // Decide whether stage 1 can run folded (zfold.hip) and build its tables.  Needs a tensor
 // grid whose uy are centre-symmetric to within 1e-13 rad of phase at the aperture edge.
 static int plan_fold(ml_ctx *ctx, const double *uy) {
@@ -492,12 +479,9 @@ static int plan_fold(ml_ctx *ctx, const double *uy) {
 static int plan_fft_axis(ml_ctx *ctx, ZfftAxis &ax, int n, double step, const double *u, int m) {
     FarfieldPlan &pl = ctx->plan;
     ax.ok = false;
-    const long double kappa = (long double)pl.n_glass / (long double)pl.wavelength;
-    const long double p_max = 0.5L * (n + 1) * fabsl((long double)step);
     int N_eff = 0, j0 = 0, jstep = 1;
     int N_plain = 0;
-    const bool fits256 = zfft_commensurate(n, step, kappa, u, m, symmetry_tolerance(kappa, p_max, u, m), &N_eff, &j0,
-                                           &jstep, &N_plain);
+    const bool fits256 = zfft_axis_lattice(n, step, pl.wavelength, pl.n_glass, u, m, &N_eff, &j0, &jstep, &N_plain);
     ax.A = ax.B = ax.R = 0;
     // 'fft-mixed': a lattice that is not a multiple of 256 long runs unpadded or padded 2-fold as A x B x R samples
     // where the factor chooser finds legs for it (zfft_core.h mixed_choose; up to 8192 samples, one rank) - 729 =
@@ -529,22 +513,11 @@ static int plan_fft_axis(ml_ctx *ctx, ZfftAxis &ax, int n, double step, const do
         }
     }
     if (!fits256) return ML_OK;
-    // A lattice that is not a multiple of 256 long runs jstep-fold padded, at jstep times the arithmetic and (beyond
-    // 8192 padded samples) as many passes over the rows.  Measured against the folded GEMMs on square apertures
-    // (tools/padded_fft_sweep.py, profiles/r06_padded_fft_sweep.txt; M = 64, 256, N directions): jstep 2 (1920, 3200
-    // samples) 1.7-5.3 x faster, 4 (320, 960, 1600) 1.1-2.5 x, 8 (800, 1440, 2400) 0.5-1.1 x, 16 (400, 2000, 3600)
-    // 0.1-0.7 x, 32 (1000, 3000) 0.1-0.2 x, 128 (250) 0.1 x.  `auto` leaves the lattices padded more than 4-fold to
-    // the GEMMs; `fft-streamed` takes the FFT wherever there is one
-    if (pl.method == ML_METHOD_AUTO && jstep > 4) return ML_OK;
-    int split = zfft_split(N_eff);
-    // 8192 < N_eff <= 16384 with at most 1024 wanted bins: one launch in two residue passes (every
-    // row read once, whole 128-byte lines, no accumulating store) instead of two sub-sequences
-    const int r3 = N_eff / 256;
-    ax.passes = 0;
-    if (r3 == 64 && m <= 1024) {   // (the two-pass kernel exists for groups of 16 and 32 residues)
-        split = 1;
-        ax.passes = 2;
-    }
+    // whether this method takes the axis, and in how many sub-sequences or passes: transform_route.h zfft_axis_rule
+    const ZfftAxisRule rule = zfft_axis_rule(pl.method, N_eff, jstep, m);
+    if (!rule.taken) return ML_OK;
+    const int split = rule.split;
+    ax.passes = rule.passes;
     ML_TRY(pl.fft_tw1.reserve(256 * 2 * sizeof(double)));
     ML_TRY(ax.wk.reserve((size_t)m * 2 * sizeof(double)));
     ML_TRY(ax.pj.reserve((size_t)split * m * 2 * sizeof(double)));
@@ -825,29 +798,13 @@ int ml_farfield_plan(ml_ctx *ctx, int nx_total, int ny, double dxp, double dyp, 
 // or mirrored block of rows costs every rank the full-length pass.  Needs the x axis on the pruned
 // FFT with a lattice of exactly the aperture's rows; Nsub = 256 R3 with R3 <= 32.  s is taken as
 // large as that allows (up to 8: the synthesis works on 8-row patches and wants neighbouring rows).
-// A short transform of n_sub samples runs on the lattice of n_sub * stuff = 256 R3 samples, zero-
-// stuffed when n_sub is below 256 (zfft_interleaved_kernel); 0: n_sub does not fit
-static int interleave_stuff(int n_sub) {
-    for (int z = 1; z <= 8; z <<= 1)
-        if ((n_sub * z) % 256 == 0) return z;
-    return 0;
-}
-
+// (transform_route.h interleave_stuff, interleave_block_of)
 static int interleave_block(const FarfieldPlan &pl, int n_ranks) {
     if (!pl.ready || pl.pair_list || !pl.fft_x.ok || pl.fft_x.A || n_ranks < 2) return 0;
     // N = the x axis' lattice (longer than the aperture when the direction grid is finer than the
     // aperture's own: the rows beyond nx_total are zeros nobody holds); the rows that exist must
     // deal out evenly
-    const int N = pl.fft_x.N_eff;
-    for (int s = 8; s >= 1; s >>= 1) {
-        if (N % (s * n_ranks) != 0 || pl.nx_total % (s * n_ranks) != 0) continue;
-        const int stuff = interleave_stuff(N / (s * n_ranks));
-        if (!stuff) continue;
-        const int r3 = N / (s * n_ranks) * stuff / 256;
-        // (the s transforms of a column share one workgroup: 16 r3 s threads, s buffers of 4 r3 KB)
-        if (r3 >= 1 && r3 <= 32 && r3 * s <= 32) return s;
-    }
-    return 0;
+    return interleave_block_of(pl.fft_x.N_eff, pl.nx_total, n_ranks);
 }
 
 static int validate_shard(ml_ctx *ctx, const Shard &sh, int accumulate) {

@@ -8,6 +8,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <float.h>
+#include <math.h>
+#include <stdlib.h>
+
 #include <algorithm>
 
 #include "metalens_hip.h"
@@ -246,6 +250,251 @@ inline int zgemm_tile(int M, int N, int batch) {
     if (t128 >= 256) return 15;
     if (t64 >= 256) return 10;
     return 11;
+}
+
+// ---- The launch rules of the pruned FFT on lattices of 256 R3 samples (zfft.hip): how an axis is cut
+// into launches (farfield.hip plan_fft_axis), the block of an interleaved shard (farfield.hip interleave_block) and
+// which kernel instantiation a call launches (zfft.hip zfft_run, zfft_run_tiles, zfft_run_interleaved) - pure
+// arithmetic over the call's facts, applied by those launchers and printed by tools/transform_route.cpp
+// (tests/fft_cases.py).  The reasons and measurements stand with the kernels.
+
+#ifndef ML_ZFFT_IP
+// exchange 2 of the one-level kernel in place for lattices up to this many residues (A/B builds: 0 =
+// never).  Measured on one box, stage 1: R3 = 16 (4096^2) 0.183 -> 0.179 ms, R3 = 8 (2048^2) 0.0585 ->
+// 0.0579, R3 = 32 (8192^2, NA 0.94, one workgroup per CU) 0.678 -> 0.713: the longer bank-conflict
+// tail of the in-place pattern costs more than the barrier where nothing else is resident to hide it
+#define ML_ZFFT_IP 16
+#endif
+#ifndef ML_FFT_PASSES_R32
+// default: two passes for 8192-sample lattices (one 131 KB workgroup per CU otherwise:
+// stage 1 0.77 -> 0.71 ms at 8192^2); one pass below - at 4096 samples four two-wave
+// workgroups per CU measured 12 % SLOWER than two four-wave ones with the register prefetch
+// (R3 = 16 as 2 x 8: stage 1 0.201 against 0.178 ms; R3 = 8 as 2 x 4: 0.108 against 0.060)
+#define ML_FFT_PASSES_R32 2
+#endif
+
+// Two-level transforms: an axis of N_eff = 256 R3 samples with R3 > 32 is transformed as s
+// interleaved sub-sequences of N_eff / s samples (decimation in time: X[k] = sum_i W_N^(i k) X_i[k
+// mod N / s]), each by one launch of the one-level kernel that adds its bins - carried to the full
+// lattice by a per-bin phasor - to the result.  Smallest s that brings R3 / s to <= 32; 0 if none
+// up to 16 does (R3 with no such divisor).
+inline int zfft_split(int N_eff) {
+    if (N_eff % 256) return 0;
+    const int R3 = N_eff / 256;
+    for (int s = 1; s <= 16; ++s)
+        if (R3 % s == 0 && R3 / s <= 32) return s;
+    return 0;
+}
+
+// Is the uniform grid u[0..M) a run of consecutive bins of the FFT lattice of an axis of n samples
+// `step` apart?  kappa = n_glass / wavelength (turns per unit length per unit direction cosine).
+// `tol`: allowed phase deviation [rad] at the aperture edge.  On success fills N_eff and j0.
+// (N_plain, if given: the lattice the grid sits on, 0 if none, and *j0 its first bin - also where the function
+// returns false because the 256 R3 scheme has no place for that lattice)
+inline bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
+                       long double tol, int *N_eff, int *j0, int *jstep, int *N_plain = nullptr) {
+    if (N_plain) *N_plain = 0;
+    if (M < 2 || n < 2) return false;
+    const long double du = ((long double)u[M - 1] - (long double)u[0]) / (M - 1);
+    const long double turns = kappa * fabsl((long double)step) * du;   // per (sample, bin)
+    if (!(turns > 0)) return false;                    // descending or degenerate grids: GEMM
+    if (step < 0) return false;
+    const long double inv = 1.0L / turns;
+    if (!(inv < 1e7L)) return false;
+    const long N = lrintl(inv);                        // the lattice the directions sit on
+    if (N < n || N < M) return false;
+    const long double du_exact = 1.0L / (kappa * fabsl((long double)step) * N);
+    const long jj = lrintl((long double)u[0] / du_exact);
+    // worst phase error over the grid at the outermost sample
+    const long double p_max = 0.5L * n * fabsl((long double)step) + fabsl((long double)step);
+    long double worst = 0;
+    for (int j = 0; j < M; ++j)
+        worst = fmaxl(worst, fabsl((long double)u[j] - (jj + j) * du_exact));
+    const bool on_lattice = !(2 * M_PIl * kappa * p_max * worst > tol);
+    // (N_plain: the lattice itself and its first bin, for the mixed-radix kernels - whether or not the 256 R3
+    // scheme below has a place for it)
+    if (on_lattice && N_plain && labs(jj) <= (1L << 29)) {
+        *N_plain = (int)N;
+        *j0 = (int)jj;
+    }
+    // The kernels transform 256 R3 samples.  A lattice that is not a multiple of 256 long - the
+    // reference's default grids are the smallest 2^a 3^b 5^c above a goal (nearfield.py:30-36: 400, 1920,
+    // 2000 ...) - runs on the s-times finer lattice of N s samples, s = 256 / gcd(N, 256), the aperture
+    // zero-padded: its every s-th bin is a bin of the lattice asked for (Geo::jstep)
+    long g = 256, r = N % 256;
+    while (r) {
+        const long t = g % r;
+        g = r;
+        r = t;
+    }
+    const long s = 256 / g, Ne = N * s;
+    if (Ne > (1L << 20)) return false;
+    const int R3 = (int)(Ne / 256);
+    // one workgroup holds 8192 samples in LDS (257 * R3 * 16 bytes, R3 <= 32); longer lattices are
+    // split into up to 16 interleaved sub-sequences, one launch each (zfft_split)
+    if (R3 < 1 || zfft_split((int)Ne) == 0) return false;
+    if (labs(jj) > (1L << 30) / s) return false;
+    if (!on_lattice) return false;
+    *N_eff = (int)Ne;
+    *j0 = (int)jj;
+    *jstep = (int)s;
+    return true;
+}
+
+// How far (in radians of phase at the aperture edge) a direction grid may deviate from exact
+// centre symmetry and still take the folded path: 1e-13 rad, or - for large apertures, where
+// that is less than the grid's own representation error - four times the phase uncertainty that
+// half an ulp of the largest direction cosine already carries (2 pi kappa p_max eps/2 max|u|).
+// A grid computed as centre +/- k*step in floating point is symmetric to about one ulp; without
+// the second term a 16384-sample aperture (4.3 mm at lambda/2.2) falls back to the generic
+// complex GEMM, 5x slower, for an asymmetry of 3e-13 rad that the inputs cannot resolve anyway.
+inline long double symmetry_tolerance(long double kappa, long double p_max, const double *u, int n) {
+    long double umax = 0;
+    for (int k = 0; k < n; ++k) umax = fmaxl(umax, fabsl((long double)u[k]));
+    const long double inherent = 2 * M_PIl * kappa * p_max * umax * (long double)DBL_EPSILON * 0.5L;
+    return fmaxl(1e-13L, 4 * inherent);
+}
+
+// the lattice of one axis of a plan, as plan_fft_axis asks for it: n samples `step` apart, sample j at
+// (j - ceil(n / 2)) step, the m directions u
+inline bool zfft_axis_lattice(int n, double step, double wavelength, double n_glass, const double *u, int m,
+                              int *N_eff, int *j0, int *jstep, int *N_plain = nullptr) {
+    const long double kappa = (long double)n_glass / (long double)wavelength;
+    const long double p_max = 0.5L * (n + 1) * fabsl((long double)step);
+    return zfft_commensurate(n, step, kappa, u, m, symmetry_tolerance(kappa, p_max, u, m), N_eff, j0, jstep, N_plain);
+}
+
+// How plan_fft_axis runs an axis whose M wanted bins sit on the lattice of N_eff = 256 R3 samples, every jstep-th bin
+// a bin of the lattice asked for (zfft_commensurate): `split` launches over sub-sequences, or one launch in `passes`
+// residue passes; taken = false: the method leaves this axis to the GEMMs
+struct ZfftAxisRule {
+    bool taken;
+    int split, passes;
+};
+
+inline ZfftAxisRule zfft_axis_rule(int method, int N_eff, int jstep, int M) {
+    ZfftAxisRule r{true, 0, 0};
+    // A lattice that is not a multiple of 256 long runs jstep-fold padded, at jstep times the arithmetic and (beyond
+    // 8192 padded samples) as many passes over the rows.  Measured against the folded GEMMs on square apertures
+    // (tools/padded_fft_sweep.py, profiles/r06_padded_fft_sweep.txt; M = 64, 256, N directions): jstep 2 (1920, 3200
+    // samples) 1.7-5.3 x faster, 4 (320, 960, 1600) 1.1-2.5 x, 8 (800, 1440, 2400) 0.5-1.1 x, 16 (400, 2000, 3600)
+    // 0.1-0.7 x, 32 (1000, 3000) 0.1-0.2 x, 128 (250) 0.1 x.  `auto` leaves the lattices padded more than 4-fold to
+    // the GEMMs; `fft-streamed` takes the FFT wherever there is one
+    if (method == ML_METHOD_AUTO && jstep > 4) r.taken = false;
+    r.split = zfft_split(N_eff);
+    // 8192 < N_eff <= 16384 with at most 1024 wanted bins: one launch in two residue passes (every
+    // row read once, whole 128-byte lines, no accumulating store) instead of two sub-sequences
+    if (N_eff / 256 == 64 && M <= 1024) {   // (the two-pass kernel exists for groups of 16 and 32 residues)
+        r.split = 1;
+        r.passes = 2;
+    }
+    return r;
+}
+
+// A short transform of n_sub samples of an interleaved shard runs on the lattice of n_sub * stuff = 256 R3 samples,
+// zero-stuffed when n_sub is below 256 (zfft_interleaved_kernel); 0: n_sub does not fit
+inline int interleave_stuff(int n_sub) {
+    for (int z = 1; z <= 8; z <<= 1)
+        if ((n_sub * z) % 256 == 0) return z;
+    return 0;
+}
+
+// Block size s of an interleaved shard over n_ranks ranks of an x axis on the lattice of N samples, nx_total of which
+// exist (farfield.hip interleave_block: what the plan must be like); s as large as fits, up to 8; 0: none
+inline int interleave_block_of(int N, int nx_total, int n_ranks) {
+    if (n_ranks < 2) return 0;
+    for (int s = 8; s >= 1; s >>= 1) {
+        if (N % (s * n_ranks) != 0 || nx_total % (s * n_ranks) != 0) continue;
+        const int stuff = interleave_stuff(N / (s * n_ranks));
+        if (!stuff) continue;
+        const int r3 = N / (s * n_ranks) * stuff / 256;
+        // (the s transforms of a column share one workgroup: 16 r3 s threads, s buffers of 4 r3 KB)
+        if (r3 >= 1 && r3 <= 32 && r3 * s <= 32) return s;
+    }
+    return 0;
+}
+
+// the facts of one launch: the lattice of the (sub-sequence of the) axis, the wanted bins, the axis' passes, how the
+// rows lie (ZfftCall in_es == 1, second, tiled_out), the entry point (tiles: zfft_run_tiles; s > 0:
+// zfft_run_interleaved with s transforms of n_valid samples, zero-stuffed `stuff`-fold, per column)
+struct ZfftLaunchFacts {
+    int N_eff = 0, M = 0, passes = 0;
+    bool contiguous = false, second = false, tiled_out = false;
+    bool tiles = false;
+    int s = 0, stuff = 1, n_valid = 0;
+};
+
+enum class ZfftFamily { none, one, pass, multi, tiles, interleaved, cols128 };
+
+// family = none: no kernel takes the facts (more than 32 residues in one launch)
+struct ZfftLaunch {
+    ZfftFamily family = ZfftFamily::none;
+    int R3T = 0, PASS = 0;        // zfft_kernel<R3T, ., ., PASS, ip>: R3T = 0 the generic residue count; multi: PASS
+    bool ip = false;              // exchange 2 in place
+    int R3P = 0, P = 0, NB = 0;   // zfft_pass_kernel<R3P, P, NB, ., PASS>
+    int threads = 0;              // of a workgroup
+    int cpw = 0;                  // multi: rows per workgroup
+    bool repad = false;           // the launcher chooses the paddings again (in place, pass geometry)
+};
+
+inline ZfftLaunch zfft_launch_rule(const ZfftLaunchFacts &f) {
+    ZfftLaunch L;
+    const int R3 = f.N_eff / 256;
+    if (f.tiles) {
+        L.family = ZfftFamily::tiles;
+        L.threads = zf::TL_NT;
+        return L;
+    }
+    if (f.s > 0) {
+#ifndef ML_NO_COLS128
+        if (f.stuff == 2 && f.N_eff == 256 && f.s == 8 && f.n_valid <= 128) {
+            // eight 128-sample transforms per column: one wave each (zfft_cols128_kernel)
+            L.family = ZfftFamily::cols128;
+            L.threads = 64;
+            return L;
+        }
+#endif
+        L.family = ZfftFamily::interleaved;
+        L.threads = 16 * R3 * f.s;
+        return L;
+    }
+    // PASS (a template argument so that profiles can tell the launches apart): 1 rows of the aperture,
+    // 2 strided columns of a row-major stage-1 result, 3 contiguous rows of a transposed one, 4 rows of the
+    // aperture into a tiled one
+    if (R3 <= 2) {
+        // short transforms: 64 threads = 4 or 2 rows per workgroup (zfft_multi_kernel)
+        L.family = ZfftFamily::multi;
+        L.cpw = 4 / std::max(R3, 1);
+        L.PASS = f.contiguous ? 1 : 2;
+        L.threads = 16 * R3 * L.cpw;
+        return L;
+    }
+    // pass-split form (zfft_pass_kernel): passes = 2 groups of residues, where an instantiation covers the shape
+    const int P = f.passes > 0 ? f.passes : (R3 == 32 ? ML_FFT_PASSES_R32 : 1);
+    if (P > 1 && R3 % P == 0) {
+        const int R3P = R3 / P;
+        if (P == 2 && (R3P == 16 || R3P == 32) && f.M <= 2 * 16 * R3P) {   // (NB = 2 wanted bins per thread)
+            L.family = ZfftFamily::pass;
+            L.R3P = R3P, L.P = P, L.NB = 2;
+            L.PASS = f.contiguous ? (f.second ? 3 : 1) : 2;
+            L.threads = 16 * R3P;
+            L.repad = true;
+            return L;
+        }
+    }
+    if (R3 > 32) return L;
+    const bool pow2 = R3 == 4 || R3 == 8 || R3 == 16 || R3 == 32;
+    L.family = ZfftFamily::one;
+    L.threads = 16 * R3;
+    // the in-place layout answers to one padding, chosen for its four access patterns
+    L.ip = L.repad = R3 <= ML_ZFFT_IP && pow2;
+    if (f.contiguous && f.second && (R3 == 8 || R3 == 16 || R3 == 32))
+        L.PASS = 3, L.R3T = R3;
+    else if (f.tiled_out)   // pass 1 into a tiled G
+        L.PASS = 4, L.R3T = pow2 && R3 != 32 ? R3 : 0;
+    else
+        L.PASS = f.contiguous ? 1 : 2, L.R3T = pow2 ? R3 : 0;
+    return L;
 }
 
 }  // namespace ml

@@ -777,17 +777,18 @@ int zfft_run_interleaved(hipStream_t stream, const ZfftCall &c, int s, int64_t s
     a.rows = c.rows;
     a.accumulate = c.accumulate;
     a.chunk = (c.rows + 7) / 8;
-#ifndef ML_NO_COLS128
-    if (stuff == 2 && c.N_eff == 256 && s == 8 && c.n_valid <= 128) {
+    ZfftLaunchFacts f;
+    f.N_eff = c.N_eff, f.M = c.M, f.s = s, f.stuff = stuff, f.n_valid = c.n_valid;
+    const ZfftLaunch L = zfft_launch_rule(f);
+    if (L.family == ZfftFamily::cols128) {
         // eight 128-sample transforms per column: one wave each (zfft_cols128_kernel)
         int grid = std::min(256 * 8, a.chunk * 8);
         grid = (grid + 7) / 8 * 8;
-        hipLaunchKernelGGL(zfft_cols128_kernel, dim3(grid), dim3(64), 0, stream, a, sub_off);
+        hipLaunchKernelGGL(zfft_cols128_kernel, dim3(grid), dim3(L.threads), 0, stream, a, sub_off);
         ML_HIP(hipGetLastError());
         return ML_OK;
     }
-#endif
-    const int threads = 16 * a.g.R3 * s;
+    const int threads = L.threads;
     const size_t bytes = ((size_t)s * zf::lds_elems(a.g) + 256) * sizeof(cd);
     ML_REQUIRE(threads <= 512 && bytes <= 160 * 1024, "interleaved column pass: %d transforms of %d points "
                "do not fit one workgroup", s, c.N_eff);
@@ -864,72 +865,7 @@ __global__ __launch_bounds__(256) void zfft_tables_kernel(cd *tw1, cd *wk, cd *p
     }
 }
 
-// Is the uniform grid u[0..M) a run of consecutive bins of the FFT lattice of an axis of n samples
-// `step` apart?  kappa = n_glass / wavelength (turns per unit length per unit direction cosine).
-// `tol`: allowed phase deviation [rad] at the aperture edge.  On success fills N_eff and j0.
-// Two-level transforms: an axis of N_eff = 256 R3 samples with R3 > 32 is transformed as s
-// interleaved sub-sequences of N_eff / s samples (decimation in time: X[k] = sum_i W_N^(i k) X_i[k
-// mod N / s]), each by one launch of the one-level kernel that adds its bins - carried to the full
-// lattice by a per-bin phasor - to the result.  Smallest s that brings R3 / s to <= 32; 0 if none
-// up to 16 does (R3 with no such divisor).
-int zfft_split(int N_eff) {
-    if (N_eff % 256) return 0;
-    const int R3 = N_eff / 256;
-    for (int s = 1; s <= 16; ++s)
-        if (R3 % s == 0 && R3 / s <= 32) return s;
-    return 0;
-}
-
-bool zfft_commensurate(int n, double step, long double kappa, const double *u, int M,
-                       long double tol, int *N_eff, int *j0, int *jstep, int *N_plain) {
-    if (N_plain) *N_plain = 0;
-    if (M < 2 || n < 2) return false;
-    const long double du = ((long double)u[M - 1] - (long double)u[0]) / (M - 1);
-    const long double turns = kappa * fabsl((long double)step) * du;   // per (sample, bin)
-    if (!(turns > 0)) return false;                    // descending or degenerate grids: GEMM
-    if (step < 0) return false;
-    const long double inv = 1.0L / turns;
-    if (!(inv < 1e7L)) return false;
-    const long N = lrintl(inv);                        // the lattice the directions sit on
-    if (N < n || N < M) return false;
-    const long double du_exact = 1.0L / (kappa * fabsl((long double)step) * N);
-    const long jj = lrintl((long double)u[0] / du_exact);
-    // worst phase error over the grid at the outermost sample
-    const long double p_max = 0.5L * n * fabsl((long double)step) + fabsl((long double)step);
-    long double worst = 0;
-    for (int j = 0; j < M; ++j)
-        worst = fmaxl(worst, fabsl((long double)u[j] - (jj + j) * du_exact));
-    const bool on_lattice = !(2 * M_PIl * kappa * p_max * worst > tol);
-    // (N_plain: the lattice itself and its first bin, for the mixed-radix kernels - whether or not the 256 R3
-    // scheme below has a place for it)
-    if (on_lattice && N_plain && labs(jj) <= (1L << 29)) {
-        *N_plain = (int)N;
-        *j0 = (int)jj;
-    }
-    // The kernels transform 256 R3 samples.  A lattice that is not a multiple of 256 long - the
-    // reference's default grids are the smallest 2^a 3^b 5^c above a goal (nearfield.py:30-36: 400, 1920,
-    // 2000 ...) - runs on the s-times finer lattice of N s samples, s = 256 / gcd(N, 256), the aperture
-    // zero-padded: its every s-th bin is a bin of the lattice asked for (Geo::jstep)
-    long g = 256, r = N % 256;
-    while (r) {
-        const long t = g % r;
-        g = r;
-        r = t;
-    }
-    const long s = 256 / g, Ne = N * s;
-    if (Ne > (1L << 20)) return false;
-    const int R3 = (int)(Ne / 256);
-    // one workgroup holds 8192 samples in LDS (257 * R3 * 16 bytes, R3 <= 32); longer lattices are
-    // split into up to 16 interleaved sub-sequences, one launch each (zfft_split)
-    if (R3 < 1 || zfft_split((int)Ne) == 0) return false;
-    if (labs(jj) > (1L << 30) / s) return false;
-    if (!on_lattice) return false;
-    *N_eff = (int)Ne;
-    *j0 = (int)jj;
-    *jstep = (int)s;
-    return true;
-}
-
+// (zfft_commensurate - is a direction grid a run of bins of the axis' FFT lattice? - : transform_route.h)
 int zfft_build_tables(hipStream_t stream, double *tw1, double *wk, double *pj, int *kbin, int M, int j0,
                       int N_eff, int c, int jstep, int A, int B) {
     const int n = M > 256 ? M : 256;
@@ -940,13 +876,7 @@ int zfft_build_tables(hipStream_t stream, double *tw1, double *wk, double *pj, i
     return ML_OK;
 }
 
-#ifndef ML_ZFFT_IP
-// exchange 2 of the one-level kernel in place for lattices up to this many residues (A/B builds: 0 =
-// never).  Measured on one box, stage 1: R3 = 16 (4096^2) 0.183 -> 0.179 ms, R3 = 8 (2048^2) 0.0585 ->
-// 0.0579, R3 = 32 (8192^2, NA 0.94, one workgroup per CU) 0.678 -> 0.713: the longer bank-conflict
-// tail of the in-place pattern costs more than the barrier where nothing else is resident to hide it
-#define ML_ZFFT_IP 16
-#endif
+// (ML_ZFFT_IP, up to how many residues exchange 2 runs in place: transform_route.h)
 template <int R3T, int NTMAX, int MINW, int PASS>
 static int launch_one(hipStream_t stream, const FftArgs &a, int grid, size_t lds_bytes) {
     constexpr bool IP = R3T != 0 && R3T <= ML_ZFFT_IP;
@@ -1008,6 +938,9 @@ int zfft_run_tiles(hipStream_t stream, const ZfftCall &c) {
     ML_REQUIRE(c.N_eff % 256 == 0 && c.M <= zf::TL_NT && c.rows % 8 == 0 && (c.sub_s <= 1) && c.in_es == 8,
                "tiled column pass: %d samples, %d bins, %d rows", c.N_eff, c.M, c.rows);
     const FftArgs a = args_of(c);
+    ZfftLaunchFacts f;
+    f.N_eff = c.N_eff, f.M = c.M, f.tiles = true;
+    const ZfftLaunch L = zfft_launch_rule(f);
     const size_t bytes = ((size_t)zf::TL_SLOTS * zf::TL_SS + 256) * sizeof(cd);
     static bool attr_done = false;
     if (!attr_done) {
@@ -1016,7 +949,7 @@ int zfft_run_tiles(hipStream_t stream, const ZfftCall &c) {
         attr_done = true;
     }
     const int tiles = c.rows / 8, grid = std::min(tiles, 256);   // (one 149 KB workgroup per CU)
-    hipLaunchKernelGGL(zfft_tiles_kernel, dim3(grid), dim3(zf::TL_NT), bytes, stream, a);
+    hipLaunchKernelGGL(zfft_tiles_kernel, dim3(grid), dim3(L.threads), bytes, stream, a);
     ML_HIP(hipGetLastError());
     return ML_OK;
 }
@@ -1053,17 +986,22 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
     // a tiled result (PASS 4) is stored by the one-level kernel only
     ML_REQUIRE(!c.tiled_out || (a.g.R3 >= 3 && a.g.R3 <= 16 && c.passes <= 1 && c.in_es == 1 && !c.second),
                "tiled row pass: %d samples", c.N_eff);
-    if (a.g.R3 <= 2) {
+    // which kernel: transform_route.h zfft_launch_rule
+    ZfftLaunchFacts f;
+    f.N_eff = c.N_eff, f.M = c.M, f.passes = c.passes;
+    f.contiguous = c.in_es == 1, f.second = c.second != 0, f.tiled_out = c.tiled_out != 0;
+    const ZfftLaunch L = zfft_launch_rule(f);
+    if (L.family == ZfftFamily::multi) {
         // short transforms: 64 threads = 4 or 2 rows per workgroup (zfft_multi_kernel)
-        const int cpw = 4 / a.g.R3;
+        const int cpw = L.cpw;
         const size_t bytes = ((size_t)cpw * zf::lds_elems(a.g) + 256) * sizeof(cd);
         const int groups = (a.rows + cpw - 1) / cpw;
         int grid = std::min(256 * 8, (groups + 7) / 8 * 8);
         grid = std::max(grid, 8);
-        if (c.in_es == 1)
-            hipLaunchKernelGGL(zfft_multi_kernel<1>, dim3(grid), dim3(16 * a.g.R3 * cpw), bytes, stream, a, cpw);
+        if (L.PASS == 1)
+            hipLaunchKernelGGL(zfft_multi_kernel<1>, dim3(grid), dim3(L.threads), bytes, stream, a, cpw);
         else
-            hipLaunchKernelGGL(zfft_multi_kernel<2>, dim3(grid), dim3(16 * a.g.R3 * cpw), bytes, stream, a, cpw);
+            hipLaunchKernelGGL(zfft_multi_kernel<2>, dim3(grid), dim3(L.threads), bytes, stream, a, cpw);
         ML_HIP(hipGetLastError());
         return ML_OK;
     }
@@ -1073,69 +1011,54 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
     const int per_cu = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / lds_bytes));
     int grid = std::min(256 * per_cu, a.chunk * 8);
     grid = (grid + 7) / 8 * 8;
-    // pass-split form (zfft_pass_kernel): passes = 2 or 4 groups of residues, where an
-    // instantiation covers the shape
-    {
-        // default: two passes for 8192-sample lattices (one 131 KB workgroup per CU otherwise:
-        // stage 1 0.77 -> 0.71 ms at 8192^2); one pass below - at 4096 samples four two-wave
-        // workgroups per CU measured 12 % SLOWER than two four-wave ones with the register prefetch
-        const int R3 = a.g.R3;
-        // (R3 = 16 as 2 x 8: stage 1 0.201 against 0.178 ms; R3 = 8 as 2 x 4: 0.108 against 0.060)
-#ifndef ML_FFT_PASSES_R32
-#define ML_FFT_PASSES_R32 2
-#endif
-        const int P = c.passes > 0 ? c.passes : (R3 == 32 ? ML_FFT_PASSES_R32 : 1);
-        if (P > 1 && R3 % P == 0) {
-            const int R3P = R3 / P, NTp = 16 * R3P, M = a.g.M;
-            FftArgs ap = a;
-            zfft_choose_pads(c.N_eff / P, M, c.j0, &ap.g.pad1, &ap.g.pad2, c.jstep);
-            zf::Geo gp = ap.g;
-            gp.R3 = R3P;
-            const size_t bytes = ((size_t)zf::lds_elems(gp) + 256 + M) * sizeof(cd);   // + twiddles + pass ratios
-            const int per = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / bytes));
-            int gridp = std::min(256 * per, a.chunk * 8);
-            gridp = (gridp + 7) / 8 * 8;
-            const bool p1 = c.in_es == 1;
-#define ML_PASS(R, PP, NBB)                                                                   \
-    if (R3P == R && P == PP && M <= NBB * NTp)                                                \
-        return p1 ? (c.second ? launch_pass<R, PP, NBB, 2, 3>(stream, ap, gridp, bytes)       \
-                              : launch_pass<R, PP, NBB, 2, 1>(stream, ap, gridp, bytes))      \
-                  : launch_pass<R, PP, NBB, 2, 2>(stream, ap, gridp, bytes);
-            ML_PASS(16, 2, 2)
-            ML_PASS(32, 2, 2)
+    if (L.family == ZfftFamily::pass) {
+        // pass-split form (zfft_pass_kernel): the paddings of the pass geometry
+        const int P = L.P, M = a.g.M;
+        FftArgs ap = a;
+        zfft_choose_pads(c.N_eff / P, M, c.j0, &ap.g.pad1, &ap.g.pad2, c.jstep);
+        zf::Geo gp = ap.g;
+        gp.R3 = L.R3P;
+        const size_t bytes = ((size_t)zf::lds_elems(gp) + 256 + M) * sizeof(cd);   // + twiddles + pass ratios
+        const int per = (int)std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / bytes));
+        int gridp = std::min(256 * per, a.chunk * 8);
+        gridp = (gridp + 7) / 8 * 8;
+#define ML_PASS(R, PP, NBB)                                                                          \
+    if (L.R3P == R && L.P == PP && L.NB == NBB)                                                      \
+        return L.PASS == 3   ? launch_pass<R, PP, NBB, 2, 3>(stream, ap, gridp, bytes)               \
+               : L.PASS == 1 ? launch_pass<R, PP, NBB, 2, 1>(stream, ap, gridp, bytes)               \
+                             : launch_pass<R, PP, NBB, 2, 2>(stream, ap, gridp, bytes);
+        ML_PASS(16, 2, 2)
+        ML_PASS(32, 2, 2)
 #undef ML_PASS
-        }
     }
-    ML_REQUIRE(a.g.R3 <= 32, "a lattice of %d samples does not fit one workgroup (%d wanted bins)", c.N_eff, c.M);
-    if (a.g.R3 <= ML_ZFFT_IP && (a.g.R3 == 4 || a.g.R3 == 8 || a.g.R3 == 16 || a.g.R3 == 32)) {
+    ML_REQUIRE(L.family == ZfftFamily::one, "a lattice of %d samples does not fit one workgroup (%d wanted bins)",
+               c.N_eff, c.M);
+    if (L.ip) {
         // the in-place layout answers to one padding, chosen for its four access patterns
         a.g.ip = 1;
         zfft_choose_pads(-c.N_eff, c.M, c.j0, &a.g.pad1, &a.g.pad2, c.jstep);
         lds_bytes = ((size_t)zf::lds_elems(a.g) + 256) * sizeof(cd);
     }
-    // PASS (a template argument so that profiles can tell the launches apart): 1 rows of the aperture,
-    // 2 strided columns of a row-major stage-1 result, 3 contiguous rows of a transposed one, 4 rows of the
-    // aperture into a tiled one
-    if (c.in_es == 1 && c.second) switch (a.g.R3) {
+    // (R3T = 0: the instantiation for any residue count)
+    if (L.PASS == 3) switch (L.R3T) {   // contiguous rows of a transposed stage-1 result
             case 8: return launch_one<8, 128, 2, 3>(stream, a, grid, lds_bytes);
             case 16: return launch_one<16, 256, 2, 3>(stream, a, grid, lds_bytes);
-            case 32: return launch_one<32, 512, 2, 3>(stream, a, grid, lds_bytes);
-            default: break;
+            default: return launch_one<32, 512, 2, 3>(stream, a, grid, lds_bytes);
         }
-    if (c.tiled_out) switch (a.g.R3) {   // pass 1 into a tiled G (out_es: the tile's stride)
+    if (L.PASS == 4) switch (L.R3T) {   // pass 1 into a tiled G (out_es: the tile's stride)
             case 4: return launch_one<4, 64, 2, 4>(stream, a, grid, lds_bytes);
             case 8: return launch_one<8, 128, 2, 4>(stream, a, grid, lds_bytes);
             case 16: return launch_one<16, 256, 2, 4>(stream, a, grid, lds_bytes);
             default: return launch_one<0, 512, 1, 4>(stream, a, grid, lds_bytes);
         }
-    if (c.in_es == 1) switch (a.g.R3) {   // pass 1: contiguous rows
+    if (L.PASS == 1) switch (L.R3T) {   // pass 1: contiguous rows
             case 4: return launch_one<4, 64, 2, 1>(stream, a, grid, lds_bytes);
             case 8: return launch_one<8, 128, 2, 1>(stream, a, grid, lds_bytes);
             case 16: return launch_one<16, 256, 2, 1>(stream, a, grid, lds_bytes);
             case 32: return launch_one<32, 512, 2, 1>(stream, a, grid, lds_bytes);
             default: return launch_one<0, 512, 1, 1>(stream, a, grid, lds_bytes);
         }
-    switch (a.g.R3) {                     // pass 2: strided columns
+    switch (L.R3T) {                     // pass 2: strided columns
         case 4: return launch_one<4, 64, 2, 2>(stream, a, grid, lds_bytes);
         case 8: return launch_one<8, 128, 2, 2>(stream, a, grid, lds_bytes);
         case 16: return launch_one<16, 256, 2, 2>(stream, a, grid, lds_bytes);

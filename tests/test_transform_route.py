@@ -21,6 +21,7 @@ def route(tmp_path_factory):
         res = subprocess.run([out + 'transform_route'] + args, capture_output=True, text=True, timeout=60)
         assert res.returncode == 0, res.stdout + res.stderr
         return dict(kv.split('=') for kv in res.stdout.split())
+    run.exe = out + 'transform_route'
     return run
 
 

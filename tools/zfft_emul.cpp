@@ -1,6 +1,8 @@
 // Host emulation of zfft.hip's per-thread programme (metalens_amd/csrc/zfft_core.h): runs the
 // phases thread by thread against a direct DFT in long double and reports the LDS bank-conflict
 // cycles of the chosen paddings.  Build + run:  make -C tools zfft_emul && tools/zfft_emul
+// With arguments, one axis row of tests/fft_cases.py instead of the built-in cases:
+//   tools/zfft_emul R3 n_valid M j0 in_place jstep passes
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -93,9 +95,9 @@ static double run(int R3, int n_valid, int M, int j0, bool verbose, int ip = 0, 
 // geometry of R3' residues (half or a quarter of the LDS), its last stage sums R3' terms with the
 // FULL lattice's ratio W_N^k, and the passes combine by Horner in W_N^(R3' k):
 //     X[k] = sum_p W_N^(p R3' k) sum_{n0' < R3'} B[p R3' + n0', k1, k2] (W_N^k)^n0'
-static double run_passes(int R3, int P, int n_valid, int M, int j0) {
+static double run_passes(int R3, int P, int n_valid, int M, int j0, int jstep = 1) {
     const int R3p = R3 / P, N = 256 * R3, NTp = 16 * R3p;
-    zf::Geo g{R3p, n_valid, M, j0, 0, 0};
+    zf::Geo g{R3p, n_valid, M, j0, 0, 0, 0, jstep};
     zf::choose_pads(g);
     std::vector<cd> in(N), lds(zf::lds_elems(g));
     srand(R3 * 131 + M + P);
@@ -124,7 +126,7 @@ static double run_passes(int R3, int P, int n_valid, int M, int j0) {
         for (int u = 0; u < NTp; ++u) zf::gather2(g, u, v[u].data(), lds.data());
         for (int u = 0; u < NTp; ++u) zf::scatter2(g, u, v[u].data(), lds.data());
         for (int j = 0; j < M; ++j) {
-            long long k = ((long long)j + j0) % N;
+            long long k = (((long long)j + j0) * jstep) % N;
             if (k < 0) k += N;
             const cd part = zf::stage3(g, (int)k, ratio(k), lds.data());
             acc[j] = p == P - 1 ? part : zf::cmac(acc[j], ratio(k * R3p), part);
@@ -133,7 +135,7 @@ static double run_passes(int R3, int P, int n_valid, int M, int j0) {
     double worst = 0, scale = 0;
     for (int j = 0; j < M; ++j) {
         long double re = 0, im = 0;
-        long long k = ((long long)j + j0) % N;
+        long long k = (((long long)j + j0) * jstep) % N;
         if (k < 0) k += N;
         for (int n = 0; n < n_valid; ++n) {
             const long double a = -2 * M_PIl * (((long long)n * k) % N) / N;
@@ -204,8 +206,18 @@ static double run_cols128(int G, int r, int M, int j0) {
     return worst / scale;
 }
 
-int main() {
+int main(int argc, char **argv) {
     double worst = 0;
+    if (argc > 1) {
+        if (argc != 8) return fprintf(stderr, "usage: %s [R3 n_valid M j0 in_place jstep passes]\n", argv[0]), 2;
+        int v[7];
+        for (int k = 0; k < 7; ++k) v[k] = atoi(argv[k + 1]);
+        if (v[0] < 1 || v[1] < 1 || v[1] > 256 * v[0] || v[2] < 1 || v[5] < 1 || (v[6] > 1 && v[0] % v[6]))
+            return fprintf(stderr, "no such transform\n"), 2;
+        worst = v[6] > 1 ? run_passes(v[0], v[6], v[1], v[2], v[3], v[5]) : run(v[0], v[1], v[2], v[3], true, v[4], v[5]);
+        printf("worst relative error %.3e -> %s\n", worst, worst < 1e-13 ? "OK" : "FAIL");
+        return worst < 1e-13 ? 0 : 1;
+    }
     const int cases[][4] = {{16, 4096, 512, -256}, {8, 2048, 256, -128}, {32, 8192, 512, -256},
                             {16, 4000, 512, -256}, {4, 1024, 64, -32},   {4, 1000, 100, -37},
                             {16, 4096, 300, 1000}, {1, 256, 64, -32},    {2, 512, 512, -256},

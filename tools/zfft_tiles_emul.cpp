@@ -3,6 +3,8 @@
 // thread by thread, round by round, on one tile and are checked against a direct DFT of every column in long double.
 // Also reports the LDS cycles of one round against the conflict-free count.
 // Build + run:  make -C tools zfft_tiles_emul && tools/zfft_tiles_emul
+// With arguments, one column pass of tests/fft_cases.py instead of the built-in cases (resident samples [a0, a0 + h0)
+// of the columns):  tools/zfft_tiles_emul R3 a0 h0 M j0
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -87,8 +89,18 @@ static double run(int R3, int a0, int h0, int M, int j0, int ld_skew) {
     return rel;
 }
 
-int main() {
+int main(int argc, char **argv) {
     double worst = 0;
+    if (argc > 1) {
+        if (argc != 6) return fprintf(stderr, "usage: %s [R3 a0 h0 M j0]\n", argv[0]), 2;
+        int v[5];
+        for (int k = 0; k < 5; ++k) v[k] = atoi(argv[k + 1]);
+        if (v[0] < 1 || v[1] < 0 || v[2] < 1 || v[1] + v[2] > 256 * v[0] || v[3] < 1 || v[3] > zf::TL_NT)
+            return fprintf(stderr, "no such column pass\n"), 2;
+        worst = run(v[0], v[1], v[2], v[3], v[4], 8);
+        printf("worst rel err %.3e -> %s\n", worst, worst <= 1e-15 ? "OK" : "FAIL");
+        return worst <= 1e-15 ? 0 : 1;
+    }
     worst = fmax(worst, run(16, 0, 4096, 512, -256, 8));    // the benchmark's geometry
     worst = fmax(worst, run(16, 150, 3796, 512, -250, 8));  // trimmed rows, a window not on a 256 boundary
     worst = fmax(worst, run(8, 0, 2000, 256, 3, 8));        // a lattice longer than the aperture
