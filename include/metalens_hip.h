@@ -359,6 +359,15 @@ int ml_farfield_project_async(ml_ctx *ctx, double Z0);
  * ml_nearfield_async / ml_nearfield are the n = 1 case.                                       */
 int ml_nearfield_batch_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts,
                              int nx, const double *y_pts, int ny);
+/* As ml_nearfield_batch_async, but EVERY member goes through the single-source kernels one after the other, also
+ * when the members share one position: field set m then has the bits ml_nearfield_async gives for member m alone
+ * (members at one position synthesised together share the per-sample evaluation and round differently, by a few
+ * 1e-16 of the field's scale - nearfield.py has one source per call, so this is the reference's granularity).
+ * keep_powers != 0: a re-synthesis of the batch that is resident (same n, nx, ny; ML_ESTATE otherwise) - the
+ * incident powers stay those of the synthesis before, ml_nearfield_powers returns them unchanged.  Used by the
+ * image of a sweep (ml_propagate_sets), whose per-source fields are those of the source alone.           */
+int ml_nearfield_members_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts,
+                               int nx, const double *y_pts, int ny, int keep_powers);
 int ml_fields_select(ml_ctx *ctx, int set);
 int ml_nearfield_powers(ml_ctx *ctx, double *power, int n);
 /* Sums over the sources of a sweep, kept on the GPU: after ml_farfield_project[_async],
@@ -448,6 +457,34 @@ int ml_propagate(ml_ctx *ctx, double Z0);
  * plan's order).  H may be NULL, and must be for a plan with want_h == 0.  Synchronises.  Replaces no
  * reference lines (convention: nearfield_farfield.py:94-101, 183-185).                    */
 int ml_propagate_download(ml_ctx *ctx, double *E, double *H);
+/* Several resident field sets in ONE pass: the sets first_set ... first_set + n_sets - 1 of the last synthesis
+ * batch (ml_nearfield_batch_async; 1 <= n_sets <= 3, inside the resident sets) for the active propagation plan,
+ * queued on the context's stream.  What depends on the (sample, target) pair alone - R, Rhat, the sincos of k R -
+ * is computed once for all sets; the fields of every set have the bits that ml_fields_select(set) + ml_propagate
+ * give.  The result is complex128 [n_sets][6 or 3][targets] on the device (ml_propagate_download_set,
+ * ml_propagate_accumulate).  Checks as ml_propagate; the selected set (ml_fields_select) is not changed.
+ * Replaces no reference lines; Z0 as for ml_propagate.                                     */
+int ml_propagate_sets(ml_ctx *ctx, double Z0, int first_set, int n_sets);
+/* How many field sets are resident (the members of the last ml_nearfield_batch_async; 1 after a single
+ * synthesis or ml_fields_upload): what ml_propagate_sets may range over.  Replaces no reference lines.   */
+int ml_fields_sets(ml_ctx *ctx, int *n_sets);
+/* E, H of member `set` (0 ... n_sets - 1) of the last ml_propagate_sets, laid out as for
+ * ml_propagate_download (which returns member 0).  H may be NULL, and must be for a plan with want_h == 0.
+ * Synchronises.  Replaces no reference lines.                                             */
+int ml_propagate_download_set(ml_ctx *ctx, int set, double *E, double *H);
+/* Image-plane sums kept on the GPU, double [2][targets] of the active propagation plan: with
+ *   i_m = (|Ex|^2 + |Ey|^2) + |Ez|^2   and   s_m = 0.5 ((Re Ex Hy* ) - (Re Ey Hx*))   of member m of the last pass,
+ *   I += weights[0] i_0 + ... + weights[n - 1] i_(n - 1),   Sz += weights[0] s_0 + ...   (plans with H only):
+ * the pass's own sum is formed in member order and then added ONCE to the running sum (reset != 0: to zero, so
+ * the sums then hold this pass alone).  n = 1 ... the sets of the last pass.  The first call on a plan needs
+ * reset != 0 (ML_ESTATE otherwise); ml_propagate_plan drops results and sums.  Asynchronous, no atomics:
+ * repeatable bit for bit.  Replaces no reference lines: the reference sums powers in direction
+ * space only (nearfield.py:69-73), this is the same incoherent sum on an image plane.                    */
+int ml_propagate_accumulate(ml_ctx *ctx, const double *weights, int n, int reset);
+/* The sums of ml_propagate_accumulate: I, Sz double [targets].  Sz may be NULL, and must be for a plan with
+ * want_h == 0.  ML_ESTATE if no accumulation has run on the active propagation plan.  Synchronises.
+ * Replaces no reference lines.                                                            */
+int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,8 @@ SYMBOLS = (
     'ml_farfield_accumulate', 'ml_farfield_sums', 'ml_farfield_total_power', 'ml_host_alloc', 'ml_host_free',
     'ml_comm_info', 'ml_comm_set_reduce', 'ml_farfield_gather', 'ml_nearfield_kernel_info',
     'ml_comm_set_max_channels', 'ml_propagate_plan', 'ml_propagate', 'ml_propagate_download',
+    'ml_propagate_sets', 'ml_propagate_download_set', 'ml_propagate_accumulate', 'ml_propagate_sums',
+    'ml_fields_sets', 'ml_nearfield_members_async',
 )
 
 
@@ -102,6 +104,8 @@ def load():
     lib.ml_nearfield_async.argtypes = [c_void_p, POINTER(NearfieldParams), _dp, c_int, _dp, c_int]
     lib.ml_nearfield_batch_async.argtypes = [c_void_p, POINTER(NearfieldParams), c_int, _dp, c_int,
                                              _dp, c_int]
+    lib.ml_nearfield_members_async.argtypes = [c_void_p, POINTER(NearfieldParams), c_int, _dp, c_int,
+                                               _dp, c_int, c_int]
     lib.ml_fields_select.argtypes = [c_void_p, c_int]
     lib.ml_nearfield_powers.argtypes = [c_void_p, _dp, c_int]
     lib.ml_farfield_accumulate.argtypes = [c_void_p, c_double, c_double, c_double, c_double, c_int, c_int]
@@ -155,6 +159,11 @@ def load():
                                       _dp, c_int, _dp, c_int, _dp, c_int, c_int, c_int]
     lib.ml_propagate.argtypes = [c_void_p, c_double]
     lib.ml_propagate_download.argtypes = [c_void_p, _dp, _dp]
+    lib.ml_propagate_sets.argtypes = [c_void_p, c_double, c_int, c_int]
+    lib.ml_propagate_download_set.argtypes = [c_void_p, c_int, _dp, _dp]
+    lib.ml_propagate_accumulate.argtypes = [c_void_p, _dp, c_int, c_int]
+    lib.ml_propagate_sums.argtypes = [c_void_p, _dp, _dp]
+    lib.ml_fields_sets.argtypes = [c_void_p, POINTER(c_int)]
     lib.ml_profile_enable.argtypes = [c_void_p, c_int]
     lib.ml_profile_reset.argtypes = [c_void_p]
     lib.ml_profile_get.argtypes = [c_void_p, c_int, POINTER(c_int64), _dp]

@@ -366,12 +366,14 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
 // Targets and buffers of the finite-distance propagator (propagate.hip).  Its own: nothing here is shared with the
 // far-field plan, the radiation vectors or the sweep sums.
 struct PropagatePlan {
-    bool ready = false, have_result = false;
+    bool ready = false, have_result = false, have_sums = false;
     int T = 0, want_h = 1;
+    int result_sets = 0;   // field sets in `result`: 1 after ml_propagate, n after ml_propagate_sets
     double x0 = 0, y0 = 0, dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
     DevBuf targets;   // double [3][T]: x - x0, y - y0, z of every target
-    DevBuf partial;   // double [splits][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
-    DevBuf result;    // complex [6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz)
+    DevBuf partial;   // double [splits][sets][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
+    DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
+    DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
 };
 
 }  // namespace ml
@@ -600,7 +602,10 @@ int comm_allgather(ml_ctx *ctx, double *buf, size_t chunk, hipStream_t stream);
 int comm_join(ml_ctx *ctx, bool host);
 
 // nearfield.hip: synthesis of a batch of n sources that differ in polarisation only
-int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny);
+// members_alone: every member through the single-source kernels, also when all share one position; keep_powers: the
+// incident powers of the synthesis before stay what ml_nearfield_powers returns (ml_nearfield_members_async)
+int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny, bool members_alone = false,
+                     bool keep_powers = false);
 // sum the pending power partials now (no-op if none are pending)
 int power_flush(ml_ctx *ctx);
 // ML_NO_PLAN_CACHE=1: rebuild every geometry-only table on every call (for timing them)

@@ -922,7 +922,7 @@ int ml_upload_layout(ml_ctx *ctx, int n_rings, const double *B, const double *r_
 }
 
 static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts,
-                             int nx, const double *y_pts, int ny) {
+                             int nx, const double *y_pts, int ny, bool members_alone = false, bool keep_powers = false) {
     ML_REQUIRE(ctx && p && x_pts && y_pts, "NULL argument");
     ML_REQUIRE(nx >= 1 && ny >= 1, "empty grid (%d x %d)", nx, ny);
     ML_REQUIRE(n >= 1 && n <= 3, "a batch has 1 to 3 members, got %d", n);
@@ -988,7 +988,7 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
     ML_TRY(ctx->active_list.reserve((size_t)4 * blocks * 2 * sizeof(int)));           // four lists (NfArgs::active_list)
     ML_TRY(ctx->active_count.reserve((size_t)4 * (blocks / 1024 + 4) * sizeof(int)));   // each: total + one per chunk of 1024 patches
     ML_TRY(ctx->active_flag.reserve((size_t)blocks * sizeof(int)));
-    return nearfield_launch(ctx, p, n, nx, ny);
+    return nearfield_launch(ctx, p, n, nx, ny, members_alone, keep_powers);
 }
 
 int ml_nearfield_async(ml_ctx *ctx, const ml_nearfield_params *p, const double *x_pts, int nx,
@@ -999,6 +999,17 @@ int ml_nearfield_async(ml_ctx *ctx, const ml_nearfield_params *p, const double *
 int ml_nearfield_batch_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts,
                              int nx, const double *y_pts, int ny) {
     return nearfield_prepare(ctx, p, n, x_pts, nx, y_pts, ny);
+}
+
+int ml_nearfield_members_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts, int nx,
+                               const double *y_pts, int ny, int keep_powers) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    if (keep_powers && !(ctx->power.p && ctx->nx == nx && ctx->ny == ny && ctx->n_sets == n)) {
+        set_error("ml_nearfield_members_async: keep_powers needs a synthesis of %d members on %d x %d samples before it", n,
+                  nx, ny);
+        return ML_ESTATE;
+    }
+    return nearfield_prepare(ctx, p, n, x_pts, nx, y_pts, ny, true, keep_powers != 0);
 }
 
 int ml_fields_select(ml_ctx *ctx, int set) {

@@ -211,7 +211,9 @@ void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int 
     ctx->fields_premod_serial = premod ? pl.serial : -1;
 }
 
-int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny) {
+int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny, bool members_alone,
+                     bool keep_powers) {
+    if (keep_powers) ML_TRY(power_flush(ctx));   // partials of the synthesis before, about to be overwritten
     NfArgs a;
     // this launch reports into the half the previous launch cleared
     ctx->viol_half = 1 - ctx->viol_half;
@@ -295,7 +297,7 @@ int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, i
                        p[m].source_z == p[0].source_z;
     {
         ProfScope scope(ctx, ML_K_NEARFIELD);
-        if (one_position) {
+        if (one_position && !members_alone) {
             ML_TRY(nearfield_fast_launch(ctx, a, &n_partials));
         } else {
             for (int m = 0; m < n; ++m) {
@@ -315,6 +317,7 @@ int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, i
     ML_HIP(hipGetLastError());
     // the partials are summed by the projection kernel if one follows, else on demand
     ctx->n_partials = n_partials;
+    if (keep_powers) return ML_OK;   // (the partials just written are not summed: `power` stays as it is)
     ctx->power_pending = true;
     // a batch sums the partials of all its members now (the projection kernel's spare block,
     // which does it for free in the single-source pipeline, knows one set only)

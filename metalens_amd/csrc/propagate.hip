@@ -17,6 +17,13 @@
 // workgroups per target tile - few targets still fill the chip, and every workgroup crosses the lens
 // alike - each of which leaves a partial sum; a second pass adds the partials in their order.  No atomics:
 // the result is bit-for-bit repeatable, and `splits` depends on the sizes alone.
+// Several field sets in one pass (NS = 2, 3: the members of a synthesis batch, ml_propagate_sets).  Everything above
+// that depends on the pair alone - dy, R, 1 / R, Rhat, q, the sincos of k R, w, a, b: about 68 of the 176 vector
+// instructions of a pair - is computed once per pair and serves every set; a tile is staged as
+// [sample][set][current] (64 NS bytes per sample, 24 KiB at NS = 3) and pair_term runs once per set into that set's own
+// accumulators.  The per-pair expressions are the same inlined functions in the same order whatever NS is, nothing is
+// contracted (-ffp-contract=off, explicit fma() only) and `splits` does not depend on NS: the result of a set has
+// the bits of that set propagated alone.
 // A synthesised field carries row extents (nearfield.hip row_extent_kernel): samples outside them are
 // exact zeros and are not visited.  The extents are read from the device's own array.  A skipped sample
 // would have added +-0 to every accumulator, so the result has the bits of the whole sum.
@@ -27,14 +34,15 @@
 namespace ml {
 
 constexpr int PROP_THREADS = 256;   // targets per workgroup
-constexpr int PROP_TILE = 128;      // aperture samples per LDS tile (8 KiB)
+constexpr int PROP_TILE = 128;      // aperture samples per LDS tile (8 KiB per field set)
+constexpr int PROP_MAX_SETS = 3;    // field sets per pass (the members of a synthesis batch, nearfield_dev.h MAX_POL)
 constexpr int PROP_BLOCKS = 2048;   // workgroups aimed at: eight per compute unit
 
 struct PropArgs {
-    const double2 *fields;   // [4][nx][ny]: Ex, Ey, Hx, Hy of the selected field set
+    const double2 *fields;   // [NS][4][nx][ny]: Ex, Ey, Hx, Hy of the first field set of the pass, the others behind it
     const int *row_first;    // [nx] (row_extent_kernel) or nullptr: every sample is read
     const double *tx, *ty, *tz;   // [T]: x - x0, y - y0, z
-    double *partial;         // [splits][12 or 6][T]
+    double *partial;         // [splits][NS][12 or 6][T]
     int nx, ny, T, splits;
     double dxp, dyp, k, inv_k, Z;
 };
@@ -64,20 +72,25 @@ __device__ __forceinline__ void pair_term(c2 acc[3], c2 w, double q, c2 a, c2 b,
     cfma(acc[2], w, fma(s, fma(-q, Xz.r, -Xz.i), -Dz.i), fma(s, fma(-q, Xz.i, Xz.r), Dz.r));
 }
 
-template <bool WANT_H>
+template <bool WANT_H, int NS>
 __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs a) {
-    __shared__ double2 s_cur[PROP_TILE][4];   // Jx, Jy, Mx / Z, My / Z
+    __shared__ double2 s_cur[PROP_TILE][NS][4];   // per field set: Jx, Jy, Mx / Z, My / Z
     const int tid = threadIdx.x;
     const int t = blockIdx.x * PROP_THREADS + tid;
     const int tc = min(t, a.T - 1);   // (lanes past the last target work on a copy of it and store nothing)
     const double tx = a.tx[tc], ty = a.ty[tc], z = a.tz[tc];
     const double zz = z * z;
     const bool wave_live = blockIdx.x * PROP_THREADS + (tid & ~63) < a.T;
-    // staging: this thread converts field f of the columns c and c + 64 of a tile into current 3 - f:
+    // staging: this thread converts field f of the columns c and c + 64 of a tile into current 3 - f, set by set:
     // Ex -> My / Z = -Ex / Z, Ey -> Mx / Z, Hx -> Jy, Hy -> Jx = -Hy  (a division: exact for Z = 1, and x 2 commutes)
     const int f = tid >> 6, c = tid & 63;
     const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? a.Z : 1.0;
-    c2 E[3] = {{0, 0}, {0, 0}, {0, 0}}, H[3] = {{0, 0}, {0, 0}, {0, 0}};
+    const size_t set_stride = (size_t)4 * a.nx * a.ny;
+    c2 E[NS][3], H[NS][3];
+#pragma unroll
+    for (int m = 0; m < NS; ++m)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) E[m][d] = H[m][d] = c2{0, 0};
     for (int i = blockIdx.y; i < a.nx; i += a.splits) {
         const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
         const int j_hi = a.ny - first;
@@ -89,14 +102,15 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
             const int n = min(PROP_TILE, j_hi - j0);
             __syncthreads();   // the previous tile has been read
             for (int cc = c; cc < n; cc += 64) {
-                const double2 v = row[j0 + cc];
-                s_cur[cc][3 - f] = make_double2(sg * v.x / den, sg * v.y / den);
+#pragma unroll
+                for (int m = 0; m < NS; ++m) {
+                    const double2 v = (row + m * set_stride)[j0 + cc];
+                    s_cur[cc][m][3 - f] = make_double2(sg * v.x / den, sg * v.y / den);
+                }
             }
             __syncthreads();
             if (!wave_live) continue;
             for (int s = 0; s < n; ++s) {
-                const double2 v0 = s_cur[s][0], v1 = s_cur[s][1], v2 = s_cur[s][2], v3 = s_cur[s][3];
-                const c2 Jx = {v0.x, v0.y}, Jy = {v1.x, v1.y}, Mx = {v2.x, v2.y}, My = {v3.x, v3.y};
                 const double dy = fma(-(double)(j0 + s), a.dyp, ty);
                 const double R = sqrt_exact(fma(dy, dy, s_row));
                 const double iR = recip(R);
@@ -106,37 +120,139 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
                 sincos_cw(a.k * R, sn, cs);
                 const c2 w = {cs * q, sn * q};
                 const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
-                pair_term<-1>(E, w, q, ca, cb, ux, uy, uz, Jx, Jy, Mx, My);
-                if (WANT_H) pair_term<1>(H, w, q, ca, cb, ux, uy, uz, Mx, My, Jx, Jy);
+#pragma unroll
+                for (int m = 0; m < NS; ++m) {
+                    const double2 v0 = s_cur[s][m][0], v1 = s_cur[s][m][1], v2 = s_cur[s][m][2], v3 = s_cur[s][m][3];
+                    const c2 Jx = {v0.x, v0.y}, Jy = {v1.x, v1.y}, Mx = {v2.x, v2.y}, My = {v3.x, v3.y};
+                    pair_term<-1>(E[m], w, q, ca, cb, ux, uy, uz, Jx, Jy, Mx, My);
+                    if (WANT_H) pair_term<1>(H[m], w, q, ca, cb, ux, uy, uz, Mx, My, Jx, Jy);
+                }
             }
         }
     }
     if (t >= a.T) return;
     constexpr int NQ = WANT_H ? 12 : 6;
-    double *out = a.partial + (size_t)blockIdx.y * NQ * a.T + t;
-    for (int m = 0; m < 3; ++m) {
-        out[(size_t)(2 * m) * a.T] = E[m].r;
-        out[(size_t)(2 * m + 1) * a.T] = E[m].i;
-        if (WANT_H) {
-            out[(size_t)(6 + 2 * m) * a.T] = H[m].r;
-            out[(size_t)(7 + 2 * m) * a.T] = H[m].i;
+    double *out = a.partial + (size_t)blockIdx.y * NS * NQ * a.T + t;
+#pragma unroll
+    for (int m = 0; m < NS; ++m)
+        for (int d = 0; d < 3; ++d) {
+            out[(size_t)(m * NQ + 2 * d) * a.T] = E[m][d].r;
+            out[(size_t)(m * NQ + 2 * d + 1) * a.T] = E[m][d].i;
+            if (WANT_H) {
+                out[(size_t)(m * NQ + 6 + 2 * d) * a.T] = H[m][d].r;
+                out[(size_t)(m * NQ + 7 + 2 * d) * a.T] = H[m][d].i;
+            }
         }
-    }
 }
 
-// second pass: result[component][target] = scale * (partial 0 + partial 1 + ...), in that order
+// second pass: result[set][component][target] = scale * (partial 0 + partial 1 + ...), in that order
 __global__ __launch_bounds__(256) void propagate_reduce_kernel(const double *partial, double2 *result, int T, int splits,
                                                                int nq, double scale_e, double scale_h) {
     const int t = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y;   // m: complex component, 0-2 E, 3-5 H
+    const int set = blockIdx.z, ns = gridDim.z;
     if (t >= T) return;
     double re = 0.0, im = 0.0;
     for (int s = 0; s < splits; ++s) {
-        const double *p = partial + ((size_t)s * nq + 2 * m) * T + t;
+        const double *p = partial + (((size_t)s * ns + set) * nq + 2 * m) * T + t;
         re += p[0];
         im += p[T];
     }
     const double scale = m < 3 ? scale_e : scale_h;
-    result[(size_t)m * T + t] = make_double2(scale * re, scale * im);
+    result[((size_t)set * (nq / 2) + m) * T + t] = make_double2(scale * re, scale * im);
+}
+
+struct PropWeights {
+    double w[PROP_MAX_SETS];
+};
+
+// sums[0][t] (+)= sum_m w_m |E_m|^2, sums[1][t] (+)= sum_m w_m Re(E_m x H_m*)_z / 2 over the n sets of `result`: the pass's
+// own sum is formed first, in set order, and then added once to what the sums hold (`reset`: to zero) - one lane per
+// target, plain stores
+__global__ __launch_bounds__(256) void propagate_accumulate_kernel(const double2 *result, double *sums, int T, int n,
+                                                                   int want_h, int reset, const PropWeights wt) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const int nc = want_h ? 6 : 3;
+    double I = 0.0, Sz = 0.0;
+    for (int m = 0; m < n; ++m) {
+        const double2 *r = result + (size_t)m * nc * T + t;
+        const double2 Ex = r[0], Ey = r[T], Ez = r[2 * (size_t)T];
+        const double i_m = ((Ex.x * Ex.x + Ex.y * Ex.y) + (Ey.x * Ey.x + Ey.y * Ey.y)) + (Ez.x * Ez.x + Ez.y * Ez.y);
+        const double wi = wt.w[m] * i_m;
+        I = m == 0 ? wi : I + wi;
+        if (want_h) {
+            const double2 Hx = r[3 * (size_t)T], Hy = r[4 * (size_t)T];
+            const double s_m = 0.5 * ((Ex.x * Hy.x + Ex.y * Hy.y) - (Ey.x * Hx.x + Ey.y * Hx.y));
+            const double ws = wt.w[m] * s_m;
+            Sz = m == 0 ? ws : Sz + ws;
+        }
+    }
+    sums[t] = reset ? I : sums[t] + I;
+    if (want_h) sums[(size_t)T + t] = reset ? Sz : sums[(size_t)T + t] + Sz;
+}
+
+template <bool WANT_H>
+static void launch_pairs(hipStream_t stream, dim3 grid, const PropArgs &a, int ns) {
+    if (ns == 1)
+        hipLaunchKernelGGL((propagate_kernel<WANT_H, 1>), grid, dim3(PROP_THREADS), 0, stream, a);
+    else if (ns == 2)
+        hipLaunchKernelGGL((propagate_kernel<WANT_H, 2>), grid, dim3(PROP_THREADS), 0, stream, a);
+    else
+        hipLaunchKernelGGL((propagate_kernel<WANT_H, 3>), grid, dim3(PROP_THREADS), 0, stream, a);
+}
+
+// the sets first ... first + n - 1 of the resident field in one pass -> pp.result [n][6 or 3][T]
+static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, int n) {
+    PropagatePlan &pp = ctx->prop;
+    if (!pp.ready) {
+        set_error("ml_propagate_plan has not been called");
+        return ML_ESTATE;
+    }
+    if (ctx->nx == 0 || ctx->ny == 0) {
+        set_error("no resident field set");
+        return ML_ESTATE;
+    }
+    ML_REQUIRE(ctx->n_ranks <= 1, "%s: this context belongs to a communicator of %d ranks", who, ctx->n_ranks);
+    ML_REQUIRE(Z0 > 0, "Z0 must be positive");
+    ML_REQUIRE(n >= 1 && n <= PROP_MAX_SETS, "%s: a pass takes 1 to %d field sets, got %d", who, PROP_MAX_SETS, n);
+    ML_REQUIRE(first >= 0 && first + n <= ctx->n_sets, "%s: field sets %d ... %d asked for, %d resident", who, first,
+               first + n - 1, ctx->n_sets);
+    ML_HIP(hipSetDevice(ctx->device));
+    ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
+    const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
+    const int splits = std::max(1, std::min(ctx->nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
+    pp.have_result = false;
+    ML_TRY(pp.partial.reserve((size_t)splits * n * nq * T * sizeof(double)));
+    ML_TRY(pp.result.reserve((size_t)n * (nq / 2) * T * 2 * sizeof(double)));
+    PropArgs a;
+    a.fields = ctx->fields.as<double2>() + (size_t)first * 4 * ctx->nx * ctx->ny;
+    a.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr;
+    a.tx = pp.targets.as<double>();
+    a.ty = a.tx + T;
+    a.tz = a.tx + 2 * (size_t)T;
+    a.partial = pp.partial.as<double>();
+    a.nx = ctx->nx;
+    a.ny = ctx->ny;
+    a.T = T;
+    a.splits = splits;
+    a.dxp = pp.dxp;
+    a.dyp = pp.dyp;
+    a.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
+    a.inv_k = 1.0 / a.k;
+    a.Z = Z0 / pp.n_glass;
+    const dim3 grid(tiles, splits);
+    if (pp.want_h)
+        launch_pairs<true>(ctx->stream, grid, a, n);
+    else
+        launch_pairs<false>(ctx->stream, grid, a, n);
+    ML_HIP(hipGetLastError());
+    const double scale_h = a.k * a.k / (4.0 * M_PI) * pp.dxp * pp.dyp;
+    hipLaunchKernelGGL(propagate_reduce_kernel, dim3((T + 255) / 256, nq / 2, n), dim3(256), 0, ctx->stream,
+                       pp.partial.as<double>(), pp.result.as<double2>(), T, splits, nq, a.Z * scale_h, scale_h);
+    ML_HIP(hipGetLastError());
+    pp.have_result = true;
+    pp.result_sets = n;
+    return ML_OK;
 }
 
 }  // namespace ml
@@ -163,7 +279,7 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
     for (int d = 0; d < nz; ++d) ML_REQUIRE(z[d] > 0, "target %d lies at z = %g: the propagator needs z > 0", d, z[d]);
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
-    pp.ready = pp.have_result = false;
+    pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
     std::vector<double> h((size_t)3 * T);
     for (long long t = 0; t < T; ++t) {
         const int ix = point_list ? (int)t : (int)(t / ny_t), iy = point_list ? (int)t : (int)(t % ny_t);
@@ -188,65 +304,83 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
 
 int ml_propagate(ml_ctx *ctx, double Z0) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    PropagatePlan &pp = ctx->prop;
-    if (!pp.ready) {
-        set_error("ml_propagate_plan has not been called");
-        return ML_ESTATE;
-    }
-    if (ctx->nx == 0 || ctx->ny == 0) {
-        set_error("no resident field set");
-        return ML_ESTATE;
-    }
-    ML_REQUIRE(ctx->n_ranks <= 1, "ml_propagate: this context belongs to a communicator of %d ranks", ctx->n_ranks);
-    ML_REQUIRE(Z0 > 0, "Z0 must be positive");
-    ML_HIP(hipSetDevice(ctx->device));
-    ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
-    const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
-    const int splits = std::max(1, std::min(ctx->nx, (PROP_BLOCKS + tiles - 1) / tiles));
-    ML_TRY(pp.partial.reserve((size_t)splits * nq * T * sizeof(double)));
-    ML_TRY(pp.result.reserve((size_t)(nq / 2) * T * 2 * sizeof(double)));
-    PropArgs a;
-    a.fields = reinterpret_cast<const double2 *>(ctx->set_ptr());
-    a.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr;
-    a.tx = pp.targets.as<double>();
-    a.ty = a.tx + T;
-    a.tz = a.tx + 2 * (size_t)T;
-    a.partial = pp.partial.as<double>();
-    a.nx = ctx->nx;
-    a.ny = ctx->ny;
-    a.T = T;
-    a.splits = splits;
-    a.dxp = pp.dxp;
-    a.dyp = pp.dyp;
-    a.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
-    a.inv_k = 1.0 / a.k;
-    a.Z = Z0 / pp.n_glass;
-    const dim3 grid(tiles, splits);
-    if (pp.want_h)
-        hipLaunchKernelGGL(propagate_kernel<true>, grid, dim3(PROP_THREADS), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL(propagate_kernel<false>, grid, dim3(PROP_THREADS), 0, ctx->stream, a);
-    ML_HIP(hipGetLastError());
-    const double scale_h = a.k * a.k / (4.0 * M_PI) * pp.dxp * pp.dyp;
-    hipLaunchKernelGGL(propagate_reduce_kernel, dim3((T + 255) / 256, nq / 2), dim3(256), 0, ctx->stream,
-                       pp.partial.as<double>(), pp.result.as<double2>(), T, splits, nq, a.Z * scale_h, scale_h);
-    ML_HIP(hipGetLastError());
-    pp.have_result = true;
+    return propagate_sets(ctx, "ml_propagate", Z0, ctx->field_set, 1);
+}
+
+int ml_propagate_sets(ml_ctx *ctx, double Z0, int first_set, int n_sets) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    return propagate_sets(ctx, "ml_propagate_sets", Z0, first_set, n_sets);
+}
+
+int ml_fields_sets(ml_ctx *ctx, int *n_sets) {
+    ML_REQUIRE(ctx && n_sets, "NULL argument");
+    *n_sets = (ctx->nx && ctx->ny) ? ctx->n_sets : 0;
     return ML_OK;
 }
 
-int ml_propagate_download(ml_ctx *ctx, double *E, double *H) {
-    ML_REQUIRE(ctx && E, "NULL argument");
+static int download_set(ml_ctx *ctx, int set, double *E, double *H) {
     PropagatePlan &pp = ctx->prop;
     if (!pp.ready || !pp.have_result) {
         set_error("ml_propagate has not run on the active propagation plan");
         return ML_ESTATE;
     }
+    ML_REQUIRE(set >= 0 && set < pp.result_sets, "member %d asked for, the last pass propagated %d field sets", set,
+               pp.result_sets);
     ML_REQUIRE(!H || pp.want_h, "the active propagation plan computes E only");
     ML_HIP(hipSetDevice(ctx->device));
     const size_t bytes = (size_t)3 * pp.T * 2 * sizeof(double);
-    ML_HIP(hipMemcpyAsync(E, pp.result.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (H) ML_HIP(hipMemcpyAsync(H, (const char *)pp.result.p + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    const char *src = (const char *)pp.result.p + (size_t)set * (pp.want_h ? 2 : 1) * bytes;
+    ML_HIP(hipMemcpyAsync(E, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (H) ML_HIP(hipMemcpyAsync(H, src + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ML_HIP(hipStreamSynchronize(ctx->stream));
+    return ML_OK;
+}
+
+int ml_propagate_download(ml_ctx *ctx, double *E, double *H) {
+    ML_REQUIRE(ctx && E, "NULL argument");
+    return download_set(ctx, 0, E, H);
+}
+
+int ml_propagate_download_set(ml_ctx *ctx, int set, double *E, double *H) {
+    ML_REQUIRE(ctx && E, "NULL argument");
+    return download_set(ctx, set, E, H);
+}
+
+int ml_propagate_accumulate(ml_ctx *ctx, const double *weights, int n, int reset) {
+    ML_REQUIRE(ctx && weights, "NULL argument");
+    PropagatePlan &pp = ctx->prop;
+    if (!pp.ready || !pp.have_result) {
+        set_error("ml_propagate has not run on the active propagation plan");
+        return ML_ESTATE;
+    }
+    ML_REQUIRE(n >= 1 && n <= pp.result_sets, "%d field sets to add, the last pass propagated %d", n, pp.result_sets);
+    if (!reset && !pp.have_sums) {
+        set_error("ml_propagate_accumulate: the active propagation plan has no sums yet (the first call needs reset = 1)");
+        return ML_ESTATE;
+    }
+    ML_HIP(hipSetDevice(ctx->device));
+    ML_TRY(pp.sums.reserve((size_t)2 * pp.T * sizeof(double)));
+    PropWeights wt = {};
+    for (int m = 0; m < n; ++m) wt.w[m] = weights[m];
+    hipLaunchKernelGGL(propagate_accumulate_kernel, dim3((pp.T + 255) / 256), dim3(256), 0, ctx->stream,
+                       pp.result.as<double2>(), pp.sums.as<double>(), pp.T, n, (int)pp.want_h, reset, wt);
+    ML_HIP(hipGetLastError());
+    pp.have_sums = true;
+    return ML_OK;
+}
+
+int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz) {
+    ML_REQUIRE(ctx && I, "NULL argument");
+    PropagatePlan &pp = ctx->prop;
+    if (!pp.ready || !pp.have_sums) {
+        set_error("ml_propagate_accumulate has not run on the active propagation plan");
+        return ML_ESTATE;
+    }
+    ML_REQUIRE(!Sz || pp.want_h, "the active propagation plan computes E only");
+    ML_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)pp.T * sizeof(double);
+    ML_HIP(hipMemcpyAsync(I, pp.sums.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (Sz) ML_HIP(hipMemcpyAsync(Sz, (const char *)pp.sums.p + bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
     return ML_OK;
 }

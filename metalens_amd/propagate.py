@@ -47,6 +47,9 @@ class PlanePropagator:
     ``x[:, None] x y[None, :]`` in the plane ``z`` (one number), or with ``point_list=True`` the ``len(x)``
     points ``(x[d], y[d], z[d])`` - a cut through a focus is a point list.  Every ``z`` must be > 0.
 
+    ``propagate_sets()`` does the same for all field sets of a synthesis batch (the x, y, z dipoles of an emitter)
+    in one pass and ``accumulate()`` keeps their weighted intensity sums on the GPU (``SourceSweep.run(image=...)``).
+
     ``propagate()`` sums the field set resident on the GPU (the selected one of a batch) and returns a dict
     with ``Ex, Ey, Ez, Hx, Hy, Hz`` (complex128, shape ``(len(x), len(y))`` or ``(len(x),)``) and
     ``Sz = Re(E x H*)_z / 2``; with ``want_h=False`` ``Ex, Ey, Ez`` and ``I = |E|^2`` only (about 40 % less
@@ -76,9 +79,9 @@ class PlanePropagator:
             _lib.dptr(self.z), self.z.size, int(self.point_list), int(self.want_h)))
         ctx.propagate_owner = self.owner
 
-    def propagate(self):
-        """-> dict of the fields at the targets, from the resident near field (plans again if another
-        propagator has planned on the context since)"""
+    def _ready(self):
+        """the resident field must have the aperture's shape; plans again if another propagator has planned on the
+        context since"""
         ctx = self.ctx
         nx, ny = _lib.c_int(0), _lib.c_int(0)
         _lib.check(ctx.lib.ml_fields_shape(ctx.handle, _lib.byref(nx), _lib.byref(ny)))
@@ -87,10 +90,16 @@ class PlanePropagator:
                              'points' % ((nx.value, ny.value) + self.aperture_shape))
         if ctx.propagate_owner != self.owner:
             self._plan()
-        _lib.check(ctx.lib.ml_propagate(ctx.handle, self.Z0))
+
+    def _download(self, member):
+        """-> the result dict of member ``member`` of the last pass (``None``: of ``ml_propagate``)"""
+        ctx = self.ctx
         E = np.empty((3,) + self.shape, dtype=np.complex128)
         H = np.empty((3,) + self.shape, dtype=np.complex128) if self.want_h else None
-        _lib.check(ctx.lib.ml_propagate_download(ctx.handle, _lib.dptr(E), _lib.dptr(H)))
+        if member is None:
+            _lib.check(ctx.lib.ml_propagate_download(ctx.handle, _lib.dptr(E), _lib.dptr(H)))
+        else:
+            _lib.check(ctx.lib.ml_propagate_download_set(ctx.handle, member, _lib.dptr(E), _lib.dptr(H)))
         out = {'Ex': E[0], 'Ey': E[1], 'Ez': E[2]}
         if self.want_h:
             out.update(Hx=H[0], Hy=H[1], Hz=H[2])
@@ -98,6 +107,50 @@ class PlanePropagator:
         else:
             out['I'] = (np.abs(E) ** 2).sum(axis=0)
         return out
+
+    def propagate(self):
+        """-> dict of the fields at the targets, from the resident near field (plans again if another
+        propagator has planned on the context since)"""
+        self._ready()
+        _lib.check(self.ctx.lib.ml_propagate(self.ctx.handle, self.Z0))
+        return self._download(None)
+
+    def queue_sets(self, first=0, n=None):
+        """queue ONE pass over the resident field sets ``first ... first + n - 1`` (default: all of them; at most
+        three - the members of a synthesis batch) without synchronising; -> n.  The geometry of a (sample, target)
+        pair is computed once for all sets; every set's fields have the bits ``propagate()`` gives for it."""
+        self._ready()
+        ctx = self.ctx
+        if n is None:
+            resident = _lib.c_int(0)
+            _lib.check(ctx.lib.ml_fields_sets(ctx.handle, _lib.byref(resident)))
+            n = resident.value - first
+        _lib.check(ctx.lib.ml_propagate_sets(ctx.handle, self.Z0, int(first), int(n)))
+        return n
+
+    def propagate_sets(self, first=0, n=None):
+        """-> list of the dicts ``propagate()`` returns, one per resident field set ``first ... first + n - 1``
+        (default: all of them), from one pass over the aperture (``queue_sets``)"""
+        n = self.queue_sets(first, n)
+        return [self._download(m) for m in range(n)]
+
+    def accumulate(self, weights, reset=False):
+        """add the sets of the last ``queue_sets`` / ``propagate_sets`` pass into the sums kept on the GPU:
+        ``I += sum_m weights[m] |E_m|^2`` and, with ``want_h``, ``Sz += sum_m weights[m] Sz_m``
+        (``reset``: the sums start from zero).  Asynchronous."""
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        w = _lib.f64(np.ravel(np.asarray(weights, dtype=float)))
+        _lib.check(ctx.lib.ml_propagate_accumulate(ctx.handle, _lib.dptr(w), w.size, int(bool(reset))))
+
+    def sums(self):
+        """-> ``(I_sum, Sz_sum)`` of ``accumulate``, of shape ``self.shape``; ``Sz_sum`` is None without ``want_h``"""
+        ctx = self.ctx
+        I = np.empty(self.shape)
+        Sz = np.empty(self.shape) if self.want_h else None
+        _lib.check(ctx.lib.ml_propagate_sums(ctx.handle, _lib.dptr(I), _lib.dptr(Sz)))
+        return I, Sz
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,

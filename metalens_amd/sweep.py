@@ -15,7 +15,11 @@ What a sweep shares:
   member;
 * the sums: ``P_sum``, per-source ``total_P`` and encircled power are accumulated by a kernel
   right after each projection (``ml_farfield_accumulate``); only ``P_sum`` and two scalars per
-  source cross PCIe, whatever the sweep's length.
+  source cross PCIe, whatever the sweep's length;
+* with ``image=`` (a ``PlanePropagator``): the image of the emitter at finite distance.  The field sets of a
+  group are propagated to the image plane in ONE pass (``ml_propagate_sets``: the geometry of a (sample, target)
+  pair serves all members) and their weighted ``|E|^2`` and ``Sz`` are summed on the GPU
+  (``ml_propagate_accumulate``); two real maps cross PCIe at the end.
 """
 import numpy as np
 
@@ -79,7 +83,17 @@ class SourceSweep:
                                         self.ux.size, _lib.dptr(self.uy), self.uy.size, 0))
         ctx.plan_owner = ctx.fields_owner = self.owner
 
-    def queue(self, sources):
+    def _check_image(self, image):
+        """argument errors of ``image=``, before any device call"""
+        if image is None:
+            return
+        if image.ctx is not self.ctx:
+            raise ValueError('image= must be a PlanePropagator built on the context of this sweep (ctx=sweep.ctx)')
+        if tuple(image.aperture_shape) != (self.x.size, self.y.size):
+            raise ValueError('image= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
+                             % (tuple(image.aperture_shape) + (self.x.size, self.y.size)))
+
+    def queue(self, sources, image=None):
         """queue the whole sweep on the GPU and return without synchronising (benchmarks);
         tie settlement and the downloads are ``run``'s business.
 
@@ -87,11 +101,14 @@ class SourceSweep:
         of this object.  An IN-PLACE edit of a table or of ``lens_center_summary`` made since then is
         not noticed and the pass runs on the resident (older) content - call ``prepare()`` (or
         ``run``) after editing.  Another object replacing the context's tables or layout IS
-        noticed (the context's tokens change) and triggers a full re-check."""
+        noticed (the context's tokens change) and triggers a full re-check.
+
+        ``image``: as for ``run``; its sums stay on the GPU (``image.sums()``)."""
+        self._check_image(image)
         self.prepare(check_content=False)
         weights = np.ones(len(sources))
         for g in self._group(sources):
-            self._pass(g, None, (0.0, 0.0, 0.0), weights)
+            self._pass(g, None, (0.0, 0.0, 0.0), weights, image)
 
     def _group(self, sources):
         """consecutive sources at one position -> batches of up to MAX_BATCH polarisations (one
@@ -122,8 +139,9 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights):
-        """queue one group: batched synthesis, then per member transform -> projection -> sums"""
+    def _pass(self, group, slots_done, cone, weights, image=None):
+        """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
+        group's field sets are then propagated to its targets in one pass and added to the image sums"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -144,9 +162,20 @@ class SourceSweep:
             _lib.check(lib.ml_farfield_project_async(ctx.handle, self.Z0))
             _lib.check(lib.ml_farfield_accumulate(ctx.handle, float(weights[k]), cone[0], cone[1],
                                                   cone[2], k, int(k == 0)))
+        if image is not None:
+            # the sums start over with the group that holds source 0 (as int(k == 0) above: the first pass is
+            # repeated after tie settlement and must not count twice)
+            # members synthesised together at one position round a few 1e-16 differently from the source alone: their
+            # field sets are written once more by the single-source kernels (the incident powers stay the batch's), so
+            # that every source's image is that of the source alone
+            if n > 1 and len(set(group['positions'])) == 1:
+                _lib.check(lib.ml_nearfield_members_async(ctx.handle, params, n, _lib.dptr(self.x), self.x.size,
+                                                          _lib.dptr(self.y), self.y.size, 1))
+            image.queue_sets(0, n)
+            image.accumulate([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
         return n
 
-    def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False):
+    def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -157,7 +186,15 @@ class SourceSweep:
         nearfield.py:474-477), ``total_P`` (radiated power per source: sum of the finite
         ``P * dux * duy``, nearfield_farfield.py:74), ``efficiency`` = sum(total_P) /
         sum(power_in), ``cone_P`` / ``cone_efficiency`` if a cone was given, ``P_each`` if
-        ``keep_each`` (downloads every map: for tests)."""
+        ``keep_each`` (downloads every map: for tests).
+
+        ``image`` = a ``PlanePropagator`` built on this sweep's context and axes: the result gains ``I_sum`` =
+        ``sum_k weights[k] |E_k|^2`` at its targets and, if it has ``want_h``, ``Sz_sum`` = ``sum_k weights[k]
+        Sz_k`` (shape ``image.shape``; summed on the GPU), and with ``keep_each`` ``image_each``, the dicts of
+        ``PlanePropagator.propagate()`` per source - bit for bit those of ``build_nearfield`` + ``field_at_plane`` of
+        the source alone.  ``P_sum``, ``total_P``, ``power_in`` and ``cone_P`` are not touched by it (``P_each`` of
+        a polarisation group is then projected from the group's re-synthesised field sets)."""
+        self._check_image(image)
         sources = list(sources)
         if not 1 <= len(sources) <= MAX_SLOTS:
             raise ValueError('a sweep takes 1 to %d sources, got %d' % (MAX_SLOTS, len(sources)))
@@ -171,9 +208,10 @@ class SourceSweep:
         groups = self._group(sources)
         power_in = np.zeros(len(sources))
         each = [None] * len(sources)
+        image_each = [None] * len(sources)
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights)
+            n = self._pass(g, None, cone3, weights, image)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -185,7 +223,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights)
+                    n = self._pass(g, None, cone3, weights, image)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:
@@ -202,6 +240,8 @@ class SourceSweep:
                 power_in[k] = pw[m] * self.dxp * self.dyp
             if keep_each:   # the projections of this group's members, one at a time (tests)
                 for m, (k, pol) in enumerate(g['members']):
+                    if image is not None:
+                        image_each[k] = image._download(m)
                     _lib.check(lib.ml_fields_select(ctx.handle, m))
                     _lib.check(lib.ml_farfield_transform_async(ctx.handle, 0, 0))
                     P = np.empty((self.ux.size, self.uy.size))
@@ -219,6 +259,12 @@ class SourceSweep:
             out['cone_efficiency'] = cone_P.sum() / power_in.sum() if power_in.sum() else np.nan
         if keep_each:
             out['P_each'] = each
+        if image is not None:
+            out['I_sum'], Sz_sum = image.sums()
+            if image.want_h:
+                out['Sz_sum'] = Sz_sum
+            if keep_each:
+                out['image_each'] = image_each
         return out
 
 
