@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "metalens_hip.h"
+#include "lens_pack.h"
 #include "transform_route.h"
 
 namespace ml {
@@ -188,84 +189,10 @@ struct PieceBuf {
     }
 };
 
-constexpr int MAX_SLOTS = 32;      // grating collections per lens (+1 centre)
-constexpr int MAX_ORDERS = 32;     // diffraction orders per table
-constexpr int PACKED_AXIS = 8;     // nodes of an inline (ux or uy) table axis, see TableDesc
-
-// Device-side view of one packed table (GratingCollection or HexGridSet).
-struct TableDesc {
-    const double *axis0;   // ux nodes [n0]
-    const double *axis1;   // uy nodes [n1]
-    const double *values;  // complex [n_orders][n0][n1][n2][4]
-    const double *order_k; // [n_orders][2]  (ox*2*pi, oy*2*pi)
-    int n0, n1, n2, n_orders;
-    double bounds[6];
-    double center_kx[MAX_ORDERS];  // centre only: ox*2*pi/x_period, per order
-    double center_ky[MAX_ORDERS];
-    // ... the orders themselves and the two reciprocal-lattice steps 2*pi/x_period, 2*pi/y_period:
-    // the field kernel builds an order's phasor as E0 * Ex^ox (* exp(i oy Gy y') when oy != 0)
-    int center_ox[MAX_ORDERS], center_oy[MAX_ORDERS];
-    double center_g[2];
-    // (ux, uy) axes inline for the fast kernel when both have <= PACKED_AXIS nodes: node a for
-    // a <= n-2 (+inf beyond, so a running compare never selects a padded node) and
-    // 1 / (node[a+1] - node[a]); one round of independent loads instead of a pointer chase
-    // followed by a dependent search loop
-    int packed;   // 0 no, 1 both axes <= 5 nodes, 2 both <= PACKED_AXIS
-    // both axes uniformly spaced to a few ulp (np.linspace, what characterize() produces): the
-    // cell is floor((x - first) / step); uni_ax = {first0, step0, 1/step0, first1, step1, 1/step1}
-    int uniform;
-    double uni_ax[6];
-    double ax0[PACKED_AXIS], inv0[PACKED_AXIS], ax1[PACKED_AXIS], inv1[PACKED_AXIS];
-};
-
-// What the field kernel needs to know about a periphery sample's RING: 32 bytes per ring
-// (ring_rec: two 16-byte loads per lane),
-//   r_center, period | 2 pi / period, bits: offset of the ring's table in ring_tab (general order
-//   sets: bits 0-39, bit 40 = the period lies outside its table's period range, nearfield.py:302-305)
-// SIMPLE order sets (every table of the lens: orders (ox, 0) with |ox| <= 5 - what characterize()
-// emits for a round lens, grating.lua:417-423; nearfield_simple.hip): ring_tab holds CELL BLOCKS
-// instead, complex [ring][i0 < n0 - 1][i1 < n1 - 1][order slot < n_slots][node 2 x 2][amplitude 4] - the
-// 16 n_slots complex a sample in table cell (i0, i1) interpolates from, contiguous, n_slots = the
-// orders of the ring's OWN collection, lowest first (CollDesc::ox_lo).  Blocks are
-// addressed in UNITS of 16 complex (256 bytes): bits 0-31 of `bits` = the ring's first unit,
-// bit 32 = the period flag; the block of cell c starts at unit first + c n_slots.
-// and about the ring's GRATING COLLECTION, which almost every wave shares among all its lanes: a
-// CollDesc per collection IN USE (dense numbering, ml_upload_layout), held in the kernel arguments
-// so that a wave reads it with scalar loads - the geometry records carry the dense number.
-// ring_ok holds 4 doubles per order of the ring's table (general order sets only):
-//   ox 2 pi / period, oy 2 pi / lateral, ox, oy;  ring_ok_off[ring] = the ring's offset in it.
-constexpr int MAX_RING_COLLS = 16;   // grating collections in use by the rings of one lens
-constexpr int SIMPLE_MAX_OX = 5;                       // |ox| of a simple order set (grating.lua:417 searches -5 ... 5)
-constexpr int SIMPLE_MAX_SLOTS = 2 * SIMPLE_MAX_OX + 1;
-constexpr int SIMPLE_NARROW_SLOTS = 4;                 // up to here a collection's blocks are staged whole, six at a fixed pitch (nearfield_simple.hip)
-struct CollDesc {
-    double uni_ax[6];   // uniform (ux', uy') axes: first, step, 1 / step per axis (flags bit 0)
-    int n0, n1, n_orders;
-    int flags;          // bit 0 = axes uniform
-    // simple order sets (nearfield_simple.hip): the collection's orders are (ox, 0), ox = ox_lo ...
-    // ox_lo + n_slots - 1; slot s of a cell block is order ox_lo + s, and `present` bit s says whether
-    // the collection's data holds it (a list with holes has all-zero blocks in them; characterize()
-    // produces none: the orders that propagate at a direction are a contiguous run)
-    double lim0, lim1;  // n0 - 2, n1 - 2: the last table cell per axis
-    int n_slots, ox_lo, present, pad;
-};
-constexpr int UNIT = 16;                               // complex per unit of a cell block: [node 2 x 2][amplitude 4] of one order
-// centre table, simple order sets: complex [order slot][i0 < n0 - 1][i1 < n1 - 1][group of 20 types][node 2 x 2][amplitude 4][20]
-// - per order, table cell and group of CENTER_GROUP cell types the 16 x 20 complex the samples of that
-// cell and group interpolate from, contiguous (5 KiB: five wave-wide loads stage a block); types past
-// the table's K are zeros
-constexpr int CENTER_GROUP = 20;                       // (the reference's default K, lens_center.py:28)
-constexpr int CENTER_BLOCK = 16 * CENTER_GROUP;        // complex per centre block
-
-struct TableSlot {
-    bool present = false;
-    int n0 = 0, n1 = 0, n2 = 0, n_orders = 0;
+// (lens_pack.h: the limits and the records the near-field kernels read - MAX_SLOTS, TableDesc, CollDesc, RingBucket,
+// CellRec, the cell-block constants - and HostTable, the host's copy of a table)
+struct TableSlot : HostTable {   // (lens_pack.h: what the packing reads) and the table as uploaded
     DevBuf axis0, axis1, values, order_k;
-    std::vector<double> h_axis0, h_axis1, h_axis2;
-    std::vector<double> h_order_k;
-    std::vector<double> h_values;   // host copy, for the per-ring pre-interpolation
-    double bounds[6] = {0, 0, 0, 0, 0, 0};
-    double center_periods[2] = {0, 0};
 };
 
 struct KernelTimer {
@@ -286,21 +213,6 @@ struct Profile {
     };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> pool;
-};
-
-// One bucket of the fast kernel's ring search: the number of boundaries strictly below the
-// bucket's lower edge and the boundaries just around it, so that searchsorted needs ONE load
-// (boundaries_below: LUT entry, then two to three dependent boundary loads).
-struct RingBucket {
-    double bm1, b0, b1;   // B[first - 1] (-inf if none), B[first], B[first + 1] (+inf past the end)
-    int first, pad;
-};
-
-// a centre cell as the fast kernel's lattice shortcut reads it (nearfield_dev.h lattice_pick)
-struct CellRec {
-    double x, y;          // cell centre (NaN for an empty lattice node)
-    int which, index;     // grating type, original index in lens_center_summary
-    double pad;
 };
 
 // One axis of a plan whose direction grid sits on the aperture's FFT lattice (zfft.hip): the
@@ -391,7 +303,7 @@ struct ml_ctx {
     ml::DevBuf table_desc;   // TableDesc[MAX_SLOTS + 1], last = centre
     ml::TableDesc h_center_desc;   // the centre entry again: it travels in the kernel arguments
     bool tables_dirty = true;
-    bool simple_orders = false;   // SOME table in use holds orders (ox, 0), |ox| <= 5 only: its samples take nearfield_simple.hip (refresh_ring_locations)
+    bool simple_orders = false;   // SOME table in use holds orders (ox, 0), |ox| <= 5 only: its samples take nearfield_simple.hip (lens_pack.h classify_lens)
     // ... and the others the general kernel: bit c = dense ring collection c is general; the centre table likewise
     int general_mask = 0, centre_general = 0, narrow_mask = 0;
     int wide_mask = 0, narrow_exists = 0, narrow_slots_max = 1;   // simple order sets: NfArgs::wide_mask / narrow_exists; orders of the widest narrow collection
@@ -401,7 +313,7 @@ struct ml_ctx {
     bool have_layout = false;
     int n_rings = 0, n_cells = 0;
     std::vector<double> h_ring_period, h_ring_lateral, h_ring_rc;
-    std::vector<int32_t> h_ring_gc;
+    std::vector<int32_t> h_ring_gc, h_ring_coll;   // slot and dense collection number per ring (lens_pack.h dense_collections)
     ml::DevBuf ring_boundaries, ring_r_center, ring_period, ring_dphi, ring_lateral, ring_gc;
     ml::DevBuf rot_table, tie_table, ring_rot_center, ring_rot_half;
     ml::DevBuf ring_rec, ring_coll;                            // 4 doubles per ring (above); dense collection number per ring
@@ -411,7 +323,7 @@ struct ml_ctx {
     std::vector<ml::TableDesc> h_table_desc;                   // host copy of table_desc
     ml::DevBuf ring_tab, ring_ok, ring_ok_off;   // fast-kernel per-ring tables (offsets into ring_tab: ring_rec)
     ml::DevBuf center_qmajor;                                  // fast-kernel centre table [order][n0][n1][4][K]
-    int center_n_slots = 0, center_lo = 0, center_present_mask = 0;                     // simple order sets: as CollDesc::n_slots / ox_lo (no holes: see refresh_ring_locations)
+    int center_n_slots = 0, center_lo = 0, center_present_mask = 0;                     // simple order sets: as CollDesc::n_slots / ox_lo (lens_pack.h pack_centre_table)
     ml::DevBuf ring_lut;             // uniform-in-r bucket -> first candidate boundary
     ml::DevBuf ring_lutrec;          // fast kernel: coarser buckets that carry the boundaries
     int lutrec_buckets = 0;
@@ -435,7 +347,7 @@ struct ml_ctx {
     ml::DevBuf lattice_in;   // staging for ml_farfield_lattice_power
 
     // near-field scratch
-    // nearest-cell lattice shortcut (ctx.hip fit_lattice): cells = nodes c0 + a b1 + b b2
+    // nearest-cell lattice shortcut (lens_pack.h fit_lattice): cells = nodes c0 + a b1 + b b2
     bool lat_ok = false;
     double lat_c0x = 0, lat_c0y = 0, lat_inv[4] = {0, 0, 0, 0}, lat_accept_r2 = 0;
     double lat_g[3] = {0, 0, 0}, lat_guard = 0;

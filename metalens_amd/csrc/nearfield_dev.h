@@ -60,7 +60,7 @@ struct NfArgs {
     const int *ovr_slot;        // the cell (bin-sorted slot) to take there
     int n_ovr;
     double bx0, by0, bh, inv_bh;   // inv_bh = 1 / bh, rounded (fast kernel's bin lookup)
-    // lattice shortcut (ctx.hip fit_lattice), fast kernel: lat_map == nullptr if the cells are not
+    // lattice shortcut (lens_pack.h fit_lattice), fast kernel: lat_map == nullptr if the cells are not
     // the nodes of one lattice
     const int *lat_map;            // [lat_na][lat_nb] -> sorted slot or -1
     // the same node map carrying the cell itself: x, y, (which, original index) - one load

@@ -737,7 +737,7 @@ __global__ __launch_bounds__(64, NP == 1 ? ML_NF_WAVES : 3) void nearfield_field
                     const double2 *base = reinterpret_cast<const double2 *>(((unsigned long long)hi << 32) | lo);
                     have[s] = o < no;
                     // 32-bit element offset from the wave-uniform block address (scalar base +
-                    // lane offset; 24-bit products: o < 16, strides < 2^24 - refresh_ring_locations
+                    // lane offset; 24-bit products: o < 16, strides < 2^24 - lens_pack.h pack_ring_tables
                     // refuses larger tables), instead of 64-bit products per lane and slot
                     const unsigned off = __umul24((unsigned)o, (unsigned)so) + __umul24((unsigned)(c >> 1), (unsigned)s0) +
                                          (unsigned)((c & 1) * 4 + q);

@@ -12,7 +12,7 @@
 // What the restricted order sets buy (the kernel is bound by fp64 vector ISSUE: every vector
 // instruction holds its SIMD for four cycles, so the budget is instructions per sample):
 //   * ORDER SLOTS per collection: slot s of a collection is its order ox = lo + s, lo its lowest
-//     (CollDesc::ox_lo / n_slots / present, ctx.hip), and the order loop runs over the slots of the
+//     (CollDesc::ox_lo / n_slots / present, lens_pack.h), and the order loop runs over the slots of the
 //     wave's OWN collection - a collection of three orders pays for three, its neighbour of eleven
 //     for eleven - with nothing of an order list decoded per order: the loop knows a slot count and
 //     a bit mask of the slots the data really holds;
