@@ -39,6 +39,7 @@
 
 #include "common.h"
 #include "zfft_core.h"
+#include "zfft_rows.h"
 
 namespace ml {
 
@@ -1038,6 +1039,23 @@ int zfft_run(hipStream_t stream, const ZfftCall &c) {
         a.g.ip = 1;
         zfft_choose_pads(-c.N_eff, c.M, c.j0, &a.g.pad1, &a.g.pad2, c.jstep);
         lds_bytes = ((size_t)zf::lds_elems(a.g) + 256) * sizeof(cd);
+    }
+    // Whole contiguous rows in one resident run, 8 or 16 residues, two bins per thread - stage 1 of the default
+    // route - have a kernel of their own with the same arithmetic (zfft_rows.hip; zfft_core.h rows_kernel_takes).
+    // METALENS_HIP_FIXED_ROWS=0 in the environment, read once: zfft_kernel for every call
+    {
+        static const bool rows_off = [] { const char *e = getenv("METALENS_HIP_FIXED_ROWS"); return e && e[0] == '0'; }();
+        zf::RowsFacts rf;
+        rf.family_one = L.family == ZfftFamily::one, rf.ip = L.ip, rf.PASS = L.PASS, rf.R3 = a.g.R3, rf.M = a.g.M;
+        rf.sub_s = a.sub_s, rf.sub_i = a.sub_i, rf.in_es = a.in_es, rf.accumulate = a.accumulate;
+        rf.a0 = a.a0, rf.h0 = a.h0, rf.a1 = a.a1, rf.h1 = a.h1, rf.n_valid = a.g.n_valid;
+        rf.out_last = L.PASS == 4 ? zf::tile_off(a.g.M - 1, a.out_es) : (int64_t)(a.g.M - 1) * a.out_es;
+        if (!rows_off && zf::rows_kernel_takes(rf)) {
+            // (METALENS_HIP_FIXED_ROWS_GRID: this many workgroups instead, for tests of its turn loop)
+            static const int rows_grid = [] { const char *e = getenv("METALENS_HIP_FIXED_ROWS_GRID"); return e ? atoi(e) : 0; }();
+            const int g8 = rows_grid > 0 ? std::min(grid, (rows_grid + 7) / 8 * 8) : grid;
+            return zfft_rows_run(stream, c, a.g.pad1, g8, lds_bytes);
+        }
     }
     // (R3T = 0: the instantiation for any residue count)
     if (L.PASS == 3) switch (L.R3T) {   // contiguous rows of a transposed stage-1 result

@@ -503,6 +503,61 @@ ZF_HD MixChoice mixed_choose(int N, int M) {
     return best;
 }
 
+// ---- whole aperture rows in one resident run (zfft_rows.hip zfft_rows_kernel) --------------------------------------
+// The row pass of the default route reads rows that lie contiguous and whole: sample n of the transform is element n
+// of the row, and it is resident where first <= n < n_valid - first (zfft.hip load_row with sub_s = 1, sub_i = 0,
+// in_es = 1, one run from sample 0: its predicate min(n, n_valid - 1 - n) >= first).  The run's two ends are scalars
+// of the row, and a sample's residency one compare against them.
+// the resident run [lo, hi) of a row; a row with nothing resident (first past the half row, up to 0x7f7f7f7f for a row
+// outside the lens) gets the empty run [0, 0)
+ZF_HD void row_run(int first, int n_valid, int &lo, int &hi) {
+    lo = first, hi = n_valid - first;
+    if (hi <= lo) lo = hi = 0;
+}
+// is sample n in [lo, hi)?  One unsigned compare (lo <= hi)
+ZF_HD bool piece_lane(int n, int lo, int hi) { return (unsigned)(n - lo) < (unsigned)(hi - lo); }
+
+// The rows of a launch are dealt in 8 chunks, one per XCD (zfft.hip row_of_turn): workgroup b of a grid of G
+// (a multiple of 8) takes rows xcd chunk + idx, idx = b / 8, b / 8 + G / 8, ... below the chunk's end.
+ZF_HD int rows_begin(int block, int chunk) { return (block & 7) * chunk + (block >> 3); }
+ZF_HD int rows_end(int block, int chunk, int rows) {
+    const int e = ((block & 7) + 1) * chunk;
+    return e < rows ? e : rows;
+}
+// row = q d + r followed along a workgroup's rows, which advance by the constant step G / 8: no division per row
+struct RowWalk {
+    int q, r, d, dq, dr;
+};
+ZF_HD RowWalk walk_init(int row, int d, int step) {
+    RowWalk w;
+    w.q = row / d, w.r = row % d, w.d = d, w.dq = step / d, w.dr = step % d;
+    return w;
+}
+ZF_HD void walk_step(RowWalk &w) {
+    w.q += w.dq;
+    w.r += w.dr;
+    if (w.r >= w.d) w.r -= w.d, ++w.q;
+}
+
+// What a call must look like for zfft_rows_kernel (zfft.hip zfft_run asks; everything else keeps zfft_kernel)
+struct RowsFacts {
+    bool family_one = false, ip = false;   // zfft_launch_rule's answer
+    int PASS = 0, R3 = 0, M = 0;
+    int sub_s = 1, sub_i = 0, a0 = 0, h0 = 0, a1 = 0, h1 = 0, n_valid = 0, accumulate = 0;
+    long long in_es = 1;
+    long long out_last = 0;   // element offset of the last bin in its row (the stores take 32-bit byte offsets)
+};
+ZF_HD bool rows_kernel_takes(const RowsFacts &f) {
+    if (!f.family_one || !f.ip || (f.PASS != 1 && f.PASS != 4) || (f.R3 != 8 && f.R3 != 16)) return false;
+    // every thread owns two bins, NT apart.  With 256 threads they are a pair (equal mod 256: stage3_pair_ip, as
+    // zfft_kernel takes them); with 128 they are not and each is summed on its own, again as zfft_kernel does
+    if (f.M != 2 * 16 * f.R3) return false;
+    if (f.sub_s != 1 || f.sub_i != 0 || f.in_es != 1) return false;
+    if (f.h1 != 0 || f.a0 != 0 || f.h0 < f.n_valid || f.n_valid < 0 || f.n_valid > 256 * f.R3) return false;
+    if (f.accumulate) return false;
+    return f.out_last >= 0 && f.out_last < (1LL << 27);   // x 16 bytes < 2^31
+}
+
 }  // namespace zf
 
 // ---- host side: LDS bank-conflict model and the choice of the two paddings ---------------------

@@ -3,6 +3,8 @@
 # `bench.py --profile all` alternately, ROUNDS times, in ONE gpurun call; one compact line per run.
 #     tools/ab_run.sh OUTFILE ROUNDS "<bench args>" variant1 variant2 ...
 # e.g. tools/ab_run.sh gpurun_out/ab1.txt 2 "" product abl_tmp/lib_x.so
+# A run that fails or overruns its time limit ends the script with that status: nothing more is started on the GPU.
+set -o pipefail
 OUT=$1; ROUNDS=$2; ARGS=$3; shift 3
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $(dirname $OUT)
@@ -21,7 +23,7 @@ for line in sys.stdin:
     k={a:round(b,4) for a,b in d.get('kernels_ms_per_step',{}).items()}
     e=d.get('rel_err') or {}
     print('%-28s blocks %s kernels %s nf_err %.2e ff_pw %.2e' % (v, [round(b,4) for b in d['ms_per_step_blocks']], k, e.get('nearfield_vs_oracle',-1), e.get('farfield_E_pointwise_above_1e-3_of_peak',-1)))
-" "$v" >> $OUT
+" "$v" >> $OUT || { rc=$?; echo "ab_run: $v ended with status $rc" | tee -a $OUT; exit $rc; }
   done
 done
 cat $OUT
