@@ -222,6 +222,26 @@ struct ZfftAxis : ZfftAxisGeo {   // (transform_route.h: the axis' facts)
     DevBuf wk, pj, kbin;   // per-bin Horner ratio, origin phasor, reduced bin (zfft.hip FftArgs)
 };
 
+// The tables of the folded (even/odd) GEMM along one centre-symmetric direction axis (zfold.hip), over the S half-
+// directions of the plan's facts: farfield.hip plan_fold_axis uploads v, fold_tables fills the rest.
+struct FoldAxis {
+    bool has_E = false;        // u_c != 0: the input modulation E exists
+    DevBuf v;                  // the split directions (transform_route.h FoldSplit::v) ...
+    std::vector<double> h_v;   // ... and the host's copy of them
+    DevBuf cm, sm;             // real [T][S]: cos / sin of kappa p_t v_s over the T pairs of resident samples
+    DevBuf r4;                 // real [2][S]: the rotation that advances cm / sm by four samples
+    DevBuf E, D;               // complex [samples] input modulation, complex [directions] output diagonal
+};
+
+// the folded stage 2 leaves its split-K slabs in fold2_ot; they are summed, transposed and signed into `vectors` by
+// whoever needs the vectors next - the projection does it in the same kernel (farfield.hip flush_unfold /
+// unfold_project_kernel).  What that consumer needs to know:
+struct DeferredUnfold {
+    bool pending = false;
+    int splits = 1, accumulate = 0;
+    double alpha[4] = {0, 0, 0, 0};
+};
+
 struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's route is decided from)
     bool ready = false;
     ZfftAxis fft_y, fft_x;
@@ -255,24 +275,17 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     bool have_vectors = false;
     bool tw_x_ready = false;  // complex x twiddles built for the current plan
     int stage1_splits = 1;   // split-K slabs currently held in `stage1`
-    // folded (even/odd) stage 1, see zfold.hip; used when uy is centre-symmetric
-    bool fold_has_E = false;
-    int fold_T = 0;
-    DevBuf fold_cm, fold_sm, fold_E, fold_D, fold_v, fold_r4;
-    std::vector<double> h_ux, h_uy, h_fold_v, h_fold2_v;   // host copies of the plan's inputs
-    // folded stage 2 (needs centre-symmetric ux and a mirror-symmetric set of resident rows)
-    bool fold2_has_E = false;
-    DevBuf fold2_v, fold2_cm, fold2_sm, fold2_r4, fold2_E, fold2_D, fold2_gt, fold2_ot;
+    std::vector<double> h_ux, h_uy;   // host copies of the plan's inputs
+    // folded stage 1 along y (uy centre-symmetric) and folded stage 2 along x (centre-symmetric ux and a mirror-
+    // symmetric set of resident rows): the facts are PlanFacts::fold / fold_S and fold2 / fold2_S
+    FoldAxis fold_y, fold_x;
+    // stage 2's own: the transposed stage-1 result and its split-K output slabs
+    DevBuf fold2_gt, fold2_ot;
     // the stage-2 tables depend on the plan and on which rows are resident: rebuilt only when
     // that changes (serial, row0, resident rows, mirrored)
     long fold2_key[4] = {-1, -1, -1, -1};
     int fold2_want_split = 1;
-    // the folded stage 2 leaves its split-K slabs in fold2_ot; they are summed, transposed and
-    // signed into `vectors` by whoever needs the vectors next - the projection does it in the
-    // same kernel (farfield.hip flush_unfold / unfold_project_kernel)
-    bool unfold_pending = false;
-    int unfold_splits = 1, unfold_accumulate = 0;
-    double unfold_alpha[4] = {0, 0, 0, 0};
+    DeferredUnfold unfold;
 };
 
 // Targets and buffers of the finite-distance propagator (propagate.hip).  Its own: nothing here is shared with the
@@ -463,21 +476,21 @@ int zfold_stage1(hipStream_t stream, int M, int ny, const double *A, int64_t lda
 int zfold_splits(int T, int ksplit);
 // zfft.hip: output-pruned FFT along one axis for lattice-commensurate direction grids
 struct ZfftCall {
-    int N_eff, n_valid, M, j0, pad1, pad2;
+    int N_eff = 0, n_valid = 0, M = 0, j0 = 0, pad1 = 0, pad2 = 0;
     int jstep = 1;
-    const double *in;           // complex
-    int64_t in_s1, in_s2, in_es;
-    int in_rb, a0, h0, a1, h1;
-    const int *row_first;
-    int rf_mod;
+    const double *in = nullptr;   // complex
+    int64_t in_s1 = 0, in_s2 = 0, in_es = 0;
+    int in_rb = 0, a0 = 0, h0 = 0, a1 = 0, h1 = 0;
+    const int *row_first = nullptr;
+    int rf_mod = 0;
     int sub_s = 1, sub_i = 0;   // this launch: samples sub_i, sub_i + sub_s, ... of the axis (two-level)
-    double *out;                // complex
-    int64_t out_s1, out_s2, out_es;
-    int out_rb;
-    const double *tw1, *wk, *pj;
-    const int *kbin;
-    double alpha[4];
-    int alpha_rb, rows, accumulate;
+    double *out = nullptr;      // complex
+    int64_t out_s1 = 0, out_s2 = 0, out_es = 0;
+    int out_rb = 0;
+    const double *tw1 = nullptr, *wk = nullptr, *pj = nullptr;
+    const int *kbin = nullptr;
+    double alpha[4] = {0, 0, 0, 0};
+    int alpha_rb = 0, rows = 0, accumulate = 0;
     int passes = 0;                  // > 1: the pass-split kernel (0: the library's default)
     int second = 0;                  // contiguous rows that are the SECOND stage (of a transposed stage-1 result)
     int tiled_out = 0;               // bins stored in tiles of 8 (zfft_core.h tile_off; out_es = the tile's stride)

@@ -411,67 +411,75 @@ static int upload_if_changed(ml_ctx *ctx, DevBuf &dev, std::vector<double> &host
     return ML_OK;
 }
 
-// (symmetry_tolerance, the phase deviation a direction grid is allowed: transform_route.h)
-// Decide whether stage 1 can run folded (zfold.hip) and build its tables.  Needs a tensor
-// grid whose uy are centre-symmetric to within 1e-13 rad of phase at the aperture edge.
+// Phase tables of the folded GEMM (zfold.hip) along one axis: m directions (`directions` on the device, split into
+// S half-directions in ax.v), n_total samples `step` apart of which `rows` from row0 on are resident - or, mirrored,
+// rows / 2 from row0 and their mirror images.  Pair t of resident samples sits at +/- (half - row0 - t) step.
+static int fold_tables(ml_ctx *ctx, FoldAxis &ax, int S, const DevBuf &directions, int m, int n_total, double step,
+                       int row0, int rows, int mirrored) {
+    const FarfieldPlan &pl = ctx->plan;
+    const int T = (rows + 1) / 2;
+    ML_TRY(ax.cm.reserve((size_t)T * S * sizeof(double)));
+    ML_TRY(ax.sm.reserve((size_t)T * S * sizeof(double)));
+    ML_TRY(ax.r4.reserve((size_t)S * 2 * sizeof(double)));
+    ML_TRY(ax.E.reserve((size_t)rows * 2 * sizeof(double)));
+    ML_TRY(ax.D.reserve((size_t)m * 2 * sizeof(double)));
+    // turns per (sample index x u)
+    const long double sl = (long double)pl.n_glass / (long double)pl.wavelength * (long double)step;
+    const double s_hi = (double)sl, s_lo = (double)(sl - (long double)s_hi);
+    const double half = 0.5 * (n_total - 1);
+    // (the single direction u_c travels behind v)
+    const double *v_hi = ax.v.as<double>(), *v_lo = v_hi + S, *uc = v_hi + 2 * (size_t)S;
+    ProfScope scope(ctx, ML_K_TWIDDLE);
+    PhaseBatch pb;
+    pb.n = pb.blocks = 0;
+    // cos / sin of kappa p_t v_s, p_t = (half - row0 - t) step
+    batch_add(pb, nullptr, ax.cm.as<double>(), ax.sm.as<double>(), T, S, 1, half - row0, -1.0, s_hi, s_lo, v_hi, v_lo);
+    // rotation that advances the table by four samples: cos / sin of kappa (4 step) v_s
+    batch_add(pb, nullptr, ax.r4.as<double>(), ax.r4.as<double>() + S, 1, S, 1, 4.0, 0.0, s_hi, s_lo, v_hi, v_lo);
+    if (ax.has_E) {
+        // input modulation E_k = exp(-i kappa p_k u_c), p_k = (k - half) step, at the resident samples: one run, or
+        // two for a mirrored shard; skipped when u_c == 0
+        const int h = mirrored ? rows / 2 : rows;
+        batch_add(pb, ax.E.as<double2>(), nullptr, nullptr, 1, h, 0, row0 - half, 1.0, s_hi, s_lo, uc, uc + 1);
+        if (mirrored)
+            batch_add(pb, ax.E.as<double2>() + h, nullptr, nullptr, 1, h, 0, (double)(n_total - row0 - h) - half, 1.0,
+                      s_hi, s_lo, uc, uc + 1);
+    }
+    // output diagonal D_j = exp(-i kappa delta u_j), delta = (half - ceil(n_total / 2)) step
+    const double delta = half - (double)(n_total - n_total / 2);
+    batch_add(pb, ax.D.as<double2>(), nullptr, nullptr, 1, m, 1, delta, 0.0, s_hi, s_lo, directions.as<double>(), nullptr);
+    return batch_launch(ctx, pb);
+}
+
+// Can the GEMM along one axis run folded (zfold.hip)?  Needs directions that are centre-symmetric to within
+// symmetry_tolerance of phase at the aperture edge (transform_route.h fold_split); uploads the split directions.
+static int plan_fold_axis(ml_ctx *ctx, FoldAxis &ax, const double *u, int m, int n, double step, bool &fold, int &S) {
+    const FoldSplit f = fold_split(u, m, n, step, ctx->plan.wavelength, ctx->plan.n_glass);
+    if (!f.ok) return ML_OK;
+    ML_TRY(upload_if_changed(ctx, ax.v, ax.h_v, f.v.data(), f.v.size()));
+    ax.has_E = f.has_E;
+    fold = true;
+    S = f.S;
+    return ML_OK;
+}
+
+// stage 1 (needs a tensor grid): every sample of a row is resident, so its tables are built with the plan
 static int plan_fold(ml_ctx *ctx, const double *uy) {
     FarfieldPlan &pl = ctx->plan;
     pl.fold = false;
     static const bool disabled = diag_int("ML_NO_FOLD", 0) != 0;
-    if (disabled || pl.pair_list || pl.my < 2 || pl.ny < 2) return ML_OK;
-    const int ny = pl.ny, my = pl.my;
-    const int T = (ny + 1) / 2, S = (my + 1) / 2;
-    const long double kappa = (long double)pl.n_glass / (long double)pl.wavelength;
-    const long double p_max = 0.5L * (ny - 1) * fabsl((long double)pl.dyp);
-    const long double uc = 0.5L * ((long double)uy[0] + (long double)uy[my - 1]);
-    std::vector<double> v(2 * (size_t)S + 2);   // hi[S], lo[S], then u_c as (hi, lo)
-    long double worst = 0;
-    for (int s = 0; s < S; ++s) {
-        const long double up = uy[my - 1 - s], um = uy[s];
-        worst = fmaxl(worst, fabsl(0.5L * (up + um) - uc));
-        const long double vs = 0.5L * (up - um);
-        v[s] = (double)vs;
-        v[S + s] = (double)(vs - (long double)v[s]);
-    }
-    if (2 * M_PIl * kappa * p_max * worst > symmetry_tolerance(kappa, p_max, uy, my)) return ML_OK;
-    v[2 * (size_t)S] = (double)uc;
-    v[2 * (size_t)S + 1] = (double)(uc - (long double)v[2 * (size_t)S]);
-    ML_TRY(upload_if_changed(ctx, pl.fold_v, pl.h_fold_v, v.data(), v.size()));
-    ML_TRY(pl.fold_cm.reserve((size_t)T * S * sizeof(double)));
-    ML_TRY(pl.fold_sm.reserve((size_t)T * S * sizeof(double)));
-    ML_TRY(pl.fold_E.reserve((size_t)ny * 2 * sizeof(double)));
-    ML_TRY(pl.fold_D.reserve((size_t)my * 2 * sizeof(double)));
-    ML_TRY(pl.fold_r4.reserve((size_t)S * 2 * sizeof(double)));
-    const long double s = kappa * (long double)pl.dyp;   // turns per (sample index x u)
-    const double s_hi = (double)s, s_lo = (double)(s - (long double)s_hi);
-    const double half = 0.5 * (ny - 1);
-    ProfScope scope(ctx, ML_K_TWIDDLE);
-    PhaseBatch pb;
-    pb.n = pb.blocks = 0;
-    // cos / sin of kappa p_t v_s, p_t = (half - t) dy
-    batch_add(pb, nullptr, pl.fold_cm.as<double>(), pl.fold_sm.as<double>(), T, S, 1, half, -1.0,
-              s_hi, s_lo, pl.fold_v.as<double>(), pl.fold_v.as<double>() + S);
-    // rotation that advances the table by four samples: cos / sin of kappa (4 dy) v_s
-    batch_add(pb, nullptr, pl.fold_r4.as<double>(), pl.fold_r4.as<double>() + S, 1, S, 1, 4.0, 0.0,
-              s_hi, s_lo, pl.fold_v.as<double>(), pl.fold_v.as<double>() + S);
-    // input modulation E_k = exp(-i kappa p_k u_c), p_k = (k - half) dy; skipped when u_c == 0
-    pl.fold_has_E = (uc != 0);
-    if (pl.fold_has_E) {
-        // the single direction u_c travels behind v in fold_v
-        const double *tail = pl.fold_v.as<double>() + 2 * (size_t)S;
-        batch_add(pb, pl.fold_E.as<double2>(), nullptr, nullptr, 1, ny, 0, -half, 1.0, s_hi, s_lo,
-                  tail, tail + 1);
-    }
-    // output diagonal D_j = exp(-i kappa delta u_j), delta = (half - ceil(ny/2)) dy
-    const double delta = half - (double)(ny - ny / 2);
-    batch_add(pb, pl.fold_D.as<double2>(), nullptr, nullptr, 1, my, 1, delta, 0.0, s_hi, s_lo,
-              pl.uy.as<double>(), nullptr);
-    ML_TRY(batch_launch(ctx, pb));
-    ML_HIP(hipGetLastError());
-    pl.fold = true;
-    pl.fold_T = T;
-    pl.fold_S = S;
-    return ML_OK;
+    if (disabled || pl.pair_list) return ML_OK;
+    ML_TRY(plan_fold_axis(ctx, pl.fold_y, uy, pl.my, pl.ny, pl.dyp, pl.fold, pl.fold_S));
+    return pl.fold ? fold_tables(ctx, pl.fold_y, pl.fold_S, pl.uy, pl.my, pl.ny, pl.dyp, 0, pl.ny, 0) : ML_OK;
+}
+
+// stage 2: its tables depend on which aperture rows are resident and are built in the transform call (stage2_tables)
+static int plan_fold2(ml_ctx *ctx, const double *ux) {
+    FarfieldPlan &pl = ctx->plan;
+    pl.fold2 = false;
+    static const bool disabled = diag_int("ML_NO_FOLD2", 0) != 0;
+    if (disabled || pl.pair_list) return ML_OK;
+    return plan_fold_axis(ctx, pl.fold_x, ux, pl.mx, pl.nx_total, pl.dxp, pl.fold2, pl.fold2_S);
 }
 
 // Does the direction grid along one axis sit on the FFT lattice of that aperture axis (zfft.hip)?
@@ -539,36 +547,6 @@ static int plan_fft_axis(ml_ctx *ctx, ZfftAxis &ax, int n, double step, const do
     return ML_OK;
 }
 
-// Stage 2 can be folded the same way when ux is centre-symmetric; its tables depend on
-// which aperture rows are resident and are built in the transform call.
-static int plan_fold2(ml_ctx *ctx, const double *ux) {
-    FarfieldPlan &pl = ctx->plan;
-    pl.fold2 = false;
-    static const bool disabled = diag_int("ML_NO_FOLD2", 0) != 0;
-    if (disabled || pl.pair_list || pl.mx < 2 || pl.nx_total < 2) return ML_OK;
-    const int mx = pl.mx, S = (mx + 1) / 2;
-    const long double kappa = (long double)pl.n_glass / (long double)pl.wavelength;
-    const long double p_max = 0.5L * (pl.nx_total - 1) * fabsl((long double)pl.dxp);
-    const long double uc = 0.5L * ((long double)ux[0] + (long double)ux[mx - 1]);
-    std::vector<double> v(2 * (size_t)S + 2);
-    long double worst = 0;
-    for (int s = 0; s < S; ++s) {
-        const long double up = ux[mx - 1 - s], um = ux[s];
-        worst = fmaxl(worst, fabsl(0.5L * (up + um) - uc));
-        const long double vs = 0.5L * (up - um);
-        v[s] = (double)vs;
-        v[S + s] = (double)(vs - (long double)v[s]);
-    }
-    if (2 * M_PIl * kappa * p_max * worst > symmetry_tolerance(kappa, p_max, ux, mx)) return ML_OK;
-    v[2 * (size_t)S] = (double)uc;
-    v[2 * (size_t)S + 1] = (double)(uc - (long double)v[2 * (size_t)S]);
-    ML_TRY(upload_if_changed(ctx, pl.fold2_v, pl.h_fold2_v, v.data(), v.size()));
-    pl.fold2 = true;
-    pl.fold2_S = S;
-    pl.fold2_has_E = (uc != 0);
-    return ML_OK;
-}
-
 // Folded stage 2 for a mirror-symmetric set of resident rows: local row k pairs with local
 // row nxl-1-k, pair t sits at +/-(half_x - row0 - t) dx.  G is transposed so that the
 // reduction index is contiguous, run through the same folded kernel as stage 1 (rows = 4*my
@@ -586,35 +564,7 @@ static int stage2_tables(ml_ctx *ctx, int row0, int mirrored, int *want_split_ou
     if (!plan_cache_disabled() && memcmp(key, pl.fold2_key, sizeof key) == 0) return ML_OK;
     const int splits = zfold_splits(T, want_split);
     ML_TRY(pl.fold2_ot.reserve((size_t)splits * 4 * my * mx * 2 * sizeof(double)));
-    ML_TRY(pl.fold2_cm.reserve((size_t)T * S * sizeof(double)));
-    ML_TRY(pl.fold2_sm.reserve((size_t)T * S * sizeof(double)));
-    ML_TRY(pl.fold2_r4.reserve((size_t)S * 2 * sizeof(double)));
-    ML_TRY(pl.fold2_E.reserve((size_t)nxl * 2 * sizeof(double)));
-    ML_TRY(pl.fold2_D.reserve((size_t)mx * 2 * sizeof(double)));
-    const long double sl = (long double)pl.n_glass / (long double)pl.wavelength * (long double)pl.dxp;
-    const double s_hi = (double)sl, s_lo = (double)(sl - (long double)s_hi);
-    const double half = 0.5 * (pl.nx_total - 1);
-    const double *v_hi = pl.fold2_v.as<double>(), *v_lo = v_hi + S, *uc = v_hi + 2 * (size_t)S;
-    ProfScope scope(ctx, ML_K_TWIDDLE);
-    PhaseBatch pb;
-    pb.n = pb.blocks = 0;
-    batch_add(pb, nullptr, pl.fold2_cm.as<double>(), pl.fold2_sm.as<double>(), T, S, 1, half - row0,
-              -1.0, s_hi, s_lo, v_hi, v_lo);
-    batch_add(pb, nullptr, pl.fold2_r4.as<double>(), pl.fold2_r4.as<double>() + S, 1, S, 1, 4.0,
-              0.0, s_hi, s_lo, v_hi, v_lo);
-    if (pl.fold2_has_E) {
-        // E_k = exp(-i kappa p_k u_c) at the resident rows: one run, or two for a mirrored shard
-        const int h = mirrored ? nxl / 2 : nxl;
-        batch_add(pb, pl.fold2_E.as<double2>(), nullptr, nullptr, 1, h, 0, row0 - half, 1.0, s_hi,
-                  s_lo, uc, uc + 1);
-        if (mirrored)
-            batch_add(pb, pl.fold2_E.as<double2>() + h, nullptr, nullptr, 1, h, 0,
-                      (double)(pl.nx_total - row0 - h) - half, 1.0, s_hi, s_lo, uc, uc + 1);
-    }
-    const double delta = half - (double)(pl.nx_total - pl.nx_total / 2);
-    batch_add(pb, pl.fold2_D.as<double2>(), nullptr, nullptr, 1, mx, 1, delta, 0.0, s_hi, s_lo,
-              pl.ux.as<double>(), nullptr);
-    ML_TRY(batch_launch(ctx, pb));
+    ML_TRY(fold_tables(ctx, pl.fold_x, S, pl.ux, mx, pl.nx_total, pl.dxp, row0, nxl, mirrored));
     memcpy(pl.fold2_key, key, sizeof key);
     return ML_OK;
 }
@@ -622,14 +572,14 @@ static int stage2_tables(ml_ctx *ctx, int row0, int mirrored, int *want_split_ou
 // Materialise the radiation vectors of a folded stage 2 whose unfold was deferred.
 int flush_unfold(ml_ctx *ctx) {
     FarfieldPlan &pl = ctx->plan;
-    if (!pl.unfold_pending) return ML_OK;
+    if (!pl.unfold.pending) return ML_OK;
     Alpha4f al;
-    for (int k = 0; k < 4; ++k) al.v[k] = pl.unfold_alpha[k];
+    for (int k = 0; k < 4; ++k) al.v[k] = pl.unfold.alpha[k];
     hipLaunchKernelGGL(zunfold_out_kernel, dim3((pl.mx + 31) / 32, (pl.my + 31) / 32, 4), dim3(256),
                        0, ctx->stream, pl.fold2_ot.as<double2>(), pl.vectors.as<double2>(), pl.my,
-                       pl.mx, al, pl.unfold_accumulate, pl.unfold_splits);
+                       pl.mx, al, pl.unfold.accumulate, pl.unfold.splits);
     ML_HIP(hipGetLastError());
-    pl.unfold_pending = false;
+    pl.unfold.pending = false;
     return ML_OK;
 }
 
@@ -659,16 +609,16 @@ static int stage2_folded(ml_ctx *ctx, int row0, int mirrored, int accumulate, co
     }
     pl.stage1_splits = 1;   // consumed
     ML_TRY(zfold_stage1(ctx->stream, 4 * my, nxl, gt, nxl,
-                        pl.fold2_cm.as<double>(), pl.fold2_sm.as<double>(), pl.fold2_r4.as<double>(),
-                        T, S, pl.fold2_has_E && !gt_direct ? pl.fold2_E.as<double>() : nullptr,
-                        pl.fold2_D.as<double>(), pl.fold2_ot.as<double>(), mx, mx, nullptr, 1,
+                        pl.fold_x.cm.as<double>(), pl.fold_x.sm.as<double>(), pl.fold_x.r4.as<double>(),
+                        T, S, pl.fold_x.has_E && !gt_direct ? pl.fold_x.E.as<double>() : nullptr,
+                        pl.fold_x.D.as<double>(), pl.fold2_ot.as<double>(), mx, mx, nullptr, 1,
                         want_split, (int64_t)4 * my * mx, ctx->gemm_f32 != 0, io));
     // the slabs are summed / transposed / signed into `vectors` by the next consumer: the
     // projection kernel if it comes first (one launch for both), flush_unfold otherwise
-    for (int k = 0; k < 4; ++k) pl.unfold_alpha[k] = alpha[k];
-    pl.unfold_splits = splits;
-    pl.unfold_accumulate = accumulate;
-    pl.unfold_pending = true;
+    for (int k = 0; k < 4; ++k) pl.unfold.alpha[k] = alpha[k];
+    pl.unfold.splits = splits;
+    pl.unfold.accumulate = accumulate;
+    pl.unfold.pending = true;
     static const bool eager = diag_int("ML_EAGER_UNFOLD", 0) != 0;
     if (eager) ML_TRY(flush_unfold(ctx));
     return ML_OK;
@@ -709,7 +659,7 @@ int fields_unmodulate(ml_ctx *ctx) {
     }
     const size_t n = (size_t)4 * ctx->n_sets * ctx->nx * ctx->ny;   // every resident set
     hipLaunchKernelGGL(zunmodulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       ctx->stream, ctx->fields.as<double2>(), pl.fold_E.as<double2>(), ctx->ny, n);
+                       ctx->stream, ctx->fields.as<double2>(), pl.fold_y.E.as<double2>(), ctx->ny, n);
     ML_HIP(hipGetLastError());
     ctx->fields_premod_serial = -1;
     return ML_OK;
@@ -730,7 +680,7 @@ int ml_farfield_plan(ml_ctx *ctx, int nx_total, int ny, double dxp, double dyp, 
     ML_REQUIRE(wavelength > 0 && n_glass > 0 && dxp != 0 && dyp != 0, "bad geometry");
     ML_HIP(hipSetDevice(ctx->device));
     FarfieldPlan &pl = ctx->plan;
-    pl.unfold_pending = false;   // vectors of the previous plan that nobody asked for
+    pl.unfold.pending = false;   // vectors of the previous plan that nobody asked for
     // Same geometry as the active plan (a sweep over sources re-plans every pass): its phase
     // tables depend on nothing else, keep them.  ML_NO_PLAN_CACHE=1 rebuilds them every call.
     // the fp32 GEMM mode is a request for the matrix-core path: it keeps the GEMMs
@@ -984,14 +934,14 @@ static int stage1(ml_ctx *ctx, const TransformRoute &rt, double *g) {
     if (rt.stage1 == Stage1Kind::fft) return stage1_fft(ctx, rt, g);
     if (rt.stage1 == Stage1Kind::folded) {
         FoldIO io;
-        if (rt.gt_direct) {   // (stage2_tables has run: fold2_E is stage 2's input modulation)
+        const FoldAxis &fy = pl.fold_y;
+        if (rt.gt_direct) {   // (stage2_tables has run: fold_x.E is stage 2's input modulation)
             io.out_t_rows = nxl;
-            io.out_E = pl.fold2_has_E ? pl.fold2_E.as<double>() : nullptr;
+            io.out_E = pl.fold_x.has_E ? pl.fold_x.E.as<double>() : nullptr;
         }
-        return zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->set_ptr(), ny, pl.fold_cm.as<double>(),
-                            pl.fold_sm.as<double>(), pl.fold_r4.as<double>(), pl.fold_T, pl.fold_S,
-                            pl.fold_has_E && !fields_premodulated ? pl.fold_E.as<double>() : nullptr,
-                            pl.fold_D.as<double>(), g, my, my,
+        return zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->set_ptr(), ny, fy.cm.as<double>(), fy.sm.as<double>(),
+                            fy.r4.as<double>(), (ny + 1) / 2, pl.fold_S,
+                            fy.has_E && !fields_premodulated ? fy.E.as<double>() : nullptr, fy.D.as<double>(), g, my, my,
                             ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr, nxl, rt.want_split1,
                             (int64_t)4 * nxl * my, ctx->gemm_f32 != 0, io);
     }
@@ -1153,10 +1103,10 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     if (accumulate)
         ML_TRY(flush_unfold(ctx));
     else
-        pl.unfold_pending = false;
+        pl.unfold.pending = false;
     const TransformRoute rt =
         transform_route(pl, pl.fft_y, pl.fft_x, sh, ctx->nx, trim_rows_of(ctx), ctx->trim_rows, route_knobs());
-    pl.stage1_splits = pl.fold ? zfold_splits(pl.fold_T, rt.want_split1) : 1;
+    pl.stage1_splits = pl.fold ? zfold_splits((pl.ny + 1) / 2, rt.want_split1) : 1;
     double *g = nullptr;
     ML_TRY(reserve_g(pl, rt, &g));
     int want_split2 = 1;
@@ -1254,15 +1204,15 @@ static int project_stage(ml_ctx *ctx, double Z0, int stage, hipStream_t stream =
             a.row_hi = a.row_lo + pl.amp_rows;
         }
     }
-    if (pl.unfold_pending && stage != 2) {
+    if (pl.unfold.pending && stage != 2) {
         // vectors still in split-K slabs: unfold and project in one kernel, and let a spare
         // block sum the synthesis kernel's power partials if they are waiting too
         UnfoldArgs u;
         u.in = pl.fold2_ot.as<double2>();
         u.out = pl.vectors.as<double2>();
-        for (int k = 0; k < 4; ++k) u.alpha.v[k] = pl.unfold_alpha[k];
-        u.accumulate = pl.unfold_accumulate;
-        u.splits = pl.unfold_splits;
+        for (int k = 0; k < 4; ++k) u.alpha.v[k] = pl.unfold.alpha[k];
+        u.accumulate = pl.unfold.accumulate;
+        u.splits = pl.unfold.splits;
         u.partial = ctx->power_pending ? ctx->partial_power.as<double>() : nullptr;
         u.n_partials = ctx->n_partials;
         u.power_out = ctx->power.as<double>();
@@ -1271,7 +1221,7 @@ static int project_stage(ml_ctx *ctx, double Z0, int stage, hipStream_t stream =
                            dim3((mx + 7) / 8, (my + 7) / 8 + (u.partial ? 1 : 0)), dim3(256), 0,
                            ctx->stream, a, u);
         ML_HIP(hipGetLastError());
-        pl.unfold_pending = false;
+        pl.unfold.pending = false;
         ctx->power_pending = false;
         return ML_OK;
     }

@@ -206,8 +206,8 @@ void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int 
     // opt-in fusion: write the fields already multiplied by the plan's column phasors
     const FarfieldPlan &pl = ctx->plan;
     const bool premod = ctx->premod_enabled && pl.ready && pl.fold &&
-                        pl.fold_has_E && pl.ny == ny;
-    a.premod = premod ? pl.fold_E.as<double2>() : nullptr;
+                        pl.fold_y.has_E && pl.ny == ny;
+    a.premod = premod ? pl.fold_y.E.as<double2>() : nullptr;
     ctx->fields_premod_serial = premod ? pl.serial : -1;
 }
 

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "metalens_hip.h"
 #include "zfft_core.h"
@@ -42,7 +43,7 @@ struct ZfftAxisGeo {
 };
 
 // the facts of a FarfieldPlan (common.h adds its tables and buffers).  Set in farfield.hip: method and the sizes by
-// ml_farfield_plan, fold / fold_S by plan_fold, fold2 / fold2_S by plan_fold2 (ZfftAxisGeo: plan_fft_axis)
+// ml_farfield_plan, fold / fold_S and fold2 / fold2_S by plan_fold_axis from fold_split (ZfftAxisGeo: plan_fft_axis)
 struct PlanFacts {
     int method = 0;    // ml_farfield_set_method value the plan was made under
     int nx_total = 0, ny = 0, mx = 0, my = 0, pair_list = 0;
@@ -353,6 +354,43 @@ inline long double symmetry_tolerance(long double kappa, long double p_max, cons
     for (int k = 0; k < n; ++k) umax = fmaxl(umax, fabsl((long double)u[k]));
     const long double inherent = 2 * M_PIl * kappa * p_max * umax * (long double)DBL_EPSILON * 0.5L;
     return fmaxl(1e-13L, 4 * inherent);
+}
+
+// Does the axis of m direction cosines u fold - is it centre-symmetric to symmetry_tolerance at the edge of an aperture
+// axis of n samples `step` apart?  If so the folded (even/odd) GEMM (zfold.hip) runs over S = ceil(m / 2) half-
+// directions v_s = (u[m-1-s] - u[s]) / 2 about the centre u_c = (u[0] + u[m-1]) / 2, both computed in long double and
+// split into (hi, lo) doubles for the phase tables (farfield.hip fold_tables).  m < 2 or n < 2: does not fold.
+struct FoldSplit {
+    bool ok = false;
+    int S = 0;
+    bool has_E = false;      // u_c != 0: the input carries the modulation E_k = exp(-i kappa p_k u_c)
+    std::vector<double> v;   // hi[S], lo[S], then u_c as (hi, lo)
+};
+
+inline FoldSplit fold_split(const double *u, int m, int n, double step, double wavelength, double n_glass) {
+    FoldSplit f;
+    if (m < 2 || n < 2) return f;
+    const int S = (m + 1) / 2;
+    const long double kappa = (long double)n_glass / (long double)wavelength;
+    const long double p_max = 0.5L * (n - 1) * fabsl((long double)step);
+    const long double uc = 0.5L * ((long double)u[0] + (long double)u[m - 1]);
+    std::vector<double> v(2 * (size_t)S + 2);
+    long double worst = 0;
+    for (int s = 0; s < S; ++s) {
+        const long double up = u[m - 1 - s], um = u[s];
+        worst = fmaxl(worst, fabsl(0.5L * (up + um) - uc));
+        const long double vs = 0.5L * (up - um);
+        v[s] = (double)vs;
+        v[S + s] = (double)(vs - (long double)v[s]);
+    }
+    if (2 * M_PIl * kappa * p_max * worst > symmetry_tolerance(kappa, p_max, u, m)) return f;
+    v[2 * (size_t)S] = (double)uc;
+    v[2 * (size_t)S + 1] = (double)(uc - (long double)v[2 * (size_t)S]);
+    f.ok = true;
+    f.S = S;
+    f.has_E = (uc != 0);
+    f.v.swap(v);
+    return f;
 }
 
 // the lattice of one axis of a plan, as plan_fft_axis asks for it: n samples `step` apart, sample j at

@@ -742,42 +742,15 @@ __global__ __launch_bounds__(64) void zfft_cols128_kernel(const FftArgs a, int64
     }
 }
 
+static FftArgs args_of(const ZfftCall &c);
+
 int zfft_run_interleaved(hipStream_t stream, const ZfftCall &c, int s, int64_t sub_off, int stuff) {
-    FftArgs a;
-    a.g.R3 = c.N_eff / 256;
-    a.g.n_valid = c.n_valid;
-    a.g.M = c.M;
-    a.g.j0 = c.j0;
-    a.g.pad1 = c.pad1;
-    a.g.pad2 = c.pad2;
-    a.g.ip = 0;
-    a.g.jstep = c.jstep;
-    a.in = reinterpret_cast<const cd *>(c.in);
-    a.in_s1 = c.in_s1;
-    a.in_s2 = c.in_s2;
-    a.in_es = c.in_es;
-    a.in_rb = c.in_rb;
-    a.a0 = c.a0;       // LOCAL rows that exist in the stage-1 result (interleaved kernels)
-    a.h0 = c.h0;
+    FftArgs a = args_of(c);   // (a0 / h0: the LOCAL rows that exist in the stage-1 result)
     a.a1 = a.h1 = 0;
     a.row_first = nullptr;
     a.rf_mod = 1;
     a.sub_s = 1;
     a.sub_i = 0;
-    a.out = reinterpret_cast<cd *>(c.out);
-    a.out_s1 = c.out_s1;
-    a.out_s2 = c.out_s2;
-    a.out_es = c.out_es;
-    a.out_rb = c.out_rb;
-    a.tw1 = reinterpret_cast<const cd *>(c.tw1);
-    a.wk = reinterpret_cast<const cd *>(c.wk);
-    a.pj = reinterpret_cast<const cd *>(c.pj);
-    a.kbin = c.kbin;
-    for (int k = 0; k < 4; ++k) a.alpha[k] = c.alpha[k];
-    a.alpha_rb = c.alpha_rb;
-    a.rows = c.rows;
-    a.accumulate = c.accumulate;
-    a.chunk = (c.rows + 7) / 8;
     ZfftLaunchFacts f;
     f.N_eff = c.N_eff, f.M = c.M, f.s = s, f.stuff = stuff, f.n_valid = c.n_valid;
     const ZfftLaunch L = zfft_launch_rule(f);

@@ -1,9 +1,13 @@
 """The route of a far-field transform call (metalens_amd/csrc/transform_route.h: stage kinds, layout of the row
 transform's result G, allocator, row trim) for the cases DESIGN.md 4.2 / 7 state in words, computed on the host by
-tools/transform_route.cpp from the plan facts ml_farfield_plan would arrive at.  No GPU."""
+tools/transform_route.cpp from the plan facts ml_farfield_plan would arrive at; and the acceptance rule of the folded
+GEMMs (transform_route.h fold_split) through the tool's `fold` subcommand.  No GPU."""
+import math
 import os
 import subprocess
+from fractions import Fraction
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,3 +140,138 @@ def test_diagnostic_knobs_keep_their_meaning(route):
     assert (r['stage2'], r['gt_direct']) == ('generic', '0')
     r = route(ML_FOLD2_MIN_TILES=256, **sym)
     assert (r['stage2'], r['gt_direct']) == ('folded', '1')
+
+
+# ---- fold_split: does a direction axis take the folded GEMM, and the split directions the planner uploads
+
+WL, N_GLASS = 580e-9, 1.459
+FOLD_N, FOLD_STEP = 200, 580e-9 / 2.2
+
+
+@pytest.fixture(scope='module')
+def fold(tmp_path_factory):
+    """fold(u, n=, step=, exe=) -> (ok, S, has_E, v as floats) from `transform_route fold`, the doubles passed and read
+    back as hexadecimal; exe='transform_route_san': the same program under the address and undefined-behaviour
+    sanitizers"""
+    out = str(tmp_path_factory.mktemp('fold')) + os.sep
+    subprocess.check_call(['make', '-s', '-j2', '-C', os.path.join(ROOT, 'tools'), 'OUT=' + out, out + 'transform_route',
+                           out + 'transform_route_san'])
+
+    def run(u, n=FOLD_N, step=FOLD_STEP, exe='transform_route'):
+        args = [str(n)] + [float(v).hex() for v in (step, WL, N_GLASS)] + [float(v).hex() for v in u]
+        res = subprocess.run([out + exe, 'fold'] + args, capture_output=True, text=True, timeout=60)
+        assert res.returncode == 0, res.stdout + res.stderr
+        assert 'runtime error' not in res.stderr and 'AddressSanitizer' not in res.stderr, res.stderr
+        got = dict(kv.split('=') for kv in res.stdout.split())
+        v = [float.fromhex(t) for t in got['v'].split(',')] if got['v'] else []
+        return int(got['ok']), int(got['S']), int(got['has_E']), v
+    return run
+
+
+def _fits_long_double(q):
+    """is the rational q a number of at most 64 significant bits (what an x86 long double carries)?"""
+    if q == 0:
+        return True
+    num, den = abs(q.numerator), q.denominator
+    assert den & (den - 1) == 0                 # sums and differences of doubles are dyadic
+    return (num >> ((num & -num).bit_length() - 1)).bit_length() <= 64
+
+
+def _check_pair(hi, lo, exact):
+    """(hi, lo) splits `exact`: hi its correctly rounded double, hi + lo within 2^-60 relative of it"""
+    assert hi == float(exact)                   # (Fraction -> float rounds correctly)
+    assert abs(Fraction(hi) + Fraction(lo) - exact) <= abs(exact) * Fraction(1, 2 ** 60)
+
+
+def _check_uniform(fold, m, shift):
+    """np.linspace over +/- 0.5, shifted: folds over ceil(m / 2) half-directions v_s = (u[m-1-s] - u[s]) / 2 about
+    u_c = (u[0] + u[m-1]) / 2.  The grids are chosen so that every difference u[m-1-s] - u[s] and the sum
+    u[0] + u[m-1] have at most 64 significant bits (asserted below): the long-double arithmetic of fold_split is
+    then exact, and hi must be the correctly rounded exact value, not merely close to it."""
+    u = np.linspace(-0.5, 0.5, m) + shift
+    ok, S, has_E, v = fold(u)
+    assert (ok, S, has_E) == (1, (m + 1) // 2, int(shift != 0))
+    assert len(v) == 2 * S + 2
+    for s in range(S):
+        diff = Fraction(float(u[m - 1 - s])) - Fraction(float(u[s]))
+        assert _fits_long_double(diff), (m, shift, s)
+        _check_pair(v[s], v[S + s], diff / 2)
+    if m % 2:
+        assert v[S - 1] == 0 and v[2 * S - 1] == 0      # the middle direction is its own partner
+    total = Fraction(float(u[0])) + Fraction(float(u[m - 1]))
+    assert _fits_long_double(total)
+    _check_pair(v[2 * S], v[2 * S + 1], total / 2)
+    if not shift:
+        assert v[2 * S] == 0 and v[2 * S + 1] == 0
+
+
+def _check_warped(fold):
+    u = np.linspace(-0.5, 0.5, 40)
+    assert fold(u + 0.05 * u * u)[:2] == (0, 0)
+
+
+def _symmetry_tolerance(u, n, step):
+    """transform_route.h symmetry_tolerance, restated: (radians of phase per unit of asymmetry at the aperture's
+    edge, the phase allowed) for the axis fold_split tests - p_max = (n - 1) / 2 samples"""
+    per_u = 2 * math.pi * (N_GLASS / WL) * 0.5 * (n - 1) * abs(step)
+    inherent = per_u * max(abs(float(a)) for a in u) * (2.0 ** -52) * 0.5
+    return per_u, max(1e-13, 4 * inherent)
+
+
+def _check_edge(fold):
+    """A grid that is symmetric to the bit, then its upper end moved.  Moving u[m-1] by d moves the centre by d / 2
+    while every other pair keeps its midpoint 0: the worst asymmetry is d / 2."""
+    half = np.linspace(0.0, 0.5, 21)[1:]
+    u = np.concatenate((-half[::-1], half))
+    per_u, tol = _symmetry_tolerance(u, FOLD_N, FOLD_STEP)
+    assert fold(u)[:3] == (1, 20, 0)
+    # one ulp: the phase half an ulp of the largest cosine carries - the tolerance's "inherent" term, of which it
+    # allows four
+    ulp = np.nextafter(u[-1], 1.0) - u[-1]
+    assert per_u * ulp / 2 <= tol / 4 * (1 + 1e-9)
+    moved = u.copy()
+    moved[-1] += ulp
+    assert fold(moved)[:3] == (1, 20, 1)
+    # 1000 times the tolerance
+    moved[-1] = u[-1] + 2 * 1000 * tol / per_u
+    assert per_u * (moved[-1] - u[-1]) / 2 > 999 * tol
+    assert fold(moved)[:2] == (0, 0)
+
+
+def _check_degenerate(fold):
+    assert fold([0.25]) == (0, 0, 0, [])
+    assert fold(np.linspace(-0.5, 0.5, 8), n=1) == (0, 0, 0, [])
+    assert fold(np.linspace(-0.5, 0.5, 8), n=2)[0] == 1
+
+
+FOLD_CASES = [(_check_uniform, 40, 0.0), (_check_uniform, 33, 0.0), (_check_uniform, 40, 0.1), (_check_uniform, 33, 0.1),
+              (_check_warped,), (_check_edge,), (_check_degenerate,)]
+
+
+@pytest.mark.parametrize('m', [40, 33])
+def test_fold_split_of_a_uniform_grid_about_zero(fold, m):
+    _check_uniform(fold, m, 0.0)
+
+
+@pytest.mark.parametrize('m', [40, 33])
+def test_fold_split_of_a_shifted_grid_carries_its_centre(fold, m):
+    _check_uniform(fold, m, 0.1)
+
+
+def test_a_warped_grid_does_not_fold(fold):
+    _check_warped(fold)
+
+
+def test_fold_acceptance_edge(fold):
+    _check_edge(fold)
+
+
+def test_degenerate_axes_do_not_fold(fold):
+    _check_degenerate(fold)
+
+
+def test_fold_cases_under_sanitizers(fold):
+    """every case above through the same program under the address and undefined-behaviour sanitizers: same results,
+    nothing reported (the fixture fails a run whose stderr carries a report)"""
+    for check, *args in FOLD_CASES:
+        check(lambda *a, **kw: fold(*a, exe='transform_route_san', **kw), *args)

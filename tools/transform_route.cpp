@@ -8,7 +8,9 @@
 // y.jstep-th a wanted one, under `method` (zfft_axis_rule) - instead of y.ok, y.N, y.split, y.passes given one by one;
 // y.M / x.M: the wanted bins where they are not my / mx.  n_ranks=G with shard=2: the interleaved shard's block as
 // interleave_block_of gives it, unless block= is given.  `lattice n step wavelength n_glass u...`: which lattice
-// plan_fft_axis finds for an axis and its direction grid.  Runs without a GPU.
+// plan_fft_axis finds for an axis and its direction grid.  `fold n step wavelength n_glass u...`: whether that axis takes
+// the folded GEMM, over how many half-directions, and the split directions the planner uploads (fold_split), the
+// doubles as %a.  Runs without a GPU.
 // Build + run:  make -C tools transform_route && tools/transform_route ny=4096 nx_total=4096 nxl=4096 mx=512 my=512 \
 //                   y.ok=1 y.N=4096 x.ok=1 x.N=4096 row_first=1 trim_lo=150 trim_hi=3946
 #include <cstdio>
@@ -35,8 +37,23 @@ static int lattice_main(int argc, char **argv) {
     return 0;
 }
 
+// `fold n step wavelength n_glass u[0] u[1] ...`: what the planner of a folded GEMM axis finds for that axis
+// (transform_route.h fold_split); v = hi[S], lo[S], then u_c as (hi, lo)
+static int fold_main(int argc, char **argv) {
+    if (argc < 7) return fprintf(stderr, "usage: %s fold n step wavelength n_glass u[0] u[1] ...\n", argv[0]), 2;
+    std::vector<double> u;
+    for (int i = 6; i < argc; ++i) u.push_back(strtod(argv[i], nullptr));
+    const FoldSplit f = fold_split(u.data(), (int)u.size(), atoi(argv[2]), strtod(argv[3], nullptr),
+                                   strtod(argv[4], nullptr), strtod(argv[5], nullptr));
+    printf("ok=%d S=%d has_E=%d v=", f.ok, f.S, f.has_E);
+    for (size_t k = 0; k < f.v.size(); ++k) printf("%s%a", k ? "," : "", f.v[k]);
+    printf("\n");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 1 && !strcmp(argv[1], "lattice")) return lattice_main(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "fold")) return fold_main(argc, argv);
     std::map<std::string, long> a = {{"method", ML_METHOD_AUTO}, {"nx_total", 0}, {"ny", 0}, {"mx", 0}, {"my", 0},
         {"pair_list", 0}, {"fold", 0}, {"fold_S", 0}, {"fold2", 0}, {"fold2_S", 0}, {"nxl", 0}, {"shard", 0}, {"row0", 0},
         {"row_first", 0}, {"trim_lo", 0}, {"trim_hi", 0}, {"f32", 0}, {"y.ok", 0}, {"y.N", 0}, {"y.split", 1}, {"y.passes", 0},
