@@ -486,6 +486,33 @@ int ml_propagate_accumulate(ml_ctx *ctx, const double *weights, int n, int reset
  * Replaces no reference lines.                                                            */
 int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
 
+/* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
+ * (csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the
+ * origin (tx0 - x0, ty0 - y0) is arbitrary.  Every factor of a (sample, target) pair of the direct sum depends on
+ * the lag (i_t - i_s, j_t - j_s) alone, so the sum is a discrete convolution of the four currents with eight
+ * kernels; it is computed as a zero-padded circular convolution of Lx x Ly points, L = the smallest power of two
+ * >= max(16, n + m - 1) per axis - the same sum in another order, not an approximation.  The aperture's shape
+ * n is the resident set's when a pass runs (as for ml_propagate_plan): the first pass on a shape reserves the
+ * workspace and computes the eight kernel spectra, which are kept until the plan is dropped or the shape changes.
+ * L > 8192 is refused with ML_EINVAL: by this call if a field set is resident - n is then that set's shape, so
+ * upload or synthesise the field first - and the previous plan stays as it was; by the pass otherwise, and
+ * whenever a pass meets another shape.  The other arguments and checks as for ml_propagate_plan, which this call
+ * replaces as the active plan: it drops results and sums, and ml_propagate, ml_propagate_sets,
+ * ml_propagate_download[_set], ml_propagate_accumulate and ml_propagate_sums serve it with the same layouts and
+ * scales.  fp64, no atomics, bit-for-bit repeatable; the sets of a pass run one after another and each has the
+ * bits of that set propagated alone.  Replaces no reference lines.                         */
+int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                           double wavelength, double n_glass,
+                           double tx0, double ty0, int mx, int my, double z, int want_h);
+#define ML_PROPAGATE_DIRECT 0
+#define ML_PROPAGATE_FFT 1
+/* The active propagation plan: method (ML_PROPAGATE_*), the padded lengths lx, ly (0 for a direct plan, and for
+ * an fft plan that has met no resident field set yet) and the bytes of device workspace it holds besides targets,
+ * result and sums (direct: the row-set partial sums of the last pass; fft: spectra, currents and outputs, from
+ * the first pass on).  ML_ESTATE without a plan.  Any pointer may be NULL.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,7 +48,7 @@ SYMBOLS = (
     'ml_comm_info', 'ml_comm_set_reduce', 'ml_farfield_gather', 'ml_nearfield_kernel_info',
     'ml_comm_set_max_channels', 'ml_propagate_plan', 'ml_propagate', 'ml_propagate_download',
     'ml_propagate_sets', 'ml_propagate_download_set', 'ml_propagate_accumulate', 'ml_propagate_sums',
-    'ml_fields_sets', 'ml_nearfield_members_async',
+    'ml_fields_sets', 'ml_nearfield_members_async', 'ml_propagate_plan_grid', 'ml_propagate_plan_info',
 )
 
 
@@ -164,6 +164,9 @@ def load():
     lib.ml_propagate_accumulate.argtypes = [c_void_p, _dp, c_int, c_int]
     lib.ml_propagate_sums.argtypes = [c_void_p, _dp, _dp]
     lib.ml_fields_sets.argtypes = [c_void_p, POINTER(c_int)]
+    lib.ml_propagate_plan_grid.argtypes = [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double,
+                                           c_double, c_double, c_int, c_int, c_double, c_int]
+    lib.ml_propagate_plan_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]
     lib.ml_profile_enable.argtypes = [c_void_p, c_int]
     lib.ml_profile_reset.argtypes = [c_void_p]
     lib.ml_profile_get.argtypes = [c_void_p, c_int, POINTER(c_int64), _dp]

@@ -16,6 +16,7 @@
 #include "metalens_hip.h"
 #include "lens_pack.h"
 #include "transform_route.h"
+#include "propagate_grid.h"
 
 namespace ml {
 
@@ -299,6 +300,13 @@ struct PropagatePlan {
     DevBuf partial;   // double [splits][sets][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
+    // the FFT form (propagate_grid.hip, ml_propagate_plan_grid): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
+    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT
+    GridPlanFacts grid;   // (propagate_grid.h) for the aperture shape last met; spectra_ready: its kernel spectra are in grid_work
+    bool spectra_ready = false;
+    double tx_off = 0, ty_off = 0, z = 0;
+    DevBuf grid_work;     // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; released by a direct plan
+    DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
 };
 
 }  // namespace ml
@@ -517,6 +525,8 @@ void comm_release(ml_ctx *ctx);
 int fields_unmodulate(ml_ctx *ctx);
 // farfield.hip: write the radiation vectors a folded stage 2 left in split-K slabs (no-op if none)
 int flush_unfold(ml_ctx *ctx);
+// propagate_grid.hip: the pass of propagate.hip's propagate_sets for a plan of ml_propagate_plan_grid (checks done)
+int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n);
 // in-place sum of `count` doubles over the communicator, queued on `stream` (no-op without one)
 int comm_allreduce_sum(ml_ctx *ctx, double *buf, size_t count, hipStream_t stream);
 // buf = n_ranks chunks of `chunk` doubles: afterwards chunk `rank` holds the sum over the ranks of

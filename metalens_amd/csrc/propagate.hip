@@ -219,6 +219,7 @@ static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, in
                first + n - 1, ctx->n_sets);
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
+    if (pp.method == ML_PROPAGATE_FFT) return propagate_grid_sets(ctx, Z0, first, n);
     const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
     const int splits = std::max(1, std::min(ctx->nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
     pp.have_result = false;
@@ -280,6 +281,9 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
+    pp.method = ML_PROPAGATE_DIRECT;
+    pp.spectra_ready = false;
+    pp.grid_work.release();   // (the spectra of an FFT plan live as long as that plan)
     std::vector<double> h((size_t)3 * T);
     for (long long t = 0; t < T; ++t) {
         const int ix = point_list ? (int)t : (int)(t / ny_t), iy = point_list ? (int)t : (int)(t % ny_t);

@@ -1,0 +1,506 @@
+// The finite-distance propagator for a tensor grid of targets on the aperture's own pitch, as an FFT convolution
+// (ml_propagate_plan_grid; plan arithmetic: propagate_grid.h).  fp64 throughout, no atomics.
+//
+// With the notation of propagate.hip - R = r - r', q = 1 / (k R), w = e^{i k R} / (k R), a = 1 + i q - q^2,
+// b = 1 + 3 i q - 3 q^2, u = Rhat, m = M / Z - the braces of its pair sum are linear in the four currents with
+// coefficients that depend on the lag (i_t - i_s, j_t - j_s) alone.  Eight kernels:
+//   Kxx = i w (a - b ux^2)   Kxy = -i w b ux uy   Kyy = i w (a - b uy^2)   Kzx = -i w b uz ux   Kzy = -i w b uz uy
+//   Cx = w (i - q) ux        Cy = w (i - q) uy    Cz = w (i - q) uz
+//   E / scale_e:  Ex = Kxx Jx + Kxy Jy + Cz my     Ey = Kxy Jx + Kyy Jy - Cz mx     Ez = Kzx Jx + Kzy Jy + Cy mx - Cx my
+//   H / scale_h:  Hx = Kxx mx + Kxy my - Cz Jy     Hy = Kxy mx + Kyy my + Cz Jx     Hz = Kzx mx + Kzy my + Cx Jy - Cy Jx
+// each product a convolution over the aperture.  R, 1 / R, the sincos of k R, q, w, a, b and Rhat of a lag are the
+// inlined functions of propagate_kernel in its order.
+//
+// A pass: pad the four currents of a set into Lx x Ly planes (zeros outside the aperture and outside the row extents
+// of a synthesised field), transform them, contract bin by bin with the eight kernel spectra into 6 (3) output
+// spectra, transform back, crop [0, mx) x [0, my) into the result with the direct path's scales times 1 / (Lx Ly) (a
+// power of two).  The sets of a pass run one after another through the same launches: a set has the bits of that set
+// propagated alone, and every operation is linear in the fields, so a field times two gives the output times two.
+//
+// The transform (propagate_grid.h): radix-2 stages, decimation in frequency forward and in time back, no reordering;
+// up to three stages in registers per exchange.  Twiddles from the host's table (long double, rounded once).
+//   rows:    contiguous along y, a whole row (or several short ones) per workgroup in the LDS;
+//   columns: GRID_COLS = 8 adjacent columns per workgroup - every global access is 128 contiguous bytes - with blocks
+//            of up to 1024 elements in the LDS; the stages above 1024 in a streaming pass (8 elements per thread, a
+//            wave reads 1 KiB contiguous per element).
+// Rows that are zero are not transformed: the forward row pass takes the nx aperture rows, the inverse row pass the mx
+// target rows (launch arguments; the column passes take every column).
+#include "nearfield_math.h"
+
+namespace ml {
+
+typedef double2 d2;
+
+// forward: (a, b) -> (a + b, (a - b) conj(w));  back: (a, b) -> (a + w b, a - w b);  w = (cos, sin)
+template <bool INV>
+__device__ __forceinline__ void bfly(d2 &a, d2 &b, d2 w) {
+    if (!INV) {
+        const d2 s = make_double2(a.x + b.x, a.y + b.y), d = make_double2(a.x - b.x, a.y - b.y);
+        a = s;
+        b = make_double2(fma(d.x, w.x, d.y * w.y), fma(d.y, w.x, -(d.x * w.y)));
+    } else {
+        const d2 t = make_double2(fma(b.x, w.x, -(b.y * w.y)), fma(b.x, w.y, b.y * w.x));
+        b = make_double2(a.x - t.x, a.y - t.y);
+        a = make_double2(a.x + t.x, a.y + t.y);
+    }
+}
+
+// R stages in registers: v[e] is the element at pos0 + e estride of a block of B = estride 2^R (pos0 < estride) of a
+// transform of length L; stage t has blocks of B >> t (forward: t = 0 ... R - 1, back: the reverse)
+template <int R, bool INV>
+__device__ __forceinline__ void stage_group(d2 (&v)[1 << R], const d2 *__restrict__ tw, int L, int B, int pos0, int estride) {
+#pragma unroll
+    for (int tt = 0; tt < R; ++tt) {
+        const int t = INV ? R - 1 - tt : tt;
+        const int he = (1 << R) >> (t + 1);       // partner distance in elements of v
+        const int tw_step = L / (B >> t);          // table entries per position of the stage's block
+#pragma unroll
+        for (int e = 0; e < (1 << R); ++e) {
+            if (e & he) continue;
+            const int p_low = pos0 + (e & (he - 1)) * estride;   // < (B >> t) / 2
+            bfly<INV>(v[e], v[e + he], tw[p_low * tw_step]);
+        }
+    }
+}
+
+template <int R, bool INV>
+__device__ __forceinline__ void lds_group(d2 *s, int nseq, int len, int seq_slots, const d2 *__restrict__ tw, int L, int B) {
+    const int per_seq = len >> R, estride = B >> R;
+    for (int wi = threadIdx.x; wi < nseq * per_seq; wi += blockDim.x) {
+        const int seq = wi / per_seq, rem = wi - seq * per_seq;
+        const int blk = rem / estride, pos0 = rem - blk * estride;
+        d2 *base = s + (size_t)seq * seq_slots;
+        const int p0 = blk * B + pos0;
+        d2 v[1 << R];
+#pragma unroll
+        for (int e = 0; e < (1 << R); ++e) v[e] = base[grid_lds_slot(p0 + e * estride)];
+        stage_group<R, INV>(v, tw, L, B, pos0, estride);
+#pragma unroll
+        for (int e = 0; e < (1 << R); ++e) base[grid_lds_slot(p0 + e * estride)] = v[e];
+    }
+    __syncthreads();
+}
+
+// the stages of block size len ... 2 (back: 2 ... len) of nseq sequences of len elements in the LDS, each a block of a
+// transform of length L.  Groups of three stages; the one or two left over run at the large end.
+template <bool INV>
+__device__ __forceinline__ void lds_stages(d2 *s, int nseq, int len, int seq_slots, const d2 *__restrict__ tw, int L) {
+    const int S = 31 - __clz(len), rest = S % 3;
+    if (!INV) {
+        int B = len;
+        if (rest == 1) lds_group<1, false>(s, nseq, len, seq_slots, tw, L, B);
+        if (rest == 2) lds_group<2, false>(s, nseq, len, seq_slots, tw, L, B);
+        for (B >>= rest; B > 1; B >>= 3) lds_group<3, false>(s, nseq, len, seq_slots, tw, L, B);
+    } else {
+        for (int B = 8; B <= (len >> rest); B <<= 3) lds_group<3, true>(s, nseq, len, seq_slots, tw, L, B);
+        if (rest == 1) lds_group<1, true>(s, nseq, len, seq_slots, tw, L, len);
+        if (rest == 2) lds_group<2, true>(s, nseq, len, seq_slots, tw, L, len);
+    }
+}
+
+struct GridFftArgs {
+    d2 *planes;             // [planes][Lx][Ly]
+    size_t plane_stride;    // elements
+    const d2 *tw;           // the axis' table
+    int Lx, Ly;
+    int rows;               // row pass: the rows [0, rows) are transformed
+    int per_wg;             // row pass: rows per workgroup;  column pass: elements of a column in the LDS
+};
+
+// rows [blockIdx.x per_wg, ...) of plane blockIdx.y along y
+template <bool INV>
+__global__ __launch_bounds__(1024) void grid_rows_kernel(const GridFftArgs a) {
+    extern __shared__ __align__(16) unsigned char grid_lds_raw[];
+    d2 *s = reinterpret_cast<d2 *>(grid_lds_raw);
+    const int L = a.Ly, row0 = blockIdx.x * a.per_wg, nseq = min(a.per_wg, a.rows - row0);
+    const int seq_slots = grid_lds_seq(L);
+    d2 *g = a.planes + blockIdx.y * a.plane_stride + (size_t)row0 * L;
+    for (int idx = threadIdx.x; idx < nseq * L; idx += blockDim.x) {
+        const int r = idx / L, p = idx - r * L;
+        s[(size_t)r * seq_slots + grid_lds_slot(p)] = g[idx];
+    }
+    __syncthreads();
+    lds_stages<INV>(s, nseq, L, seq_slots, a.tw, L);
+    for (int idx = threadIdx.x; idx < nseq * L; idx += blockDim.x) {
+        const int r = idx / L, p = idx - r * L;
+        g[idx] = s[(size_t)r * seq_slots + grid_lds_slot(p)];
+    }
+}
+
+// the rows [blockIdx.y per_wg, + per_wg) of the columns [8 blockIdx.x, + 8) of plane blockIdx.z along x: the stages of
+// block size per_wg and below
+template <bool INV>
+__global__ __launch_bounds__(1024) void grid_cols_kernel(const GridFftArgs a) {
+    extern __shared__ __align__(16) unsigned char grid_lds_raw[];
+    d2 *s = reinterpret_cast<d2 *>(grid_lds_raw);
+    const int len = a.per_wg, seq_slots = grid_lds_seq(len);
+    d2 *g = a.planes + blockIdx.z * a.plane_stride + (size_t)blockIdx.y * len * a.Ly + blockIdx.x * GRID_COLS;
+    for (int idx = threadIdx.x; idx < len * GRID_COLS; idx += blockDim.x) {
+        const int i = idx / GRID_COLS, c = idx % GRID_COLS;
+        s[(size_t)c * seq_slots + grid_lds_slot(i)] = g[(size_t)i * a.Ly + c];
+    }
+    __syncthreads();
+    lds_stages<INV>(s, GRID_COLS, len, seq_slots, a.tw, a.Lx);
+    for (int idx = threadIdx.x; idx < len * GRID_COLS; idx += blockDim.x) {
+        const int i = idx / GRID_COLS, c = idx % GRID_COLS;
+        g[(size_t)i * a.Ly + c] = s[(size_t)c * seq_slots + grid_lds_slot(i)];
+    }
+}
+
+// the R stages of block size Lx ... Lx >> (R - 1) along x, without LDS: a thread holds the 2^R elements
+// pos0 + e (Lx >> R) of one column; adjacent lanes take adjacent columns
+template <int R, bool INV>
+__global__ __launch_bounds__(256) void grid_cols_top_kernel(const GridFftArgs a) {
+    const int estride = a.Lx >> R;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < estride Ly (a multiple of 256)
+    const int pos0 = (int)(id / a.Ly), j = (int)(id - (size_t)pos0 * a.Ly);
+    d2 *g = a.planes + blockIdx.y * a.plane_stride + (size_t)pos0 * a.Ly + j;
+    const size_t step = (size_t)estride * a.Ly;
+    d2 v[1 << R];
+#pragma unroll
+    for (int e = 0; e < (1 << R); ++e) v[e] = g[e * step];
+    stage_group<R, INV>(v, a.tw, a.Lx, a.Lx, pos0, estride);
+#pragma unroll
+    for (int e = 0; e < (1 << R); ++e) g[e * step] = v[e];
+}
+
+struct GridGeoArgs {
+    d2 *out;               // kernel planes [8][Lx][Ly]
+    size_t plane_stride;
+    int Lx, Ly, mx, my;
+    double tx_off, ty_off, dxp, dyp, z, k, inv_k;
+};
+
+// the eight kernels at every index of the padded grid: index p holds lag p (p < m) or p - L
+__global__ __launch_bounds__(256) void grid_fill_kernel(const GridGeoArgs a) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly (a multiple of 256)
+    const int p = (int)(id / a.Ly), r = (int)(id - (size_t)p * a.Ly);
+    const int lx = p < a.mx ? p : p - a.Lx, ly = r < a.my ? r : r - a.Ly;
+    const double dx = fma((double)lx, a.dxp, a.tx_off), dy = fma((double)ly, a.dyp, a.ty_off);
+    const double s_row = fma(dx, dx, a.z * a.z);
+    const double R = sqrt_exact(fma(dy, dy, s_row));
+    const double iR = recip(R);
+    const double ux = dx * iR, uy = dy * iR, uz = a.z * iR;
+    const double q = iR * a.inv_k, q2 = q * q;
+    double sn, cs;
+    sincos_cw(a.k * R, sn, cs);
+    const c2 w = {cs * q, sn * q};
+    const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
+    const c2 wb = cmulf(w, cb);
+    const c2 txx = {fma(-(ux * ux), cb.r, ca.r), fma(-(ux * ux), cb.i, ca.i)};
+    const c2 tyy = {fma(-(uy * uy), cb.r, ca.r), fma(-(uy * uy), cb.i, ca.i)};
+    const c2 wxx = cmulf(w, txx), wyy = cmulf(w, tyy);
+    const c2 ci = {fma(-q, w.r, -w.i), fma(-q, w.i, w.r)};   // w (i - q)
+    const double gxy = ux * uy, gzx = uz * ux, gzy = uz * uy;
+    d2 *o = a.out + id;
+    o[0] = make_double2(-wxx.i, wxx.r);                  // i w (a - b ux^2)
+    o[a.plane_stride] = make_double2(wb.i * gxy, -(wb.r * gxy));   // -i w b ux uy
+    o[2 * a.plane_stride] = make_double2(-wyy.i, wyy.r);
+    o[3 * a.plane_stride] = make_double2(wb.i * gzx, -(wb.r * gzx));
+    o[4 * a.plane_stride] = make_double2(wb.i * gzy, -(wb.r * gzy));
+    o[5 * a.plane_stride] = make_double2(ci.r * ux, ci.i * ux);
+    o[6 * a.plane_stride] = make_double2(ci.r * uy, ci.i * uy);
+    o[7 * a.plane_stride] = make_double2(ci.r * uz, ci.i * uz);
+}
+
+// current c = blockIdx.y of one field set into its padded plane: Jx = -Hy, Jy = Hx, Mx / Z = Ey / Z, My / Z = -Ex / Z
+// (the conversion of propagate_kernel's staging: field f = 3 - c, the same signs, the same division)
+__global__ __launch_bounds__(256) void grid_pad_kernel(const d2 *fields, const int *row_first, d2 *cur, size_t plane_stride,
+                                                       int nx, int ny, int Lx, int Ly, double Z) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
+    const int i = (int)(id / Ly), j = (int)(id - (size_t)i * Ly);
+    const int c = blockIdx.y, f = 3 - c;
+    d2 v = make_double2(0.0, 0.0);
+    if (i < nx && j < ny) {
+        const int first = row_first ? row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
+        if (j >= first && j < ny - first) {
+            const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? Z : 1.0;
+            const d2 s = fields[((size_t)f * nx + i) * ny + j];
+            v = make_double2(sg * s.x / den, sg * s.y / den);
+        }
+    }
+    cur[c * plane_stride + id] = v;
+}
+
+// acc += k v
+__device__ __forceinline__ void zfma(d2 &acc, d2 k, d2 v) {
+    acc.x = fma(-k.y, v.y, fma(k.x, v.x, acc.x));
+    acc.y = fma(k.y, v.x, fma(k.x, v.y, acc.y));
+}
+__device__ __forceinline__ d2 zmul(d2 k, d2 v) { return make_double2(fma(k.x, v.x, -(k.y * v.y)), fma(k.x, v.y, k.y * v.x)); }
+__device__ __forceinline__ d2 zneg(d2 v) { return make_double2(-v.x, -v.y); }
+
+// per bin: the 6 (3) output spectra from the 4 current spectra and the 8 kernel spectra (the table on top)
+template <bool WANT_H>
+__global__ __launch_bounds__(256) void grid_contract_kernel(const d2 *K, const d2 *cur, d2 *out, size_t ps) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
+    const d2 Kxx = K[id], Kxy = K[ps + id], Kyy = K[2 * ps + id], Kzx = K[3 * ps + id], Kzy = K[4 * ps + id];
+    const d2 Cx = K[5 * ps + id], Cy = K[6 * ps + id], Cz = K[7 * ps + id];
+    const d2 Jx = cur[id], Jy = cur[ps + id], mx = cur[2 * ps + id], my = cur[3 * ps + id];
+    d2 e;
+    e = zmul(Kxx, Jx);
+    zfma(e, Kxy, Jy);
+    zfma(e, Cz, my);
+    out[id] = e;
+    e = zmul(Kxy, Jx);
+    zfma(e, Kyy, Jy);
+    zfma(e, zneg(Cz), mx);
+    out[ps + id] = e;
+    e = zmul(Kzx, Jx);
+    zfma(e, Kzy, Jy);
+    zfma(e, Cy, mx);
+    zfma(e, zneg(Cx), my);
+    out[2 * ps + id] = e;
+    if (WANT_H) {
+        e = zmul(Kxx, mx);
+        zfma(e, Kxy, my);
+        zfma(e, zneg(Cz), Jy);
+        out[3 * ps + id] = e;
+        e = zmul(Kxy, mx);
+        zfma(e, Kyy, my);
+        zfma(e, Cz, Jx);
+        out[4 * ps + id] = e;
+        e = zmul(Kzx, mx);
+        zfma(e, Kzy, my);
+        zfma(e, Cx, Jy);
+        zfma(e, zneg(Cy), Jx);
+        out[5 * ps + id] = e;
+    }
+}
+
+// result[component blockIdx.y][i my + j] = scale out[component][i][j], i < mx, j < my
+__global__ __launch_bounds__(256) void grid_crop_kernel(const d2 *out, size_t ps, d2 *result, int mx, int my, int Ly,
+                                                        double scale_e, double scale_h) {
+    const int t = blockIdx.x * 256 + threadIdx.x, T = mx * my;
+    if (t >= T) return;
+    const int i = t / my, j = t - i * my, m = blockIdx.y;
+    const double scale = m < 3 ? scale_e : scale_h;
+    const d2 v = out[m * ps + (size_t)i * Ly + j];
+    result[(size_t)m * T + t] = make_double2(scale * v.x, scale * v.y);
+}
+
+template <typename Kern>
+static int big_lds(Kern kern, bool &done) {
+    if (!done) {
+        ML_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        done = true;
+    }
+    return ML_OK;
+}
+
+// `planes` planes along y, rows [0, rows)
+template <bool INV>
+static int fft_rows(ml_ctx *ctx, d2 *planes, int n_planes, int rows) {
+    const PropagatePlan &pp = ctx->prop;
+    static bool attr_done = false;   // per instantiation
+    ML_TRY(big_lds(grid_rows_kernel<INV>, attr_done));
+    GridFftArgs a;
+    a.planes = planes;
+    a.plane_stride = (size_t)pp.grid.Lx * pp.grid.Ly;
+    a.tw = pp.grid_tw_y.as<d2>();
+    a.Lx = pp.grid.Lx;
+    a.Ly = pp.grid.Ly;
+    a.rows = rows;
+    a.per_wg = std::max(1, 2048 / a.Ly);
+    const int elems = a.per_wg * a.Ly, threads = std::min(1024, std::max(256, elems / 8));
+    const size_t lds = (size_t)a.per_wg * grid_lds_seq(a.Ly) * sizeof(d2);
+    hipLaunchKernelGGL(grid_rows_kernel<INV>, dim3((rows + a.per_wg - 1) / a.per_wg, n_planes), dim3(threads), lds,
+                       ctx->stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+template <bool INV>
+static int fft_cols_lds(ml_ctx *ctx, GridFftArgs a, int n_planes) {
+    static bool attr_done = false;   // per instantiation
+    ML_TRY(big_lds(grid_cols_kernel<INV>, attr_done));
+    const int threads = std::min(1024, std::max(64, a.per_wg));
+    const size_t lds = (size_t)GRID_COLS * grid_lds_seq(a.per_wg) * sizeof(d2);
+    hipLaunchKernelGGL(grid_cols_kernel<INV>, dim3(a.Ly / GRID_COLS, a.Lx / a.per_wg, n_planes), dim3(threads), lds,
+                       ctx->stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+template <bool INV>
+static int fft_cols_top(ml_ctx *ctx, const GridFftArgs &a, int n_planes) {
+    const int R = grid_log2(a.Lx / a.per_wg);   // 1 ... 3
+    const dim3 grid((unsigned)(((size_t)(a.Lx >> R) * a.Ly) / 256), n_planes);
+    if (R == 1)
+        hipLaunchKernelGGL((grid_cols_top_kernel<1, INV>), grid, dim3(256), 0, ctx->stream, a);
+    else if (R == 2)
+        hipLaunchKernelGGL((grid_cols_top_kernel<2, INV>), grid, dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((grid_cols_top_kernel<3, INV>), grid, dim3(256), 0, ctx->stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+// `planes` planes along x, every column
+template <bool INV>
+static int fft_cols(ml_ctx *ctx, d2 *planes, int n_planes) {
+    const PropagatePlan &pp = ctx->prop;
+    GridFftArgs a;
+    a.planes = planes;
+    a.plane_stride = (size_t)pp.grid.Lx * pp.grid.Ly;
+    a.tw = pp.grid_tw_x.as<d2>();
+    a.Lx = pp.grid.Lx;
+    a.Ly = pp.grid.Ly;
+    a.rows = a.Lx;
+    a.per_wg = std::min(a.Lx, GRID_COL_LDS);
+    const bool top = a.Lx > a.per_wg;
+    if (top && !INV) ML_TRY(fft_cols_top<INV>(ctx, a, n_planes));
+    ML_TRY(fft_cols_lds<INV>(ctx, a, n_planes));
+    if (top && INV) ML_TRY(fft_cols_top<INV>(ctx, a, n_planes));
+    return ML_OK;
+}
+
+static int upload_twiddles(ml_ctx *ctx, DevBuf &buf, int L) {
+    const std::vector<double> t = grid_twiddles(L);
+    ML_TRY(buf.reserve(t.size() * sizeof(double)));
+    ML_HIP(hipMemcpyAsync(buf.p, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ML_HIP(hipStreamSynchronize(ctx->stream));   // (`t` goes away)
+    return ML_OK;
+}
+
+// the workspace and the kernel spectra for the resident field's shape (kept while the shape stays)
+static int grid_prepare(ml_ctx *ctx) {
+    PropagatePlan &pp = ctx->prop;
+    if (pp.spectra_ready && pp.grid.nx == ctx->nx && pp.grid.ny == ctx->ny) return ML_OK;
+    pp.spectra_ready = false;
+    const int mx = pp.grid.mx, my = pp.grid.my;
+    char why[320];
+    GridPlanFacts f;
+    if (grid_plan_facts(ctx->nx, ctx->ny, mx, my, pp.want_h, &f, why, sizeof why) != 0) {
+        set_error("%s", why);
+        return ML_EINVAL;
+    }
+    pp.grid = f;
+    ML_TRY(pp.grid_work.reserve((size_t)f.workspace_bytes));
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
+    GridGeoArgs g;
+    g.out = pp.grid_work.as<d2>();
+    g.plane_stride = (size_t)f.Lx * f.Ly;
+    g.Lx = f.Lx;
+    g.Ly = f.Ly;
+    g.mx = mx;
+    g.my = my;
+    g.tx_off = pp.tx_off;
+    g.ty_off = pp.ty_off;
+    g.dxp = pp.dxp;
+    g.dyp = pp.dyp;
+    g.z = pp.z;
+    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
+    g.inv_k = 1.0 / g.k;
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)(g.plane_stride / 256)), dim3(256), 0, ctx->stream, g);
+    ML_HIP(hipGetLastError());
+    ML_TRY(fft_rows<false>(ctx, g.out, GRID_KERNELS, f.Lx));
+    ML_TRY(fft_cols<false>(ctx, g.out, GRID_KERNELS));
+    pp.spectra_ready = true;
+    return ML_OK;
+}
+
+int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
+    PropagatePlan &pp = ctx->prop;
+    pp.have_result = false;
+    ML_TRY(grid_prepare(ctx));
+    const GridPlanFacts &f = pp.grid;
+    const int T = pp.T, nc = f.outputs;
+    ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
+    const size_t ps = (size_t)f.Lx * f.Ly;
+    d2 *K = pp.grid_work.as<d2>(), *cur = K + GRID_KERNELS * ps, *out = cur + GRID_CURRENTS * ps;
+    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
+    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
+    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const unsigned blocks = (unsigned)(ps / 256);
+    // rows that are zero need no transform (diagnostic build: ML_GRID_ALL_ROWS=1 transforms them all, for timing)
+    const bool all_rows = diag_int("ML_GRID_ALL_ROWS", 0) != 0;
+    const int rows_fwd = all_rows ? f.Lx : ctx->nx, rows_inv = all_rows ? f.Lx : f.mx;
+    for (int m = 0; m < n; ++m) {
+        const d2 *fields = ctx->fields.as<d2>() + (size_t)(first + m) * 4 * ctx->nx * ctx->ny;
+        hipLaunchKernelGGL(grid_pad_kernel, dim3(blocks, GRID_CURRENTS), dim3(256), 0, ctx->stream, fields,
+                           ctx->row_first_valid ? ctx->row_first.as<int>() : (const int *)nullptr, cur, ps, ctx->nx, ctx->ny,
+                           f.Lx, f.Ly, Z);
+        ML_HIP(hipGetLastError());
+        ML_TRY(fft_rows<false>(ctx, cur, GRID_CURRENTS, rows_fwd));
+        ML_TRY(fft_cols<false>(ctx, cur, GRID_CURRENTS));
+        if (pp.want_h)
+            hipLaunchKernelGGL(grid_contract_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, K, cur, out, ps);
+        else
+            hipLaunchKernelGGL(grid_contract_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, K, cur, out, ps);
+        ML_HIP(hipGetLastError());
+        ML_TRY(fft_cols<true>(ctx, out, nc));
+        ML_TRY(fft_rows<true>(ctx, out, nc, rows_inv));
+        hipLaunchKernelGGL(grid_crop_kernel, dim3((T + 255) / 256, nc), dim3(256), 0, ctx->stream, out, ps,
+                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, Z * scale_h * inv_n, scale_h * inv_n);
+        ML_HIP(hipGetLastError());
+    }
+    pp.have_result = true;
+    pp.result_sets = n;
+    return ML_OK;
+}
+
+}  // namespace ml
+
+using namespace ml;
+
+extern "C" {
+
+int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                           double tx0, double ty0, int mx, int my, double z, int want_h) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    ML_REQUIRE(ctx->n_ranks <= 1, "ml_propagate_plan_grid: this context belongs to a communicator of %d ranks; the "
+               "finite-distance propagator sums a whole aperture on one GPU (sharded propagation is not implemented)",
+               ctx->n_ranks);
+    ML_REQUIRE(mx >= 1 && my >= 1, "no targets");
+    ML_REQUIRE(wavelength > 0 && n_glass > 0 && dxp > 0 && dyp > 0, "bad geometry");
+    ML_REQUIRE(z > 0, "the target plane lies at z = %g: the propagator needs z > 0", z);
+    ML_REQUIRE((long long)mx * my <= (1 << 26), "%lld targets: at most 2^26 per plan", (long long)mx * my);
+    GridPlanFacts f;
+    f.mx = mx;
+    f.my = my;
+    if (ctx->nx && ctx->ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
+        char why[320];
+        if (grid_plan_facts(ctx->nx, ctx->ny, mx, my, want_h, &f, why, sizeof why) != 0) {
+            set_error("ml_propagate_plan_grid: %s", why);
+            return ML_EINVAL;
+        }
+    }
+    ML_HIP(hipSetDevice(ctx->device));
+    PropagatePlan &pp = ctx->prop;
+    pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
+    pp.spectra_ready = false;
+    pp.method = ML_PROPAGATE_FFT;
+    pp.grid = f;
+    pp.T = mx * my;
+    pp.want_h = want_h != 0;
+    pp.x0 = x0;
+    pp.y0 = y0;
+    pp.dxp = dxp;
+    pp.dyp = dyp;
+    pp.wavelength = wavelength;
+    pp.n_glass = n_glass;
+    pp.tx_off = tx0 - x0;
+    pp.ty_off = ty0 - y0;
+    pp.z = z;
+    pp.ready = true;
+    return ML_OK;
+}
+
+int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *workspace_bytes) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    const PropagatePlan &pp = ctx->prop;
+    if (!pp.ready) {
+        set_error("no propagation plan is active");
+        return ML_ESTATE;
+    }
+    const bool fft = pp.method == ML_PROPAGATE_FFT;
+    if (method) *method = pp.method;
+    if (lx) *lx = fft ? pp.grid.Lx : 0;
+    if (ly) *ly = fft ? pp.grid.Ly : 0;
+    if (workspace_bytes) *workspace_bytes = (int64_t)(fft ? pp.grid_work.bytes : pp.partial.bytes);
+    return ML_OK;
+}
+
+}  // extern "C"

@@ -15,6 +15,10 @@ with ``R = |r - r'|``, ``g = exp(ikR) / (4 pi R)``, ``a = 1 + i/(kR) - 1/(kR)^2`
 The sum runs in the HIP kernel ``propagate_kernel`` (csrc/propagate.hip) as a direct fp64 pair sum over the
 GPU-resident near field; for ``R -> infinity`` it reduces to the amplitudes behind ``farfield_direct``'s ``P``:
 ``rho^2 S_r -> P uz / 2``.  There is no CPU path.
+
+``method='fft'``: for a tensor grid of targets on the aperture's own pitch every factor of a (sample, target) pair
+depends on the lag ``(i_t - i_s, j_t - j_s)`` alone, and the same sum runs as a zero-padded circular convolution
+(csrc/propagate_grid.hip): ``O(L^2 log L)`` with ``L >= n + m - 1`` per axis instead of ``n^2 m^2`` pairs.
 """
 import numpy as np
 
@@ -39,6 +43,40 @@ def _targets(x, y, z, point_list):
     return x, y, z
 
 
+METHODS = ('direct', 'fft')
+GRID_L_MAX = 8192   # csrc/propagate_grid.h
+
+
+def _padded_length(n, m):
+    """the padded length of an axis of n samples and m targets (csrc/propagate_grid.h grid_padded_length)"""
+    L = 16
+    while L < n + m - 1:
+        L *= 2
+    return L
+
+
+def _on_pitch(name, t, pitch):
+    """``method='fft'``: the target axis ``t`` must be ``t[0] + i pitch`` to within 4 spacings of its largest value
+    (the deviation changes the phase k x of the direct sum by a few 1e-13 rad at that level)"""
+    tol = 4 * np.spacing(np.abs(t).max())
+    off = np.abs(t - (t[0] + np.arange(t.size) * pitch)) > tol
+    if off.any():
+        i = int(np.argmax(off))
+        own = t[1] - t[0]
+        raise ValueError("method='fft' needs the targets on the aperture's pitch: %s[%d] = %.17g is not %s[0] + %d x %.17g "
+                         "(the aperture's pitch along %s; the target axis steps by %.17g)"
+                         % (name, i, t[i], name, i, pitch, name, own))
+
+
+def plan_info(ctx):
+    """-> ``{'method', 'Lx', 'Ly', 'workspace_bytes'}`` of the context's active propagation plan
+    (ml_propagate_plan_info): the padded lengths are 0 for the direct method"""
+    method, lx, ly, ws = _lib.c_int(0), _lib.c_int(0), _lib.c_int(0), _lib.c_int64(0)
+    _lib.check(ctx.lib.ml_propagate_plan_info(ctx.handle, _lib.byref(method), _lib.byref(lx), _lib.byref(ly),
+                                              _lib.byref(ws)))
+    return {'method': METHODS[method.value], 'Lx': lx.value, 'Ly': ly.value, 'workspace_bytes': ws.value}
+
+
 class PlanePropagator:
     """The field of one aperture geometry at one set of targets.
 
@@ -55,29 +93,60 @@ class PlanePropagator:
     ``Sz = Re(E x H*)_z / 2``; with ``want_h=False`` ``Ex, Ey, Ez`` and ``I = |E|^2`` only (about 40 % less
     arithmetic).  The far-field plan, the sweep sums, the method and the precision of the context are not
     touched.  A context that belongs to a multi-rank communicator is refused.
+
+    ``method='direct'`` (default) is the pair sum.  ``method='fft'`` computes the same sum as an FFT convolution
+    (csrc/propagate_grid.hip).  It takes a tensor grid only, both of whose axes lie on the aperture's pitch as the C
+    ABI defines it (``xp_list[1] - xp_list[0]``, likewise y): ``|x[i] - (x[0] + i dxp)| <= 4 spacing(max |x|)``; one
+    target along an axis is accepted, and the origin ``x[0] - xp_list[0]`` is arbitrary (no multiple of the pitch).
+    Each axis is padded to ``L`` = the smallest power of two ``>= max(16, n + m - 1)``, at most 8192; the workspace is
+    ``(12 + 6 or 3) Lx Ly`` complex128 (``plan_info()``).  Everything else - ``propagate_sets``, ``accumulate``,
+    ``sums``, ``SourceSweep.run(image=...)`` - is as for the direct method.  The kernel spectra are computed by the
+    first pass and kept while this propagator stays the one that planned last on the context.
     """
 
     def __init__(self, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False, want_h=True,
-                 units=None, Z0=None, ctx=None):
+                 units=None, Z0=None, ctx=None, method='direct'):
+        if method not in METHODS:
+            raise ValueError('method must be one of %s, got %r' % (METHODS, method))
+        self.method = method
         self.Z0 = constants.as_units(units).Z0 if Z0 is None else Z0
         _check_axis(xp_list, wavelength)
         _check_axis(yp_list, wavelength)
         self.point_list, self.want_h = bool(point_list), bool(want_h)
+        if method == 'fft' and self.point_list:
+            raise ValueError("method='fft' takes a tensor grid of targets on the aperture's pitch, not a point list")
         self.x, self.y, self.z = _targets(x, y, z, self.point_list)
         self.shape = (self.x.size,) if self.point_list else (self.x.size, self.y.size)
         self.aperture_shape = (len(xp_list), len(yp_list))
         self._geometry = (float(xp_list[0]), float(yp_list[0]), float(xp_list[1] - xp_list[0]),
                           float(yp_list[1] - yp_list[0]), float(wavelength), float(n_glass))
+        if method == 'fft':
+            _on_pitch('x', self.x, self._geometry[2])
+            _on_pitch('y', self.y, self._geometry[3])
+            for name, n, m in (('x', self.aperture_shape[0], self.x.size), ('y', self.aperture_shape[1], self.y.size)):
+                L = _padded_length(n, m)
+                if L > GRID_L_MAX:
+                    raise ValueError("method='fft' pads the %s axis of n = %d samples and m = %d targets to L = %d > %d; "
+                                     "use method='direct' or fewer targets per propagator" % (name, n, m, L, GRID_L_MAX))
         self.ctx = ctx or _lib.default_context()
         self.owner = _lib.new_owner()
         self._plan()
 
     def _plan(self):
         ctx = self.ctx
-        _lib.check(ctx.lib.ml_propagate_plan(
-            ctx.handle, *self._geometry, _lib.dptr(self.x), self.x.size, _lib.dptr(self.y), self.y.size,
-            _lib.dptr(self.z), self.z.size, int(self.point_list), int(self.want_h)))
+        if self.method == 'fft':
+            _lib.check(ctx.lib.ml_propagate_plan_grid(
+                ctx.handle, *self._geometry, float(self.x[0]), float(self.y[0]), self.x.size, self.y.size,
+                float(self.z[0]), int(self.want_h)))
+        else:
+            _lib.check(ctx.lib.ml_propagate_plan(
+                ctx.handle, *self._geometry, _lib.dptr(self.x), self.x.size, _lib.dptr(self.y), self.y.size,
+                _lib.dptr(self.z), self.z.size, int(self.point_list), int(self.want_h)))
         ctx.propagate_owner = self.owner
+
+    def plan_info(self):
+        """``plan_info(self.ctx)``: of the plan that is active on the context now, whoever made it"""
+        return plan_info(self.ctx)
 
     def _ready(self):
         """the resident field must have the aperture's shape; plans again if another propagator has planned on the
@@ -154,12 +223,12 @@ class PlanePropagator:
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,
-                   want_h=True, units=None, Z0=None, ctx=None):
+                   want_h=True, units=None, Z0=None, ctx=None, method='direct'):
     """One-shot convenience, modelled on ``farfield_direct``: the field of host arrays ``Ex..Hy`` (or of the
     field set already resident on the GPU if ``Ex is None``, e.g. after ``build_nearfield(..., download=False)``
     or a ``HotPath`` step) at the targets.  Arguments and the returned dict as for ``PlanePropagator``."""
     p = PlanePropagator(xp_list, yp_list, wavelength, n_glass, x, y, z, point_list=point_list, want_h=want_h,
-                        units=units, Z0=Z0, ctx=ctx)
+                        units=units, Z0=Z0, ctx=ctx, method=method)
     ctx = p.ctx
     if Ex is not None:
         arrs = [_lib.c128(a) for a in (Ex, Ey, Hx, Hy)]

@@ -18,7 +18,17 @@ loop's instructions account for (a v_fma_f64 holds a SIMD four cycles per wave).
 ml_fields_select + ml_propagate calls on the same sets (the single-set kernel, which the NS parameter left as it
 was), 2048^2 -> 64^2, E + H and E only, timed as above; ratio = ms of the one pass / ms of the three.  The fields are
 a synthetic lens' (row extents: only samples inside the lens circle are summed, in both paths alike).  The static
-count covers NS = 1, 2, 3: per (sample, target) pair, all sets of the pass together."""
+count covers NS = 1, 2, 3: per (sample, target) pair, all sets of the pass together.
+
+    python tools/propagate_bench.py --method fft [--quick] >> profiles/propagate_bench.txt     (needs an MI355X)
+
+--method fft: ``PlanePropagator(method='fft')`` (csrc/propagate_grid.hip) against the direct sum on the SAME targets - an
+m x m patch on the aperture's pitch around the focus, off its lattice by 0.3 / 0.6 pitch - for 2048^2 -> 64^2, 4096^2 ->
+64^2 and 4096^2 -> 256^2, E + H and E only: ms of a pass on cached kernel spectra (timed as above), ms_first = plan +
+first pass (workspace, kernel fill and its transform, once), the direct pass, max |E_fft - E_direct| / max |E|, and crossover_targets = the target count
+from which the cached FFT pass is the faster one, by the direct sum's time per target (it is linear in the targets).
+Then 'fft' alone: 4096^2 -> 4096^2 (L = 8192^2, 18 / 15 GiB of workspace), and the three sets of a synthesised x, y, z
+batch in one ml_propagate_sets call, 2048^2 -> 64^2."""
 import json
 import os
 import re
@@ -126,7 +136,107 @@ def sets_against_singles(valu, n=2048, m=64):
         _lib.check(ctx.lib.ml_fields_select(ctx.handle, 0))
 
 
+def converging_wave(ctx, n, wl, n_glass):
+    """upload the ideal converging wave on a circular pupil of n^2 samples -> axis, focal length"""
+    import numpy as np
+
+    from metalens_amd import _lib, constants
+    k, Z = 2 * np.pi * n_glass / wl, constants.Z0 / n_glass
+    x = (np.arange(n) - (n - 1) / 2) * (wl / 2.2)
+    f = x.max() / np.tan(np.arcsin(0.5))
+    r2 = x[:, None] ** 2 + x[None, :] ** 2
+    Ex = np.where(r2 <= x.max() ** 2, np.exp(-1j * k * np.sqrt(r2 + f * f)), 0)
+    zero = np.zeros_like(Ex)
+    _lib.check(ctx.lib.ml_fields_upload(ctx.handle, n, n, *[_lib.dptr(_lib.c128(a)) for a in (Ex, zero, zero, Ex / Z)]))
+    return x, f
+
+
+def patch_on_pitch(x, m):
+    """m targets per axis on the aperture's pitch around its centre, 0.3 (x) and 0.6 (y) of a pitch off its lattice"""
+    import numpy as np
+    d = x[1] - x[0]
+    first = (x.size - m) // 2
+    return x[0] + (first + 0.3) * d + np.arange(m) * d, x[0] + (first + 0.6) * d + np.arange(m) * d
+
+
+def fft_against_direct(quick):
+    import numpy as np
+
+    from metalens_amd import _lib
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl, n_glass = 580e-9, 1.46
+    cases = [(1024, 64, True)] if quick else [(2048, 64, True), (4096, 64, True), (4096, 256, True), (4096, 4096, False)]
+    resident = None
+    for n, m, with_direct in cases:
+        if resident != n:
+            x, f = converging_wave(ctx, n, wl, n_glass)
+            resident = n
+        tx, ty = patch_on_pitch(x, m)
+        for want_h in (True, False):
+            t0 = time.perf_counter()
+            p = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx, method='fft')
+            _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0))
+            ctx.sync()
+            ms_first = (time.perf_counter() - t0) * 1e3
+            ms_fft = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0)))
+            info = p.plan_info()
+            line = {'case': '%d^2 -> %d^2 on the pitch' % (n, m), 'fields': 'E+H' if want_h else 'E', 'method': 'fft',
+                    'ms': round(ms_fft, 3), 'ms_first': round(ms_first, 3), 'L': [info['Lx'], info['Ly']],
+                    'workspace_MiB': round(info['workspace_bytes'] / 2 ** 20, 1)}
+            if with_direct:
+                got = p._download(None)
+                pd = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx)
+                ms_direct = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, pd.Z0)))
+                want = pd._download(None)
+                diff = max(np.abs(got[c] - want[c]).max() for c in ('Ex', 'Ey', 'Ez')) / max(np.abs(want[c]).max() for c in ('Ex', 'Ey', 'Ez'))
+                line.update(ms_direct=round(ms_direct, 3), speedup=round(ms_direct / ms_fft, 2),
+                            crossover_targets=int(np.ceil(ms_fft / (ms_direct / (m * m)))),
+                            max_E_difference_of_the_methods=float('%.3e' % diff))
+            print(json.dumps(line), flush=True)
+
+
+def fft_three_sets(n=2048, m=64):
+    """the three sets of a synthesised x, y, z batch through ONE ml_propagate_sets call of an 'fft' plan"""
+    import math
+
+    import numpy as np
+
+    import metalens_amd as ma
+    from metalens_amd import _lib, layout, synthetic
+    from metalens_amd.nearfield import nearfield_params
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl = 580e-9
+    x = (np.arange(n) - (n - 1) / 2) * (wl / 2.2)
+    lens = synthetic.make_lens((ma.Grating, ma.GratingCollection, ma.HexGridSet), layout.make_design,
+                               radius=x.max(), numerical_aperture=0.4, wavelength=wl, switch_angle=9 * math.pi / 180,
+                               num_gratings=20, num_entries=12, design_kwargs={'wavelength': wl})
+    f = lens['source_distance']
+    common = (wl, lens['lens_periphery_summary'], lens['lens_center_summary'], lens['hexgridset'])
+    n_glass = ma.build_nearfield(0.0, 0.0, -f, 'x', *common, x_pts=x, y_pts=x, ctx=ctx, download=False)[7]
+    params = (_lib.NearfieldParams * 3)()
+    for k, pol in enumerate('xyz'):
+        params[k] = nearfield_params(0.0, 0.0, -f, pol, wl, n_glass, 1e-30, ma.constants.c0, ma.constants.Z0)
+    xs = _lib.f64(x)
+    _lib.check(ctx.lib.ml_nearfield_batch_async(ctx.handle, params, 3, _lib.dptr(xs), xs.size, _lib.dptr(xs), xs.size))
+    ctx.sync()
+    tx, ty = patch_on_pitch(x, m)
+    for want_h in (True, False):
+        p = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx, method='fft')
+        ms_one = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate_sets(ctx.handle, p.Z0, 0, 1)))
+        ms_three = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate_sets(ctx.handle, p.Z0, 0, 3)))
+        print(json.dumps({'case': '%d^2 -> %d^2 on the pitch, x + y + z dipoles' % (n, m), 'fields': 'E+H' if want_h else 'E',
+                          'method': 'fft', 'ms_one_pass_of_three_sets': round(ms_three, 3), 'ms_one_set': round(ms_one, 3),
+                          'ratio_to_three_single_passes': round(ms_three / (3 * ms_one), 4)}), flush=True)
+
+
 def main():
+    if '--method' in sys.argv and sys.argv[sys.argv.index('--method') + 1] == 'fft':
+        quick = '--quick' in sys.argv
+        fft_against_direct(quick)
+        fft_three_sets(*((1024, 64) if quick else ()))
+        return
     valu = inner_loop_valu()
     if '--static' in sys.argv:
         print(json.dumps({'valu_per_pair': {'E+H': valu[True, 1], 'E': valu[False, 1]},
