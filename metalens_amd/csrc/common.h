@@ -15,6 +15,7 @@
 
 #include "metalens_hip.h"
 #include "lens_pack.h"
+#include "synth_caches.h"
 #include "transform_route.h"
 #include "propagate_grid.h"
 
@@ -250,7 +251,7 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     // column pass of an interleaved row shard (farfield.hip stage2_interleaved): tables of its `block` short
     // transforms and what they were built for (plan serial, block, ranks, rank)
     DevBuf il_wk, il_pj, il_kbin;
-    long il_key[4] = {-1, -1, -1, -1};
+    Stamp<4> il_for;
     int il_pad1 = 0, il_pad2 = 0;
     long serial = 0;   // incremented by every ml_farfield_plan call
     bool amplitudes_reduced = false;   // ml_farfield_project_reduce ran on the current vectors
@@ -284,8 +285,7 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     DevBuf fold2_gt, fold2_ot;
     // the stage-2 tables depend on the plan and on which rows are resident: rebuilt only when
     // that changes (serial, row0, resident rows, mirrored)
-    long fold2_key[4] = {-1, -1, -1, -1};
-    int fold2_want_split = 1;
+    Stamp<4> fold2_for;
     DeferredUnfold unfold;
 };
 
@@ -309,6 +309,88 @@ struct PropagatePlan {
     DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
 };
 
+// What the kernels read about the lens (lens_pack.h lays it out, ctx.hip uploads it): the tables, the layout and what is
+// packed from both.  The scalars are held as the packers return them.
+struct Lens {
+    // tables
+    TableSlot slots[MAX_SLOTS];
+    TableSlot center;
+    DevBuf table_desc;                       // TableDesc[MAX_SLOTS + 1], last = centre
+    std::vector<TableDesc> h_table_desc;     // host copy of table_desc
+    TableDesc h_center_desc;                 // the centre entry again: it travels in the kernel arguments
+    bool tables_dirty = true;
+    // which kernel takes which table's samples (classify_lens): cls.simple - SOME table in use holds orders (ox, 0),
+    // |ox| <= 5 only, its samples take nearfield_simple.hip - and the others the general kernel
+    LensClass cls;
+    // packed from tables and layout (refresh_ring_locations)
+    DevBuf ring_rec, ring_coll;              // 4 doubles per ring; dense collection number per ring
+    DevBuf ring_tab, ring_ok, ring_ok_off;   // fast-kernel per-ring tables (offsets into ring_tab: ring_rec)
+    DevBuf center_qmajor;                    // fast-kernel centre table [order][n0][n1][4][K]
+    CentreSlots centre;                      // (pack_centre_table)
+    CollDesc h_coll[MAX_RING_COLLS] = {};
+    double ring_bounds_all[4] = {0, 0, 0, 0};   // intersection of the ring tables' (ux', uy') bounds (NfArgs)
+
+    // layout
+    bool have_layout = false;
+    int n_rings = 0, n_cells = 0;
+    std::vector<double> h_ring_period, h_ring_lateral, h_ring_rc;
+    std::vector<int32_t> h_ring_gc, h_ring_coll;   // slot and dense collection number per ring (dense_collections)
+    int n_colls = 0;
+    int32_t coll_slot[MAX_RING_COLLS] = {0};       // dense collection number -> slot
+    DevBuf ring_boundaries, ring_r_center, ring_period, ring_dphi, ring_lateral, ring_gc;
+    DevBuf rot_table, tie_table, ring_rot_center, ring_rot_half;
+    DevBuf ring_lut;       // uniform-in-r bucket -> first candidate boundary
+    DevBuf ring_lutrec;    // fast kernel: coarser buckets that carry the boundaries
+    RingSearchFacts search;
+    DevBuf cell_x, cell_y, cell_xy, cell_which, cell_index, bin_start;
+    BinFacts bins;
+    std::vector<int32_t> h_slot_of_cell;   // original cell index -> bin-sorted slot
+    // nearest-cell lattice shortcut (fit_lattice): cells = nodes c0 + a b1 + b b2
+    LatticeFacts lattice;
+    DevBuf cell_lattice_map, cell_lattice_rec;
+};
+
+// The grid a synthesis runs on and what is derived from grid and lens alone; synth_caches.h says when each is rebuilt.
+struct SynthGrid {
+    DevBuf x_pts, y_pts;
+    std::vector<double> h_x_pts, h_y_pts;   // what x_pts / y_pts hold (re-uploaded only on change)
+    DevBuf row_first;                       // see row_extent_kernel
+    int trim_rows[2] = {0, 0};              // rows of the local aperture that meet the lens circle, [lo, hi) - farfield.hip
+    // per-sample geometry records and the four patch lists (nearfield_fast.hip; NfArgs::active_list)
+    DevBuf geo_ix, active_list, active_count, active_flag;
+    int n_active[4] = {0, 0, 0, 0};         // the lists' lengths, once SynthCaches::lengths == KNOWN
+};
+
+// exact nearest-cell ties (nearfield_dev.h settle_tie): samples the last synthesis could not settle, and the host's
+// answers for the current (grid, layout)
+struct Ties {
+    DevBuf count, list, ovr_key, ovr_slot;
+    int n_ovr = 0;
+};
+
+// resident field sets: complex [n_sets][4][nx][ny] (one set per member of a polarisation batch); the far-field and
+// download entry points work on set `field_set`
+struct FieldSets {
+    DevBuf buf;
+    int nx = 0, ny = 0, n_sets = 1, field_set = 0;
+    double *set_ptr() const { return reinterpret_cast<double *>(buf.p) + (size_t)field_set * 4 * nx * ny * 2; }
+    // ml_nearfield_premodulate: serial of the plan whose stage-1 input modulation the sets carry (-1: none)
+    long premod_serial = -1;
+};
+
+// what a synthesis leaves besides the fields
+struct SynthOut {
+    DevBuf partial_power, power, violations;
+    // bound-violation keys are double-buffered: the synthesis kernel that fills one half clears
+    // the other for the next launch (no separate memset per call)
+    int viol_half = 0;
+    bool viol_zeroed = false;
+    // the per-block power partials of the last synthesis have not been summed into `power` yet:
+    // the projection kernel does it in a spare block, ml_nearfield_result otherwise
+    bool power_pending = false;
+    int n_partials = 0;
+};
+
 }  // namespace ml
 
 struct ml_ctx {
@@ -318,106 +400,23 @@ struct ml_ctx {
     int cu_count = 0;
     int64_t hbm_bytes = 0;
 
-    // tables
-    ml::TableSlot slots[ml::MAX_SLOTS];
-    ml::TableSlot center;
-    ml::DevBuf table_desc;   // TableDesc[MAX_SLOTS + 1], last = centre
-    ml::TableDesc h_center_desc;   // the centre entry again: it travels in the kernel arguments
-    bool tables_dirty = true;
-    bool simple_orders = false;   // SOME table in use holds orders (ox, 0), |ox| <= 5 only: its samples take nearfield_simple.hip (lens_pack.h classify_lens)
-    // ... and the others the general kernel: bit c = dense ring collection c is general; the centre table likewise
-    int general_mask = 0, centre_general = 0, narrow_mask = 0;
-    int wide_mask = 0, narrow_exists = 0, narrow_slots_max = 1;   // simple order sets: NfArgs::wide_mask / narrow_exists; orders of the widest narrow collection
-    double ring_bounds_all[4] = {0, 0, 0, 0};   // intersection of the ring tables' (ux', uy') bounds (NfArgs)
-
-    // layout
-    bool have_layout = false;
-    int n_rings = 0, n_cells = 0;
-    std::vector<double> h_ring_period, h_ring_lateral, h_ring_rc;
-    std::vector<int32_t> h_ring_gc, h_ring_coll;   // slot and dense collection number per ring (lens_pack.h dense_collections)
-    ml::DevBuf ring_boundaries, ring_r_center, ring_period, ring_dphi, ring_lateral, ring_gc;
-    ml::DevBuf rot_table, tie_table, ring_rot_center, ring_rot_half;
-    ml::DevBuf ring_rec, ring_coll;                            // 4 doubles per ring (above); dense collection number per ring
-    int n_colls = 0;
-    int32_t coll_slot[ml::MAX_RING_COLLS] = {0};               // dense collection number -> slot
-    ml::CollDesc h_coll[ml::MAX_RING_COLLS] = {};
-    std::vector<ml::TableDesc> h_table_desc;                   // host copy of table_desc
-    ml::DevBuf ring_tab, ring_ok, ring_ok_off;   // fast-kernel per-ring tables (offsets into ring_tab: ring_rec)
-    ml::DevBuf center_qmajor;                                  // fast-kernel centre table [order][n0][n1][4][K]
-    int center_n_slots = 0, center_lo = 0, center_present_mask = 0;                     // simple order sets: as CollDesc::n_slots / ox_lo (lens_pack.h pack_centre_table)
-    ml::DevBuf ring_lut;             // uniform-in-r bucket -> first candidate boundary
-    ml::DevBuf ring_lutrec;          // fast kernel: coarser buckets that carry the boundaries
-    int lutrec_buckets = 0;
-    double lutrec_inv_h = 0, r_outer = 0, r_centre = 0;   // (r_centre: inner boundary of ring 0 = radius of the centre disc)
-    int lut_buckets = 0;
-    double lut_inv_h = 0;
-    ml::DevBuf cell_x, cell_y, cell_xy, cell_which, cell_index, bin_start;
-    int bins_x = 0, bins_y = 0;
-    double bin_x0 = 0, bin_y0 = 0, bin_h = 0;
-
-    // resident field sets: complex [n_sets][4][nx][ny] (one set per member of a polarisation
-    // batch); the far-field and download entry points work on set `field_set`
-    int nx = 0, ny = 0, n_sets = 1, field_set = 0;
-    ml::DevBuf fields;
-    double *set_ptr() const {
-        return reinterpret_cast<double *>(fields.p) + (size_t)field_set * 4 * nx * ny * 2;
-    }
-    // far-field sums kept on the GPU across the sources of a sweep (farfield.hip, ml_farfield_accumulate)
-    ml::DevBuf acc_P, acc_partials, acc_sums;
-    int acc_blocks = 0;
-    ml::DevBuf lattice_in;   // staging for ml_farfield_lattice_power
-
-    // near-field scratch
-    // nearest-cell lattice shortcut (lens_pack.h fit_lattice): cells = nodes c0 + a b1 + b b2
-    bool lat_ok = false;
-    double lat_c0x = 0, lat_c0y = 0, lat_inv[4] = {0, 0, 0, 0}, lat_accept_r2 = 0;
-    double lat_g[3] = {0, 0, 0}, lat_guard = 0;
-    int lat_amin = 0, lat_bmin = 0, lat_na = 0, lat_nb = 0;
-    ml::DevBuf cell_lattice_map, cell_lattice_rec;
-    // exact nearest-cell ties (nearfield_dev.h settle_tie): samples the last synthesis could not
-    // settle, and the host's answers for the current (grid, layout)
-    ml::DevBuf tie_count, tie_list, ovr_key, ovr_slot;
-    int n_ovr = 0;
-    long ovr_serial = 0;                    // bumped whenever the override list changes
-    // per-sample geometry records (nearfield_fast.hip) and what they were built for:
-    // (grid_serial, layout_serial, ovr_serial, samples)
-    ml::DevBuf geo_ix, active_list, active_count, active_flag;
-    long geo_key[5] = {-1, -1, -1, -1, -1};
-    int n_active[4] = {-1, 0, 0, 0};   // entries of the four patch lists (NfArgs::active_list); [0] = -1: not read back yet
-    // the lists' lengths on their way back (page-locked; queued right behind the scans that make them, so that the
-    // second synthesis on a geometry finds them there instead of draining the stream for four integers)
+    ml::Lens lens;
+    ml::SynthGrid grid;
+    ml::Ties ties;
+    ml::FieldSets fields;
+    ml::SynthOut out;
+    ml::SynthCaches caches;
+    // the patch lists' lengths on their way back (page-locked; queued right behind the scans that make them, so that
+    // the second synthesis on a geometry finds them there instead of draining the stream for four integers)
     int *counts_pinned = nullptr;
     hipEvent_t counts_ready = nullptr;
-    bool counts_queued = false;
-    long ovr_for[2] = {-1, -1};             // (grid_serial, layout_serial) the overrides belong to
-    std::vector<int32_t> h_slot_of_cell;   // original cell index -> bin-sorted slot
+
+    // far-field sums kept on the GPU across the sources of a sweep (farfield.hip, ml_farfield_accumulate)
+    ml::DevBuf acc_P, acc_partials, acc_sums;
+    ml::DevBuf lattice_in;   // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only
-    // ml_nearfield_premodulate: the synthesis applies the active plan's stage-1 input modulation;
-    // fields_premod_serial = serial of the plan whose modulation the resident fields carry (-1: none)
-    bool premod_enabled = false;
-    long fields_premod_serial = -1;
-    // what the zeros outside the lens in `fields` were written for: (buffer, bytes, sets, nx * ny,
-    // grid_serial, layout_serial); a synthesis with the same key does not store them again
-    long zero_key[6] = {0, -1, -1, -1, -1, -1};
-    ml::DevBuf x_pts, y_pts, partial_power, power, violations;
-    std::vector<double> h_x_pts, h_y_pts;   // what x_pts / y_pts hold (re-uploaded only on change)
-    ml::DevBuf row_first;          // see row_extent_kernel; valid only for synthesised fields
-    bool row_first_valid = false;
-    // rows of the local aperture that meet the lens circle, [trim_rows[0], trim_rows[1]) - farfield.hip; key: (grid, layout)
-    long trim_key[2] = {-1, -1};
-    int trim_rows[2] = {0, 0};
-    // row_first depends on the grid and the lens radius only: recomputed when either changes
-    long grid_serial = 0, layout_serial = 0, row_first_key[2] = {-1, -1};
-    // bound-violation keys are double-buffered: the synthesis kernel that fills one half clears
-    // the other for the next launch (no separate memset per call)
-    int viol_half = 0;
-    bool viol_zeroed = false;
-    // the per-block power partials of the last synthesis have not been summed into `power` yet:
-    // the projection kernel does it in a spare block, ml_nearfield_result otherwise
-    bool power_pending = false;
-    int n_partials = 0;
-    int nf_blocks = 0;
+    bool premod_enabled = false;   // ml_nearfield_premodulate: the synthesis applies the active plan's stage-1 input modulation
 
     ml::FarfieldPlan plan;
     ml::PropagatePlan prop;

@@ -77,11 +77,12 @@ static int fail_synced(ml_ctx *ctx, const PackError &e) {
 }
 
 static int refresh_table_desc(ml_ctx *ctx) {
-    if (!ctx->tables_dirty) return ML_OK;
+    Lens &lens = ctx->lens;
+    if (!lens.tables_dirty) return ML_OK;
     std::vector<TableDesc> h(MAX_SLOTS + 1);
     memset(h.data(), 0, h.size() * sizeof(TableDesc));
     for (int s = 0; s <= MAX_SLOTS; ++s) {
-        const TableSlot &t = (s == MAX_SLOTS) ? ctx->center : ctx->slots[s];
+        const TableSlot &t = (s == MAX_SLOTS) ? lens.center : lens.slots[s];
         if (!t.present) continue;
         TableDesc &d = h[s];
         d = describe_table(t, s == MAX_SLOTS);
@@ -90,64 +91,51 @@ static int refresh_table_desc(ml_ctx *ctx) {
         d.values = t.values.as<double>();
         d.order_k = t.order_k.as<double>();
     }
-    ML_TRY(h2d(ctx, ctx->table_desc, h.data(), h.size() * sizeof(TableDesc)));
-    ctx->h_center_desc = h[MAX_SLOTS];
-    ctx->h_table_desc = h;
+    ML_TRY(h2d(ctx, lens.table_desc, h.data(), h.size() * sizeof(TableDesc)));
+    lens.h_center_desc = h[MAX_SLOTS];
+    lens.h_table_desc = h;
     ML_HIP(hipStreamSynchronize(ctx->stream));   // h goes out of scope
-    ctx->tables_dirty = false;
+    lens.tables_dirty = false;
     return ML_OK;
 }
 
 // The per-ring tables, records and collection descriptors and the centre table in the fast kernels' form
 // (lens_pack.h locate_rings, classify_lens, pack_ring_tables, pack_centre_table).
 static int refresh_ring_locations(ml_ctx *ctx) {
+    Lens &lens = ctx->lens;
     const HostTable *slots[MAX_SLOTS], *colls[MAX_RING_COLLS];
     const TableDesc *desc[MAX_RING_COLLS];
-    for (int s = 0; s < MAX_SLOTS; ++s) slots[s] = &ctx->slots[s];
-    const RingLocations at = locate_rings(slots, ctx->h_ring_gc.data(), ctx->h_ring_period.data(), ctx->n_rings);
+    for (int s = 0; s < MAX_SLOTS; ++s) slots[s] = &lens.slots[s];
+    const RingLocations at = locate_rings(slots, lens.h_ring_gc.data(), lens.h_ring_period.data(), lens.n_rings);
     if (at.err.code != ML_OK) return fail(at.err);
-    for (int c = 0; c < ctx->n_colls; ++c) {
-        colls[c] = slots[ctx->coll_slot[c]];
-        desc[c] = &ctx->h_table_desc[ctx->coll_slot[c]];
+    for (int c = 0; c < lens.n_colls; ++c) {
+        colls[c] = slots[lens.coll_slot[c]];
+        desc[c] = &lens.h_table_desc[lens.coll_slot[c]];
     }
     // (diagnostic build only: ML_FORCE_GENERAL=1 sends a lens that qualifies through the general kernels - what
     // the order-list kernels are measured against; ML_FORCE_GENERAL_COLL = mask of dense collection
     // numbers, bit 16 = the centre table: those only)
     static const bool force_general = diag_int("ML_FORCE_GENERAL", 0) != 0;
     static const int force_general_coll = diag_int("ML_FORCE_GENERAL_COLL", 0);
-    const LensClass K = classify_lens(colls, ctx->n_colls, &ctx->center, force_general, force_general_coll);
-    if (K.simple != ctx->simple_orders || K.general_mask != ctx->general_mask ||
-        (K.simple && K.centre_general != ctx->centre_general)) {
-        // which patch lists exist and what a synthesis leaves behind depend on who takes which samples
-        ctx->geo_key[0] = -1;
-        ctx->n_active[0] = -1;
-        ctx->zero_key[1] = -1;
-    }
-    ctx->simple_orders = K.simple;
-    ctx->general_mask = K.general_mask;
-    ctx->centre_general = K.centre_general;
-    ctx->wide_mask = K.wide_mask;
-    ctx->narrow_exists = K.narrow_exists;
-    ctx->narrow_mask = K.narrow_mask;
-    ctx->narrow_slots_max = K.narrow_slots_max;
-    const RingInputs rings = {ctx->n_rings, ctx->h_ring_coll.data(), ctx->h_ring_period.data(), ctx->h_ring_lateral.data(),
-                              ctx->h_ring_rc.data()};
-    const RingTables T = pack_ring_tables(colls, desc, ctx->coll_slot, ctx->n_colls, K, rings, at);
+    const LensClass K = classify_lens(colls, lens.n_colls, &lens.center, force_general, force_general_coll);
+    if (K.lists_differ(lens.cls)) ctx->caches.lens_class_changed();
+    lens.cls = K;
+    const RingInputs rings = {lens.n_rings, lens.h_ring_coll.data(), lens.h_ring_period.data(), lens.h_ring_lateral.data(),
+                              lens.h_ring_rc.data()};
+    const RingTables T = pack_ring_tables(colls, desc, lens.coll_slot, lens.n_colls, K, rings, at);
     if (T.err.code != ML_OK) return fail(T.err);
-    for (int c = 0; c < ctx->n_colls; ++c) ctx->h_coll[c] = T.coll[c];
-    for (int k = 0; k < 4; ++k) ctx->ring_bounds_all[k] = T.ring_bounds_all[k];
-    ML_TRY(h2d(ctx, ctx->ring_rec, T.rec.data(), T.rec.size() * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_tab, T.tab.data(), T.tab.size() * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_ok, T.ok.data(), T.ok.size() * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_ok_off, T.ok_off.data(), T.ok_off.size() * sizeof(int32_t)));
+    for (int c = 0; c < lens.n_colls; ++c) lens.h_coll[c] = T.coll[c];
+    for (int k = 0; k < 4; ++k) lens.ring_bounds_all[k] = T.ring_bounds_all[k];
+    ML_TRY(h2d(ctx, lens.ring_rec, T.rec.data(), T.rec.size() * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_tab, T.tab.data(), T.tab.size() * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_ok, T.ok.data(), T.ok.size() * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_ok_off, T.ok_off.data(), T.ok_off.size() * sizeof(int32_t)));
     CentreTable C;
-    if (ctx->center.present) {
-        C = pack_centre_table(ctx->center, K.centre_simple, K.canon_center);
-        ML_TRY(h2d(ctx, ctx->center_qmajor, C.cq.data(), C.cq.size() * sizeof(double)));
+    if (lens.center.present) {
+        C = pack_centre_table(lens.center, K.centre_simple, K.canon_center);
+        ML_TRY(h2d(ctx, lens.center_qmajor, C.cq.data(), C.cq.size() * sizeof(double)));
     }
-    ctx->center_n_slots = C.n_slots;
-    ctx->center_lo = C.lo;
-    ctx->center_present_mask = C.present;
+    lens.centre = C.slots;
     ML_HIP(hipStreamSynchronize(ctx->stream));   // T and C go out of scope
     return ML_OK;
 }
@@ -275,7 +263,7 @@ int ml_upload_table(ml_ctx *ctx, int slot, const double *axis0, int n0, const do
                n_orders, MAX_ORDERS);
     ML_REQUIRE(slot >= 0 || center_periods, "the centre table needs center_periods");
     ML_HIP(hipSetDevice(ctx->device));
-    TableSlot &t = (slot < 0) ? ctx->center : ctx->slots[slot];
+    TableSlot &t = (slot < 0) ? ctx->lens.center : ctx->lens.slots[slot];
     ML_TRY(h2d(ctx, t.axis0, axis0, n0 * sizeof(double)));
     ML_TRY(h2d(ctx, t.axis1, axis1, n1 * sizeof(double)));
     ML_TRY(h2d(ctx, t.order_k, order_k, 2 * n_orders * sizeof(double)));
@@ -296,7 +284,7 @@ int ml_upload_table(ml_ctx *ctx, int slot, const double *axis0, int n0, const do
         t.center_periods[1] = center_periods[1];
     }
     t.present = true;
-    ctx->tables_dirty = true;
+    ctx->lens.tables_dirty = true;
     return ML_OK;
 }
 
@@ -321,83 +309,65 @@ int ml_upload_layout(ml_ctx *ctx, int n_rings, const double *B, const double *r_
     for (int r = 0; r < n_rings; ++r)
         ML_REQUIRE(B[r] <= B[r + 1], "ring boundaries must be ascending (ring %d)", r);
     ML_HIP(hipSetDevice(ctx->device));
-    ctx->have_layout = false;
-    ctx->n_rings = n_rings;
-    ML_TRY(h2d(ctx, ctx->ring_boundaries, B, (n_rings + 1) * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_r_center, r_center, n_rings * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_period, period, n_rings * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_dphi, dphi, n_rings * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_lateral, lateral, n_rings * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_gc, ring_gc, n_rings * sizeof(int32_t)));
-    ML_TRY(h2d(ctx, ctx->rot_table, rot_table, (size_t)rot_len * 2 * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->tie_table, tie_table, (size_t)rot_len * 6 * sizeof(double)));
-    ML_TRY(h2d(ctx, ctx->ring_rot_center, ring_rot_center, n_rings * sizeof(int32_t)));
-    ML_TRY(h2d(ctx, ctx->ring_rot_half, ring_rot_half, n_rings * sizeof(int32_t)));
-    ctx->h_ring_period.assign(period, period + n_rings);
-    ctx->h_ring_rc.assign(r_center, r_center + n_rings);
-    ctx->h_ring_lateral.assign(lateral, lateral + n_rings);
-    ctx->h_ring_gc.assign(ring_gc, ring_gc + n_rings);
+    Lens &lens = ctx->lens;
+    lens.have_layout = false;
+    lens.n_rings = n_rings;
+    ML_TRY(h2d(ctx, lens.ring_boundaries, B, (n_rings + 1) * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_r_center, r_center, n_rings * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_period, period, n_rings * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_dphi, dphi, n_rings * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_lateral, lateral, n_rings * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_gc, ring_gc, n_rings * sizeof(int32_t)));
+    ML_TRY(h2d(ctx, lens.rot_table, rot_table, (size_t)rot_len * 2 * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.tie_table, tie_table, (size_t)rot_len * 6 * sizeof(double)));
+    ML_TRY(h2d(ctx, lens.ring_rot_center, ring_rot_center, n_rings * sizeof(int32_t)));
+    ML_TRY(h2d(ctx, lens.ring_rot_half, ring_rot_half, n_rings * sizeof(int32_t)));
+    lens.h_ring_period.assign(period, period + n_rings);
+    lens.h_ring_rc.assign(r_center, r_center + n_rings);
+    lens.h_ring_lateral.assign(lateral, lateral + n_rings);
+    lens.h_ring_gc.assign(ring_gc, ring_gc + n_rings);
     const DenseColls D = dense_collections(ring_gc, n_rings);
     if (D.err.code != ML_OK) return fail_synced(ctx, D.err);
-    ctx->n_colls = D.n_colls;
-    for (int c = 0; c < D.n_colls; ++c) ctx->coll_slot[c] = D.coll_slot[c];
-    ctx->h_ring_coll = D.ring_coll;
-    ML_TRY(h2d(ctx, ctx->ring_coll, D.ring_coll.data(), n_rings * sizeof(int32_t)));
+    lens.n_colls = D.n_colls;
+    for (int c = 0; c < D.n_colls; ++c) lens.coll_slot[c] = D.coll_slot[c];
+    lens.h_ring_coll = D.ring_coll;
+    ML_TRY(h2d(ctx, lens.ring_coll, D.ring_coll.data(), n_rings * sizeof(int32_t)));
 
     const RingSearch S = pack_ring_search(B, n_rings);
     if (S.err.code != ML_OK) return fail_synced(ctx, S.err);
-    ML_TRY(h2d(ctx, ctx->ring_lut, S.lut.data(), S.lut.size() * sizeof(int32_t)));
-    ctx->lut_buckets = S.lut_buckets;
-    ctx->lut_inv_h = S.lut_inv_h;
-    ML_TRY(h2d(ctx, ctx->ring_lutrec, S.rec.data(), S.rec.size() * sizeof(RingBucket)));
-    ctx->lutrec_buckets = S.lutrec_buckets;
-    ctx->lutrec_inv_h = S.lutrec_inv_h;
-    ctx->r_outer = S.r_outer;
-    ctx->r_centre = S.r_centre;
+    ML_TRY(h2d(ctx, lens.ring_lut, S.lut.data(), S.lut.size() * sizeof(int32_t)));
+    ML_TRY(h2d(ctx, lens.ring_lutrec, S.rec.data(), S.rec.size() * sizeof(RingBucket)));
+    lens.search = S.facts;
 
-    ctx->n_cells = n_cells;
-    ctx->lat_ok = false;
+    lens.n_cells = n_cells;
+    lens.lattice = LatticeFacts();
     if (n_cells > 0) {
         const CellBins C = bin_cells(cells, n_cells);
         if (C.err.code != ML_OK) return fail_synced(ctx, C.err);
-        ML_TRY(h2d(ctx, ctx->cell_x, C.sx.data(), n_cells * sizeof(double)));
-        ML_TRY(h2d(ctx, ctx->cell_y, C.sy.data(), n_cells * sizeof(double)));
-        ML_TRY(h2d(ctx, ctx->cell_xy, C.sxy.data(), C.sxy.size() * sizeof(double)));
-        ML_TRY(h2d(ctx, ctx->cell_which, C.sw.data(), n_cells * sizeof(int32_t)));
-        ML_TRY(h2d(ctx, ctx->cell_index, C.si.data(), n_cells * sizeof(int32_t)));
-        ctx->h_slot_of_cell = C.slot_of_cell;
-        ML_TRY(h2d(ctx, ctx->bin_start, C.start.data(), C.start.size() * sizeof(int32_t)));
+        ML_TRY(h2d(ctx, lens.cell_x, C.sx.data(), n_cells * sizeof(double)));
+        ML_TRY(h2d(ctx, lens.cell_y, C.sy.data(), n_cells * sizeof(double)));
+        ML_TRY(h2d(ctx, lens.cell_xy, C.sxy.data(), C.sxy.size() * sizeof(double)));
+        ML_TRY(h2d(ctx, lens.cell_which, C.sw.data(), n_cells * sizeof(int32_t)));
+        ML_TRY(h2d(ctx, lens.cell_index, C.si.data(), n_cells * sizeof(int32_t)));
+        lens.h_slot_of_cell = C.slot_of_cell;
+        ML_TRY(h2d(ctx, lens.bin_start, C.start.data(), C.start.size() * sizeof(int32_t)));
         // lattice shortcut for the nearest-cell search (sorted slots index the arrays above)
         static const bool no_lattice = diag_int("ML_NO_CELL_LATTICE", 0) != 0;
         const LatticeFit L = no_lattice ? LatticeFit() : fit_lattice(C.sx, C.sy);
         std::vector<CellRec> rec;
-        ctx->lat_ok = L.ok;
-        if (L.ok) {
-            ML_TRY(h2d(ctx, ctx->cell_lattice_map, L.map.data(), L.map.size() * sizeof(int32_t)));
+        if (L.facts.ok) {
+            ML_TRY(h2d(ctx, lens.cell_lattice_map, L.map.data(), L.map.size() * sizeof(int32_t)));
             rec = lattice_records(L, C);
-            ML_TRY(h2d(ctx, ctx->cell_lattice_rec, rec.data(), rec.size() * sizeof(CellRec)));
-            ctx->lat_c0x = L.c0x;
-            ctx->lat_c0y = L.c0y;
-            for (int k = 0; k < 4; ++k) ctx->lat_inv[k] = L.inv[k];
-            ctx->lat_amin = L.amin;
-            ctx->lat_bmin = L.bmin;
-            ctx->lat_na = L.na;
-            ctx->lat_nb = L.nb;
-            ctx->lat_accept_r2 = L.accept_r2;
-            for (int k = 0; k < 3; ++k) ctx->lat_g[k] = L.g[k];
-            ctx->lat_guard = L.guard;
+            ML_TRY(h2d(ctx, lens.cell_lattice_rec, rec.data(), rec.size() * sizeof(CellRec)));
+            lens.lattice = L.facts;
         }
         ML_HIP(hipStreamSynchronize(ctx->stream));   // C, L and rec go out of scope
-        ctx->bins_x = C.bins_x;
-        ctx->bins_y = C.bins_y;
-        ctx->bin_x0 = C.x0;
-        ctx->bin_y0 = C.y0;
-        ctx->bin_h = C.h;
+        lens.bins = C.facts;
     }
     ML_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->have_layout = true;
-    ++ctx->layout_serial;
-    ctx->tables_dirty = true;   // per-ring table locations depend on the ring periods
+    lens.have_layout = true;
+    ctx->caches.layout_changed();
+    lens.tables_dirty = true;   // per-ring table locations depend on the ring periods
     return ML_OK;
 }
 
@@ -411,16 +381,16 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
                        p[m].Z0 == p[0].Z0 && p[m].plane_wave == p[0].plane_wave,
                    "members of a batch share wavelength, substrate and source kind (member %d): they may differ "
                    "in position, polarisation and dipole moment", m);
-    if (!ctx->have_layout) {
+    if (!ctx->lens.have_layout) {
         set_error("ml_upload_layout has not been called");
         return ML_ESTATE;
     }
     ML_HIP(hipSetDevice(ctx->device));
-    if (ctx->n_cells > 0 && !ctx->center.present) {
+    if (ctx->lens.n_cells > 0 && !ctx->lens.center.present) {
         set_error("centre cells present but no HexGridSet table uploaded (slot -1)");
         return ML_ESTATE;
     }
-    if (ctx->tables_dirty) {
+    if (ctx->lens.tables_dirty) {
         ML_TRY(refresh_table_desc(ctx));
         ML_TRY(refresh_ring_locations(ctx));
     }
@@ -430,44 +400,41 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
             return ML_OK;
         ML_HIP(hipStreamSynchronize(ctx->stream));   // an earlier async copy may still read `host`
         host.assign(src, src + n);
-        ++ctx->grid_serial;
+        ctx->caches.grid_changed();
         return h2d(ctx, dev, host.data(), n * sizeof(double));
     };
-    ML_TRY(grid_axis(ctx->x_pts, ctx->h_x_pts, x_pts, nx));
-    ML_TRY(grid_axis(ctx->y_pts, ctx->h_y_pts, y_pts, ny));
+    ML_TRY(grid_axis(ctx->grid.x_pts, ctx->grid.h_x_pts, x_pts, nx));
+    ML_TRY(grid_axis(ctx->grid.y_pts, ctx->grid.h_y_pts, y_pts, ny));
     const size_t plane = (size_t)nx * ny;
-    ML_TRY(ctx->fields.reserve((size_t)n * 4 * plane * 2 * sizeof(double)));
-    ctx->nx = nx;
-    ctx->ny = ny;
-    ctx->n_sets = n;
-    ctx->field_set = 0;
+    ML_TRY(ctx->fields.buf.reserve((size_t)n * 4 * plane * 2 * sizeof(double)));
+    ctx->fields.nx = nx;
+    ctx->fields.ny = ny;
+    ctx->fields.n_sets = n;
+    ctx->fields.field_set = 0;
     // four power partials per wave (8 x 8 samples: one per row of sixteen lanes, nearfield_dev.h wave_power)
     const int blocks = ((ny + 7) / 8) * ((nx + 7) / 8);
-    ML_TRY(ctx->partial_power.reserve((size_t)n * blocks * 4 * sizeof(double)));
-    ML_TRY(ctx->power.reserve((size_t)n * POWER_GROUPS * sizeof(double)));
+    ML_TRY(ctx->out.partial_power.reserve((size_t)n * blocks * 4 * sizeof(double)));
+    ML_TRY(ctx->out.power.reserve((size_t)n * POWER_GROUPS * sizeof(double)));
     // two halves: each synthesis launch clears the one the next launch reports into
     const size_t viol_bytes = (size_t)2 * (MAX_SLOTS + 1) * MAX_ORDERS * 6 * sizeof(unsigned long long);
-    ML_TRY(ctx->violations.reserve(viol_bytes));
-    if (!ctx->viol_zeroed) {
-        ML_HIP(hipMemsetAsync(ctx->violations.p, 0, viol_bytes, ctx->stream));
-        ctx->viol_zeroed = true;
+    ML_TRY(ctx->out.violations.reserve(viol_bytes));
+    if (!ctx->out.viol_zeroed) {
+        ML_HIP(hipMemsetAsync(ctx->out.violations.p, 0, viol_bytes, ctx->stream));
+        ctx->out.viol_zeroed = true;
     }
-    ML_TRY(ctx->row_first.reserve((size_t)nx * sizeof(int)));
-    ctx->row_first_valid = true;
+    ML_TRY(ctx->grid.row_first.reserve((size_t)nx * sizeof(int)));
+    ctx->caches.rows_describe_fields = true;
     // nearest-cell ties: answers for another geometry are dropped
-    if (!ctx->tie_count.p) {
-        ML_TRY(ctx->tie_count.reserve(2 * sizeof(int)));
-        ML_HIP(hipMemsetAsync(ctx->tie_count.p, 0, 2 * sizeof(int), ctx->stream));
+    if (!ctx->ties.count.p) {
+        ML_TRY(ctx->ties.count.reserve(2 * sizeof(int)));
+        ML_HIP(hipMemsetAsync(ctx->ties.count.p, 0, 2 * sizeof(int), ctx->stream));
     }
-    ML_TRY(ctx->tie_list.reserve((size_t)ML_TIE_CAPACITY * sizeof(long long)));
-    if (ctx->n_ovr && (ctx->ovr_for[0] != ctx->grid_serial || ctx->ovr_for[1] != ctx->layout_serial)) {
-        ctx->n_ovr = 0;
-        ++ctx->ovr_serial;
-    }
-    ML_TRY(ctx->geo_ix.reserve((size_t)blocks * 64 * 2 * sizeof(int)));   // patch-major, 64 per patch
-    ML_TRY(ctx->active_list.reserve((size_t)4 * blocks * 2 * sizeof(int)));           // four lists (NfArgs::active_list)
-    ML_TRY(ctx->active_count.reserve((size_t)4 * (blocks / 1024 + 4) * sizeof(int)));   // each: total + one per chunk of 1024 patches
-    ML_TRY(ctx->active_flag.reserve((size_t)blocks * sizeof(int)));
+    ML_TRY(ctx->ties.list.reserve((size_t)ML_TIE_CAPACITY * sizeof(long long)));
+    if (ctx->caches.drop_foreign_answers()) ctx->ties.n_ovr = 0;
+    ML_TRY(ctx->grid.geo_ix.reserve((size_t)blocks * 64 * 2 * sizeof(int)));   // patch-major, 64 per patch
+    ML_TRY(ctx->grid.active_list.reserve((size_t)4 * blocks * 2 * sizeof(int)));           // four lists (NfArgs::active_list)
+    ML_TRY(ctx->grid.active_count.reserve((size_t)4 * (blocks / 1024 + 4) * sizeof(int)));   // each: total + one per chunk of 1024 patches
+    ML_TRY(ctx->grid.active_flag.reserve((size_t)blocks * sizeof(int)));
     return nearfield_launch(ctx, p, n, nx, ny, members_alone, keep_powers);
 }
 
@@ -484,7 +451,7 @@ int ml_nearfield_batch_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
 int ml_nearfield_members_async(ml_ctx *ctx, const ml_nearfield_params *p, int n, const double *x_pts, int nx,
                                const double *y_pts, int ny, int keep_powers) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    if (keep_powers && !(ctx->power.p && ctx->nx == nx && ctx->ny == ny && ctx->n_sets == n)) {
+    if (keep_powers && !(ctx->out.power.p && ctx->fields.nx == nx && ctx->fields.ny == ny && ctx->fields.n_sets == n)) {
         set_error("ml_nearfield_members_async: keep_powers needs a synthesis of %d members on %d x %d samples before it", n,
                   nx, ny);
         return ML_ESTATE;
@@ -494,20 +461,20 @@ int ml_nearfield_members_async(ml_ctx *ctx, const ml_nearfield_params *p, int n,
 
 int ml_fields_select(ml_ctx *ctx, int set) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    ML_REQUIRE(set >= 0 && set < ctx->n_sets, "field set %d out of range (%d resident)", set,
-               ctx->n_sets);
-    ctx->field_set = set;
+    ML_REQUIRE(set >= 0 && set < ctx->fields.n_sets, "field set %d out of range (%d resident)", set,
+               ctx->fields.n_sets);
+    ctx->fields.field_set = set;
     return ML_OK;
 }
 
 int ml_nearfield_powers(ml_ctx *ctx, double *power, int n) {
     ML_REQUIRE(ctx && power, "NULL argument");
-    ML_REQUIRE(n >= 1 && n <= ctx->n_sets, "%d powers asked for, %d field sets resident", n, ctx->n_sets);
-    ML_REQUIRE(ctx->power.p, "no near field has been synthesised");
+    ML_REQUIRE(n >= 1 && n <= ctx->fields.n_sets, "%d powers asked for, %d field sets resident", n, ctx->fields.n_sets);
+    ML_REQUIRE(ctx->out.power.p, "no near field has been synthesised");
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(power_flush(ctx));
     std::vector<double> groups((size_t)n * POWER_GROUPS);
-    ML_HIP(hipMemcpyAsync(groups.data(), ctx->power.p, groups.size() * sizeof(double),
+    ML_HIP(hipMemcpyAsync(groups.data(), ctx->out.power.p, groups.size() * sizeof(double),
                           hipMemcpyDeviceToHost, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
     for (int m = 0; m < n; ++m) {
@@ -528,20 +495,20 @@ static double decode_key(unsigned long long k, int check) {
 
 int ml_nearfield_ties(ml_ctx *ctx, int64_t *sample_ids, int max_ids, int *n_ties) {
     ML_REQUIRE(ctx && n_ties, "NULL argument");
-    if (!ctx->tie_count.p) {   // nothing synthesised yet: nothing pending
+    if (!ctx->ties.count.p) {   // nothing synthesised yet: nothing pending
         *n_ties = 0;
         return ML_OK;
     }
     ML_HIP(hipSetDevice(ctx->device));
     int count = 0;
-    ML_HIP(hipMemcpyAsync(&count, ctx->tie_count.as<int>(), sizeof count,
+    ML_HIP(hipMemcpyAsync(&count, ctx->ties.count.as<int>(), sizeof count,
                           hipMemcpyDeviceToHost, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
     *n_ties = count;
     const int n = std::min(std::min(count, ML_TIE_CAPACITY), max_ids);
     if (sample_ids && n > 0) {
         static_assert(sizeof(long long) == sizeof(int64_t), "sample ids are 64-bit");
-        ML_HIP(hipMemcpy(sample_ids, ctx->tie_list.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        ML_HIP(hipMemcpy(sample_ids, ctx->ties.list.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     }
     return ML_OK;
 }
@@ -553,9 +520,9 @@ int ml_nearfield_tie_answers(ml_ctx *ctx, const int64_t *sample_ids, const int32
     ML_HIP(hipStreamSynchronize(ctx->stream));   // a running synthesis may be reading the old list
     std::vector<std::pair<long long, int>> kv((size_t)n);
     for (int k = 0; k < n; ++k) {
-        ML_REQUIRE(cell_index[k] >= 0 && (size_t)cell_index[k] < ctx->h_slot_of_cell.size(),
+        ML_REQUIRE(cell_index[k] >= 0 && (size_t)cell_index[k] < ctx->lens.h_slot_of_cell.size(),
                    "cell index %d out of range", cell_index[k]);
-        kv[k] = {(long long)sample_ids[k], ctx->h_slot_of_cell[cell_index[k]]};
+        kv[k] = {(long long)sample_ids[k], ctx->lens.h_slot_of_cell[cell_index[k]]};
     }
     std::sort(kv.begin(), kv.end());
     std::vector<long long> keys((size_t)n);
@@ -565,14 +532,12 @@ int ml_nearfield_tie_answers(ml_ctx *ctx, const int64_t *sample_ids, const int32
         slots[k] = kv[k].second;
     }
     if (n > 0) {
-        ML_TRY(h2d(ctx, ctx->ovr_key, keys.data(), keys.size() * sizeof(long long)));
-        ML_TRY(h2d(ctx, ctx->ovr_slot, slots.data(), slots.size() * sizeof(int32_t)));
+        ML_TRY(h2d(ctx, ctx->ties.ovr_key, keys.data(), keys.size() * sizeof(long long)));
+        ML_TRY(h2d(ctx, ctx->ties.ovr_slot, slots.data(), slots.size() * sizeof(int32_t)));
         ML_HIP(hipStreamSynchronize(ctx->stream));   // the staging vectors go out of scope
     }
-    ctx->n_ovr = n;
-    ++ctx->ovr_serial;
-    ctx->ovr_for[0] = ctx->grid_serial;
-    ctx->ovr_for[1] = ctx->layout_serial;
+    ctx->ties.n_ovr = n;
+    ctx->caches.answers_given(n);
     return ML_OK;
 }
 
@@ -583,12 +548,12 @@ int ml_nearfield_result(ml_ctx *ctx, double *power, ml_bound_violation *violatio
     const size_t n_keys = (size_t)(MAX_SLOTS + 1) * MAX_ORDERS * 6;
     std::vector<unsigned long long> keys(n_keys);
     double pw = 0, group_sums[POWER_GROUPS];
-    ML_REQUIRE(ctx->power.p && ctx->violations.p, "no near field has been synthesised");
+    ML_REQUIRE(ctx->out.power.p && ctx->out.violations.p, "no near field has been synthesised");
     ML_TRY(power_flush(ctx));
-    ML_HIP(hipMemcpyAsync(group_sums, ctx->power.p, sizeof group_sums, hipMemcpyDeviceToHost,
+    ML_HIP(hipMemcpyAsync(group_sums, ctx->out.power.p, sizeof group_sums, hipMemcpyDeviceToHost,
                           ctx->stream));
     ML_HIP(hipMemcpyAsync(keys.data(),
-                          ctx->violations.as<unsigned long long>() + (size_t)ctx->viol_half * n_keys,
+                          ctx->out.violations.as<unsigned long long>() + (size_t)ctx->out.viol_half * n_keys,
                           n_keys * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
     ML_TRY(prof_harvest(ctx));
@@ -598,7 +563,7 @@ int ml_nearfield_result(ml_ctx *ctx, double *power, ml_bound_violation *violatio
     // reference check order: collections in list order, then the centre; per order; ux<, ux>,
     // uy<, uy>, period<, period>
     for (int s = 0; s <= MAX_SLOTS; ++s) {
-        const TableSlot &t = (s == MAX_SLOTS) ? ctx->center : ctx->slots[s];
+        const TableSlot &t = (s == MAX_SLOTS) ? ctx->lens.center : ctx->lens.slots[s];
         if (!t.present) continue;
         for (int o = 0; o < t.n_orders; ++o)
             for (int c = 0; c < 6; ++c) {
@@ -622,15 +587,15 @@ int ml_nearfield_result(ml_ctx *ctx, double *power, ml_bound_violation *violatio
 
 int ml_nearfield_kernel_info(ml_ctx *ctx, int *family, int *ring_orders_max, int *centre_orders) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    if (ctx->tables_dirty || !ctx->have_layout) {
+    if (ctx->lens.tables_dirty || !ctx->lens.have_layout) {
         set_error("no near field has been synthesised from the current tables and layout");
         return ML_ESTATE;
     }
     int widest = 0;
-    for (int c = 0; c < ctx->n_colls; ++c) widest = std::max(widest, ctx->h_coll[c].n_slots);
-    if (family) *family = ctx->simple_orders ? ((ctx->general_mask || ctx->centre_general) ? 2 : 1) : 0;
-    if (ring_orders_max) *ring_orders_max = ctx->simple_orders ? widest : 0;
-    if (centre_orders) *centre_orders = ctx->simple_orders ? ctx->center_n_slots : 0;
+    for (int c = 0; c < ctx->lens.n_colls; ++c) widest = std::max(widest, ctx->lens.h_coll[c].n_slots);
+    if (family) *family = ctx->lens.cls.simple ? ((ctx->lens.cls.general_mask || ctx->lens.cls.centre_general) ? 2 : 1) : 0;
+    if (ring_orders_max) *ring_orders_max = ctx->lens.cls.simple ? widest : 0;
+    if (centre_orders) *centre_orders = ctx->lens.cls.simple ? ctx->lens.centre.n_slots : 0;
     return ML_OK;
 }
 
@@ -643,25 +608,25 @@ int ml_nearfield(ml_ctx *ctx, const ml_nearfield_params *p, const double *x_pts,
 
 int ml_fields_shape(ml_ctx *ctx, int *nx, int *ny) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    if (nx) *nx = ctx->nx;
-    if (ny) *ny = ctx->ny;
+    if (nx) *nx = ctx->fields.nx;
+    if (ny) *ny = ctx->fields.ny;
     return ML_OK;
 }
 
 int ml_fields_download(ml_ctx *ctx, double *Ex, double *Ey, double *Hx, double *Hy) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    if (ctx->nx == 0 || ctx->ny == 0) {
+    if (ctx->fields.nx == 0 || ctx->fields.ny == 0) {
         set_error("no resident field set");
         return ML_ESTATE;
     }
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(comm_join(ctx, false));
     ML_TRY(fields_unmodulate(ctx));   // the host always sees the plain near field
-    const size_t plane_bytes = (size_t)ctx->nx * ctx->ny * 2 * sizeof(double);
+    const size_t plane_bytes = (size_t)ctx->fields.nx * ctx->fields.ny * 2 * sizeof(double);
     double *dst[4] = {Ex, Ey, Hx, Hy};
     for (int f = 0; f < 4; ++f)
         if (dst[f])
-            ML_HIP(hipMemcpyAsync(dst[f], (char *)ctx->set_ptr() + f * plane_bytes, plane_bytes,
+            ML_HIP(hipMemcpyAsync(dst[f], (char *)ctx->fields.set_ptr() + f * plane_bytes, plane_bytes,
                                   hipMemcpyDeviceToHost, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
     return ML_OK;
@@ -673,19 +638,18 @@ int ml_fields_upload(ml_ctx *ctx, int nx, int ny, const double *Ex, const double
     ML_REQUIRE(nx >= 1 && ny >= 1, "empty grid (%d x %d)", nx, ny);
     ML_HIP(hipSetDevice(ctx->device));
     const size_t plane_bytes = (size_t)nx * ny * 2 * sizeof(double);
-    ML_TRY(ctx->fields.reserve(4 * plane_bytes));
+    ML_TRY(ctx->fields.buf.reserve(4 * plane_bytes));
     const double *src[4] = {Ex, Ey, Hx, Hy};
-    ctx->fields_premod_serial = -1;
+    ctx->fields.premod_serial = -1;
     for (int f = 0; f < 4; ++f)
-        ML_HIP(hipMemcpyAsync((char *)ctx->fields.p + f * plane_bytes, src[f], plane_bytes,
+        ML_HIP(hipMemcpyAsync((char *)ctx->fields.buf.p + f * plane_bytes, src[f], plane_bytes,
                               hipMemcpyHostToDevice, ctx->stream));
     ML_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->nx = nx;
-    ctx->ny = ny;
-    ctx->n_sets = 1;
-    ctx->field_set = 0;
-    ctx->zero_key[1] = -1;          // caller-supplied fields: nothing known about zeros
-    ctx->row_first_valid = false;
+    ctx->fields.nx = nx;
+    ctx->fields.ny = ny;
+    ctx->fields.n_sets = 1;
+    ctx->fields.field_set = 0;
+    ctx->caches.fields_overwritten();
     return ML_OK;
 }
 

@@ -555,17 +555,17 @@ static int plan_fft_axis(ml_ctx *ctx, ZfftAxis &ax, int n, double step, const do
 // result, so they can be queued ahead of it).  Returns the split-K factor through *want_split.
 static int stage2_tables(ml_ctx *ctx, int row0, int mirrored, int *want_split_out) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, mx = pl.mx, my = pl.my, S = pl.fold2_S, T = (nxl + 1) / 2;
+    const int nxl = ctx->fields.nx, mx = pl.mx, my = pl.my, S = pl.fold2_S, T = (nxl + 1) / 2;
     // few rows (4*my) and a long reduction: split the pairs over several workgroups per tile
     static const int forced_split2 = diag_int("ML_STAGE2_SPLIT", 0);
     const int want_split = forced_split2 > 0 ? forced_split2 : fold2_want_split(my, S);
     *want_split_out = want_split;
     const long key[4] = {pl.serial, row0, nxl, mirrored};
-    if (!plan_cache_disabled() && memcmp(key, pl.fold2_key, sizeof key) == 0) return ML_OK;
+    if (!plan_cache_disabled() && pl.fold2_for.matches(key)) return ML_OK;
     const int splits = zfold_splits(T, want_split);
     ML_TRY(pl.fold2_ot.reserve((size_t)splits * 4 * my * mx * 2 * sizeof(double)));
     ML_TRY(fold_tables(ctx, pl.fold_x, S, pl.ux, mx, pl.nx_total, pl.dxp, row0, nxl, mirrored));
-    memcpy(pl.fold2_key, key, sizeof key);
+    pl.fold2_for.set(key);
     return ML_OK;
 }
 
@@ -589,7 +589,7 @@ int flush_unfold(ml_ctx *ctx) {
 static int stage2_folded(ml_ctx *ctx, int row0, int mirrored, int accumulate, const double *alpha,
                          bool gt_direct, bool tables_ready, int want_split) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, mx = pl.mx, my = pl.my, S = pl.fold2_S, T = (nxl + 1) / 2;
+    const int nxl = ctx->fields.nx, mx = pl.mx, my = pl.my, S = pl.fold2_S, T = (nxl + 1) / 2;
     const size_t g_elems = (size_t)4 * nxl * my;
     if (!gt_direct) ML_TRY(pl.fold2_gt.reserve(g_elems * 2 * sizeof(double)));
     if (!tables_ready) ML_TRY(stage2_tables(ctx, row0, mirrored, &want_split));
@@ -650,18 +650,18 @@ static int project_launch(ml_ctx *ctx, const ProjArgs &a, int kernel_id, hipStre
 
 // called by ml_fields_download: give the host the plain fields
 int fields_unmodulate(ml_ctx *ctx) {
-    if (ctx->fields_premod_serial < 0) return ML_OK;
+    if (ctx->fields.premod_serial < 0) return ML_OK;
     FarfieldPlan &pl = ctx->plan;
-    if (ctx->fields_premod_serial != pl.serial) {
+    if (ctx->fields.premod_serial != pl.serial) {
         set_error("the resident fields carry the input modulation of an earlier far-field plan and "
                   "cannot be restored");
         return ML_ESTATE;
     }
-    const size_t n = (size_t)4 * ctx->n_sets * ctx->nx * ctx->ny;   // every resident set
+    const size_t n = (size_t)4 * ctx->fields.n_sets * ctx->fields.nx * ctx->fields.ny;   // every resident set
     hipLaunchKernelGGL(zunmodulate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       ctx->stream, ctx->fields.as<double2>(), pl.fold_y.E.as<double2>(), ctx->ny, n);
+                       ctx->stream, ctx->fields.buf.as<double2>(), pl.fold_y.E.as<double2>(), ctx->fields.ny, n);
     ML_HIP(hipGetLastError());
-    ctx->fields_premod_serial = -1;
+    ctx->fields.premod_serial = -1;
     return ML_OK;
 }
 
@@ -765,28 +765,28 @@ static int validate_shard(ml_ctx *ctx, const Shard &sh, int accumulate) {
         set_error("ml_farfield_plan has not been called");
         return ML_ESTATE;
     }
-    if (ctx->nx == 0) {
+    if (ctx->fields.nx == 0) {
         set_error("no resident field set");
         return ML_ESTATE;
     }
-    ML_REQUIRE(ctx->ny == pl.ny, "resident fields have ny=%d but the plan has ny=%d", ctx->ny,
+    ML_REQUIRE(ctx->fields.ny == pl.ny, "resident fields have ny=%d but the plan has ny=%d", ctx->fields.ny,
                pl.ny);
     if (sh.kind == ShardKind::interleaved) {
         ML_REQUIRE(sh.block >= 1 && sh.block == interleave_block(pl, sh.n_ranks),
                    "interleaved shard: block %d is not what ml_farfield_interleave_block gives for %d ranks "
                    "on this plan (%d)", sh.block, sh.n_ranks, interleave_block(pl, sh.n_ranks));
-        ML_REQUIRE(sh.rank >= 0 && sh.rank < sh.n_ranks && ctx->nx == pl.nx_total / sh.n_ranks,
+        ML_REQUIRE(sh.rank >= 0 && sh.rank < sh.n_ranks && ctx->fields.nx == pl.nx_total / sh.n_ranks,
                    "interleaved shard: rank %d of %d with %d resident rows of %d", sh.rank, sh.n_ranks,
-                   ctx->nx, pl.nx_total);
+                   ctx->fields.nx, pl.nx_total);
     } else if (sh.kind == ShardKind::mirrored) {
-        ML_REQUIRE(ctx->nx % 2 == 0 && row0 >= 0 && 2 * row0 + ctx->nx <= pl.nx_total,
+        ML_REQUIRE(ctx->fields.nx % 2 == 0 && row0 >= 0 && 2 * row0 + ctx->fields.nx <= pl.nx_total,
                    "mirrored shard: %d resident rows starting at %d do not form row pairs of a "
-                   "%d-row aperture", ctx->nx, row0, pl.nx_total);
+                   "%d-row aperture", ctx->fields.nx, row0, pl.nx_total);
         ML_REQUIRE(!pl.pair_list, "mirrored shards are for tensor grids");
     } else {
-        ML_REQUIRE(row0 >= 0 && row0 + ctx->nx <= pl.nx_total,
+        ML_REQUIRE(row0 >= 0 && row0 + ctx->fields.nx <= pl.nx_total,
                    "rows [%d, %d) fall outside the planned aperture of %d rows", row0,
-                   row0 + ctx->nx, pl.nx_total);
+                   row0 + ctx->fields.nx, pl.nx_total);
     }
     ML_REQUIRE(!accumulate || pl.have_vectors, "accumulate requested but nothing to add to");
     return ML_OK;
@@ -807,29 +807,31 @@ static const RouteKnobs &route_knobs() {
     return knobs;
 }
 
-// The resident rows that meet the lens circle (transform_route.h), into ctx->trim_rows, found once per (grid, layout).
+// The resident rows that meet the lens circle (transform_route.h), into ctx->grid.trim_rows, found once per (grid, layout).
 // false: the resident fields carry no row_first for their grid (uploaded fields) - nothing is known about their rows.
 static bool trim_rows_of(ml_ctx *ctx) {
-    const int nxl = ctx->nx;
-    if (!ctx->row_first_valid || (int)ctx->h_x_pts.size() != nxl || (int)ctx->h_y_pts.size() != ctx->ny ||
-        !(ctx->r_outer > 0))
+    const SynthGrid &grid = ctx->grid;
+    const int nxl = ctx->fields.nx;
+    const double r_outer = ctx->lens.search.r_outer;
+    if (!ctx->caches.rows_describe_fields || (int)grid.h_x_pts.size() != nxl || (int)grid.h_y_pts.size() != ctx->fields.ny ||
+        !(r_outer > 0))
         return false;
-    if (ctx->trim_key[0] != ctx->grid_serial || ctx->trim_key[1] != ctx->layout_serial) {
+    const Key<2> key = ctx->caches.grid_layout_key();
+    if (!ctx->caches.trim.matches(key.v)) {
         double ymin = INFINITY;
-        for (double y : ctx->h_y_pts) ymin = std::min(ymin, std::fabs(y));
+        for (double y : grid.h_y_pts) ymin = std::min(ymin, std::fabs(y));
         int lo = nxl, hi = 0;
         for (int i = 0; i < nxl; ++i) {
-            const double x = ctx->h_x_pts[i];
-            if (!(std::sqrt(x * x + ymin * ymin) > ctx->r_outer)) {
+            const double x = grid.h_x_pts[i];
+            if (!(std::sqrt(x * x + ymin * ymin) > r_outer)) {
                 lo = std::min(lo, i);
                 hi = i + 1;
             }
         }
         if (lo >= hi) lo = 0, hi = std::min(nxl, 1);   // (an empty window keeps one row: nothing to gain)
-        ctx->trim_rows[0] = lo;
-        ctx->trim_rows[1] = hi;
-        ctx->trim_key[0] = ctx->grid_serial;
-        ctx->trim_key[1] = ctx->layout_serial;
+        ctx->grid.trim_rows[0] = lo;
+        ctx->grid.trim_rows[1] = hi;
+        ctx->caches.trim.set(key.v);
     }
     return true;
 }
@@ -887,13 +889,13 @@ static int run_subsequences(hipStream_t stream, ZfftCall &c, const ZfftAxis &ax,
 // stage 1 as a pruned FFT along y
 static int stage1_fft(ml_ctx *ctx, const TransformRoute &rt, double *g) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, ny = pl.ny, my = pl.my, trim_lo = rt.trim_lo, nxt = rt.trim_hi - rt.trim_lo;
+    const int nxl = ctx->fields.nx, ny = pl.ny, my = pl.my, trim_lo = rt.trim_lo, nxt = rt.trim_hi - rt.trim_lo;
     const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, trim_lo);
     ZfftCall c;
     call_axis(c, pl, pl.fft_y, my);
     c.n_valid = ny;
     // row (f, n1') of the launch = row n1 = trim_lo + n1' of field plane f
-    c.in = ctx->set_ptr() + (size_t)trim_lo * ny * 2;
+    c.in = ctx->fields.set_ptr() + (size_t)trim_lo * ny * 2;
     c.rows = 4 * nxt;
     c.in_rb = nxt;
     c.in_s1 = (int64_t)nxl * ny;
@@ -902,7 +904,7 @@ static int stage1_fft(ml_ctx *ctx, const TransformRoute &rt, double *g) {
     c.a0 = 0;
     c.h0 = ny;
     c.a1 = c.h1 = 0;
-    c.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() + trim_lo : nullptr;
+    c.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() + trim_lo : nullptr;
     c.rf_mod = nxt;
     c.out = g + (size_t)v.off * 2;
     c.out_rb = nxt;
@@ -918,12 +920,12 @@ static int stage1_fft(ml_ctx *ctx, const TransformRoute &rt, double *g) {
 // stage 1: G[(f, n1)][b] = sum_n2 F_f[n1][n2] * exp(-i k y'_n2 uy_b)
 static int stage1(ml_ctx *ctx, const TransformRoute &rt, double *g) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, ny = pl.ny, my = pl.my;
+    const int nxl = ctx->fields.nx, ny = pl.ny, my = pl.my;
     // resident fields that the synthesis already multiplied by this plan's input modulation
     // (ml_nearfield_premodulate): stage 1 then runs without it
     bool fields_premodulated = false;
-    if (ctx->fields_premod_serial >= 0) {
-        if (ctx->fields_premod_serial != pl.serial || !pl.fold) {
+    if (ctx->fields.premod_serial >= 0) {
+        if (ctx->fields.premod_serial != pl.serial || !pl.fold) {
             set_error("the resident fields carry the input modulation of an earlier far-field plan "
                       "(ml_nearfield_premodulate): synthesise them again after ml_farfield_plan");
             return ML_ESTATE;
@@ -939,14 +941,14 @@ static int stage1(ml_ctx *ctx, const TransformRoute &rt, double *g) {
             io.out_t_rows = nxl;
             io.out_E = pl.fold_x.has_E ? pl.fold_x.E.as<double>() : nullptr;
         }
-        return zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->set_ptr(), ny, fy.cm.as<double>(), fy.sm.as<double>(),
+        return zfold_stage1(ctx->stream, 4 * nxl, ny, ctx->fields.set_ptr(), ny, fy.cm.as<double>(), fy.sm.as<double>(),
                             fy.r4.as<double>(), (ny + 1) / 2, pl.fold_S,
                             fy.has_E && !fields_premodulated ? fy.E.as<double>() : nullptr, fy.D.as<double>(), g, my, my,
-                            ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr, nxl, rt.want_split1,
+                            ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : nullptr, nxl, rt.want_split1,
                             (int64_t)4 * nxl * my, ctx->gemm_f32 != 0, io);
     }
     const double one[4] = {1.0, 1.0, 1.0, 1.0};
-    return zgemm(ctx->stream, 4 * nxl, my, ny, one, ctx->set_ptr(), ny, 0, pl.tw_y.as<double>(), my, 0, g, my, 0, 1,
+    return zgemm(ctx->stream, 4 * nxl, my, ny, one, ctx->fields.set_ptr(), ny, 0, pl.tw_y.as<double>(), my, 0, g, my, 0, 1,
                  0);
 }
 
@@ -954,7 +956,7 @@ static int stage1(ml_ctx *ctx, const TransformRoute &rt, double *g) {
 static int collapse_stage1(ml_ctx *ctx, double *g) {
     FarfieldPlan &pl = ctx->plan;
     if (pl.stage1_splits > 1) {
-        const size_t n = (size_t)4 * ctx->nx * pl.my;
+        const size_t n = (size_t)4 * ctx->fields.nx * pl.my;
         hipLaunchKernelGGL(zsum_slabs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                            ctx->stream, reinterpret_cast<double2 *>(g), n, pl.stage1_splits);
         ML_HIP(hipGetLastError());
@@ -969,12 +971,12 @@ static int collapse_stage1(ml_ctx *ctx, double *g) {
 static int stage2_interleaved(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, const double *g,
                               const double *alpha, int accumulate) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, mx = pl.mx, my = pl.my;
+    const int nxl = ctx->fields.nx, mx = pl.mx, my = pl.my;
     const int s = sh.block, G = sh.n_ranks, N = pl.fft_x.N_eff;
     const int stuff = interleave_stuff(N / (s * G)), Nsub = N / (s * G) * stuff;   // the lattice it runs on
     const int n_have = pl.nx_total / (s * G);   // samples of each short transform that exist
     const long key[4] = {pl.serial, s, G, sh.rank};
-    if (memcmp(key, pl.il_key, sizeof key) != 0) {
+    if (!pl.il_for.matches(key)) {
         ML_TRY(pl.il_wk.reserve((size_t)mx * 2 * sizeof(double)));
         ML_TRY(pl.il_kbin.reserve((size_t)mx * sizeof(int)));
         ML_TRY(pl.il_pj.reserve((size_t)s * mx * 2 * sizeof(double)));
@@ -982,7 +984,7 @@ static int stage2_interleaved(ml_ctx *ctx, const TransformRoute &rt, const Shard
                                             pl.il_kbin.as<int>(), mx, pl.fft_x.j0, Nsub, N,
                                             pl.nx_total - pl.nx_total / 2, s * sh.rank, s, pl.fft_x.jstep));
         zfft_choose_pads(Nsub, mx, pl.fft_x.j0, &pl.il_pad1, &pl.il_pad2, pl.fft_x.jstep);
-        memcpy(pl.il_key, key, sizeof key);
+        pl.il_for.set(key);
     }
     // (the row-major G from its first local row: the rows stage 1 left out are told by a0 / h0)
     const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, 0);
@@ -1020,7 +1022,7 @@ static int stage2_interleaved(ml_ctx *ctx, const TransformRoute &rt, const Shard
 static int stage2_fft(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, const double *g, const double *alpha,
                       int accumulate) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, mx = pl.mx, my = pl.my;
+    const int nxl = ctx->fields.nx, mx = pl.mx, my = pl.my;
     const GView v = g_view(rt.g_layout, nxl, my, rt.g_ld, rt.trim_lo);
     ZfftCall c;
     call_axis(c, pl, pl.fft_x, mx);
@@ -1057,7 +1059,7 @@ static int stage2_fft(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, co
 // batch entry f writes radiation-vector slot 3 - f.  One GEMM per run of resident rows: two on a mirrored shard
 static int stage2_generic(ml_ctx *ctx, const Shard &sh, const double *g, const double *alpha, int accumulate) {
     FarfieldPlan &pl = ctx->plan;
-    const int nxl = ctx->nx, mx = pl.mx, my = pl.my, row0 = sh.row0;
+    const int nxl = ctx->fields.nx, mx = pl.mx, my = pl.my, row0 = sh.row0;
     const int runs = sh.kind == ShardKind::mirrored ? 2 : 1, h = nxl / runs;
     double *slot3 = pl.vectors.as<double>() + (size_t)3 * mx * my * 2;
     for (int run = 0; run < runs; ++run) {
@@ -1088,7 +1090,7 @@ static int stage2(ml_ctx *ctx, const TransformRoute &rt, const Shard &sh, double
     case Stage2Kind::fft:
     case Stage2Kind::fft_tiles: return stage2_fft(ctx, rt, sh, g, alpha, accumulate);
     case Stage2Kind::coldot:
-        return zcoldot(ctx->stream, 4, ctx->nx, pl.mx, alpha, pl.tw_x.as<double>(), pl.mx, sh.row0, g,
+        return zcoldot(ctx->stream, 4, ctx->fields.nx, pl.mx, alpha, pl.tw_x.as<double>(), pl.mx, sh.row0, g,
                        pl.vectors.as<double>(), accumulate);
     default: return stage2_generic(ctx, sh, g, alpha, accumulate);
     }
@@ -1105,7 +1107,7 @@ static int transform_impl(ml_ctx *ctx, const Shard &sh, int accumulate) {
     else
         pl.unfold.pending = false;
     const TransformRoute rt =
-        transform_route(pl, pl.fft_y, pl.fft_x, sh, ctx->nx, trim_rows_of(ctx), ctx->trim_rows, route_knobs());
+        transform_route(pl, pl.fft_y, pl.fft_x, sh, ctx->fields.nx, trim_rows_of(ctx), ctx->grid.trim_rows, route_knobs());
     pl.stage1_splits = pl.fold ? zfold_splits((pl.ny + 1) / 2, rt.want_split1) : 1;
     double *g = nullptr;
     ML_TRY(reserve_g(pl, rt, &g));
@@ -1213,16 +1215,16 @@ static int project_stage(ml_ctx *ctx, double Z0, int stage, hipStream_t stream =
         for (int k = 0; k < 4; ++k) u.alpha.v[k] = pl.unfold.alpha[k];
         u.accumulate = pl.unfold.accumulate;
         u.splits = pl.unfold.splits;
-        u.partial = ctx->power_pending ? ctx->partial_power.as<double>() : nullptr;
-        u.n_partials = ctx->n_partials;
-        u.power_out = ctx->power.as<double>();
+        u.partial = ctx->out.power_pending ? ctx->out.partial_power.as<double>() : nullptr;
+        u.n_partials = ctx->out.n_partials;
+        u.power_out = ctx->out.power.as<double>();
         ProfScope scope(ctx, ML_K_PROJECT);
         hipLaunchKernelGGL(unfold_project_kernel,
                            dim3((mx + 7) / 8, (my + 7) / 8 + (u.partial ? 1 : 0)), dim3(256), 0,
                            ctx->stream, a, u);
         ML_HIP(hipGetLastError());
         pl.unfold.pending = false;
-        ctx->power_pending = false;
+        ctx->out.power_pending = false;
         return ML_OK;
     }
     ML_TRY(flush_unfold(ctx));
@@ -1454,7 +1456,6 @@ static int accumulate_impl(ml_ctx *ctx, double weight, double cone_u, double con
     hipLaunchKernelGGL(accumulate_finish_kernel, dim3(1), dim3(256), 0, ctx->stream,
                        ctx->acc_partials.as<double>(), blocks, ctx->acc_sums.as<double>() + 2 * slot);
     ML_HIP(hipGetLastError());
-    ctx->acc_blocks = blocks;
     return ML_OK;
 }
 

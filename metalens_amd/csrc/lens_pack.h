@@ -1,7 +1,7 @@
 // How a lens is laid out for the near-field kernels: table descriptors, per-ring tables and records, the centre
 // table's blocks, the ring-search tables, the binned cells and their lattice - each a pure function from plain arrays
 // to a struct of vectors and scalars.  ctx.hip validates, calls these, uploads what they return and copies the
-// returned scalars into ml_ctx; nothing here knows of either.
+// scalars each returns as one small struct (its `facts`); nothing here knows of either.
 //
 // Host code without HIP types: compiled by hipcc into ctx.hip and by the host compiler into tools/lens_pack.cpp,
 // which runs these functions over a file of arrays and writes every buffer and scalar (tests/test_lens_pack.py).
@@ -280,8 +280,14 @@ struct LensClass {
     bool simple = false;                         // some table in use is simple
     int general_mask = 0, centre_general = 0;    // bit c: dense collection c is general; the centre table (both 0 unless `simple`)
     // which ring collections go to the wide instantiation of the ring kernel (nearfield_simple.hip): part of
-    // what the patch lists were built for (nearfield.hip geo_key)
+    // what the patch lists were built for (list_word below, synth_caches.h geometry_key)
     int narrow_mask = 0, wide_mask = 0, narrow_exists = 0, narrow_slots_max = 1;
+    // one word of the above for the key of the patch lists; -2: the general kernel alone
+    long list_word() const { return simple ? (long)wide_mask | (long)general_mask << 20 | (long)centre_general << 40 : -2; }
+    // the lists and what a synthesis leaves outside the lens were made for another assignment of samples to kernels
+    bool lists_differ(const LensClass &o) const {
+        return simple != o.simple || general_mask != o.general_mask || (simple && centre_general != o.centre_general);
+    }
 };
 // colls[c]: the table of dense collection c; centre: null or not present = none.  force_general sends a lens that
 // qualifies through the general kernels, force_general_coll = mask of dense collection numbers, bit 16 = the centre
@@ -492,16 +498,17 @@ inline RingTables pack_ring_tables(const HostTable *const *colls, const TableDes
 // Simple order sets: CELL BLOCKS (CENTER_BLOCK above) - complex [order slot][i0][i1][group][node 4][amplitude 4][20]:
 // the table's orders from the lowest ox upwards, per table cell and group of 20 cell types the 320
 // complex its samples interpolate from, contiguous (a hole in the list: zeros).
+struct CentreSlots {
+    int n_slots = 0, lo = 0, present = 0;   // simple order sets: as CollDesc::n_slots / ox_lo / present
+};
 struct CentreTable {
     std::vector<double> cq;
-    int n_slots = 0, lo = 0, present = 0;   // simple order sets: as CollDesc::n_slots / ox_lo / present
+    CentreSlots slots;
 };
 inline CentreTable pack_centre_table(const HostTable &t, bool centre_simple, const Canon &L) {
     CentreTable out;
     if (centre_simple) {
-        out.n_slots = L.n;
-        out.lo = L.lo;
-        out.present = L.present;
+        out.slots = {L.n, L.lo, L.present};
         const int groups = (t.n2 + CENTER_GROUP - 1) / CENTER_GROUP;
         const size_t cells = (size_t)std::max(t.n0 - 1, 0) * std::max(t.n1 - 1, 0);
         out.cq.assign((size_t)L.n * cells * groups * CENTER_BLOCK * 2, 0.0);
@@ -541,17 +548,19 @@ inline CentreTable pack_centre_table(const HostTable &t, bool centre_simple, con
 
 // ---- layout --------------------------------------------------------------------------------
 // The two tables searchsorted(boundaries, r, 'left') starts from, B = the n_rings + 1 ring boundaries.
+struct RingSearchFacts {
+    int lut_buckets = 0, lutrec_buckets = 0;
+    double lut_inv_h = 0, lutrec_inv_h = 0;
+    double r_outer = 0, r_centre = 0;   // (r_centre: inner boundary of ring 0 = radius of the centre disc)
+};
 struct RingSearch {
     PackError err;
+    RingSearchFacts facts;
     // uniform-in-r lookup: lut[b] = number of boundaries strictly below the lower edge of bucket b
     std::vector<int32_t> lut;
-    int lut_buckets = 0;
-    double lut_inv_h = 0;
     // fast kernel: buckets about half the narrowest ring wide (so that a bucket rarely holds
     // more than one boundary), each carrying the boundaries around its lower edge
     std::vector<RingBucket> rec;
-    int lutrec_buckets = 0;
-    double lutrec_inv_h = 0, r_outer = 0, r_centre = 0;   // (r_centre: inner boundary of ring 0 = radius of the centre disc)
 };
 inline RingSearch pack_ring_search(const double *B, int n_rings) {
     RingSearch out;
@@ -566,8 +575,8 @@ inline RingSearch pack_ring_search(const double *B, int n_rings) {
         while (idx <= n_rings && B[idx] < edge) ++idx;
         out.lut[b] = idx;
     }
-    out.lut_buckets = buckets;
-    out.lut_inv_h = 1.0 / h;
+    out.facts.lut_buckets = buckets;
+    out.facts.lut_inv_h = 1.0 / h;
     double narrowest = r_max;
     for (int k = 1; k <= n_rings; ++k)
         if (B[k] > B[k - 1]) narrowest = std::min(narrowest, B[k] - B[k - 1]);
@@ -584,19 +593,22 @@ inline RingSearch pack_ring_search(const double *B, int n_rings) {
         out.rec[b].b0 = at <= n_rings ? B[at] : INFINITY;
         out.rec[b].b1 = at + 1 <= n_rings ? B[at + 1] : INFINITY;
     }
-    out.lutrec_buckets = nb;
-    out.lutrec_inv_h = 1.0 / hb;
-    out.r_outer = r_max;
-    out.r_centre = B[0];
+    out.facts.lutrec_buckets = nb;
+    out.facts.lutrec_inv_h = 1.0 / hb;
+    out.facts.r_outer = r_max;
+    out.facts.r_centre = B[0];
     return out;
 }
 
 // centre cells (x, y, type per cell) -> uniform grid of bins (about one cell per bin), cells stored in bin
 // order; within a bin the original order is kept (ties resolve to the lowest index)
-struct CellBins {
-    PackError err;
+struct BinFacts {
     int bins_x = 0, bins_y = 0;
     double x0 = 0, y0 = 0, h = 0;
+};
+struct CellBins {
+    PackError err;
+    BinFacts facts;
     std::vector<double> sx, sy, sxy;         // sorted cells: x, y, and (x, y) interleaved
     std::vector<int32_t> sw, si;             // ... their types and original indices
     std::vector<int32_t> start;              // [bins_x bins_y + 1]: first sorted slot of every bin
@@ -652,11 +664,7 @@ inline CellBins bin_cells(const double *cells, int n_cells) {
     }
     out.slot_of_cell.assign(n_cells, 0);
     for (int c = 0; c < n_cells; ++c) out.slot_of_cell[out.si[c]] = c;
-    out.bins_x = bxn;
-    out.bins_y = byn;
-    out.x0 = x0;
-    out.y0 = y0;
-    out.h = hbin;
+    out.facts = {bxn, byn, x0, y0, hbin};
     return out;
 }
 
@@ -667,12 +675,15 @@ inline CellBins bin_cells(const double *cells, int n_cells) {
 // can start from the four nodes around the sample instead of scanning bins.  The result is
 // accepted only when it is provably nearest (see nearest_cell_fast), so a wrong fit can cost
 // time but never correctness; anything irregular simply reports `ok = false`.
-struct LatticeFit {
+struct LatticeFacts {
     bool ok = false;
     double c0x = 0, c0y = 0, inv[4] = {0, 0, 0, 0};   // (u, v) = inv * (p - c0)
     int amin = 0, bmin = 0, na = 0, nb = 0;
     double accept_r2 = 0;
     double g[3] = {0, 0, 0}, guard = 0;   // metric of the basis; ambiguity guard for the analytic pick
+};
+struct LatticeFit {
+    LatticeFacts facts;
     std::vector<int32_t> map;                          // [na][nb] -> sorted slot, -1 empty
 };
 
@@ -790,22 +801,23 @@ inline LatticeFit fit_lattice(const std::vector<double> &sx, const std::vector<d
     // parallelogram picked by floor(); keep a margin for both
     const double r = h_min - 2 * eps_max - 1e-9 * pitch;
     if (!(r > 0.5 * pitch)) return L;                  // degenerate lattice: not worth it
-    L.ok = true;
-    L.c0x = sx[o];
-    L.c0y = sy[o];
-    for (int k = 0; k < 4; ++k) L.inv[k] = inv[k];
-    L.amin = amin;
-    L.bmin = bmin;
-    L.na = (int)na;
-    L.nb = (int)nb;
-    L.accept_r2 = r * r;
-    L.g[0] = b1x * b1x + b1y * b1y;
-    L.g[1] = b1x * b2x + b1y * b2y;
-    L.g[2] = b2x * b2x + b2y * b2y;
+    LatticeFacts &F = L.facts;
+    F.ok = true;
+    F.c0x = sx[o];
+    F.c0y = sy[o];
+    for (int k = 0; k < 4; ++k) F.inv[k] = inv[k];
+    F.amin = amin;
+    F.bmin = bmin;
+    F.na = (int)na;
+    F.nb = (int)nb;
+    F.accept_r2 = r * r;
+    F.g[0] = b1x * b1x + b1y * b1y;
+    F.g[1] = b1x * b2x + b1y * b2y;
+    F.g[2] = b2x * b2x + b2y * b2y;
     // |d^2(cell) - d^2(node)| <= 2 d eps + eps^2 with d <= ~2 pitch, for each of two candidates,
     // plus the rounding of the lattice-coordinate expressions (coordinates up to ~1e4 pitches
     // at 1e-16): a few 1e-12 pitch^2; generous factor on top
-    L.guard = 8.0 * pitch * (eps_max + 1e-11 * pitch) + 1e-9 * pitch * pitch;
+    F.guard = 8.0 * pitch * (eps_max + 1e-11 * pitch) + 1e-9 * pitch * pitch;
     return L;
 }
 

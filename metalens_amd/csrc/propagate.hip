@@ -208,32 +208,32 @@ static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, in
         set_error("ml_propagate_plan has not been called");
         return ML_ESTATE;
     }
-    if (ctx->nx == 0 || ctx->ny == 0) {
+    if (ctx->fields.nx == 0 || ctx->fields.ny == 0) {
         set_error("no resident field set");
         return ML_ESTATE;
     }
     ML_REQUIRE(ctx->n_ranks <= 1, "%s: this context belongs to a communicator of %d ranks", who, ctx->n_ranks);
     ML_REQUIRE(Z0 > 0, "Z0 must be positive");
     ML_REQUIRE(n >= 1 && n <= PROP_MAX_SETS, "%s: a pass takes 1 to %d field sets, got %d", who, PROP_MAX_SETS, n);
-    ML_REQUIRE(first >= 0 && first + n <= ctx->n_sets, "%s: field sets %d ... %d asked for, %d resident", who, first,
-               first + n - 1, ctx->n_sets);
+    ML_REQUIRE(first >= 0 && first + n <= ctx->fields.n_sets, "%s: field sets %d ... %d asked for, %d resident", who, first,
+               first + n - 1, ctx->fields.n_sets);
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     if (pp.method == ML_PROPAGATE_FFT) return propagate_grid_sets(ctx, Z0, first, n);
     const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
-    const int splits = std::max(1, std::min(ctx->nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
+    const int splits = std::max(1, std::min(ctx->fields.nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
     pp.have_result = false;
     ML_TRY(pp.partial.reserve((size_t)splits * n * nq * T * sizeof(double)));
     ML_TRY(pp.result.reserve((size_t)n * (nq / 2) * T * 2 * sizeof(double)));
     PropArgs a;
-    a.fields = ctx->fields.as<double2>() + (size_t)first * 4 * ctx->nx * ctx->ny;
-    a.row_first = ctx->row_first_valid ? ctx->row_first.as<int>() : nullptr;
+    a.fields = ctx->fields.buf.as<double2>() + (size_t)first * 4 * ctx->fields.nx * ctx->fields.ny;
+    a.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : nullptr;
     a.tx = pp.targets.as<double>();
     a.ty = a.tx + T;
     a.tz = a.tx + 2 * (size_t)T;
     a.partial = pp.partial.as<double>();
-    a.nx = ctx->nx;
-    a.ny = ctx->ny;
+    a.nx = ctx->fields.nx;
+    a.ny = ctx->fields.ny;
     a.T = T;
     a.splits = splits;
     a.dxp = pp.dxp;
@@ -308,7 +308,7 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
 
 int ml_propagate(ml_ctx *ctx, double Z0) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    return propagate_sets(ctx, "ml_propagate", Z0, ctx->field_set, 1);
+    return propagate_sets(ctx, "ml_propagate", Z0, ctx->fields.field_set, 1);
 }
 
 int ml_propagate_sets(ml_ctx *ctx, double Z0, int first_set, int n_sets) {
@@ -318,7 +318,7 @@ int ml_propagate_sets(ml_ctx *ctx, double Z0, int first_set, int n_sets) {
 
 int ml_fields_sets(ml_ctx *ctx, int *n_sets) {
     ML_REQUIRE(ctx && n_sets, "NULL argument");
-    *n_sets = (ctx->nx && ctx->ny) ? ctx->n_sets : 0;
+    *n_sets = (ctx->fields.nx && ctx->fields.ny) ? ctx->fields.n_sets : 0;
     return ML_OK;
 }
 

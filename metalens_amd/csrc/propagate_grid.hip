@@ -366,12 +366,12 @@ static int upload_twiddles(ml_ctx *ctx, DevBuf &buf, int L) {
 // the workspace and the kernel spectra for the resident field's shape (kept while the shape stays)
 static int grid_prepare(ml_ctx *ctx) {
     PropagatePlan &pp = ctx->prop;
-    if (pp.spectra_ready && pp.grid.nx == ctx->nx && pp.grid.ny == ctx->ny) return ML_OK;
+    if (pp.spectra_ready && pp.grid.nx == ctx->fields.nx && pp.grid.ny == ctx->fields.ny) return ML_OK;
     pp.spectra_ready = false;
     const int mx = pp.grid.mx, my = pp.grid.my;
     char why[320];
     GridPlanFacts f;
-    if (grid_plan_facts(ctx->nx, ctx->ny, mx, my, pp.want_h, &f, why, sizeof why) != 0) {
+    if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, pp.want_h, &f, why, sizeof why) != 0) {
         set_error("%s", why);
         return ML_EINVAL;
     }
@@ -416,11 +416,12 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     const unsigned blocks = (unsigned)(ps / 256);
     // rows that are zero need no transform (diagnostic build: ML_GRID_ALL_ROWS=1 transforms them all, for timing)
     const bool all_rows = diag_int("ML_GRID_ALL_ROWS", 0) != 0;
-    const int rows_fwd = all_rows ? f.Lx : ctx->nx, rows_inv = all_rows ? f.Lx : f.mx;
+    const int rows_fwd = all_rows ? f.Lx : ctx->fields.nx, rows_inv = all_rows ? f.Lx : f.mx;
     for (int m = 0; m < n; ++m) {
-        const d2 *fields = ctx->fields.as<d2>() + (size_t)(first + m) * 4 * ctx->nx * ctx->ny;
+        const d2 *fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * ctx->fields.nx * ctx->fields.ny;
         hipLaunchKernelGGL(grid_pad_kernel, dim3(blocks, GRID_CURRENTS), dim3(256), 0, ctx->stream, fields,
-                           ctx->row_first_valid ? ctx->row_first.as<int>() : (const int *)nullptr, cur, ps, ctx->nx, ctx->ny,
+                           ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr, cur, ps,
+                           ctx->fields.nx, ctx->fields.ny,
                            f.Lx, f.Ly, Z);
         ML_HIP(hipGetLastError());
         ML_TRY(fft_rows<false>(ctx, cur, GRID_CURRENTS, rows_fwd));
@@ -460,9 +461,9 @@ int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double
     GridPlanFacts f;
     f.mx = mx;
     f.my = my;
-    if (ctx->nx && ctx->ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
+    if (ctx->fields.nx && ctx->fields.ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
         char why[320];
-        if (grid_plan_facts(ctx->nx, ctx->ny, mx, my, want_h, &f, why, sizeof why) != 0) {
+        if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, &f, why, sizeof why) != 0) {
             set_error("ml_propagate_plan_grid: %s", why);
             return ML_EINVAL;
         }

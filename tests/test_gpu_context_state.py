@@ -35,9 +35,14 @@ def ma():
 
 @functools.lru_cache(None)
 def lens(name):
-    """'A': three orders per table; 'B': the orders characterize() would record ('physical')"""
+    """'A': three orders per table; 'B': the orders characterize() would record ('physical'); 'G', 'M': lens A's
+    layout with an order (0, 1) in every ring table / in the second of its two collections' tables only"""
     if name == 'A':
         return _synthetic_lens(20e-6, 0.35, WL, switch_deg=9.0)
+    if name in ('G', 'M'):
+        simple, general = ((0, 0), (-1, 0), (1, 0)), ((0, 0), (-1, 0), (0, 1))
+        return _synthetic_lens(20e-6, 0.35, WL, switch_deg=9.0,
+                               periphery_orders=general if name == 'G' else (simple, general))
     return _synthetic_lens(16e-6, 0.4, WL, switch_deg=9.0, periphery_orders='physical',
                            center_orders='physical')
 
@@ -59,6 +64,9 @@ def grid(name):
     if name == 'off':         # 200 x 136, off centre, different pitches
         return (4e-6 + (np.arange(200) - 99.5) * PITCH,
                 -2.5e-6 + (np.arange(136) - 67.5) * 0.97 * PITCH)
+    if name == 'tie':         # 61^2, symmetric with x[30] == 0.0 exactly: samples on mirror lines of the cell lattice
+        x = (np.arange(61) - 30) * PITCH
+        return x, x.copy()
     if name == 'strip':       # 3 x 2050
         return 0.3e-6 + (np.arange(3) - 1.0) * PITCH, (np.arange(2050) - 1024.5) * 0.05e-6
     raise KeyError(name)
@@ -511,6 +519,32 @@ def test_one_context_through_grid_batch_and_plan_transitions(ma, ctx):
         if desc[0] == 'shard':
             assert got['sharding'].startswith({'mirrored': 'mirrored', 'interleaved': 'interleaved',
                                                'auto': 'whole'}[desc[6]]), (desc, got['sharding'])
+
+
+def test_lens_class_and_tie_answers_between_syntheses(ma, ctx):
+    """the lens-class edge: ONE layout (lens A's) and one grid, the ring tables' order sets changed under it -
+    simple (every table the order-list kernels'), an order (0, 1) in every ring table (the rings through the general
+    kernel), one collection of each, simple again.  Neither the grid nor the layout serial moves, so only the class
+    event (synth_caches.h lens_class_changed) drops the patch lists and the zeros outside the lens.  Then the tie edge:
+    a grid with exact nearest-cell ties (answered inside build_nearfield), another grid, the tie grid again - the
+    answers are dropped with their (grid, layout) and given anew."""
+    from oracle import nearfield_oracle
+    assert len(lens('A')['lens_periphery_summary']['gratingcollection_list']) == 2
+    pool, infos, tokens = {}, [], []
+    for L in ('A', 'G', 'M', 'A'):
+        for _ in range(2):               # (the second finds the zeros stored and launches the patch lists)
+            check(ma, ctx, pool, ('nf', L, 'off', 0, True))
+        infos.append(ctx.nearfield_kernels())
+        tokens.append(ctx.layout_token)
+    assert [i['family'] for i in infos] == ['orders-along-x', 'mixed', 'mixed', 'orders-along-x'], infos
+    assert [i['ring_orders_max'] for i in infos] == [3, 0, 3, 3], infos     # (all rings general; one collection simple)
+    assert tokens[0] is not None and len(set(tokens)) == 1, tokens       # the layout was not uploaded again
+    dec = {}
+    x, y = grid('tie')
+    nearfield_oracle.build_nearfield(*source('A', 0), WL, *lens_args('A'), x_pts=x, y_pts=y, decisions=dec)
+    assert np.count_nonzero(dec['nearest_tie']) > 0     # the grid really has ties
+    for g in ('tie', 'off', 'tie', 'tie'):
+        check(ma, ctx, pool, ('nf', 'A', g, 0, True))
 
 
 def _as_table_object(ns, centre):

@@ -15,10 +15,10 @@
 //   layout.B .r_center .period .lateral f8, layout.ring_gc i4, layout.cells f8[3 n_cells]
 //   (layout.dphi .rot_table .tie_table .rot_center .rot_half are uploaded as they are: accepted, not read)
 //   force_general, force_general_coll   i4[1]   the diagnostic build's two knobs (default 0)
-// OUT holds every buffer the context would upload, under the name of its ml_ctx member, and every scalar it would
-// keep: records (table_desc = TableDesc[33] with null pointers, coll = CollDesc[n_colls], ring_lutrec = RingBucket[],
-// cell_lattice_rec = CellRec[]) as u1, scalars as arrays of one item.  After an error OUT holds error_code i4[1] and
-// error_message u1[] alone.
+// OUT holds every buffer the context would upload, under the name of its member of the context's Lens (common.h), and
+// every scalar it would keep, under the name the kernel arguments give it: records (table_desc = TableDesc[33] with
+// null pointers, coll = CollDesc[n_colls], ring_lutrec = RingBucket[], cell_lattice_rec = CellRec[]) as u1, scalars as
+// arrays of one item.  After an error OUT holds error_code i4[1] and error_message u1[] alone.
 // Build + run:  make -C tools lens_pack && tools/lens_pack lens.in lens.out
 #include <cstdio>
 #include <cstdlib>
@@ -117,13 +117,13 @@ int main(int argc, char **argv) {
     const RingSearch S = pack_ring_search(B.data(), n_rings);
     if (S.err.code != ML_OK) return fail(argv[2], S.err);
     put("ring_lut", S.lut);
-    put("lut_buckets", S.lut_buckets);
-    put("lut_inv_h", S.lut_inv_h);
+    put("lut_buckets", S.facts.lut_buckets);
+    put("lut_inv_h", S.facts.lut_inv_h);
     put("ring_lutrec", "u1", S.rec.data(), S.rec.size() * sizeof(RingBucket), 1);
-    put("lutrec_buckets", S.lutrec_buckets);
-    put("lutrec_inv_h", S.lutrec_inv_h);
-    put("r_outer", S.r_outer);
-    put("r_centre", S.r_centre);
+    put("lutrec_buckets", S.facts.lutrec_buckets);
+    put("lutrec_inv_h", S.facts.lutrec_inv_h);
+    put("r_outer", S.facts.r_outer);
+    put("r_centre", S.facts.r_centre);
     put("n_cells", n_cells);
     if (n_cells > 0) {
         const CellBins C = bin_cells(cells.data(), n_cells);
@@ -135,27 +135,27 @@ int main(int argc, char **argv) {
         put("cell_index", C.si);
         put("slot_of_cell", C.slot_of_cell);
         put("bin_start", C.start);
-        put("bins_x", C.bins_x);
-        put("bins_y", C.bins_y);
-        put("bin_x0", C.x0);
-        put("bin_y0", C.y0);
-        put("bin_h", C.h);
+        put("bins_x", C.facts.bins_x);
+        put("bins_y", C.facts.bins_y);
+        put("bin_x0", C.facts.x0);
+        put("bin_y0", C.facts.y0);
+        put("bin_h", C.facts.h);
         const LatticeFit L = fit_lattice(C.sx, C.sy);
-        put("lat_ok", (int)L.ok);
-        if (L.ok) {
+        put("lat_ok", (int)L.facts.ok);
+        if (L.facts.ok) {
             const std::vector<CellRec> rec = lattice_records(L, C);
             put("cell_lattice_map", L.map);
             put("cell_lattice_rec", "u1", rec.data(), rec.size() * sizeof(CellRec), 1);
-            put("lat_c0x", L.c0x);
-            put("lat_c0y", L.c0y);
-            put("lat_inv", "f8", L.inv, 4, 8);
-            put("lat_amin", L.amin);
-            put("lat_bmin", L.bmin);
-            put("lat_na", L.na);
-            put("lat_nb", L.nb);
-            put("lat_accept_r2", L.accept_r2);
-            put("lat_g", "f8", L.g, 3, 8);
-            put("lat_guard", L.guard);
+            put("lat_c0x", L.facts.c0x);
+            put("lat_c0y", L.facts.c0y);
+            put("lat_inv", "f8", L.facts.inv, 4, 8);
+            put("lat_amin", L.facts.amin);
+            put("lat_bmin", L.facts.bmin);
+            put("lat_na", L.facts.na);
+            put("lat_nb", L.facts.nb);
+            put("lat_accept_r2", L.facts.accept_r2);
+            put("lat_g", "f8", L.facts.g, 3, 8);
+            put("lat_guard", L.facts.guard);
         }
     }
 
@@ -196,8 +196,8 @@ int main(int argc, char **argv) {
         C = pack_centre_table(tables[MAX_SLOTS], K.centre_simple, K.canon_center);
         put("center_qmajor", C.cq);
     }
-    put("center_n_slots", C.n_slots);
-    put("center_lo", C.lo);
-    put("center_present_mask", C.present);
+    put("center_n_slots", C.slots.n_slots);
+    put("center_lo", C.slots.lo);
+    put("center_present_mask", C.slots.present);
     return fclose(g_out) ? 1 : 0;
 }
