@@ -504,8 +504,21 @@ int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
 int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
                            double wavelength, double n_glass,
                            double tx0, double ty0, int mx, int my, double z, int want_h);
+/* ml_propagate_plan_grid with padded axes of up to L = 16384 (arguments, checks, layouts and scales as there; L >
+ * 16384 is refused in the same way, with n, m and L in the message): apertures of 4097 ... 8192 samples a side, which
+ * ml_propagate_plan_grid can give one target per axis at the most.  An axis of L <= 8192 is transformed as there and
+ * the results of a plan both entries accept have the same bits; an axis of L = 16384 takes one streaming pass more
+ * per transform (csrc/propagate_grid.h grid_axis_route).  A call of its own because of what it may reserve: the
+ * workspace of (12 + 6 or 3) Lx Ly complex128 is up to 77 GB (E only: 64 GB) where ml_propagate_plan_grid never
+ * reserves more than 18 GB; the first pass reserves it and fails with ML_ENOMEM and the bytes asked for in
+ * ml_last_error if the device cannot give them.  At most 2^26 targets per plan, as there.  ml_propagate_plan_info
+ * reports ML_PROPAGATE_FFT_LONG.  Replaces no reference lines.                              */
+int ml_propagate_plan_grid_long(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                                double wavelength, double n_glass,
+                                double tx0, double ty0, int mx, int my, double z, int want_h);
 #define ML_PROPAGATE_DIRECT 0
 #define ML_PROPAGATE_FFT 1
+#define ML_PROPAGATE_FFT_LONG 2
 /* The active propagation plan: method (ML_PROPAGATE_*), the padded lengths lx, ly (0 for a direct plan, and for
  * an fft plan that has met no resident field set yet) and the bytes of device workspace it holds besides targets,
  * result and sums (direct: the row-set partial sums of the last pass; fft: spectra, currents and outputs, from

@@ -49,6 +49,7 @@ SYMBOLS = (
     'ml_comm_set_max_channels', 'ml_propagate_plan', 'ml_propagate', 'ml_propagate_download',
     'ml_propagate_sets', 'ml_propagate_download_set', 'ml_propagate_accumulate', 'ml_propagate_sums',
     'ml_fields_sets', 'ml_nearfield_members_async', 'ml_propagate_plan_grid', 'ml_propagate_plan_info',
+    'ml_propagate_plan_grid_long',
 )
 
 
@@ -166,6 +167,8 @@ def load():
     lib.ml_fields_sets.argtypes = [c_void_p, POINTER(c_int)]
     lib.ml_propagate_plan_grid.argtypes = [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double,
                                            c_double, c_double, c_int, c_int, c_double, c_int]
+    if hasattr(lib, 'ml_propagate_plan_grid_long'):
+        lib.ml_propagate_plan_grid_long.argtypes = lib.ml_propagate_plan_grid.argtypes
     lib.ml_propagate_plan_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]
     lib.ml_profile_enable.argtypes = [c_void_p, c_int]
     lib.ml_profile_reset.argtypes = [c_void_p]

@@ -219,7 +219,7 @@ static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, in
                first + n - 1, ctx->fields.n_sets);
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
-    if (pp.method == ML_PROPAGATE_FFT) return propagate_grid_sets(ctx, Z0, first, n);
+    if (pp.method != ML_PROPAGATE_DIRECT) return propagate_grid_sets(ctx, Z0, first, n);
     const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
     const int splits = std::max(1, std::min(ctx->fields.nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
     pp.have_result = false;

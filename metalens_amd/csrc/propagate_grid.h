@@ -10,7 +10,9 @@
 // Per axis, n samples and m targets: the lags l = i_t - i_s range over [-(n - 1), m - 1], n + m - 1 of them.
 //   L = the smallest power of two >= max(16, n + m - 1); lag l is stored at index l mod L; index p holds lag
 //   p (p < m) or p - L (otherwise) - indices in [m, L - n] are no lag of the problem.
-//   L > 8192 is refused: one row of 8192 complex128 is 128 KiB of the 160 KiB LDS of a compute unit.
+//   L > 8192 is refused: one row of 8192 complex128 is 128 KiB of the 160 KiB LDS of a compute unit.  The long plan
+//   (ml_propagate_plan_grid_long) takes L = 16384 too, an axis of that length in two passes (grid_axis_route below);
+//   it stops there because the 18 planes of L = 32768 a side are 309 GB.
 #pragma once
 
 #include <cmath>
@@ -21,6 +23,7 @@
 namespace ml {
 
 constexpr int GRID_L_MIN = 16, GRID_L_MAX = 8192;
+constexpr int GRID_L_LONG_MAX = 16384;   // the cap of the long plan
 constexpr int GRID_KERNELS = 8;    // kernel spectra kept for the life of a plan
 constexpr int GRID_CURRENTS = 4;   // Jx, Jy, Mx / Z, My / Z
 
@@ -41,15 +44,20 @@ struct GridPlanFacts {
     int64_t plane_bytes = 0, workspace_bytes = 0;
 };
 
-// -> 0, or -1 with `why` filled: an axis whose padded length exceeds GRID_L_MAX
-inline int grid_plan_facts(int nx, int ny, int mx, int my, int want_h, GridPlanFacts *f, char *why, size_t why_len) {
+// -> 0, or -1 with `why` filled: an axis whose padded length exceeds `cap` (GRID_L_MAX, or GRID_L_LONG_MAX for the
+// long plan)
+inline int grid_plan_facts(int nx, int ny, int mx, int my, int want_h, GridPlanFacts *f, char *why, size_t why_len,
+                           int cap = GRID_L_MAX) {
     const long long Lx = grid_padded_length(nx, mx), Ly = grid_padded_length(ny, my);
-    if (Lx > GRID_L_MAX || Ly > GRID_L_MAX) {
-        const bool bad_x = Lx > GRID_L_MAX;
+    if (Lx > cap || Ly > cap) {
+        const bool bad_x = Lx > cap;
         snprintf(why, why_len,
-                 "the FFT form pads the %s axis of n = %d samples and m = %d targets to L = %lld > %d (one row of L "
-                 "complex128 must fit the LDS); use the direct method or fewer targets per plan",
-                 bad_x ? "x" : "y", bad_x ? nx : ny, bad_x ? mx : my, bad_x ? Lx : Ly, GRID_L_MAX);
+                 cap > GRID_L_MAX
+                     ? "the FFT form pads the %s axis of n = %d samples and m = %d targets to L = %lld > %d (the planes "
+                       "of a longer axis do not fit the card); use the direct method or fewer targets per plan"
+                     : "the FFT form pads the %s axis of n = %d samples and m = %d targets to L = %lld > %d (one row of L "
+                       "complex128 must fit the LDS); use the direct method or fewer targets per plan",
+                 bad_x ? "x" : "y", bad_x ? nx : ny, bad_x ? mx : my, bad_x ? Lx : Ly, cap);
         return -1;
     }
     f->nx = nx;
@@ -84,7 +92,13 @@ inline std::vector<double> grid_twiddles(int L) {
 //   columns (stride Ly):   GRID_COLS adjacent columns per workgroup (128 contiguous bytes per access); blocks of up
 //                          to GRID_COL_LDS elements in the LDS, and for longer axes the stages above that in one
 //                          streaming pass without LDS (L / GRID_COL_LDS <= 8 elements per thread).
+// An axis of the long plan with L > GRID_L_MAX:
+//   rows:                  the stages above a block of GRID_ROW_BLOCK elements in one streaming pass without LDS
+//                          (L / GRID_ROW_BLOCK elements of one row per thread, adjacent lanes adjacent elements), the rest
+//                          on blocks of a row in the LDS;
+//   columns:               as above, with L / GRID_COL_LDS = 16 elements per thread in the streaming pass.
 constexpr int GRID_COLS = 8, GRID_COL_LDS = 1024;
+constexpr int GRID_ROW_BLOCK = 4096;   // 68 KiB with its padding: two workgroups per compute unit
 
 inline int grid_log2(int L) {
     int s = 0;
@@ -96,5 +110,28 @@ inline int grid_log2(int L) {
 constexpr int grid_lds_slot(int p) { return p + (p >> 4); }
 // slots of one sequence of `len` elements, odd so that adjacent sequences start on different slots
 constexpr int grid_lds_seq(int len) { return grid_lds_slot(len) | 1; }
+
+
+// The launches of one axis: `top_stages` stages (block sizes L ... 2 lds_len) in ONE streaming pass without LDS - none
+// if 0 - and the stages of block size lds_len ... 2 in the LDS, sequences of lds_len elements.  Forward (decimation in
+// frequency) the streaming pass runs first, back (decimation in time) last.
+struct GridAxisRoute {
+    int top_stages = 0;
+    int lds_len = 0;
+};
+
+// `row_block`: the block of a row longer than GRID_L_MAX (GRID_ROW_BLOCK or GRID_L_MAX)
+inline GridAxisRoute grid_axis_route(int L, bool columns, int row_block = GRID_ROW_BLOCK) {
+    GridAxisRoute r;
+    const int whole = columns ? GRID_COL_LDS : GRID_L_MAX;   // the longest axis that runs in the LDS alone
+    r.lds_len = L <= whole ? L : columns ? GRID_COL_LDS : row_block;
+    r.top_stages = grid_log2(L / r.lds_len);
+    return r;
+}
+
+// "top,lds" / "lds,top" / "lds": the kernels of an axis in launch order
+inline const char *grid_route_order(const GridAxisRoute &r, bool inverse) {
+    return r.top_stages == 0 ? "lds" : inverse ? "lds,top" : "top,lds";
+}
 
 }  // namespace ml

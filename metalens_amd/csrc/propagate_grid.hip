@@ -25,6 +25,12 @@
 //            wave reads 1 KiB contiguous per element).
 // Rows that are zero are not transformed: the forward row pass takes the nx aperture rows, the inverse row pass the mx
 // target rows (launch arguments; the column passes take every column).
+// The long plan (ml_propagate_plan_grid_long) takes an axis of L = 16384 as well (grid_axis_route):
+//   rows:    the stages above a block of GRID_ROW_BLOCK elements in a streaming pass (grid_rows_top_kernel: the
+//            L / GRID_ROW_BLOCK elements of one row at that stride per thread, adjacent lanes adjacent elements), the
+//            rest on blocks of a row in the LDS (grid_rows_block_kernel);
+//   columns: the streaming pass with 16 elements per thread, then the blocks of 1024.
+// An axis of L <= 8192 of a long plan goes through the launches above.
 #include "nearfield_math.h"
 
 namespace ml {
@@ -164,6 +170,36 @@ __global__ __launch_bounds__(256) void grid_cols_top_kernel(const GridFftArgs a)
     for (int e = 0; e < (1 << R); ++e) g[e * step] = v[e];
 }
 
+// the R stages of block size Ly ... Ly >> (R - 1) along y of the rows [0, rows), without LDS: a thread holds the 2^R
+// elements pos0 + e (Ly >> R) of one row; adjacent lanes take adjacent pos0 (a wave reads 1 KiB contiguous per element)
+template <int R, bool INV>
+__global__ __launch_bounds__(256) void grid_rows_top_kernel(const GridFftArgs a) {
+    const int estride = a.Ly >> R;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < rows estride (estride: a multiple of 256)
+    const int row = (int)(id / estride), pos0 = (int)(id - (size_t)row * estride);
+    d2 *g = a.planes + blockIdx.y * a.plane_stride + (size_t)row * a.Ly + pos0;
+    d2 v[1 << R];
+#pragma unroll
+    for (int e = 0; e < (1 << R); ++e) v[e] = g[(size_t)e * estride];
+    stage_group<R, INV>(v, a.tw, a.Ly, a.Ly, pos0, estride);
+#pragma unroll
+    for (int e = 0; e < (1 << R); ++e) g[(size_t)e * estride] = v[e];
+}
+
+// block blockIdx.x of per_wg elements of the rows [0, rows) of plane blockIdx.y along y (the blocks of a plane's leading
+// rows are contiguous: block b of row r starts at (r Ly / per_wg + b) per_wg): the stages of block size per_wg and below
+template <bool INV>
+__global__ __launch_bounds__(1024) void grid_rows_block_kernel(const GridFftArgs a) {
+    extern __shared__ __align__(16) unsigned char grid_lds_raw[];
+    d2 *s = reinterpret_cast<d2 *>(grid_lds_raw);
+    const int len = a.per_wg;
+    d2 *g = a.planes + blockIdx.y * a.plane_stride + (size_t)blockIdx.x * len;
+    for (int p = threadIdx.x; p < len; p += blockDim.x) s[grid_lds_slot(p)] = g[p];
+    __syncthreads();
+    lds_stages<INV>(s, 1, len, grid_lds_seq(len), a.tw, a.Ly);
+    for (int p = threadIdx.x; p < len; p += blockDim.x) g[p] = s[grid_lds_slot(p)];
+}
+
 struct GridGeoArgs {
     d2 *out;               // kernel planes [8][Lx][Ly]
     size_t plane_stride;
@@ -288,6 +324,35 @@ static int big_lds(Kern kern, bool &done) {
     return ML_OK;
 }
 
+template <bool INV>
+static int fft_rows_top(ml_ctx *ctx, const GridFftArgs &a, int n_planes, int R) {   // R = 1, 2
+    const dim3 grid((unsigned)(((size_t)a.rows * (a.Ly >> R)) / 256), n_planes);
+    if (R == 1)
+        hipLaunchKernelGGL((grid_rows_top_kernel<1, INV>), grid, dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((grid_rows_top_kernel<2, INV>), grid, dim3(256), 0, ctx->stream, a);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+// a row longer than GRID_L_MAX: the top stages streaming, blocks of the row in the LDS (grid_axis_route)
+template <bool INV>
+static int fft_rows_long(ml_ctx *ctx, GridFftArgs a, int n_planes) {
+    static bool attr_done = false;   // per instantiation
+    ML_TRY(big_lds(grid_rows_block_kernel<INV>, attr_done));
+    // (diagnostic build: ML_GRID_ROW_BLOCK=8192 takes whole blocks of GRID_L_MAX, one stage streaming, for timing)
+    const bool whole = diag_int("ML_GRID_ROW_BLOCK", GRID_ROW_BLOCK) == GRID_L_MAX;
+    const GridAxisRoute r = grid_axis_route(a.Ly, false, whole ? GRID_L_MAX : GRID_ROW_BLOCK);
+    a.per_wg = r.lds_len;
+    if (!INV) ML_TRY(fft_rows_top<INV>(ctx, a, n_planes, r.top_stages));
+    const size_t lds = (size_t)grid_lds_seq(a.per_wg) * sizeof(d2);
+    hipLaunchKernelGGL(grid_rows_block_kernel<INV>, dim3((unsigned)((size_t)a.rows * (a.Ly / a.per_wg)), n_planes),
+                       dim3(std::min(1024, a.per_wg / 8)), lds, ctx->stream, a);
+    ML_HIP(hipGetLastError());
+    if (INV) ML_TRY(fft_rows_top<INV>(ctx, a, n_planes, r.top_stages));
+    return ML_OK;
+}
+
 // `planes` planes along y, rows [0, rows)
 template <bool INV>
 static int fft_rows(ml_ctx *ctx, d2 *planes, int n_planes, int rows) {
@@ -301,6 +366,7 @@ static int fft_rows(ml_ctx *ctx, d2 *planes, int n_planes, int rows) {
     a.Lx = pp.grid.Lx;
     a.Ly = pp.grid.Ly;
     a.rows = rows;
+    if (a.Ly > GRID_L_MAX) return fft_rows_long<INV>(ctx, a, n_planes);
     a.per_wg = std::max(1, 2048 / a.Ly);
     const int elems = a.per_wg * a.Ly, threads = std::min(1024, std::max(256, elems / 8));
     const size_t lds = (size_t)a.per_wg * grid_lds_seq(a.Ly) * sizeof(d2);
@@ -324,14 +390,16 @@ static int fft_cols_lds(ml_ctx *ctx, GridFftArgs a, int n_planes) {
 
 template <bool INV>
 static int fft_cols_top(ml_ctx *ctx, const GridFftArgs &a, int n_planes) {
-    const int R = grid_log2(a.Lx / a.per_wg);   // 1 ... 3
+    const int R = grid_log2(a.Lx / a.per_wg);   // 1 ... 3; 4: Lx = 16384 of the long plan
     const dim3 grid((unsigned)(((size_t)(a.Lx >> R) * a.Ly) / 256), n_planes);
     if (R == 1)
         hipLaunchKernelGGL((grid_cols_top_kernel<1, INV>), grid, dim3(256), 0, ctx->stream, a);
     else if (R == 2)
         hipLaunchKernelGGL((grid_cols_top_kernel<2, INV>), grid, dim3(256), 0, ctx->stream, a);
-    else
+    else if (R == 3)
         hipLaunchKernelGGL((grid_cols_top_kernel<3, INV>), grid, dim3(256), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((grid_cols_top_kernel<4, INV>), grid, dim3(256), 0, ctx->stream, a);
     ML_HIP(hipGetLastError());
     return ML_OK;
 }
@@ -347,8 +415,9 @@ static int fft_cols(ml_ctx *ctx, d2 *planes, int n_planes) {
     a.Lx = pp.grid.Lx;
     a.Ly = pp.grid.Ly;
     a.rows = a.Lx;
-    a.per_wg = std::min(a.Lx, GRID_COL_LDS);
-    const bool top = a.Lx > a.per_wg;
+    const GridAxisRoute r = grid_axis_route(a.Lx, true);
+    a.per_wg = r.lds_len;
+    const bool top = r.top_stages > 0;
     if (top && !INV) ML_TRY(fft_cols_top<INV>(ctx, a, n_planes));
     ML_TRY(fft_cols_lds<INV>(ctx, a, n_planes));
     if (top && INV) ML_TRY(fft_cols_top<INV>(ctx, a, n_planes));
@@ -363,6 +432,8 @@ static int upload_twiddles(ml_ctx *ctx, DevBuf &buf, int L) {
     return ML_OK;
 }
 
+static int grid_cap(int method) { return method == ML_PROPAGATE_FFT_LONG ? GRID_L_LONG_MAX : GRID_L_MAX; }
+
 // the workspace and the kernel spectra for the resident field's shape (kept while the shape stays)
 static int grid_prepare(ml_ctx *ctx) {
     PropagatePlan &pp = ctx->prop;
@@ -371,7 +442,7 @@ static int grid_prepare(ml_ctx *ctx) {
     const int mx = pp.grid.mx, my = pp.grid.my;
     char why[320];
     GridPlanFacts f;
-    if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, pp.want_h, &f, why, sizeof why) != 0) {
+    if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, pp.want_h, &f, why, sizeof why, grid_cap(pp.method)) != 0) {
         set_error("%s", why);
         return ML_EINVAL;
     }
@@ -446,14 +517,13 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
 
 using namespace ml;
 
-extern "C" {
-
-int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
-                           double tx0, double ty0, int mx, int my, double z, int want_h) {
+// ml_propagate_plan_grid and ml_propagate_plan_grid_long: `entry` is the caller's name, `method` its ML_PROPAGATE_*
+static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, double y0, double dxp, double dyp, double wavelength,
+                     double n_glass, double tx0, double ty0, int mx, int my, double z, int want_h) {
     ML_REQUIRE(ctx, "ctx is NULL");
-    ML_REQUIRE(ctx->n_ranks <= 1, "ml_propagate_plan_grid: this context belongs to a communicator of %d ranks; the "
+    ML_REQUIRE(ctx->n_ranks <= 1, "%s: this context belongs to a communicator of %d ranks; the "
                "finite-distance propagator sums a whole aperture on one GPU (sharded propagation is not implemented)",
-               ctx->n_ranks);
+               entry, ctx->n_ranks);
     ML_REQUIRE(mx >= 1 && my >= 1, "no targets");
     ML_REQUIRE(wavelength > 0 && n_glass > 0 && dxp > 0 && dyp > 0, "bad geometry");
     ML_REQUIRE(z > 0, "the target plane lies at z = %g: the propagator needs z > 0", z);
@@ -463,8 +533,8 @@ int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double
     f.my = my;
     if (ctx->fields.nx && ctx->fields.ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
         char why[320];
-        if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, &f, why, sizeof why) != 0) {
-            set_error("ml_propagate_plan_grid: %s", why);
+        if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, &f, why, sizeof why, grid_cap(method)) != 0) {
+            set_error("%s: %s", entry, why);
             return ML_EINVAL;
         }
     }
@@ -472,7 +542,7 @@ int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double
     PropagatePlan &pp = ctx->prop;
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
     pp.spectra_ready = false;
-    pp.method = ML_PROPAGATE_FFT;
+    pp.method = method;
     pp.grid = f;
     pp.T = mx * my;
     pp.want_h = want_h != 0;
@@ -489,6 +559,20 @@ int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double
     return ML_OK;
 }
 
+extern "C" {
+
+int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                           double tx0, double ty0, int mx, int my, double z, int want_h) {
+    return plan_grid(ctx, "ml_propagate_plan_grid", ML_PROPAGATE_FFT, x0, y0, dxp, dyp, wavelength, n_glass, tx0, ty0, mx, my, z,
+                     want_h);
+}
+
+int ml_propagate_plan_grid_long(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                                double tx0, double ty0, int mx, int my, double z, int want_h) {
+    return plan_grid(ctx, "ml_propagate_plan_grid_long", ML_PROPAGATE_FFT_LONG, x0, y0, dxp, dyp, wavelength, n_glass, tx0, ty0,
+                     mx, my, z, want_h);
+}
+
 int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *workspace_bytes) {
     ML_REQUIRE(ctx, "ctx is NULL");
     const PropagatePlan &pp = ctx->prop;
@@ -496,7 +580,7 @@ int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *
         set_error("no propagation plan is active");
         return ML_ESTATE;
     }
-    const bool fft = pp.method == ML_PROPAGATE_FFT;
+    const bool fft = pp.method != ML_PROPAGATE_DIRECT;
     if (method) *method = pp.method;
     if (lx) *lx = fft ? pp.grid.Lx : 0;
     if (ly) *ly = fft ? pp.grid.Ly : 0;

@@ -19,6 +19,8 @@ GPU-resident near field; for ``R -> infinity`` it reduces to the amplitudes behi
 ``method='fft'``: for a tensor grid of targets on the aperture's own pitch every factor of a (sample, target) pair
 depends on the lag ``(i_t - i_s, j_t - j_s)`` alone, and the same sum runs as a zero-padded circular convolution
 (csrc/propagate_grid.hip): ``O(L^2 log L)`` with ``L >= n + m - 1`` per axis instead of ``n^2 m^2`` pairs.
+``method='fft-long'`` is the same with padded axes of up to 16384 instead of 8192 - apertures of 4097 ... 8192 samples a
+side - and a workspace of up to 77 GB.
 """
 import numpy as np
 
@@ -43,8 +45,10 @@ def _targets(x, y, z, point_list):
     return x, y, z
 
 
-METHODS = ('direct', 'fft')
+METHODS = ('direct', 'fft', 'fft-long')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
 GRID_L_MAX = 8192   # csrc/propagate_grid.h
+GRID_L_LONG_MAX = 16384
+_GRID_CAP = {'fft': GRID_L_MAX, 'fft-long': GRID_L_LONG_MAX}
 
 
 def _padded_length(n, m):
@@ -102,6 +106,13 @@ class PlanePropagator:
     ``(12 + 6 or 3) Lx Ly`` complex128 (``plan_info()``).  Everything else - ``propagate_sets``, ``accumulate``,
     ``sums``, ``SourceSweep.run(image=...)`` - is as for the direct method.  The kernel spectra are computed by the
     first pass and kept while this propagator stays the one that planned last on the context.
+
+    ``method='fft-long'`` is ``'fft'`` with ``L`` of at most 16384 (ml_propagate_plan_grid_long): for apertures of 4097
+    ... 8192 samples a side, which ``'fft'`` can give one target per axis at the most.  The same checks, the same
+    results - bit for bit where both methods accept a problem; an axis of ``L = 16384`` takes one more pass over the
+    planes per transform.  It is a method of its own because of its workspace: ``(12 + 6 or 3) Lx Ly 16`` bytes are up
+    to 77 GB (64 GB with ``want_h=False``) where ``'fft'`` never reserves more than 18 GB.  The first pass reserves it
+    and raises ``MetalensHipError`` with the bytes asked for if the device cannot give them.
     """
 
     def __init__(self, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False, want_h=True,
@@ -113,29 +124,33 @@ class PlanePropagator:
         _check_axis(xp_list, wavelength)
         _check_axis(yp_list, wavelength)
         self.point_list, self.want_h = bool(point_list), bool(want_h)
-        if method == 'fft' and self.point_list:
-            raise ValueError("method='fft' takes a tensor grid of targets on the aperture's pitch, not a point list")
+        if method in _GRID_CAP and self.point_list:
+            raise ValueError("method=%r takes a tensor grid of targets on the aperture's pitch, not a point list" % method)
         self.x, self.y, self.z = _targets(x, y, z, self.point_list)
         self.shape = (self.x.size,) if self.point_list else (self.x.size, self.y.size)
         self.aperture_shape = (len(xp_list), len(yp_list))
         self._geometry = (float(xp_list[0]), float(yp_list[0]), float(xp_list[1] - xp_list[0]),
                           float(yp_list[1] - yp_list[0]), float(wavelength), float(n_glass))
-        if method == 'fft':
+        if method in _GRID_CAP:
             _on_pitch('x', self.x, self._geometry[2])
             _on_pitch('y', self.y, self._geometry[3])
+            cap = _GRID_CAP[method]
             for name, n, m in (('x', self.aperture_shape[0], self.x.size), ('y', self.aperture_shape[1], self.y.size)):
                 L = _padded_length(n, m)
-                if L > GRID_L_MAX:
-                    raise ValueError("method='fft' pads the %s axis of n = %d samples and m = %d targets to L = %d > %d; "
-                                     "use method='direct' or fewer targets per propagator" % (name, n, m, L, GRID_L_MAX))
+                if L > cap:
+                    hint = " or, up to L = %d, method='fft-long'" % GRID_L_LONG_MAX if method == 'fft' else ''
+                    raise ValueError("method=%r pads the %s axis of n = %d samples and m = %d targets to L = %d > %d; "
+                                     "use method='direct' or fewer targets per propagator%s"
+                                     % (method, name, n, m, L, cap, hint))
         self.ctx = ctx or _lib.default_context()
         self.owner = _lib.new_owner()
         self._plan()
 
     def _plan(self):
         ctx = self.ctx
-        if self.method == 'fft':
-            _lib.check(ctx.lib.ml_propagate_plan_grid(
+        if self.method in _GRID_CAP:
+            entry = ctx.lib.ml_propagate_plan_grid if self.method == 'fft' else ctx.lib.ml_propagate_plan_grid_long
+            _lib.check(entry(
                 ctx.handle, *self._geometry, float(self.x[0]), float(self.y[0]), self.x.size, self.y.size,
                 float(self.z[0]), int(self.want_h)))
         else:

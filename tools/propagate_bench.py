@@ -28,7 +28,17 @@ m x m patch on the aperture's pitch around the focus, off its lattice by 0.3 / 0
 first pass (workspace, kernel fill and its transform, once), the direct pass, max |E_fft - E_direct| / max |E|, and crossover_targets = the target count
 from which the cached FFT pass is the faster one, by the direct sum's time per target (it is linear in the targets).
 Then 'fft' alone: 4096^2 -> 4096^2 (L = 8192^2, 18 / 15 GiB of workspace), and the three sets of a synthesised x, y, z
-batch in one ml_propagate_sets call, 2048^2 -> 64^2."""
+batch in one ml_propagate_sets call, 2048^2 -> 64^2.
+
+    python tools/propagate_bench.py --method fft-long [--quick] >> profiles/propagate_bench.txt     (needs an MI355X)
+
+--method fft-long: ``PlanePropagator(method='fft-long')`` for the 8192^2 aperture (L = 16384^2, 72 / 60 GiB of workspace):
+8192^2 -> 64^2 and 8192^2 -> 4096^2 on the pitch, E + H and E only.  ms = a pass on cached kernel spectra, ms_first = plan
++ first pass with the workspace already reserved (kernel fill and the transform of the eight spectra),
+ms_first_with_workspace = the same from a context that holds no workspace (the hipMalloc on top).  The direct sum runs
+once, on 8192^2 -> 64^2 with E + H (best of two passes): max |E_fft-long - E_direct| / max |E| and crossover_targets as
+above.  A workspace the device cannot give is reported with the library's message, and the E-only rows follow.
+--quick: 8192^2 -> 64^2, E + H, without the direct sum."""
 import json
 import os
 import re
@@ -196,6 +206,58 @@ def fft_against_direct(quick):
             print(json.dumps(line), flush=True)
 
 
+def fft_long(quick, n=8192):
+    import numpy as np
+
+    from metalens_amd import _lib
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl, n_glass = 580e-9, 1.46
+    x, f = converging_wave(ctx, n, wl, n_glass)
+    one_target = x[:1] + 0.3 * (x[1] - x[0])
+    for m in (64,) if quick else (64, 4096):
+        tx, ty = patch_on_pitch(x, m)
+        for want_h in (True,) if quick else (True, False):
+            line = {'case': '%d^2 -> %d^2 on the pitch' % (n, m), 'fields': 'E+H' if want_h else 'E', 'method': 'fft-long'}
+
+            def first_pass():
+                t0 = time.perf_counter()
+                p = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx, method='fft-long')
+                _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0))
+                ctx.sync()
+                return p, (time.perf_counter() - t0) * 1e3
+            # a direct plan releases the workspace of an FFT plan: the first pass after it reserves it again
+            PlanePropagator(x, x, wl, n_glass, one_target, one_target, f, want_h=want_h, ctx=ctx)
+            try:
+                p, ms_cold = first_pass()
+            except _lib.MetalensHipError as e:
+                line['error'] = str(e)
+                print(json.dumps(line), flush=True)
+                continue
+            p, ms_first = first_pass()
+            ms = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0)))
+            info = p.plan_info()
+            line.update(ms=round(ms, 3), ms_first=round(ms_first, 3), ms_first_with_workspace=round(ms_cold, 3),
+                        ms_workspace_hipMalloc=round(ms_cold - ms_first, 3), L=[info['Lx'], info['Ly']],
+                        workspace_MiB=round(info['workspace_bytes'] / 2 ** 20, 1))
+            if m == 64 and want_h and not quick:
+                got = p._download(None)
+                pd = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx)
+
+                def one():
+                    t0 = time.perf_counter()
+                    _lib.check(ctx.lib.ml_propagate(ctx.handle, pd.Z0))
+                    ctx.sync()
+                    return (time.perf_counter() - t0) * 1e3
+                ms_direct = min(one(), one())
+                want = pd._download(None)
+                diff = max(np.abs(got[c] - want[c]).max() for c in ('Ex', 'Ey', 'Ez')) / max(np.abs(want[c]).max() for c in ('Ex', 'Ey', 'Ez'))
+                line.update(ms_direct=round(ms_direct, 3), speedup=round(ms_direct / ms, 2),
+                            crossover_targets=int(np.ceil(ms / (ms_direct / (m * m)))),
+                            max_E_difference_of_the_methods=float('%.3e' % diff))
+            print(json.dumps(line), flush=True)
+
+
 def fft_three_sets(n=2048, m=64):
     """the three sets of a synthesised x, y, z batch through ONE ml_propagate_sets call of an 'fft' plan"""
     import math
@@ -232,6 +294,9 @@ def fft_three_sets(n=2048, m=64):
 
 
 def main():
+    if '--method' in sys.argv and sys.argv[sys.argv.index('--method') + 1] == 'fft-long':
+        fft_long('--quick' in sys.argv)
+        return
     if '--method' in sys.argv and sys.argv[sys.argv.index('--method') + 1] == 'fft':
         quick = '--quick' in sys.argv
         fft_against_direct(quick)
