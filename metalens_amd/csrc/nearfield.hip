@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "nearfield_dev.h"
+#include "synth_staging.h"
 
 namespace ml {
 
@@ -193,9 +194,9 @@ void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int 
     a.general_mask = K.general_mask;
     a.narrow_mask = K.narrow_mask;
     a.centre_general = K.centre_general;
-    a.narrow_pitch = UNIT * K.narrow_slots_max + 1;
-    // (eight blocks of up to three orders or six of four: nearfield_simple.hip RING_LDS_NARROW)
-    a.narrow_cap = std::min(8, (8 * (3 * UNIT + 1)) / a.narrow_pitch);
+    // (eight blocks of up to three orders or six of four: synth_staging.h)
+    a.narrow_pitch = narrow_pitch(K.narrow_slots_max);
+    a.narrow_cap = narrow_cap(a.narrow_pitch);
     a.center_tab = lens.center_qmajor.as<double2>();
     a.center_n_slots = lens.centre.n_slots;
     a.center_lo = lens.centre.lo;

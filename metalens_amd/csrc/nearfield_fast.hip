@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "nearfield_math.h"
+#include "synth_staging.h"
 
 namespace ml {
 
@@ -384,8 +385,7 @@ __global__ __launch_bounds__(COMPACT_CHUNK) void active_compact_kernel(const int
 // the wave finds its distinct (ring, cell) blocks, fetches each ONCE (one wave-wide load = the
 // 16 complex of 4 orders), parks them in LDS, and every lane then reads its block from LDS, where
 // equal addresses broadcast and a wave-wide 16-byte read costs 4 cycles instead of 16.
-constexpr int NF_SLOTS = 6;                  // distinct (ring, cell) blocks staged per round
-constexpr int NF_CHUNK = 4;                  // orders per staging pass (64 lanes = 4 x 4 x 4)
+// (NF_SLOTS distinct blocks staged per round, NF_CHUNK orders per staging pass: synth_staging.h)
 constexpr int NF_PITCH = NF_CHUNK * 16 + 1;  // +1: blocks start in different 16-byte bank slots
 static_assert(16 * CENTER_TYPES <= NF_SLOTS * NF_PITCH && CENTER_TYPES % 4 == 0, "the centre block must fit the ring slots");
 

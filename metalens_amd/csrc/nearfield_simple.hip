@@ -49,32 +49,11 @@
 #include <type_traits>
 
 #include "nearfield_math.h"
+#include "synth_staging.h"
 
 namespace ml {
 
-constexpr int SK_SLOTS = 6;                     // distinct (ring, cell) blocks staged per round, at most
-// complex in the ring kernel's block buffer.  Twenty waves of a CU (five per SIMD) could have 8 KB each
-// of its 160 KB - but at exactly that size a wave that ends leaves a hole only an identical neighbour
-// fits and the measured occupancy drops by 6 %: a lens of narrow collections (up to SIMPLE_NARROW_SLOTS
-// orders: six blocks at a fixed pitch) takes 6.2 KB, the wide instantiation ML_RING_LDS_WIDE complex
-#ifndef ML_RING_LDS_WIDE
-#define ML_RING_LDS_WIDE 448
-#endif
-// (narrow: six blocks of four orders, or EIGHT of three - the pitch is the lens' widest narrow collection's,
-// NfArgs::narrow_pitch / narrow_cap: at NA 0.94 a patch spans five to six of the outer rings and more than one
-// table cell, and every block beyond the round's capacity costs the wave a second round - the whole order loop
-// again for a few lanes)
-constexpr int SK_SLOTS_NARROW = 8;
-constexpr int RING_LDS_NARROW = SK_SLOTS_NARROW * (3 * UNIT + 1), RING_LDS = ML_RING_LDS_WIDE;
-static_assert(SK_SLOTS * (SIMPLE_NARROW_SLOTS * UNIT + 1) <= RING_LDS_NARROW, "six blocks of four orders fit");
-// order slots per pass of the wide instantiation: what n blocks leave each other of the buffer,
-// (RING_LDS / n - 1) / 16 for n = 1 ... 6 blocks, four bits each
-constexpr unsigned slots_per_pass(int n) { return (unsigned)((RING_LDS / n - 1) / UNIT < 15 ? (RING_LDS / n - 1) / UNIT : 15); }
-constexpr unsigned UPP_TABLE = slots_per_pass(1) | slots_per_pass(2) << 4 | slots_per_pass(3) << 8 | slots_per_pass(4) << 12 |
-                               slots_per_pass(5) << 16 | slots_per_pass(6) << 20;
-static_assert(slots_per_pass(SK_SLOTS) >= 1, "block buffer too small");
-constexpr int SK_TYPES = 20;                    // centre: cell types per staged block (the reference's default K, lens_center.py:28)
-static_assert(SK_TYPES == CENTER_GROUP, "the centre table's cell blocks hold groups of SK_TYPES types");
+// (SK_SLOTS, SK_SLOTS_NARROW, RING_LDS, RING_LDS_NARROW, slots_per_pass / UPP_TABLE, SK_TYPES: synth_staging.h)
 
 // The launch's scalars and table pointers a patch needs again and again.  Read from the kernel
 // arguments ONCE, at the start of the wave, and pinned in scalar registers (the empty asm statement

@@ -88,8 +88,8 @@ def build_nearfield(source_x, source_y, source_z, source_pol, wavelength,
                     decisions=None):
     """Same signature and return tuple as the reference (nearfield.py:66-68,480)
     plus explicit ``c0`` / ``Z0``.  If ``decisions`` is a dict it
-    receives the per-sample discrete decisions (ring, sector, nearest cell) for
-    parity diagnostics."""
+    receives the per-sample discrete decisions (ring, collection, sector and the
+    direction of incidence in its frame, nearest cell) for parity diagnostics."""
     assert source_z < 0
     assert source_pol in ('x', 'y', 'z')
     S = lens_periphery_summary
@@ -317,6 +317,11 @@ def build_nearfield(source_x, source_y, source_z, source_pol, wavelength,
         decisions['ring'] = ring
         decisions['in_center'] = in_center
         decisions['sector'] = sector
+        # the collection of a ring sample (-1: none) and its direction of incidence in the sector's frame: what
+        # the table cell a sample interpolates in is located by (tests/synth_cases.py census)
+        decisions['which_gc'] = which_gc
+        decisions['uxp'] = uxp
+        decisions['uyp'] = uyp
         decisions['nearest'] = nearest
         decisions.setdefault('nearest_tie', np.zeros(X.shape, dtype=bool))
     return Ex, Ey, Hx, Hy, x_pts, y_pts, power, n_glass

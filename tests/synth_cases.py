@@ -1,0 +1,411 @@
+"""The cases of the synthesis kernels' staging rounds and passes that the suite runs, in one table, and the census
+that says which of those paths an input reaches.
+
+The ring kernels of csrc/nearfield_simple.hip and the general kernel of csrc/nearfield_fast.hip serve the 64 samples
+of an 8 x 8 patch in ROUNDS of up to a capacity of distinct (ring, table cell) blocks staged through LDS, the wide
+ring instantiation a round in PASSES of as many order slots as fit its buffer (csrc/synth_staging.h).  Which of
+these paths run depends on the data: how many rings and table cells a patch spans.  The census counts, on the host,
+the distinct (ring, i0, i1) blocks per patch and collection - from the oracle's per-sample decisions (ring,
+collection, direction of incidence in the sector's frame) and the tables' own axes - and turns them into rounds and
+passes by the rules tools/synth_staging prints (never by copies of them here).  Every case CLAIMS branch tags;
+test_synth_cases.py holds the census to confirm each claim with margin and the table to reach every tag of TAGS;
+test_gpu_synth_cases.py runs every case on the GPU against the oracle.  Plain data and pure functions, no test
+collects from here.
+
+Sizes: lenses of 20 um radius at NA 0.94 (focal distance 7.3 um, 24 rings in four collections), table axes of 33
+nodes.  At that size a patch meets plenty of blocks: the rings are 0.6 to 2.8 um wide against a patch of 2.3 um, the
+direction of incidence crosses a ux' cell of 0.02 to 0.03 within a few um, and uy' - a sawtooth over the sectors of
+a ring, centred on the node uy' = 0 of an odd axis - reaches +-0.02 at the inner rings, three cells of 0.0125.  One
+window of 43 x 37 samples (partial patches on both far sides) holds patches of one block and of thirty.
+
+A pass or chunk of orders shows in the result only if one of its orders propagates in air, (ux' + ox lambda /
+period)^2 + uy'^2 <= 1: at the angles of that lens -3 ... +1 at most.  The general lists therefore END on (0, 0) or
+the design order (-1, 0), the five- and eight-slot lists have them in their last pass, and the eleven-slot list -
+slots -5 ... +5, its third pass +3 ... +5 - has a lens of its own: 204 um of focal length, rings at 4 to 12 degrees,
+the source at 0.3 of that distance so that a patch still spans up to ten blocks.  The census counts a round of n
+blocks, and an order count of the general kernel, only where every sample evaluates an order of the last pass or chunk.
+"""
+import collections
+import math
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WAVELENGTH = 580e-9
+NUM_GRATINGS = 3      # periods per collection: the period axis is interpolated on the host, per ring
+NUM_ENTRIES = 4       # centre cell types (the centre kernel's rounds are not this table's subject)
+CENTRE_U_STEPS = 5
+
+# ---- the table -----------------------------------------------------------------------------------------------------
+# Lens: synthetic.make_lens parameters.  periphery_orders: one order list per collection, cycled from the innermost
+# collection outwards (a list of one list: every collection the same).
+Lens = collections.namedtuple('Lens', 'radius na u_steps span_deg periphery_orders center_orders switch_deg')
+Lens.__new__.__defaults__ = (12,)
+# window: centre as (fraction of the lens radius, azimuth in degrees), shape (nx, ny), pitch = wavelength / pitch_div.
+# source: (x, y, h) of the dipole, h focal distances below the lens (1: where the lens was designed for).  pols: the polarisations run one by one.
+# batch: also run the three-polarisation batch.  family: what nearfield_kernels() is to report.
+Case = collections.namedtuple('Case', 'lens at shape pitch_div source pols batch family tags')
+
+
+def ox(*orders):
+    return tuple((o, 0) for o in orders)
+
+
+O1 = ox(-1)
+O2 = ox(-1, 0)
+O3 = ox(-1, 0, 1)
+O4 = ox(-2, -1, 0, 1)
+O4_HOLE = ox(-1, 2)                              # four slots from -1, the middle two holes
+O5 = ox(-4, -3, -2, -1, 0)
+O8 = ox(-4, -3, -2, -1, 0, 1, 2, 3)
+O10_SPARSE = ox(-5, -3, -1, 0, 2, 4)             # ten slots, six present
+O11 = ox(-5, -4, -3, -2, -1, 0, 1, 2, 3, 4, 5)
+# general lists: an order with oy != 0 (none of those propagates in air: the lateral period is below a wavelength);
+# sorted - the order the tables hold them in - each ends on an order that propagates everywhere, (0, 0) or the design
+# order (-1, 0), so that the last chunk of four shows in the result
+G4 = ((-2, 1), (-1, 0), (0, -1), (0, 0))
+G5 = ((-3, 0), (-2, 0), (-2, 1), (-1, 0), (0, 0))
+G9 = ((-5, 0), (-4, 0), (-3, 0), (-3, 1), (-2, -1), (-2, 0), (-2, 1), (-1, -1), (-1, 0))
+
+TAGS = (
+    'narrow:round-exactly-capacity', 'narrow:second-round-capacity-8', 'narrow:second-round-capacity-6',
+    'narrow:third-round', 'narrow:slots-1', 'narrow:slots-2', 'narrow:slots-3', 'narrow:slots-4',
+    'narrow:present-hole', 'narrow:lens-of-different-slot-counts', 'narrow:two-collections-in-a-wave',
+    'narrow:multi-round-partial-patches',
+    'wide:11-slots-round-of-1', 'wide:11-slots-round-of-2', 'wide:11-slots-round-of-3', 'wide:11-slots-round-of-4',
+    'wide:11-slots-round-of-5', 'wide:11-slots-round-of-6', 'wide:8-slots-round-of-6', 'wide:5-slots-round-of-6',
+    'wide:sparse-10-slots', 'wide:second-round', 'wide:third-round', 'wide:two-collections-in-a-wave',
+    'wide:multi-round-partial-patches',
+    'general:second-round', 'general:orders-4', 'general:orders-5', 'general:orders-9',
+    'general:multi-round-partial-patches',
+)
+
+SOURCE = (0.3e-6, -0.2e-6, 1.0)   # off the axis: no sample pair sees the same direction
+RADIUS, NA, U_STEPS, SPAN_DEG = 20e-6, 0.94, 33, 20
+# collections 0 ... 3 from the switch radius outwards: 1, 3, 6 and 14 rings, starting at 0.15, 0.21, 0.36 and 0.58 of
+# the radius
+LENS_N8 = Lens(RADIUS, NA, U_STEPS, SPAN_DEG, (O3, O1, O2), O3)             # slots 3, 1, 2, 3: pitch 49, capacity 8
+LENS_N6 = Lens(RADIUS, NA, U_STEPS, SPAN_DEG, (O3, O4_HOLE, O2, O4), O3)    # slots 3, 4 (holes), 2, 4: pitch 65, capacity 6
+LENS_W = Lens(RADIUS, NA, U_STEPS, SPAN_DEG, (O5, O10_SPARSE, O8, O11), O3)
+# a long focal length (204 um; eight rings at 4 to 12 degrees, one collection): where the orders up to +5 of an
+# eleven-slot list propagate, so that the wide instantiation's second and third pass show in the result
+LENS_W11 = Lens(46e-6, 0.22, 65, SPAN_DEG, (O11,), O3, switch_deg=3)
+LENS_G = Lens(RADIUS, NA, U_STEPS, SPAN_DEG, (G4, G9, G5), O3)              # orders 4, 9, 5, 4; the centre simple
+LENS_GG = Lens(RADIUS, NA, U_STEPS, SPAN_DEG, (G4, G9, G5), G4)             # the general kernel alone
+
+
+def _case(lens, at, shape, pols, family, tags, batch=False, source=SOURCE):
+    return Case(lens, at, shape, 2.05, source, pols, batch, family, tuple(tags))
+
+
+SIMPLE, MIXED, GENERAL = 'orders-along-x', 'mixed', 'general'
+CASES = {
+    # across collections 1, 2 and 3 (slots 1, 2, 3): up to 27 blocks of a collection in a patch, four rounds
+    'narrow-8': _case(LENS_N8, (0.5, 20), (43, 37), 'x', SIMPLE, batch=True, tags=(
+        'narrow:round-exactly-capacity', 'narrow:second-round-capacity-8', 'narrow:third-round', 'narrow:slots-1',
+        'narrow:slots-2', 'narrow:slots-3', 'narrow:lens-of-different-slot-counts',
+        'narrow:two-collections-in-a-wave', 'narrow:multi-round-partial-patches')),
+    # the rim (five to six rings per patch, as on the 2 mm lens of test_gpu_parity.py - but three rounds on these
+    # axes): whole patches only, the window at 45 degrees
+    'narrow-8-rim': _case(LENS_N8, (0.93, 45), (48, 40), 'z', SIMPLE, tags=(
+        'narrow:second-round-capacity-8', 'narrow:slots-3')),
+    # a four-slot collection in the lens: six blocks per round; collections 0 ... 3 all in the window
+    'narrow-6': _case(LENS_N6, (0.35, 0), (43, 37), 'y', SIMPLE, tags=(
+        'narrow:round-exactly-capacity', 'narrow:second-round-capacity-6', 'narrow:third-round', 'narrow:slots-2',
+        'narrow:slots-3', 'narrow:slots-4', 'narrow:present-hole', 'narrow:lens-of-different-slot-counts',
+        'narrow:two-collections-in-a-wave', 'narrow:multi-round-partial-patches')),
+    # the wide instantiation: eleven slots in collection 3 (of which -3 ... +1 propagate at these angles: the first
+    # pass of a round of three blocks and more), eight in 2, ten with holes in 1, five in 0
+    'wide-a': _case(LENS_W, (0.5, 45), (43, 37), 'z', SIMPLE, batch=True, tags=(
+        'wide:11-slots-round-of-1', 'wide:8-slots-round-of-6', 'wide:sparse-10-slots', 'wide:second-round',
+        'wide:third-round', 'wide:two-collections-in-a-wave', 'wide:multi-round-partial-patches')),
+    'wide-b': _case(LENS_W, (0.4, 20), (43, 37), 'x', SIMPLE, tags=(
+        'wide:5-slots-round-of-6', 'wide:second-round', 'wide:third-round')),
+    # eleven slots in rounds of 1 ... 6 blocks whose last pass holds an order in air: the source at 0.3 of the focal
+    # distance (directions of 0.2 to 0.4 across a patch of up to ten blocks, inside the table's range)
+    'wide-11': _case(LENS_W11, (0.4, 20), (43, 37), 'y', SIMPLE, source=(0.3e-6, -0.2e-6, 0.3), tags=(
+        'wide:11-slots-round-of-1', 'wide:11-slots-round-of-2', 'wide:11-slots-round-of-3', 'wide:11-slots-round-of-4',
+        'wide:11-slots-round-of-5', 'wide:11-slots-round-of-6', 'wide:second-round')),
+    # the general kernel beside the simple centre kernel (from its patch list), and alone (over the whole grid)
+    'general-mixed': _case(LENS_G, (0.25, 0), (43, 37), 'x', MIXED, batch=True, tags=(
+        'general:second-round', 'general:orders-4', 'general:orders-5', 'general:orders-9',
+        'general:multi-round-partial-patches')),
+    'general-alone': _case(LENS_GG, (0.3, 20), (48, 40), 'y', GENERAL, tags=(
+        'general:second-round', 'general:orders-4', 'general:orders-5', 'general:orders-9')),
+}
+
+
+# ---- lenses --------------------------------------------------------------------------------------------------------
+_LENSES = {}
+
+
+def make_lens(spec):
+    """the synthetic lens of a Lens row, built once per row and module run"""
+    if spec not in _LENSES:
+        import metalens_amd as ma
+        from metalens_amd import layout, synthetic
+        wl = WAVELENGTH
+        lens = synthetic.make_lens((ma.Grating, ma.GratingCollection, ma.HexGridSet), layout.make_design,
+                                   radius=spec.radius, numerical_aperture=spec.na, wavelength=wl,
+                                   switch_angle=spec.switch_deg * math.pi / 180, num_gratings=NUM_GRATINGS, num_entries=NUM_ENTRIES,
+                                   max_collection_span=spec.span_deg * math.pi / 180, u_steps=spec.u_steps,
+                                   design_kwargs={'wavelength': wl}, periphery_orders=spec.periphery_orders,
+                                   center_orders=spec.center_orders)
+        if spec.u_steps != CENTRE_U_STEPS:
+            # the centre table on coarse axes whatever the rings' (its cost grows with u_steps^2 and none of these
+            # cases is about it)
+            lens['hexgridset'] = synthetic.make_hexgridset(ma.Grating, ma.HexGridSet, wl, num_entries=NUM_ENTRIES,
+                                                           u_steps=CENTRE_U_STEPS, orders=spec.center_orders)
+            lens['hexgridset'].build_interpolators()
+        _LENSES[spec] = lens
+    return _LENSES[spec]
+
+
+def call_args(case, lens, pol=None):
+    """the arguments of build_nearfield (the package's and the oracle's) for a case"""
+    nx, ny = case.shape
+    pitch = WAVELENGTH / case.pitch_div
+    r, az = case.at[0] * case.lens.radius, case.at[1] * math.pi / 180
+    x = r * math.cos(az) + (np.arange(nx) - 0.5 * (nx - 1)) * pitch
+    y = r * math.sin(az) + (np.arange(ny) - 0.5 * (ny - 1)) * pitch
+    return dict(source_x=case.source[0], source_y=case.source[1], source_z=-case.source[2] * lens['source_distance'],
+                source_pol=pol or case.pols[0], wavelength=WAVELENGTH,
+                lens_periphery_summary=lens['lens_periphery_summary'], lens_center_summary=lens['lens_center_summary'],
+                hexgridset=lens['hexgridset'], x_pts=x, y_pts=y)
+
+
+# ---- the rules -----------------------------------------------------------------------------------------------------
+def staging_rules(out_dir):
+    """what tools/synth_staging prints (csrc/synth_staging.h), as {key: int}; built into out_dir"""
+    out = os.path.join(str(out_dir), '')
+    subprocess.check_call(['make', '-s', '-C', os.path.join(ROOT, 'tools'), 'OUT=' + out, out + 'synth_staging'])
+    res = subprocess.run([out + 'synth_staging'], capture_output=True, text=True, timeout=60, check=True)
+    return {k: int(v) for k, v in (kv.split('=') for kv in res.stdout.split())}
+
+
+# ---- which kernel takes which collection (csrc/lens_pack.h canon_orders, classify_lens) -------------------------------
+Coll = collections.namedtuple('Coll', 'kernel n_slots lo present n_orders orders')
+
+
+def _canon(orders, rules):
+    """(n_slots, lo, present) of a simple order list - orders (ox, 0), |ox| <= 5, each once - else None"""
+    half = (rules['wide_slots_max'] - 1) // 2
+    if any(oy != 0 or abs(o) > half for o, oy in orders) or len(set(orders)) != len(orders):
+        return None
+    lo = min(o for o, _ in orders)
+    n = max(o for o, _ in orders) - lo + 1
+    return n, lo, sum(1 << (o - lo) for o, _ in orders)
+
+
+def classify(order_lists, centre_orders, rules):
+    """order_lists: {collection: its order list} of the collections the rings use; centre_orders: the centre table's
+    or None without centre cells.  -> ({collection: Coll}, the lens' narrow slot maximum, family)"""
+    canon = {c: _canon(o, rules) for c, o in order_lists.items()}
+    centre = _canon(centre_orders, rules) if centre_orders is not None else None
+    simple = any(v is not None for v in canon.values()) or centre is not None
+    colls, narrow_max = {}, 1
+    for c, o in order_lists.items():
+        if canon[c] is None or not simple:
+            colls[c] = Coll('general', 0, 0, 0, len(o), tuple(o))
+            continue
+        n, lo, present = canon[c]
+        narrow = n <= rules['narrow_slots_max']
+        colls[c] = Coll('narrow' if narrow else 'wide', n, lo, present, len(o), tuple(o))
+        if narrow:
+            narrow_max = max(narrow_max, n)
+    general = any(v.kernel == 'general' for v in colls.values()) or (centre_orders is not None and centre is None)
+    family = 'general' if not simple else ('mixed' if general else 'orders-along-x')
+    return colls, narrow_max, family
+
+
+# ---- the census ----------------------------------------------------------------------------------------------------
+# One Patch per 8 x 8 patch with ring samples.  blocks: {collection: distinct (ring, i0, i1) among its samples};
+# rings: the distinct rings among the patch's samples.  evaluated: {collection: the orders that propagate in air - and so
+# add to the field - at EVERY one of its samples in the patch}: a pass or chunk of orders none of which is evaluated
+# runs without a trace in the result.
+Patch = collections.namedtuple('Patch', 'bi bj partial blocks rings evaluated')
+Census = collections.namedtuple('Census', 'colls narrow_cap family patches rules')
+
+
+def _locate(axis, v):
+    """oracle/rgi.py locate's cell (scipy's find_indices)"""
+    axis = np.asarray(axis, dtype=float)
+    return np.minimum(np.maximum(np.searchsorted(axis, v, side='right') - 1, 0), axis.size - 2)
+
+
+def census(args, rules):
+    """args: build_nearfield's arguments.  Runs the oracle for its decisions and counts blocks per patch."""
+    from oracle import nearfield_oracle
+    dec = {}
+    nearfield_oracle.build_nearfield(decisions=dec, **args)
+    S = args['lens_periphery_summary']
+    gc_list = S['gratingcollection_list']
+    wl_nm = int(round(args['wavelength'] / 1e-9))
+    used = sorted(set(int(c) for c in np.asarray(S['gratingcollection_index_here_list'])))
+    order_lists = {c: tuple(nearfield_oracle._orders_of(gc_list[c].grating_list)) for c in used}
+    has_centre = len(args['lens_center_summary']) > 0
+    centre_orders = tuple(nearfield_oracle._orders_of(args['hexgridset'].grating_list)) if has_centre else None
+    colls, narrow_max, family = classify(order_lists, centre_orders, rules)
+    ring, which = dec['ring'], dec['which_gc']
+    i0 = np.zeros(ring.shape, dtype=np.int64)
+    i1 = np.zeros(ring.shape, dtype=np.int64)
+    # the oracle's own test of an order (nearfield_oracle.build_nearfield a3: kxp_all, kyp_all, sel)
+    kvac = 2 * math.pi / args['wavelength']
+    period = np.asarray(S['grating_period_list'], dtype=float)[ring]
+    lateral = (np.asarray(S['r_center_list'], dtype=float) * (2 * math.pi / np.asarray(S['num_around_circle_list'])))[ring]
+    in_air = {}
+    for c in used:
+        here = which == c
+        if not here.any():
+            continue
+        in_air[c] = [(kvac * dec['uxp'] + o * 2 * math.pi / period) ** 2 + (kvac * dec['uyp'] + oy * 2 * math.pi / lateral) ** 2
+                     <= kvac ** 2 for o, oy in order_lists[c]]
+        grid = gc_list[c].interpolators[(wl_nm, order_lists[c][0], 'x', 'ampfy')].grid
+        if colls[c].kernel == 'general':
+            # (the general kernel shares blocks among lanes for axes of up to 64 nodes only - nearfield_fast.hip
+            # `key` - so the table keeps its general collections at or below that)
+            assert len(grid[0]) <= 64 and len(grid[1]) <= 64, 'general collection %d: axes beyond 64 nodes' % c
+        i0[here] = _locate(grid[0], dec['uxp'][here])
+        i1[here] = _locate(grid[1], dec['uyp'][here])
+    nx, ny = ring.shape
+    patches = []
+    for bi in range((nx + 7) // 8):
+        for bj in range((ny + 7) // 8):
+            sl = (slice(8 * bi, 8 * bi + 8), slice(8 * bj, 8 * bj + 8))
+            w, r, a, b = which[sl].ravel(), ring[sl].ravel(), i0[sl].ravel(), i1[sl].ravel()
+            blocks, evaluated = {}, {}
+            for c in used:
+                m = w == c
+                if m.any():
+                    blocks[c] = len(set(zip(r[m].tolist(), a[m].tolist(), b[m].tolist())))
+                    evaluated[c] = frozenset(o for o, air in zip(order_lists[c], in_air[c]) if air[sl].ravel()[m].all())
+            if blocks:
+                patches.append(Patch(bi, bj, 8 * bi + 8 > nx or 8 * bj + 8 > ny, blocks, len(set(r[w >= 0].tolist())),
+                                     evaluated))
+    return Census(colls, rules['narrow_cap_%d' % narrow_max], family, patches, rules)
+
+
+def capacity(cen, kernel):
+    return {'narrow': cen.narrow_cap, 'wide': cen.rules['wide_cap'], 'general': cen.rules['general_cap']}[kernel]
+
+
+def round_sizes(n_blocks, cap):
+    """blocks per round: full rounds, then what is left"""
+    return [cap] * (n_blocks // cap) + ([n_blocks % cap] if n_blocks % cap else [])
+
+
+def wide_passes(n_blocks, n_slots, rules):
+    """passes of a wide round of n_blocks blocks of n_slots order slots"""
+    per = min(n_slots, rules['wide_slots_per_pass_%d' % n_blocks])
+    return -(-n_slots // per)
+
+
+def patch_work(cen, patch):
+    """per kernel what the wave of a patch does: {'narrow' / 'wide': [(collection, blocks, [blocks per round],
+    [passes per round])], 'general': [(None, blocks, [blocks per round], [order chunks per round])]}"""
+    out = {'narrow': [], 'wide': [], 'general': []}
+    gen_blocks, gen_orders = 0, 0
+    for c, n in patch.blocks.items():
+        K = cen.colls[c]
+        if K.kernel == 'general':
+            gen_blocks += n
+            gen_orders = max(gen_orders, K.n_orders)
+            continue
+        sizes = round_sizes(n, capacity(cen, K.kernel))
+        passes = [wide_passes(s, K.n_slots, cen.rules) if K.kernel == 'wide' else 1 for s in sizes]
+        out[K.kernel].append((c, n, sizes, passes))
+    if gen_blocks:
+        sizes = round_sizes(gen_blocks, cen.rules['general_cap'])
+        out['general'].append((None, gen_blocks, sizes, [-(-gen_orders // cen.rules['general_chunk'])] * len(sizes)))
+    return out
+
+
+def _holes(K):
+    return K.present != (1 << K.n_slots) - 1
+
+
+def last_pass_evaluated(cen, patch, c, n_blocks):
+    """a wide round of n_blocks blocks of collection c: its last pass holds an order that every sample evaluates"""
+    K = cen.colls[c]
+    per = min(K.n_slots, cen.rules['wide_slots_per_pass_%d' % n_blocks])
+    first = per * (wide_passes(n_blocks, K.n_slots, cen.rules) - 1)
+    return any((K.lo + s, 0) in patch.evaluated[c] for s in range(first, K.n_slots))
+
+
+def last_chunk_evaluated(cen, patch, c):
+    """the general kernel's last chunk of the orders of collection c holds an order that every sample evaluates"""
+    K = cen.colls[c]
+    first = cen.rules['general_chunk'] * (-(-K.n_orders // cen.rules['general_chunk']) - 1)
+    return any(o in patch.evaluated[c] for o in K.orders[first:])
+
+
+def confirm(cen, tag):
+    """the number of patches of the census that meet a tag: a claim needs MARGIN of them, and "more than the
+    capacity" means at least capacity + 2 blocks (the device may locate a sample at a cell edge one cell off)"""
+    kernel, what = tag.split(':')
+    cap = capacity(cen, kernel)
+    work = [(p, patch_work(cen, p)[kernel]) for p in cen.patches]
+    work = [(p, w) for p, w in work if w]
+    K = cen.colls
+
+    def count(pred):
+        return sum(1 for p, w in work if any(pred(p, *entry) for entry in w))
+
+    def rounds_at_least(n):   # n rounds with margin: (n - 1) capacity + 2 blocks
+        return lambda p, c, blocks, sizes, passes: blocks >= (n - 1) * cap + 2
+    if what == 'round-exactly-capacity':
+        return count(lambda p, c, blocks, sizes, passes: blocks == cap)
+    if what in ('second-round-capacity-8', 'second-round-capacity-6'):
+        return count(rounds_at_least(2)) if cap == int(what[-1]) else 0
+    if what == 'second-round':
+        return count(rounds_at_least(2))
+    if what == 'third-round':
+        return count(rounds_at_least(3))
+    if what == 'multi-round-partial-patches':
+        return count(lambda p, c, blocks, sizes, passes: p.partial and blocks >= cap + 2)
+    if what == 'present-hole':
+        return count(lambda p, c, *_: _holes(K[c]))
+    if what == 'sparse-10-slots':
+        return count(lambda p, c, *_: K[c].n_slots == 10 and _holes(K[c]))
+    if what == 'lens-of-different-slot-counts':
+        # every slot count among the lens' narrow collections met by patches; at least two of them
+        seen = collections.Counter(K[c].n_slots for p, w in work for c, *_ in w)
+        return min(seen.values()) if len(seen) >= 2 else 0
+    if what == 'two-collections-in-a-wave':
+        # two collections of this instantiation with different lists among a patch's samples; narrow: one of them
+        # in two rounds
+        def two(p, w):
+            lists = {(K[c].n_slots, K[c].lo, K[c].present) for c, *_ in w}
+            return len(lists) >= 2 and (kernel == 'wide' or any(blocks >= cap + 2 for c, blocks, *_ in w))
+        return sum(1 for p, w in work if two(p, w))
+    if what.startswith('orders-'):
+        n = int(what.split('-')[1])
+        return sum(1 for p in cen.patches if any(K[c].kernel == 'general' and K[c].n_orders == n and
+                                                 last_chunk_evaluated(cen, p, c) for c in p.blocks))
+    if what.startswith('slots-'):
+        n = int(what.split('-')[1])
+        return count(lambda p, c, *_: K[c].n_slots == n)
+    if '-slots-round-of-' in what:
+        n_slots, n = int(what.split('-')[0]), int(what.split('-')[-1])
+        # a round of exactly n blocks - of n + 2 and more where n is the capacity, so that a block less leaves it full -
+        # whose last pass shows in the result
+        return count(lambda p, c, blocks, sizes, passes: K[c].n_slots == n_slots and not _holes(K[c]) and
+                     (blocks >= n + 2 if n == cap else n in sizes) and last_pass_evaluated(cen, p, c, n))
+    raise KeyError(tag)
+
+
+def figures(cen):
+    """per kernel the census' extremes: (patches, most blocks of a collection in a patch, most rounds, most passes or
+    order chunks in a round, most collections of the kernel in a patch) - what DESIGN.md tabulates"""
+    out = {}
+    for kernel in ('narrow', 'wide', 'general'):
+        work = [w for w in (patch_work(cen, p)[kernel] for p in cen.patches) if w]
+        if work:
+            out[kernel] = (len(work), max(e[1] for w in work for e in w), max(len(e[2]) for w in work for e in w),
+                           max(max(e[3]) for w in work for e in w), max(len(w) for w in work))
+    return out
+
+
+MARGIN = 3
