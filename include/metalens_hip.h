@@ -516,11 +516,36 @@ int ml_propagate_plan_grid(ml_ctx *ctx, double x0, double y0, double dxp, double
 int ml_propagate_plan_grid_long(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
                                 double wavelength, double n_glass,
                                 double tx0, double ty0, int mx, int my, double z, int want_h);
+/* ml_propagate_plan_grid by overlap-add over TILES of the aperture, for a small patch of targets behind a large
+ * aperture (arguments, checks, layouts and scales as there).  Per axis of n samples and m targets the tile length L is
+ * a power of two in [16, 8192] with L >= m; the samples are cut into c = ceil(n / B) tiles of B = L - m + 1, each
+ * tile is convolved at the padded length L and the tiles' products are added in the spectral domain, in ascending
+ * order of the tile and without atomics, in front of one inverse transform: the padded length of the axis is c L
+ * instead of up to 2 n, and n is not bounded by the padding (a 16384^2 aperture has an FFT form).  tile_lx, tile_ly:
+ * the tile lengths, 0 for the default - the admissible L that minimises c L times the measured cost of a padded sample
+ * at that length (flat up to 512, growing beyond: csrc/propagate_grid.h grid_tile_weight), the larger one of equals.  A
+ * length that is no power of two in [16, 8192] or below m, and m > 8192 on an axis, are refused with ML_EINVAL and n, m
+ * and the length in ml_last_error; the previous plan stays as it was.  A plan of one tile (the default where a
+ * tile of at most 512 holds the axis and shorter tiles would pad it no less) has the bits of ml_propagate_plan_grid.  The first pass on a
+ * shape reserves (8 cx cy + 4 batch + 6 or 3) Lx Ly complex128 - every tile's eight kernel spectra are kept for the
+ * life of the plan - and fails with ML_ENOMEM and the bytes asked for if the device cannot give them.
+ * ml_propagate_plan_info reports ML_PROPAGATE_FFT_TILED and the TILE lengths as lx, ly.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_grid_tiled(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                                 double wavelength, double n_glass,
+                                 double tx0, double ty0, int mx, int my, double z, int want_h,
+                                 int tile_lx, int tile_ly);
+/* The tiles of the active tiled plan: tiles per axis cx, cy, samples per tile bx, by and the tiles that go through
+ * the transforms together (batch); zeros while the plan has met no resident field set.  ML_ESTATE unless a tiled
+ * plan is active.  Any pointer may be NULL.  Replaces no reference lines.                  */
+int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch);
 #define ML_PROPAGATE_DIRECT 0
 #define ML_PROPAGATE_FFT 1
 #define ML_PROPAGATE_FFT_LONG 2
+#define ML_PROPAGATE_FFT_TILED 3
 /* The active propagation plan: method (ML_PROPAGATE_*), the padded lengths lx, ly (0 for a direct plan, and for
- * an fft plan that has met no resident field set yet) and the bytes of device workspace it holds besides targets,
+ * an fft plan that has met no resident field set yet; the tile lengths of a tiled plan) and the bytes of device
+ * workspace it holds besides targets,
  * result and sums (direct: the row-set partial sums of the last pass; fft: spectra, currents and outputs, from
  * the first pass on).  ML_ESTATE without a plan.  Any pointer may be NULL.
  * Replaces no reference lines.                                                             */

@@ -301,11 +301,17 @@ struct PropagatePlan {
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
     // the FFT form (propagate_grid.hip, ml_propagate_plan_grid): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
-    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG
+    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED
     GridPlanFacts grid;   // (propagate_grid.h) for the aperture shape last met; spectra_ready: its kernel spectra are in grid_work
     bool spectra_ready = false;
     double tx_off = 0, ty_off = 0, z = 0;
-    DevBuf grid_work;     // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; released by a direct plan
+    // the tiled plan (ml_propagate_plan_grid_tiled): the tile lengths asked for (0: the default) and the plan for the
+    // aperture shape last met; grid.Lx, grid.Ly are then the TILE lengths (what the transform launchers read)
+    int tile_lx = 0, tile_ly = 0;
+    GridTilePlan tile;
+    // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; the tiled plan: [tiles][8] kernel spectra,
+    // [batch][4] currents, [6 or 3] outputs; released by a direct plan
+    DevBuf grid_work;
     DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
 };
 

@@ -72,6 +72,117 @@ inline int grid_plan_facts(int nx, int ny, int mx, int my, int want_h, GridPlanF
     return 0;
 }
 
+// The tiled plan (ml_propagate_plan_grid_tiled): overlap-add over tiles of the aperture.  The sum is linear in the
+// samples, so per axis the n samples are cut into c = ceil(n / B) tiles of B = L - m + 1 samples, each convolved at
+// the padded length L (a power of two in [GRID_L_MIN, GRID_L_MAX], >= m); the tiles' products are added in the
+// spectral domain in front of ONE inverse transform.  Tile a holds the samples [a B, min(n, a B + B)) at the local
+// indices 0 ... B - 1; index p of its kernel plane holds the true lag (p < m ? p : p - L) - a B.  The lags of a tile,
+// local target minus local sample in [-(B - 1), m - 1], are exactly L of them: no index is wasted.
+//   padded area per axis: c L instead of up to 2 n (8192 -> 64: 9 x 1024 = 9216 instead of 16384)
+constexpr int GRID_TILE_BATCH_MAX = 64;                      // tiles per launch: 512 kernel planes
+constexpr int64_t GRID_TILE_BATCH_BYTES = (int64_t)128 << 20;   // the four current planes of a batch's tiles stay below this
+
+struct GridTileAxis {
+    int L = 0, B = 0, c = 0;   // tile length, samples per tile, tiles
+};
+
+inline bool grid_tile_length_ok(long long L, int m) {
+    return L >= GRID_L_MIN && L <= GRID_L_MAX && (L & (L - 1)) == 0 && L >= m;
+}
+
+inline GridTileAxis grid_tile_axis(int n, int m, int L) {
+    GridTileAxis t;
+    t.L = L;
+    t.B = L - m + 1;
+    t.c = (n + t.B - 1) / t.B;
+    return t;
+}
+
+// What a padded sample of an axis costs at the tile length L, in 32nds of its cost at L <= 512: the square roots of the
+// measured time per padded AREA of a cached pass - 1.08 : 1.37 : 1.88 : 2.14 e-7 ms per sample at L = 512 : 1024 : 2048 :
+// 4096, the same within 8 % at 4096^2, 8192^2 and 16384^2 -> 64^2 and 4096^2 -> 256^2 (longer tiles
+// take more stages, columns above 1024 a streaming pass, and fewer tiles of a batch stay in the memory-side cache).
+// Nothing below 512 or at 8192 has been measured: flat below, the weight of 4096 at 8192.
+constexpr int grid_tile_weight(int L) { return L <= 512 ? 32 : L == 1024 ? 36 : L == 2048 ? 42 : 45; }
+
+// the admissible L that minimises the weighted padded length c L w(L) of the axis; ties go to the larger L (fewer
+// tiles): where one tile of at most 512 holds the axis and shorter tiles would pad it no less, the plan has one tile of
+// the L of the untiled plan.  m <= GRID_L_MAX.
+inline int grid_tile_default(int n, int m) {
+    int best = 0;
+    long long best_cost = 0;
+    for (int L = GRID_L_MIN; L <= GRID_L_MAX; L *= 2) {
+        if (L < m) continue;
+        const long long cost = (long long)grid_tile_axis(n, m, L).c * L * grid_tile_weight(L);
+        if (!best || cost <= best_cost) {
+            best = L;
+            best_cost = cost;
+        }
+    }
+    return best;
+}
+
+struct GridTilePlan {
+    int nx = 0, ny = 0, mx = 0, my = 0;
+    GridTileAxis x, y;
+    int tiles = 0, batch = 0;             // cx cy; tiles per pass through the transform launchers
+    int outputs = 0;                      // 6 with H, 3 without
+    int64_t plane_bytes = 0, workspace_bytes = 0;
+};
+
+// what is wrong with the tile length L (0: the default) of an axis of n samples (0: not known yet) and m targets;
+// -> 0, or -1 with `why` filled
+inline int grid_tile_check_axis(const char *axis, int n, int m, int L, char *why, size_t why_len) {
+    if (m > GRID_L_MAX) {
+        snprintf(why, why_len,
+                 "the tiled FFT form takes at most %d targets per axis (a tile is at least as long as the targets, one row "
+                 "of L complex128 must fit the LDS): the %s axis of n = %d samples has m = %d targets; use the direct "
+                 "method or fewer targets per plan",
+                 GRID_L_MAX, axis, n, m);
+        return -1;
+    }
+    if (L != 0 && !grid_tile_length_ok(L, m)) {
+        snprintf(why, why_len,
+                 "the tile length of the %s axis of n = %d samples and m = %d targets is L = %d: it must be a power of two "
+                 "in [%d, %d] and at least m (0: the default)",
+                 axis, n, m, L, GRID_L_MIN, GRID_L_MAX);
+        return -1;
+    }
+    return 0;
+}
+
+// -> 0, or -1 with `why` filled.  tile_lx, tile_ly: 0 takes grid_tile_default.  batch_bytes: GRID_TILE_BATCH_BYTES.
+//   batch G = min(cx cy, GRID_TILE_BATCH_MAX, max(1, batch_bytes / (4 plane_bytes)))
+//   workspace: all tiles' kernel spectra (kept for the life of the plan), the currents of one batch, the outputs
+inline int grid_tile_plan(int nx, int ny, int mx, int my, int want_h, int tile_lx, int tile_ly, int64_t batch_bytes,
+                          GridTilePlan *t, char *why, size_t why_len) {
+    if (grid_tile_check_axis("x", nx, mx, tile_lx, why, why_len) != 0) return -1;
+    if (grid_tile_check_axis("y", ny, my, tile_ly, why, why_len) != 0) return -1;
+    t->nx = nx;
+    t->ny = ny;
+    t->mx = mx;
+    t->my = my;
+    t->x = grid_tile_axis(nx, mx, tile_lx ? tile_lx : grid_tile_default(nx, mx));
+    t->y = grid_tile_axis(ny, my, tile_ly ? tile_ly : grid_tile_default(ny, my));
+    const int64_t tiles = (int64_t)t->x.c * t->y.c;
+    if (tiles > (1 << 20)) {
+        snprintf(why, why_len,
+                 "the tiled FFT form cuts the aperture of %d x %d samples into %d x %d tiles of %d x %d samples (tile lengths "
+                 "%d, %d for %d x %d targets): at most 2^20 tiles per plan; use longer tiles",
+                 nx, ny, t->x.c, t->y.c, t->x.B, t->y.B, t->x.L, t->y.L, mx, my);
+        return -1;
+    }
+    t->tiles = (int)tiles;
+    t->outputs = want_h ? 6 : 3;
+    t->plane_bytes = (int64_t)t->x.L * t->y.L * 16;
+    const int64_t by_bytes = batch_bytes / (GRID_CURRENTS * t->plane_bytes);
+    int64_t G = tiles < GRID_TILE_BATCH_MAX ? tiles : GRID_TILE_BATCH_MAX;
+    if (G > (by_bytes > 1 ? by_bytes : 1)) G = by_bytes > 1 ? by_bytes : 1;
+    t->batch = (int)G;
+    t->workspace_bytes = ((int64_t)GRID_KERNELS * tiles + (int64_t)GRID_CURRENTS * G + t->outputs) * t->plane_bytes;
+    return 0;
+}
+
 // cos / sin of 2 pi j / L for j < L / 2, evaluated in long double and rounded once: [L / 2][2]
 inline std::vector<double> grid_twiddles(int L) {
     std::vector<double> t((size_t)L);

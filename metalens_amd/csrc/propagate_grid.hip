@@ -31,6 +31,9 @@
 //            rest on blocks of a row in the LDS (grid_rows_block_kernel);
 //   columns: the streaming pass with 16 elements per thread, then the blocks of 1024.
 // An axis of L <= 8192 of a long plan goes through the launches above.
+// The tiled plan (ml_propagate_plan_grid_tiled) cuts the aperture into tiles, convolves each at a short padded length
+// and adds the tiles' products in the spectral domain (overlap-add; the grid_tile_* kernels below, through the same
+// transform launches with more planes per launch).
 #include "nearfield_math.h"
 
 namespace ml {
@@ -472,8 +475,273 @@ static int grid_prepare(ml_ctx *ctx) {
     return ML_OK;
 }
 
+// ---- the tiled plan (ml_propagate_plan_grid_tiled; propagate_grid.h GridTilePlan) --------------------------------
+// Tile t = a cy + b holds the samples [a Bx, a Bx + Bx) x [b By, b By + By) of the aperture.  Kernel spectra
+// [tiles][8][Lx][Ly], kept for the life of the plan; currents [batch][4][Lx][Ly]; outputs [6 or 3][Lx][Ly].  A pass
+// takes the tiles in batches through pad - row pass - column pass - contraction; the contraction adds the batch's
+// tiles, in ascending order, to the output spectra, which go back through ONE inverse transform after the last batch.
+
+struct GridTileGeoArgs {
+    GridGeoArgs g;       // out: the first plane of the launch's first tile
+    int tile0, cy;       // the launch's first tile; tiles along y
+    int Bx, By;          // samples per tile
+};
+
+// the eight kernels of tile tile0 + blockIdx.y at every index of the tile's padded grid: index p holds the lag
+// (p < m ? p : p - L) - a B, which goes into the arithmetic of grid_fill_kernel unchanged
+__global__ __launch_bounds__(256) void grid_tile_fill_kernel(const GridTileGeoArgs t) {
+    const GridGeoArgs &a = t.g;
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly (a multiple of 256)
+    const int tile = t.tile0 + blockIdx.y, ta = tile / t.cy, tb = tile - ta * t.cy;
+    const int p = (int)(id / a.Ly), r = (int)(id - (size_t)p * a.Ly);
+    const int lx = (p < a.mx ? p : p - a.Lx) - ta * t.Bx, ly = (r < a.my ? r : r - a.Ly) - tb * t.By;
+    const double dx = fma((double)lx, a.dxp, a.tx_off), dy = fma((double)ly, a.dyp, a.ty_off);
+    const double s_row = fma(dx, dx, a.z * a.z);
+    const double R = sqrt_exact(fma(dy, dy, s_row));
+    const double iR = recip(R);
+    const double ux = dx * iR, uy = dy * iR, uz = a.z * iR;
+    const double q = iR * a.inv_k, q2 = q * q;
+    double sn, cs;
+    sincos_cw(a.k * R, sn, cs);
+    const c2 w = {cs * q, sn * q};
+    const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
+    const c2 wb = cmulf(w, cb);
+    const c2 txx = {fma(-(ux * ux), cb.r, ca.r), fma(-(ux * ux), cb.i, ca.i)};
+    const c2 tyy = {fma(-(uy * uy), cb.r, ca.r), fma(-(uy * uy), cb.i, ca.i)};
+    const c2 wxx = cmulf(w, txx), wyy = cmulf(w, tyy);
+    const c2 ci = {fma(-q, w.r, -w.i), fma(-q, w.i, w.r)};   // w (i - q)
+    const double gxy = ux * uy, gzx = uz * ux, gzy = uz * uy;
+    d2 *o = a.out + (size_t)blockIdx.y * GRID_KERNELS * a.plane_stride + id;
+    o[0] = make_double2(-wxx.i, wxx.r);
+    o[a.plane_stride] = make_double2(wb.i * gxy, -(wb.r * gxy));
+    o[2 * a.plane_stride] = make_double2(-wyy.i, wyy.r);
+    o[3 * a.plane_stride] = make_double2(wb.i * gzx, -(wb.r * gzx));
+    o[4 * a.plane_stride] = make_double2(wb.i * gzy, -(wb.r * gzy));
+    o[5 * a.plane_stride] = make_double2(ci.r * ux, ci.i * ux);
+    o[6 * a.plane_stride] = make_double2(ci.r * uy, ci.i * uy);
+    o[7 * a.plane_stride] = make_double2(ci.r * uz, ci.i * uz);
+}
+
+struct GridTilePadArgs {
+    const d2 *fields;       // one field set [4][nx][ny]
+    const int *row_first;   // of a synthesised field, or NULL
+    d2 *cur;                // [tiles of the launch][4][Lx][Ly]
+    size_t plane_stride;
+    int nx, ny, Lx, Ly, Bx, By, tile0, cy;
+    double Z;
+};
+
+// current c = blockIdx.y of tile tile0 + blockIdx.z into its padded plane (the conversion of grid_pad_kernel): zeros
+// beyond the tile's samples, beyond the aperture and outside the row extents of a synthesised field
+__global__ __launch_bounds__(256) void grid_tile_pad_kernel(const GridTilePadArgs a) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
+    const int il = (int)(id / a.Ly), jl = (int)(id - (size_t)il * a.Ly);
+    const int tile = a.tile0 + blockIdx.z, ta = tile / a.cy, tb = tile - ta * a.cy;
+    const int i = ta * a.Bx + il, j = tb * a.By + jl;
+    const int c = blockIdx.y, f = 3 - c;
+    d2 v = make_double2(0.0, 0.0);
+    if (il < a.Bx && jl < a.By && i < a.nx && j < a.ny) {
+        const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
+        if (j >= first && j < a.ny - first) {
+            const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? a.Z : 1.0;
+            const d2 s = a.fields[((size_t)f * a.nx + i) * a.ny + j];
+            v = make_double2(sg * s.x / den, sg * s.y / den);
+        }
+    }
+    a.cur[((size_t)blockIdx.z * GRID_CURRENTS + c) * a.plane_stride + id] = v;
+}
+
+// a kernel spectrum is read once per pass: a streaming load
+__device__ __forceinline__ d2 ld_stream(const d2 *p) {
+    typedef double double2v __attribute__((ext_vector_type(2)));
+    const double2v t = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(p));
+    return make_double2(t.x, t.y);
+}
+
+// e = k v (START) or e += k v
+template <bool START>
+__device__ __forceinline__ void zterm(d2 &e, d2 k, d2 v) {
+    if (START)
+        e = zmul(k, v);
+    else
+        zfma(e, k, v);
+}
+
+// the products of one tile in the term order of grid_contract_kernel (the table on top)
+template <bool WANT_H, bool START>
+__device__ __forceinline__ void tile_products(d2 (&e)[6], const d2 *K, const d2 *cur, size_t ps, size_t id) {
+    const d2 Kxx = ld_stream(K + id), Kxy = ld_stream(K + ps + id), Kyy = ld_stream(K + 2 * ps + id);
+    const d2 Kzx = ld_stream(K + 3 * ps + id), Kzy = ld_stream(K + 4 * ps + id);
+    const d2 Cx = ld_stream(K + 5 * ps + id), Cy = ld_stream(K + 6 * ps + id), Cz = ld_stream(K + 7 * ps + id);
+    const d2 Jx = cur[id], Jy = cur[ps + id], mx = cur[2 * ps + id], my = cur[3 * ps + id];
+    zterm<START>(e[0], Kxx, Jx);
+    zfma(e[0], Kxy, Jy);
+    zfma(e[0], Cz, my);
+    zterm<START>(e[1], Kxy, Jx);
+    zfma(e[1], Kyy, Jy);
+    zfma(e[1], zneg(Cz), mx);
+    zterm<START>(e[2], Kzx, Jx);
+    zfma(e[2], Kzy, Jy);
+    zfma(e[2], Cy, mx);
+    zfma(e[2], zneg(Cx), my);
+    if (WANT_H) {
+        zterm<START>(e[3], Kxx, mx);
+        zfma(e[3], Kxy, my);
+        zfma(e[3], zneg(Cz), Jy);
+        zterm<START>(e[4], Kxy, mx);
+        zfma(e[4], Kyy, my);
+        zfma(e[4], Cz, Jx);
+        zterm<START>(e[5], Kzx, mx);
+        zfma(e[5], Kzy, my);
+        zfma(e[5], Cx, Jy);
+        zfma(e[5], zneg(Cy), Jx);
+    }
+}
+
+// per bin: the n tiles of a batch (K: the batch's first tile's spectra, cur: its currents) added in ascending order to
+// the 6 (3) output spectra, held in registers and written once.  FIRST (the pass' first batch): the sums start from the
+// first tile's first product, as grid_contract_kernel's do; otherwise from the stored value.  No atomics.
+template <bool WANT_H, bool FIRST>
+__global__ __launch_bounds__(256) void grid_tile_contract_kernel(const d2 *K, const d2 *cur, d2 *out, size_t ps, int n) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
+    constexpr int NC = WANT_H ? 6 : 3;
+    d2 e[6];
+    int g = 0;
+    if (FIRST) {
+        tile_products<WANT_H, true>(e, K, cur, ps, id);
+        g = 1;
+    } else {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) e[c] = out[c * ps + id];
+    }
+    for (; g < n; ++g)
+        tile_products<WANT_H, false>(e, K + (size_t)g * GRID_KERNELS * ps, cur + (size_t)g * GRID_CURRENTS * ps, ps, id);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) out[c * ps + id] = e[c];
+}
+
+// (diagnostic build: ML_GRID_TILE_BATCH_MIB sets the bytes a batch's currents may take, for timing)
+static int64_t tile_batch_bytes() { return (int64_t)diag_int("ML_GRID_TILE_BATCH_MIB", (int)(GRID_TILE_BATCH_BYTES >> 20)) << 20; }
+
+// the workspace and every tile's kernel spectra for the resident field's shape (kept while the shape stays)
+static int tile_prepare(ml_ctx *ctx) {
+    PropagatePlan &pp = ctx->prop;
+    if (pp.spectra_ready && pp.grid.nx == ctx->fields.nx && pp.grid.ny == ctx->fields.ny) return ML_OK;
+    pp.spectra_ready = false;
+    char why[400];
+    GridTilePlan t;
+    if (grid_tile_plan(ctx->fields.nx, ctx->fields.ny, pp.grid.mx, pp.grid.my, pp.want_h, pp.tile_lx, pp.tile_ly,
+                       tile_batch_bytes(), &t, why, sizeof why) != 0) {
+        set_error("%s", why);
+        return ML_EINVAL;
+    }
+    pp.tile = t;
+    GridPlanFacts &f = pp.grid;   // what the transform launchers read: the tile's lengths
+    f.nx = t.nx;
+    f.ny = t.ny;
+    f.Lx = t.x.L;
+    f.Ly = t.y.L;
+    f.outputs = t.outputs;
+    f.plane_bytes = t.plane_bytes;
+    f.workspace_bytes = t.workspace_bytes;
+    ML_TRY(pp.grid_work.reserve((size_t)t.workspace_bytes));
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
+    GridTileGeoArgs a;
+    GridGeoArgs &g = a.g;
+    g.plane_stride = (size_t)f.Lx * f.Ly;
+    g.Lx = f.Lx;
+    g.Ly = f.Ly;
+    g.mx = f.mx;
+    g.my = f.my;
+    g.tx_off = pp.tx_off;
+    g.ty_off = pp.ty_off;
+    g.dxp = pp.dxp;
+    g.dyp = pp.dyp;
+    g.z = pp.z;
+    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
+    g.inv_k = 1.0 / g.k;
+    a.cy = t.y.c;
+    a.Bx = t.x.B;
+    a.By = t.y.B;
+    for (int tile0 = 0; tile0 < t.tiles; tile0 += GRID_TILE_BATCH_MAX) {   // 512 planes per launch at the most
+        const int nt = std::min(GRID_TILE_BATCH_MAX, t.tiles - tile0);
+        a.tile0 = tile0;
+        g.out = pp.grid_work.as<d2>() + (size_t)tile0 * GRID_KERNELS * g.plane_stride;
+        hipLaunchKernelGGL(grid_tile_fill_kernel, dim3((unsigned)(g.plane_stride / 256), nt), dim3(256), 0, ctx->stream, a);
+        ML_HIP(hipGetLastError());
+        ML_TRY(fft_rows<false>(ctx, g.out, nt * GRID_KERNELS, f.Lx));
+        ML_TRY(fft_cols<false>(ctx, g.out, nt * GRID_KERNELS));
+    }
+    pp.spectra_ready = true;
+    return ML_OK;
+}
+
+template <bool WANT_H>
+static void launch_tile_contract(ml_ctx *ctx, unsigned blocks, bool first, const d2 *K, const d2 *cur, d2 *out, size_t ps, int n) {
+    if (first)
+        hipLaunchKernelGGL((grid_tile_contract_kernel<WANT_H, true>), dim3(blocks), dim3(256), 0, ctx->stream, K, cur, out, ps, n);
+    else
+        hipLaunchKernelGGL((grid_tile_contract_kernel<WANT_H, false>), dim3(blocks), dim3(256), 0, ctx->stream, K, cur, out, ps, n);
+}
+
+static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
+    PropagatePlan &pp = ctx->prop;
+    pp.have_result = false;
+    ML_TRY(tile_prepare(ctx));
+    const GridPlanFacts &f = pp.grid;
+    const GridTilePlan &t = pp.tile;
+    const int T = pp.T, nc = f.outputs;
+    ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
+    const size_t ps = (size_t)f.Lx * f.Ly;
+    d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)t.tiles * GRID_KERNELS * ps, *out = cur + (size_t)t.batch * GRID_CURRENTS * ps;
+    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
+    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
+    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const unsigned blocks = (unsigned)(ps / 256);
+    const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
+    GridTilePadArgs p;
+    p.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
+    p.cur = cur;
+    p.plane_stride = ps;
+    p.nx = t.nx;
+    p.ny = t.ny;
+    p.Lx = f.Lx;
+    p.Ly = f.Ly;
+    p.Bx = t.x.B;
+    p.By = t.y.B;
+    p.cy = t.y.c;
+    p.Z = Z;
+    for (int m = 0; m < n; ++m) {
+        p.fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
+        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {
+            const int nt = std::min(t.batch, t.tiles - tile0);
+            p.tile0 = tile0;
+            hipLaunchKernelGGL(grid_tile_pad_kernel, dim3(blocks, GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
+            ML_HIP(hipGetLastError());
+            ML_TRY(fft_rows<false>(ctx, cur, nt * GRID_CURRENTS, rows_fwd));
+            ML_TRY(fft_cols<false>(ctx, cur, nt * GRID_CURRENTS));
+            const d2 *Kt = K + (size_t)tile0 * GRID_KERNELS * ps;
+            if (pp.want_h)
+                launch_tile_contract<true>(ctx, blocks, tile0 == 0, Kt, cur, out, ps, nt);
+            else
+                launch_tile_contract<false>(ctx, blocks, tile0 == 0, Kt, cur, out, ps, nt);
+            ML_HIP(hipGetLastError());
+        }
+        ML_TRY(fft_cols<true>(ctx, out, nc));
+        ML_TRY(fft_rows<true>(ctx, out, nc, f.mx));
+        hipLaunchKernelGGL(grid_crop_kernel, dim3((T + 255) / 256, nc), dim3(256), 0, ctx->stream, out, ps,
+                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, Z * scale_h * inv_n, scale_h * inv_n);
+        ML_HIP(hipGetLastError());
+    }
+    pp.have_result = true;
+    pp.result_sets = n;
+    return ML_OK;
+}
+
 int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     PropagatePlan &pp = ctx->prop;
+    if (pp.method == ML_PROPAGATE_FFT_TILED) return propagate_tile_sets(ctx, Z0, first, n);
     pp.have_result = false;
     ML_TRY(grid_prepare(ctx));
     const GridPlanFacts &f = pp.grid;
@@ -517,9 +785,11 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
 
 using namespace ml;
 
-// ml_propagate_plan_grid and ml_propagate_plan_grid_long: `entry` is the caller's name, `method` its ML_PROPAGATE_*
+// ml_propagate_plan_grid, ml_propagate_plan_grid_long and ml_propagate_plan_grid_tiled: `entry` is the caller's name,
+// `method` its ML_PROPAGATE_*; tile_lx, tile_ly: the tile lengths of the tiled plan (0: the default)
 static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, double y0, double dxp, double dyp, double wavelength,
-                     double n_glass, double tx0, double ty0, int mx, int my, double z, int want_h) {
+                     double n_glass, double tx0, double ty0, int mx, int my, double z, int want_h, int tile_lx = 0,
+                     int tile_ly = 0) {
     ML_REQUIRE(ctx, "ctx is NULL");
     ML_REQUIRE(ctx->n_ranks <= 1, "%s: this context belongs to a communicator of %d ranks; the "
                "finite-distance propagator sums a whole aperture on one GPU (sharded propagation is not implemented)",
@@ -531,7 +801,21 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     GridPlanFacts f;
     f.mx = mx;
     f.my = my;
-    if (ctx->fields.nx && ctx->fields.ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
+    GridTilePlan tile;
+    if (method == ML_PROPAGATE_FFT_TILED) {   // what is wrong with the targets or the lengths whatever the shape, and
+        char why[400];                        // the plan for the shape a pass would meet now
+        const bool resident = ctx->fields.nx && ctx->fields.ny;
+        const int bad = resident ? grid_tile_plan(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, tile_lx, tile_ly,
+                                                  tile_batch_bytes(), &tile, why, sizeof why)
+                                 : (grid_tile_check_axis("x", 0, mx, tile_lx, why, sizeof why) ||
+                                    grid_tile_check_axis("y", 0, my, tile_ly, why, sizeof why));
+        if (bad) {
+            set_error("%s: %s", entry, why);
+            return ML_EINVAL;
+        }
+        f.Lx = resident ? tile.x.L : tile_lx;   // (the lengths asked for are known without a shape)
+        f.Ly = resident ? tile.y.L : tile_ly;
+    } else if (ctx->fields.nx && ctx->fields.ny) {   // the shape a pass would meet now: refuse here, with the previous plan as it was
         char why[320];
         if (grid_plan_facts(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, &f, why, sizeof why, grid_cap(method)) != 0) {
             set_error("%s: %s", entry, why);
@@ -544,6 +828,9 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     pp.spectra_ready = false;
     pp.method = method;
     pp.grid = f;
+    pp.tile = tile;
+    pp.tile_lx = tile_lx;
+    pp.tile_ly = tile_ly;
     pp.T = mx * my;
     pp.want_h = want_h != 0;
     pp.x0 = x0;
@@ -571,6 +858,27 @@ int ml_propagate_plan_grid_long(ml_ctx *ctx, double x0, double y0, double dxp, d
                                 double tx0, double ty0, int mx, int my, double z, int want_h) {
     return plan_grid(ctx, "ml_propagate_plan_grid_long", ML_PROPAGATE_FFT_LONG, x0, y0, dxp, dyp, wavelength, n_glass, tx0, ty0,
                      mx, my, z, want_h);
+}
+
+int ml_propagate_plan_grid_tiled(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                                 double tx0, double ty0, int mx, int my, double z, int want_h, int tile_lx, int tile_ly) {
+    return plan_grid(ctx, "ml_propagate_plan_grid_tiled", ML_PROPAGATE_FFT_TILED, x0, y0, dxp, dyp, wavelength, n_glass, tx0, ty0,
+                     mx, my, z, want_h, tile_lx, tile_ly);
+}
+
+int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    const PropagatePlan &pp = ctx->prop;
+    if (!pp.ready || pp.method != ML_PROPAGATE_FFT_TILED) {
+        set_error("ml_propagate_plan_tiles: no tiled propagation plan is active");
+        return ML_ESTATE;
+    }
+    if (cx) *cx = pp.tile.x.c;
+    if (cy) *cy = pp.tile.y.c;
+    if (bx) *bx = pp.tile.x.B;
+    if (by) *by = pp.tile.y.B;
+    if (batch) *batch = pp.tile.batch;
+    return ML_OK;
 }
 
 int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *workspace_bytes) {

@@ -20,7 +20,8 @@ GPU-resident near field; for ``R -> infinity`` it reduces to the amplitudes behi
 depends on the lag ``(i_t - i_s, j_t - j_s)`` alone, and the same sum runs as a zero-padded circular convolution
 (csrc/propagate_grid.hip): ``O(L^2 log L)`` with ``L >= n + m - 1`` per axis instead of ``n^2 m^2`` pairs.
 ``method='fft-long'`` is the same with padded axes of up to 16384 instead of 8192 - apertures of 4097 ... 8192 samples a
-side - and a workspace of up to 77 GB.
+side - and a workspace of up to 77 GB.  ``method='fft-tiled'`` cuts the aperture into tiles, convolves each at a short
+padded length ``L >= m`` and adds the tiles' products in the spectral domain (overlap-add): for ``m << n``.
 """
 import numpy as np
 
@@ -45,10 +46,11 @@ def _targets(x, y, z, point_list):
     return x, y, z
 
 
-METHODS = ('direct', 'fft', 'fft-long')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
-GRID_L_MAX = 8192   # csrc/propagate_grid.h
+METHODS = ('direct', 'fft', 'fft-long', 'fft-tiled')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
+GRID_L_MIN, GRID_L_MAX = 16, 8192   # csrc/propagate_grid.h
 GRID_L_LONG_MAX = 16384
 _GRID_CAP = {'fft': GRID_L_MAX, 'fft-long': GRID_L_LONG_MAX}
+_GRID_METHODS = ('fft', 'fft-long', 'fft-tiled')   # a tensor grid of targets on the aperture's pitch
 
 
 def _padded_length(n, m):
@@ -72,13 +74,50 @@ def _on_pitch(name, t, pitch):
                          % (name, i, t[i], name, i, pitch, name, own))
 
 
+def tile_default(n, m):
+    """the default tile length of ``method='fft-tiled'`` for an axis of n samples and m <= 8192 targets
+    (csrc/propagate_grid.h grid_tile_default): the power of two ``L`` in [16, 8192], ``L >= m``, that minimises the
+    padded length ``ceil(n / (L - m + 1)) L`` of the axis times the measured cost of a padded sample at that length
+    (1 up to 512, then 9/8, 21/16, 45/32 for 1024, 2048 and beyond); of equals the larger"""
+    best = None
+    L = GRID_L_MIN
+    while L <= GRID_L_MAX:
+        if L >= m:
+            cost = -(-n // (L - m + 1)) * L * (32 if L <= 512 else 36 if L == 1024 else 42 if L == 2048 else 45)
+            if best is None or cost <= best[0]:
+                best = (cost, L)
+        L *= 2
+    return best[1]
+
+
+def _check_tile(name, n, m, L):
+    """the refusals of ml_propagate_plan_grid_tiled for one axis, before a context is touched; L None: the default"""
+    if m > GRID_L_MAX:
+        raise ValueError("method='fft-tiled' takes at most %d targets per axis: the %s axis of n = %d samples has "
+                         "m = %d targets; use method='direct' or fewer targets per propagator" % (GRID_L_MAX, name, n, m))
+    if L is None or L == 0:
+        return 0
+    if L != int(L) or not (GRID_L_MIN <= L <= GRID_L_MAX) or int(L) & (int(L) - 1) or L < m:
+        raise ValueError("method='fft-tiled': the tile length of the %s axis of n = %d samples and m = %d targets is "
+                         "L = %s: it must be a power of two in [%d, %d] and at least m (None or 0: the default)"
+                         % (name, n, m, int(L) if L == int(L) else float(L), GRID_L_MIN, GRID_L_MAX))
+    return int(L)
+
+
 def plan_info(ctx):
     """-> ``{'method', 'Lx', 'Ly', 'workspace_bytes'}`` of the context's active propagation plan
-    (ml_propagate_plan_info): the padded lengths are 0 for the direct method"""
+    (ml_propagate_plan_info): the padded lengths are 0 for the direct method.  For ``'fft-tiled'`` they are the tile
+    lengths, and the dict has ``'tiles': (cx, cy)``, ``'tile_samples': (bx, by)`` and ``'batch'`` as well
+    (ml_propagate_plan_tiles)"""
     method, lx, ly, ws = _lib.c_int(0), _lib.c_int(0), _lib.c_int(0), _lib.c_int64(0)
     _lib.check(ctx.lib.ml_propagate_plan_info(ctx.handle, _lib.byref(method), _lib.byref(lx), _lib.byref(ly),
                                               _lib.byref(ws)))
-    return {'method': METHODS[method.value], 'Lx': lx.value, 'Ly': ly.value, 'workspace_bytes': ws.value}
+    info = {'method': METHODS[method.value], 'Lx': lx.value, 'Ly': ly.value, 'workspace_bytes': ws.value}
+    if info['method'] == 'fft-tiled':
+        t = [_lib.c_int(0) for _ in range(5)]
+        _lib.check(ctx.lib.ml_propagate_plan_tiles(ctx.handle, *[_lib.byref(v) for v in t]))
+        info.update(tiles=(t[0].value, t[1].value), tile_samples=(t[2].value, t[3].value), batch=t[4].value)
+    return info
 
 
 class PlanePropagator:
@@ -113,27 +152,49 @@ class PlanePropagator:
     planes per transform.  It is a method of its own because of its workspace: ``(12 + 6 or 3) Lx Ly 16`` bytes are up
     to 77 GB (64 GB with ``want_h=False``) where ``'fft'`` never reserves more than 18 GB.  The first pass reserves it
     and raises ``MetalensHipError`` with the bytes asked for if the device cannot give them.
+
+    ``method='fft-tiled'`` is the FFT form for a small patch behind a large aperture (ml_propagate_plan_grid_tiled):
+    overlap-add over tiles of the aperture.  Per axis the tile length ``L`` is a power of two in [16, 8192] with
+    ``L >= m``; the n samples are cut into ``ceil(n / B)`` tiles of ``B = L - m + 1``, every tile is convolved at the
+    padded length ``L`` and the tiles' products are added in the spectral domain in front of one inverse transform.
+    The padded length of an axis is ``ceil(n / B) L`` instead of up to ``2 n`` - 8192 samples to 64 targets: 19 tiles of
+    512 instead of 16384 - and n is not bounded by it: this is the only FFT form of apertures beyond 8192 samples a
+    side.  ``tile=(Lx, Ly)`` sets the tile lengths (None or 0 for an axis: its default); the default (``tile_default``)
+    minimises the padded length weighted by the measured cost of a padded sample at that length, the larger ``L`` of
+    equals.  The same checks as ``'fft'``; at most 8192 targets per axis.  A plan of one tile - the default where a tile
+    of at most 512 holds the axis and shorter tiles would pad it no less - has the bits of ``'fft'``.  The workspace is ``(8 cx cy + 4 batch + 6 or 3) Lx Ly`` complex128; ``plan_info()`` reports the tile
+    lengths as ``Lx``, ``Ly`` and adds ``'tiles'``, ``'tile_samples'`` and ``'batch'``.
     """
 
     def __init__(self, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False, want_h=True,
-                 units=None, Z0=None, ctx=None, method='direct'):
+                 units=None, Z0=None, ctx=None, method='direct', tile=None):
         if method not in METHODS:
             raise ValueError('method must be one of %s, got %r' % (METHODS, method))
+        if tile is not None and method != 'fft-tiled':
+            raise ValueError("tile=%r: the tile lengths belong to method='fft-tiled', not to method=%r" % (tile, method))
+        if tile is not None and len(tile) != 2:
+            raise ValueError('tile must be None or the two tile lengths (Lx, Ly), got %r' % (tile,))
         self.method = method
         self.Z0 = constants.as_units(units).Z0 if Z0 is None else Z0
         _check_axis(xp_list, wavelength)
         _check_axis(yp_list, wavelength)
         self.point_list, self.want_h = bool(point_list), bool(want_h)
-        if method in _GRID_CAP and self.point_list:
+        if method in _GRID_METHODS and self.point_list:
             raise ValueError("method=%r takes a tensor grid of targets on the aperture's pitch, not a point list" % method)
         self.x, self.y, self.z = _targets(x, y, z, self.point_list)
         self.shape = (self.x.size,) if self.point_list else (self.x.size, self.y.size)
         self.aperture_shape = (len(xp_list), len(yp_list))
         self._geometry = (float(xp_list[0]), float(yp_list[0]), float(xp_list[1] - xp_list[0]),
                           float(yp_list[1] - yp_list[0]), float(wavelength), float(n_glass))
-        if method in _GRID_CAP:
+        self.tile = (0, 0)   # 0: the default length
+        if method in _GRID_METHODS:
             _on_pitch('x', self.x, self._geometry[2])
             _on_pitch('y', self.y, self._geometry[3])
+        if method == 'fft-tiled':
+            Lx, Ly = (None, None) if tile is None else tile   # (None or 0 for an axis: its default)
+            self.tile = (_check_tile('x', self.aperture_shape[0], self.x.size, Lx),
+                         _check_tile('y', self.aperture_shape[1], self.y.size, Ly))
+        if method in _GRID_CAP:
             cap = _GRID_CAP[method]
             for name, n, m in (('x', self.aperture_shape[0], self.x.size), ('y', self.aperture_shape[1], self.y.size)):
                 L = _padded_length(n, m)
@@ -148,7 +209,11 @@ class PlanePropagator:
 
     def _plan(self):
         ctx = self.ctx
-        if self.method in _GRID_CAP:
+        if self.method == 'fft-tiled':
+            _lib.check(ctx.lib.ml_propagate_plan_grid_tiled(
+                ctx.handle, *self._geometry, float(self.x[0]), float(self.y[0]), self.x.size, self.y.size,
+                float(self.z[0]), int(self.want_h), *self.tile))
+        elif self.method in _GRID_CAP:
             entry = ctx.lib.ml_propagate_plan_grid if self.method == 'fft' else ctx.lib.ml_propagate_plan_grid_long
             _lib.check(entry(
                 ctx.handle, *self._geometry, float(self.x[0]), float(self.y[0]), self.x.size, self.y.size,
@@ -238,12 +303,12 @@ class PlanePropagator:
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,
-                   want_h=True, units=None, Z0=None, ctx=None, method='direct'):
+                   want_h=True, units=None, Z0=None, ctx=None, method='direct', tile=None):
     """One-shot convenience, modelled on ``farfield_direct``: the field of host arrays ``Ex..Hy`` (or of the
     field set already resident on the GPU if ``Ex is None``, e.g. after ``build_nearfield(..., download=False)``
     or a ``HotPath`` step) at the targets.  Arguments and the returned dict as for ``PlanePropagator``."""
     p = PlanePropagator(xp_list, yp_list, wavelength, n_glass, x, y, z, point_list=point_list, want_h=want_h,
-                        units=units, Z0=Z0, ctx=ctx, method=method)
+                        units=units, Z0=Z0, ctx=ctx, method=method, tile=tile)
     ctx = p.ctx
     if Ex is not None:
         arrs = [_lib.c128(a) for a in (Ex, Ey, Hx, Hy)]

@@ -38,7 +38,17 @@ batch in one ml_propagate_sets call, 2048^2 -> 64^2.
 ms_first_with_workspace = the same from a context that holds no workspace (the hipMalloc on top).  The direct sum runs
 once, on 8192^2 -> 64^2 with E + H (best of two passes): max |E_fft-long - E_direct| / max |E| and crossover_targets as
 above.  A workspace the device cannot give is reported with the library's message, and the E-only rows follow.
---quick: 8192^2 -> 64^2, E + H, without the direct sum."""
+--quick: 8192^2 -> 64^2, E + H, without the direct sum.
+
+    python tools/propagate_bench.py --method fft-tiled --case N,M [--tile L] [--against fft|fft-long] [--direct T] [--eh-only]
+
+--method fft-tiled: ``PlanePropagator(method='fft-tiled')`` for one case N^2 -> M^2 per process (default 4096,64; --quick:
+1024,64), the same converging wave and the same targets as the rows above: ms = a pass on cached kernel spectra, ms_first
+= plan + first pass (workspace, the fill of every tile's kernels and their transform), the tile lengths (--tile L: L x L
+instead of the default), tiles, batch and workspace; --against: the cached pass of that method on the same targets, its
+workspace and max |E_tiled - E_other| / max |E|; --direct T: one direct pass on a T x T corner of the patch, its time per
+target and crossover_targets (for apertures no other FFT form takes).  With a diagnostic build of the library
+(METALENS_HIP_LIB) ML_GRID_TILE_BATCH_MIB sets the bytes of a batch and is reported as batch_MiB."""
 import json
 import os
 import re
@@ -258,6 +268,67 @@ def fft_long(quick, n=8192):
             print(json.dumps(line), flush=True)
 
 
+def fft_tiled(n, m, tile=None, other=None, want_hs=(True, False), direct_targets=0):
+    """``PlanePropagator(method='fft-tiled')`` for n^2 -> m^2 on the pitch: the cached pass, plan + first pass, the
+    workspace, and against ``other`` ('fft' or 'fft-long') on the same targets its cached pass and max |dE| / max |E|.
+    direct_targets t > 0: the direct sum on a t x t corner of the patch instead - its time per target, and the
+    difference of the methods there"""
+    import numpy as np
+
+    from metalens_amd import _lib
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl, n_glass = 580e-9, 1.46
+    x, f = converging_wave(ctx, n, wl, n_glass)
+    tx, ty = patch_on_pitch(x, m)
+    keys = ('Ex', 'Ey', 'Ez')
+    for want_h in want_hs:
+        line = {'case': '%d^2 -> %d^2 on the pitch' % (n, m), 'fields': 'E+H' if want_h else 'E', 'method': 'fft-tiled'}
+        if os.environ.get('ML_GRID_TILE_BATCH_MIB'):
+            line['batch_MiB'] = int(os.environ['ML_GRID_TILE_BATCH_MIB'])
+        try:
+            t0 = time.perf_counter()
+            p = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx, method='fft-tiled', tile=tile)
+            _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0))
+            ctx.sync()
+            ms_first = (time.perf_counter() - t0) * 1e3
+        except _lib.MetalensHipError as e:
+            line['error'] = str(e)
+            print(json.dumps(line), flush=True)
+            continue
+        ms = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0)))
+        info = p.plan_info()
+        got = p._download(None)
+        # (the plan's own bytes: the buffer only grows, and an earlier plan of the process may have left it larger)
+        planes = 8 * info['tiles'][0] * info['tiles'][1] + 4 * info['batch'] + (6 if want_h else 3)
+        line.update(ms=round(ms, 3), ms_first=round(ms_first, 3), L=[info['Lx'], info['Ly']], tiles=list(info['tiles']),
+                    batch=info['batch'], workspace_MiB=round(planes * info['Lx'] * info['Ly'] * 16 / 2 ** 20, 1))
+        if other:
+            try:
+                po = PlanePropagator(x, x, wl, n_glass, tx, ty, f, want_h=want_h, ctx=ctx, method=other)
+                ms_other = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, po.Z0)))
+                want, io = po._download(None), po.plan_info()
+                diff = max(np.abs(got[c] - want[c]).max() for c in keys) / max(np.abs(want[c]).max() for c in keys)
+                line.update(other=other, ms_other=round(ms_other, 3), speedup=round(ms_other / ms, 2),
+                            workspace_MiB_other=round(io['workspace_bytes'] / 2 ** 20, 1),
+                            max_E_difference_of_the_methods=float('%.3e' % diff))
+            except _lib.MetalensHipError as e:
+                line['error_other'] = str(e)
+        if direct_targets:
+            t = direct_targets
+            pd = PlanePropagator(x, x, wl, n_glass, tx[:t], ty[:t], f, want_h=want_h, ctx=ctx)
+            t0 = time.perf_counter()
+            _lib.check(ctx.lib.ml_propagate(ctx.handle, pd.Z0))
+            ctx.sync()
+            ms_direct = (time.perf_counter() - t0) * 1e3
+            want = pd._download(None)
+            diff = max(np.abs(got[c][:t, :t] - want[c]).max() for c in keys) / max(np.abs(got[c]).max() for c in keys)
+            line.update(direct_targets=t * t, ms_direct_per_target=round(ms_direct / (t * t), 4),
+                        crossover_targets=int(np.ceil(ms / (ms_direct / (t * t)))),
+                        max_E_difference_of_the_methods_on_them=float('%.3e' % diff))
+        print(json.dumps(line), flush=True)
+
+
 def fft_three_sets(n=2048, m=64):
     """the three sets of a synthesised x, y, z batch through ONE ml_propagate_sets call of an 'fft' plan"""
     import math
@@ -293,7 +364,17 @@ def fft_three_sets(n=2048, m=64):
                           'ratio_to_three_single_passes': round(ms_three / (3 * ms_one), 4)}), flush=True)
 
 
+def _option(name, default=None):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
 def main():
+    if _option('--method') == 'fft-tiled':
+        n, m = (int(v) for v in _option('--case', '1024,64' if '--quick' in sys.argv else '4096,64').split(','))
+        tile = int(_option('--tile', 0))
+        fft_tiled(n, m, tile=(tile, tile) if tile else None, other=_option('--against'),
+                  want_hs=(True,) if '--eh-only' in sys.argv else (True, False), direct_targets=int(_option('--direct', 0)))
+        return
     if '--method' in sys.argv and sys.argv[sys.argv.index('--method') + 1] == 'fft-long':
         fft_long('--quick' in sys.argv)
         return
