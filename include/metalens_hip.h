@@ -537,14 +537,45 @@ int ml_propagate_plan_grid_tiled(ml_ctx *ctx, double x0, double y0, double dxp, 
                                  int tile_lx, int tile_ly);
 /* The tiles of the active tiled plan: tiles per axis cx, cy, samples per tile bx, by and the tiles that go through
  * the transforms together (batch); zeros while the plan has met no resident field set.  ML_ESTATE unless a tiled
- * plan is active.  Any pointer may be NULL.  Replaces no reference lines.                  */
+ * or a fine plan is active.  Any pointer may be NULL.  Replaces no reference lines.        */
 int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch);
+/* ml_propagate_plan_grid_tiled for a tensor grid of targets FINER than the aperture's pitch: mx x my targets
+ * (tx[0] + i dxp / sx, ty[0] + j dyp / sy, z) with integer ratios sx, sy in [1, 8], target t = i my + j.  Per axis the
+ * targets a, a + s, a + 2 s, ... are lattice a, on the aperture's pitch: min(s, m) lattices hold a target, lattice a
+ * holds ceil((m - a) / s).  tx_first, ty_first: the first min(sx, mx) and min(sy, my) coordinates of the fine axes, the
+ * lattices' origins - strictly ascending and spanning less than the pitch.  Every lattice is the tiled convolution of
+ * ml_propagate_plan_grid_tiled with tx0 = tx_first[a], ty0 = ty_first[b] and m_c = ceil(m / s) targets per axis (tile_lx,
+ * tile_ly and their default are checked against m_c), and has its bits where it holds m_c targets per axis; the
+ * targets of a shorter lattice beyond its own are computed and dropped.  One plan: the currents of a field set are
+ * padded and transformed once, tile by tile, and kept for the pass; the lattices are contracted two per read of the
+ * currents, transformed back and scattered into the result, which has the layout of every other plan - [6 or 3][mx my],
+ * so ml_propagate, ml_propagate_sets, ml_propagate_download[_set], ml_propagate_accumulate and ml_propagate_sums serve
+ * it unchanged.  cache_kernels != 0: the kernel spectra of all lattices are filled by the first pass and kept while the
+ * plan and the shape stay, a workspace of (8 A tiles + 4 tiles + 2 (6 or 3)) Lx Ly complex128 with A the lattices;
+ * cache_kernels == 0: those of two lattices and one batch of tiles are filled and transformed in every pass,
+ * (16 batch + 4 tiles + 2 (6 or 3)) Lx Ly complex128; the same bits.  The first pass on a shape reserves the workspace
+ * and fails with ML_ENOMEM and the bytes asked for (and, caching, those of cache_kernels == 0) if the device cannot give
+ * them.  A ratio outside [1, 8], m_c > 8192, a tile length that is no power of two in [16, 8192] or below m_c, more than
+ * 2^26 fine targets, origins that do not ascend or span the pitch, and the refusals of ml_propagate_plan_grid_tiled end
+ * in ML_EINVAL with this entry's name in ml_last_error; the previous plan stays as it was.  ml_propagate_plan_info
+ * reports ML_PROPAGATE_FFT_FINE and the TILE lengths; ml_propagate_plan_tiles serves this plan too.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_grid_fine(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                                double wavelength, double n_glass,
+                                const double *tx_first, int sx, const double *ty_first, int sy,
+                                int mx, int my, double z, int want_h, int tile_lx, int tile_ly,
+                                int cache_kernels);
+/* The lattices of the active fine plan: the ratios sx, sy, the targets per lattice as planned mcx, mcy and whether
+ * the kernel spectra are kept (cached).  ML_ESTATE unless a fine plan is active.  Any pointer may be NULL.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy, int *cached);
 #define ML_PROPAGATE_DIRECT 0
 #define ML_PROPAGATE_FFT 1
 #define ML_PROPAGATE_FFT_LONG 2
 #define ML_PROPAGATE_FFT_TILED 3
+#define ML_PROPAGATE_FFT_FINE 4
 /* The active propagation plan: method (ML_PROPAGATE_*), the padded lengths lx, ly (0 for a direct plan, and for
- * an fft plan that has met no resident field set yet; the tile lengths of a tiled plan) and the bytes of device
+ * an fft plan that has met no resident field set yet; the tile lengths of a tiled or a fine plan) and the bytes of device
  * workspace it holds besides targets,
  * result and sums (direct: the row-set partial sums of the last pass; fft: spectra, currents and outputs, from
  * the first pass on).  ML_ESTATE without a plan.  Any pointer may be NULL.

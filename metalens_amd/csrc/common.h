@@ -301,7 +301,7 @@ struct PropagatePlan {
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
     // the FFT form (propagate_grid.hip, ml_propagate_plan_grid): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
-    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED
+    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED / ML_PROPAGATE_FFT_FINE
     GridPlanFacts grid;   // (propagate_grid.h) for the aperture shape last met; spectra_ready: its kernel spectra are in grid_work
     bool spectra_ready = false;
     double tx_off = 0, ty_off = 0, z = 0;
@@ -309,8 +309,14 @@ struct PropagatePlan {
     // aperture shape last met; grid.Lx, grid.Ly are then the TILE lengths (what the transform launchers read)
     int tile_lx = 0, tile_ly = 0;
     GridTilePlan tile;
+    // the fine plan (ml_propagate_plan_grid_fine): what was asked for - the ratios, the fine counts and the mode in
+    // `fine`, the lattices' origins minus (x0, y0) - and the plan for the aperture shape last met (fine.tile; `tile` is a
+    // copy of it, for ml_propagate_plan_tiles).  grid.mx, grid.my are then the counts PER LATTICE, T the fine targets
+    GridFinePlan fine;
+    double fine_tx[GRID_FINE_S_MAX] = {}, fine_ty[GRID_FINE_S_MAX] = {};
     // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; the tiled plan: [tiles][8] kernel spectra,
-    // [batch][4] currents, [6 or 3] outputs; released by a direct plan
+    // [batch][4] currents, [6 or 3] outputs; the fine plan: [lattices][tiles][8] (or [2][batch][8]) kernel spectra,
+    // [tiles][4] currents, [2][6 or 3] outputs; released by a direct plan
     DevBuf grid_work;
     DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
 };

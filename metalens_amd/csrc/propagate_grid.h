@@ -183,6 +183,89 @@ inline int grid_tile_plan(int nx, int ny, int mx, int my, int want_h, int tile_l
     return 0;
 }
 
+// The fine plan (ml_propagate_plan_grid_fine): a tensor grid of targets on the aperture's pitch divided by an integer s
+// per axis.  Per axis, m fine targets t[i] = t[0] + i dxp / s: the targets a, a + s, a + 2 s, ... are lattice a, on the
+// aperture's pitch with the origin t[a] - what a tiled plan with tx0 = t[a] would be given.  A = min(s, m) lattices hold a
+// target, lattice a holds m_a = ceil((m - a) / s) of them; all are planned with the count m_c = ceil(m / s) = m_0 of
+// lattice 0 and share ONE tiled plan of (nx, ny, m_cx, m_cy) - the targets of a ragged lattice beyond m_a are computed and
+// dropped.  The currents of a field set are padded and transformed once, tile by tile, and kept; every lattice is a
+// contraction of them with its own kernel spectra, an inverse transform and a scatter into the interleaved result.
+//   cache_kernels: the kernel spectra of all Ax Ay lattices are kept for the life of the plan,
+//                  (8 Ax Ay tiles + 4 tiles + 2 outputs) planes;
+//   otherwise:     those of GRID_FINE_PAIR lattices and one batch of tiles are filled and transformed in every pass,
+//                  (16 batch + 4 tiles + 2 outputs) planes.
+constexpr int GRID_FINE_S_MAX = 8;
+constexpr int GRID_FINE_PAIR = 2;   // lattices contracted per read of the currents
+
+inline int grid_fine_count(int m, int s) { return (m + s - 1) / s; }                      // m_c
+inline int grid_fine_active(int m, int s) { return s < m ? s : m; }                        // A
+inline int grid_fine_lattice_count(int m, int s, int a) { return (m - a + s - 1) / s; }    // m_a, a < A
+
+struct GridFinePlan {
+    int sx = 0, sy = 0;       // the pitch ratios
+    int ax = 0, ay = 0;       // active lattices per axis
+    int mx = 0, my = 0;       // fine targets
+    int m_cx = 0, m_cy = 0;   // targets per lattice as planned
+    int cache_kernels = 1;
+    GridTilePlan tile;        // of (nx, ny, m_cx, m_cy)
+    int64_t workspace_bytes = 0;
+};
+
+// what is wrong with the ratio s, the m fine targets and the tile length L (0: the default) of an axis of n samples
+// (0: not known yet); -> 0, or -1 with `why` filled
+inline int grid_fine_check_axis(const char *axis, int n, int m, int s, int L, char *why, size_t why_len) {
+    if (s < 1 || s > GRID_FINE_S_MAX) {
+        snprintf(why, why_len,
+                 "the fine FFT form divides the aperture's pitch by an integer s in [1, %d]: the %s axis of n = %d samples "
+                 "and m = %d fine targets has s = %d",
+                 GRID_FINE_S_MAX, axis, n, m, s);
+        return -1;
+    }
+    const int m_c = grid_fine_count(m, s);
+    if (m_c > GRID_L_MAX) {
+        snprintf(why, why_len,
+                 "the fine FFT form takes at most %d targets per lattice and axis (a tile is at least as long as a lattice's "
+                 "targets, one row of L complex128 must fit the LDS): the %s axis of n = %d samples has m = %d fine targets at "
+                 "s = %d, m_c = %d per lattice; use the direct method or fewer targets per plan",
+                 GRID_L_MAX, axis, n, m, s, m_c);
+        return -1;
+    }
+    if (L != 0 && !grid_tile_length_ok(L, m_c)) {
+        snprintf(why, why_len,
+                 "the tile length of the %s axis of n = %d samples and m_c = %d targets per lattice (m = %d fine targets at "
+                 "s = %d) is L = %d: it must be a power of two in [%d, %d] and at least m_c (0: the default)",
+                 axis, n, m_c, m, s, L, GRID_L_MIN, GRID_L_MAX);
+        return -1;
+    }
+    return 0;
+}
+
+// -> 0, or -1 with `why` filled.  mx, my >= 1: the fine targets; the other arguments as grid_tile_plan's.
+inline int grid_fine_plan(int nx, int ny, int mx, int my, int sx, int sy, int want_h, int tile_lx, int tile_ly, int cache_kernels,
+                          int64_t batch_bytes, GridFinePlan *p, char *why, size_t why_len) {
+    if (grid_fine_check_axis("x", nx, mx, sx, tile_lx, why, why_len) != 0) return -1;
+    if (grid_fine_check_axis("y", ny, my, sy, tile_ly, why, why_len) != 0) return -1;
+    if ((long long)mx * my > (1 << 26)) {
+        snprintf(why, why_len, "%lld fine targets (%d x %d): at most 2^26 per plan", (long long)mx * my, mx, my);
+        return -1;
+    }
+    p->sx = sx;
+    p->sy = sy;
+    p->ax = grid_fine_active(mx, sx);
+    p->ay = grid_fine_active(my, sy);
+    p->mx = mx;
+    p->my = my;
+    p->m_cx = grid_fine_count(mx, sx);
+    p->m_cy = grid_fine_count(my, sy);
+    p->cache_kernels = cache_kernels != 0;
+    if (grid_tile_plan(nx, ny, p->m_cx, p->m_cy, want_h, tile_lx, tile_ly, batch_bytes, &p->tile, why, why_len) != 0) return -1;
+    const GridTilePlan &t = p->tile;
+    const int64_t kernels = p->cache_kernels ? (int64_t)GRID_KERNELS * p->ax * p->ay * t.tiles
+                                             : (int64_t)GRID_KERNELS * GRID_FINE_PAIR * t.batch;
+    p->workspace_bytes = (kernels + (int64_t)GRID_CURRENTS * t.tiles + GRID_FINE_PAIR * t.outputs) * t.plane_bytes;
+    return 0;
+}
+
 // cos / sin of 2 pi j / L for j < L / 2, evaluated in long double and rounded once: [L / 2][2]
 inline std::vector<double> grid_twiddles(int L) {
     std::vector<double> t((size_t)L);

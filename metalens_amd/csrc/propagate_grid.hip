@@ -34,6 +34,8 @@
 // The tiled plan (ml_propagate_plan_grid_tiled) cuts the aperture into tiles, convolves each at a short padded length
 // and adds the tiles' products in the spectral domain (overlap-add; the grid_tile_* kernels below, through the same
 // transform launches with more planes per launch).
+// The fine plan (ml_propagate_plan_grid_fine) puts targets on the pitch divided by (sx, sy): sx sy lattices on the pitch,
+// each a tiled convolution of the SAME current spectra with its own kernel spectra (the grid_fine_* kernels).
 #include "nearfield_math.h"
 
 namespace ml {
@@ -739,9 +741,303 @@ static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
     return ML_OK;
 }
 
+// ---- the fine plan (ml_propagate_plan_grid_fine; propagate_grid.h GridFinePlan) ----------------------------------
+// Targets on the aperture's pitch divided by (sx, sy): Ax Ay lattices on the pitch, lattice l = a Ay + b with the origin
+// (fine_tx[a], fine_ty[b]), all on the tiled plan of (nx, ny, m_cx, m_cy).  Current spectra [tiles][4][Lx][Ly], padded
+// and transformed once per field set in the batches of the tiled plan and kept for the pass; kernel spectra
+// [lattices][tiles][8] kept for the life of the plan (cache_kernels), or [2][batch][8] filled and transformed in every
+// pass; outputs [2][6 or 3].  Then lattice by lattice, in pairs (a single one last if Ax Ay is odd): contraction over
+// all tiles in ascending order, ONE inverse transform of the pair's planes, scatter into the interleaved result.
+
+// the products of one tile and one lattice from currents already loaded: tile_products, term by term
+template <bool WANT_H, bool START>
+__device__ __forceinline__ void fine_products(d2 (&e)[6], const d2 *K, size_t ps, size_t id, d2 Jx, d2 Jy, d2 mx, d2 my) {
+    const d2 Kxx = ld_stream(K + id), Kxy = ld_stream(K + ps + id), Kyy = ld_stream(K + 2 * ps + id);
+    const d2 Kzx = ld_stream(K + 3 * ps + id), Kzy = ld_stream(K + 4 * ps + id);
+    const d2 Cx = ld_stream(K + 5 * ps + id), Cy = ld_stream(K + 6 * ps + id), Cz = ld_stream(K + 7 * ps + id);
+    zterm<START>(e[0], Kxx, Jx);
+    zfma(e[0], Kxy, Jy);
+    zfma(e[0], Cz, my);
+    zterm<START>(e[1], Kxy, Jx);
+    zfma(e[1], Kyy, Jy);
+    zfma(e[1], zneg(Cz), mx);
+    zterm<START>(e[2], Kzx, Jx);
+    zfma(e[2], Kzy, Jy);
+    zfma(e[2], Cy, mx);
+    zfma(e[2], zneg(Cx), my);
+    if (WANT_H) {
+        zterm<START>(e[3], Kxx, mx);
+        zfma(e[3], Kxy, my);
+        zfma(e[3], zneg(Cz), Jy);
+        zterm<START>(e[4], Kxy, mx);
+        zfma(e[4], Kyy, my);
+        zfma(e[4], Cz, Jx);
+        zterm<START>(e[5], Kzx, mx);
+        zfma(e[5], Kzy, my);
+        zfma(e[5], Cx, Jy);
+        zfma(e[5], zneg(Cy), Jx);
+    }
+}
+
+// per bin: the n tiles of a launch (cur: the first one's currents) added in ascending order to the 6 (3) output spectra
+// of G lattices - K: the first tile's spectra of the first lattice, those of the second k_lattice elements behind; out:
+// [G][6 or 3] planes.  The four currents of a tile are loaded once for the G lattices; per lattice the sums are those of
+// grid_tile_contract_kernel, bit for bit (FIRST as there).  Sums in registers, no atomics.
+template <bool WANT_H, bool FIRST, int G>
+__global__ __launch_bounds__(256) void grid_fine_contract_kernel(const d2 *K, size_t k_lattice, const d2 *cur, d2 *out, size_t ps,
+                                                                 int n) {
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
+    constexpr int NC = WANT_H ? 6 : 3;
+    d2 e[G][6];
+    int g = 0;
+    if (FIRST) {
+        const d2 Jx = cur[id], Jy = cur[ps + id], mx = cur[2 * ps + id], my = cur[3 * ps + id];
+#pragma unroll
+        for (int l = 0; l < G; ++l) fine_products<WANT_H, true>(e[l], K + l * k_lattice, ps, id, Jx, Jy, mx, my);
+        g = 1;
+    } else {
+#pragma unroll
+        for (int l = 0; l < G; ++l)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) e[l][c] = out[(l * NC + c) * ps + id];
+    }
+    for (; g < n; ++g) {
+        const d2 *ct = cur + (size_t)g * GRID_CURRENTS * ps;
+        const d2 Jx = ct[id], Jy = ct[ps + id], mx = ct[2 * ps + id], my = ct[3 * ps + id];
+#pragma unroll
+        for (int l = 0; l < G; ++l)
+            fine_products<WANT_H, false>(e[l], K + l * k_lattice + (size_t)g * GRID_KERNELS * ps, ps, id, Jx, Jy, mx, my);
+    }
+#pragma unroll
+    for (int l = 0; l < G; ++l)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) out[(l * NC + c) * ps + id] = e[l][c];
+}
+
+struct GridFineScatterArgs {
+    const d2 *out;          // [lattices of the launch][nc][Lx][Ly]
+    d2 *result;             // [nc][mx my] of one field set
+    size_t plane_stride;
+    int nc, Ly;
+    int m_cx, m_cy;         // targets per lattice as planned
+    int mx, my, sx, sy;     // fine targets, pitch ratios
+    int a[GRID_FINE_PAIR], b[GRID_FINE_PAIR];   // the lattices of the launch
+    double scale_e, scale_h;
+};
+
+// lattice (a, b) = blockIdx.z of the launch, component blockIdx.y: result[component][(a + sx i) my + b + sy j] = scale
+// out[component][i][j] (the scales of grid_crop_kernel) for the targets the lattice has - (a + sx i, b + sy j) inside
+// mx x my; those of a ragged lattice beyond are dropped
+__global__ __launch_bounds__(256) void grid_fine_scatter_kernel(const GridFineScatterArgs s) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= s.m_cx * s.m_cy) return;
+    const int i = t / s.m_cy, j = t - i * s.m_cy, m = blockIdx.y, l = blockIdx.z;
+    const int fi = s.a[l] + s.sx * i, fj = s.b[l] + s.sy * j;
+    if (fi >= s.mx || fj >= s.my) return;
+    const double scale = m < 3 ? s.scale_e : s.scale_h;
+    const d2 v = s.out[((size_t)l * s.nc + m) * s.plane_stride + (size_t)i * s.Ly + j];
+    s.result[(size_t)m * s.mx * s.my + (size_t)fi * s.my + fj] = make_double2(scale * v.x, scale * v.y);
+}
+
+// (diagnostic build: ML_GRID_FINE_PAIR=1 contracts one lattice per read of the currents, for timing)
+static int fine_pair() { return diag_int("ML_GRID_FINE_PAIR", GRID_FINE_PAIR) == 1 ? 1 : GRID_FINE_PAIR; }
+
+// the eight kernel spectra of the tiles [tile0, tile0 + nt) of lattice (a, b) into K: the fill of a tiled plan whose
+// origin is the lattice's, and the forward transform
+static int fine_kernels(ml_ctx *ctx, int a, int b, int tile0, int nt, d2 *K) {
+    const PropagatePlan &pp = ctx->prop;
+    const GridPlanFacts &f = pp.grid;
+    const GridTilePlan &t = pp.fine.tile;
+    GridTileGeoArgs ta;
+    GridGeoArgs &g = ta.g;
+    g.plane_stride = (size_t)f.Lx * f.Ly;
+    g.Lx = f.Lx;
+    g.Ly = f.Ly;
+    g.mx = f.mx;
+    g.my = f.my;
+    g.tx_off = pp.fine_tx[a];
+    g.ty_off = pp.fine_ty[b];
+    g.dxp = pp.dxp;
+    g.dyp = pp.dyp;
+    g.z = pp.z;
+    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
+    g.inv_k = 1.0 / g.k;
+    ta.cy = t.y.c;
+    ta.Bx = t.x.B;
+    ta.By = t.y.B;
+    for (int done = 0; done < nt; done += GRID_TILE_BATCH_MAX) {   // 512 planes per launch at the most
+        const int now = std::min(GRID_TILE_BATCH_MAX, nt - done);
+        ta.tile0 = tile0 + done;
+        g.out = K + (size_t)done * GRID_KERNELS * g.plane_stride;
+        hipLaunchKernelGGL(grid_tile_fill_kernel, dim3((unsigned)(g.plane_stride / 256), now), dim3(256), 0, ctx->stream, ta);
+        ML_HIP(hipGetLastError());
+        ML_TRY(fft_rows<false>(ctx, g.out, now * GRID_KERNELS, f.Lx));
+        ML_TRY(fft_cols<false>(ctx, g.out, now * GRID_KERNELS));
+    }
+    return ML_OK;
+}
+
+// the plan and the workspace for the resident field's shape and, with cache_kernels, every lattice's kernel spectra
+// (kept while the shape stays)
+static int fine_prepare(ml_ctx *ctx) {
+    PropagatePlan &pp = ctx->prop;
+    if (pp.spectra_ready && pp.grid.nx == ctx->fields.nx && pp.grid.ny == ctx->fields.ny) return ML_OK;
+    pp.spectra_ready = false;
+    char why[480];
+    GridFinePlan p;
+    if (grid_fine_plan(ctx->fields.nx, ctx->fields.ny, pp.fine.mx, pp.fine.my, pp.fine.sx, pp.fine.sy, pp.want_h, pp.tile_lx,
+                       pp.tile_ly, pp.fine.cache_kernels, tile_batch_bytes(), &p, why, sizeof why) != 0) {
+        set_error("%s", why);
+        return ML_EINVAL;
+    }
+    pp.fine = p;
+    const GridTilePlan &t = pp.tile = p.tile;
+    GridPlanFacts &f = pp.grid;   // what the transform launchers read: the tile's lengths
+    f.nx = t.nx;
+    f.ny = t.ny;
+    f.mx = p.m_cx;
+    f.my = p.m_cy;
+    f.Lx = t.x.L;
+    f.Ly = t.y.L;
+    f.outputs = t.outputs;
+    f.plane_bytes = t.plane_bytes;
+    f.workspace_bytes = p.workspace_bytes;
+    if (pp.grid_work.reserve((size_t)p.workspace_bytes) != ML_OK) {
+        if (p.cache_kernels) {
+            GridFinePlan streamed;
+            grid_fine_plan(t.nx, t.ny, p.mx, p.my, p.sx, p.sy, pp.want_h, pp.tile_lx, pp.tile_ly, 0, tile_batch_bytes(), &streamed,
+                           why, sizeof why);
+            set_error("the fine FFT form keeps the kernel spectra of %d x %d lattices and %d tiles: the device did not give the "
+                      "%lld bytes of its workspace; cache_kernels=0 fills them in every pass and takes %lld bytes",
+                      p.ax, p.ay, t.tiles, (long long)p.workspace_bytes, (long long)streamed.workspace_bytes);
+        } else {
+            set_error("the fine FFT form: the device did not give the %lld bytes of its workspace (%d tiles; the current spectra "
+                      "of all tiles are kept for a pass)", (long long)p.workspace_bytes, t.tiles);
+        }
+        return ML_ENOMEM;
+    }
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
+    ML_TRY(upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
+    if (p.cache_kernels) {
+        const size_t per_lattice = (size_t)t.tiles * GRID_KERNELS * f.Lx * f.Ly;
+        for (int l = 0; l < p.ax * p.ay; ++l)
+            ML_TRY(fine_kernels(ctx, l / p.ay, l % p.ay, 0, t.tiles, pp.grid_work.as<d2>() + l * per_lattice));
+    }
+    pp.spectra_ready = true;
+    return ML_OK;
+}
+
+template <bool WANT_H, int G>
+static void launch_fine_contract(ml_ctx *ctx, unsigned blocks, bool first, const d2 *K, size_t k_lattice, const d2 *cur, d2 *out,
+                                 size_t ps, int n) {
+    if (first)
+        hipLaunchKernelGGL((grid_fine_contract_kernel<WANT_H, true, G>), dim3(blocks), dim3(256), 0, ctx->stream, K, k_lattice, cur,
+                           out, ps, n);
+    else
+        hipLaunchKernelGGL((grid_fine_contract_kernel<WANT_H, false, G>), dim3(blocks), dim3(256), 0, ctx->stream, K, k_lattice, cur,
+                           out, ps, n);
+}
+
+// the tiles [tile0, tile0 + n) into the output spectra of `lattices` (1 or 2) lattices
+static int fine_contract(ml_ctx *ctx, int lattices, unsigned blocks, bool first, const d2 *K, size_t k_lattice, const d2 *cur,
+                         d2 *out, size_t ps, int n) {
+    const bool h = ctx->prop.want_h;
+    if (lattices == 2)
+        h ? launch_fine_contract<true, 2>(ctx, blocks, first, K, k_lattice, cur, out, ps, n)
+          : launch_fine_contract<false, 2>(ctx, blocks, first, K, k_lattice, cur, out, ps, n);
+    else
+        h ? launch_fine_contract<true, 1>(ctx, blocks, first, K, k_lattice, cur, out, ps, n)
+          : launch_fine_contract<false, 1>(ctx, blocks, first, K, k_lattice, cur, out, ps, n);
+    ML_HIP(hipGetLastError());
+    return ML_OK;
+}
+
+static int propagate_fine_sets(ml_ctx *ctx, double Z0, int first, int n) {
+    PropagatePlan &pp = ctx->prop;
+    pp.have_result = false;
+    ML_TRY(fine_prepare(ctx));
+    const GridPlanFacts &f = pp.grid;
+    const GridFinePlan &fp = pp.fine;
+    const GridTilePlan &t = fp.tile;
+    const int T = pp.T, nc = f.outputs, lattices = fp.ax * fp.ay, pair = fine_pair();
+    ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
+    const size_t ps = (size_t)f.Lx * f.Ly;
+    // cached: [lattices][tiles][8]; streamed: [2][batch][8]
+    const size_t k_lattice = (size_t)(fp.cache_kernels ? t.tiles : t.batch) * GRID_KERNELS * ps;
+    d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)(fp.cache_kernels ? lattices : GRID_FINE_PAIR) * k_lattice;
+    d2 *out = cur + (size_t)t.tiles * GRID_CURRENTS * ps;
+    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
+    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
+    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const unsigned blocks = (unsigned)(ps / 256);
+    const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
+    GridTilePadArgs p;
+    p.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
+    p.plane_stride = ps;
+    p.nx = t.nx;
+    p.ny = t.ny;
+    p.Lx = f.Lx;
+    p.Ly = f.Ly;
+    p.Bx = t.x.B;
+    p.By = t.y.B;
+    p.cy = t.y.c;
+    p.Z = Z;
+    GridFineScatterArgs s;
+    s.out = out;
+    s.plane_stride = ps;
+    s.nc = nc;
+    s.Ly = f.Ly;
+    s.m_cx = fp.m_cx;
+    s.m_cy = fp.m_cy;
+    s.mx = fp.mx;
+    s.my = fp.my;
+    s.sx = fp.sx;
+    s.sy = fp.sy;
+    s.scale_e = Z * scale_h * inv_n;
+    s.scale_h = scale_h * inv_n;
+    for (int m = 0; m < n; ++m) {
+        p.fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
+        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {   // the current spectra of every tile, once per set
+            const int nt = std::min(t.batch, t.tiles - tile0);
+            p.tile0 = tile0;
+            p.cur = cur + (size_t)tile0 * GRID_CURRENTS * ps;
+            hipLaunchKernelGGL(grid_tile_pad_kernel, dim3(blocks, GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
+            ML_HIP(hipGetLastError());
+            ML_TRY(fft_rows<false>(ctx, p.cur, nt * GRID_CURRENTS, rows_fwd));
+            ML_TRY(fft_cols<false>(ctx, p.cur, nt * GRID_CURRENTS));
+        }
+        s.result = pp.result.as<d2>() + (size_t)m * nc * T;
+        for (int l0 = 0; l0 < lattices; l0 += pair) {
+            const int nl = std::min(pair, lattices - l0);
+            for (int l = 0; l < nl; ++l) {
+                s.a[l] = (l0 + l) / fp.ay;
+                s.b[l] = (l0 + l) % fp.ay;
+            }
+            if (fp.cache_kernels) {
+                ML_TRY(fine_contract(ctx, nl, blocks, true, K + (size_t)l0 * k_lattice, k_lattice, cur, out, ps, t.tiles));
+            } else {
+                for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {
+                    const int nt = std::min(t.batch, t.tiles - tile0);
+                    for (int l = 0; l < nl; ++l) ML_TRY(fine_kernels(ctx, s.a[l], s.b[l], tile0, nt, K + l * k_lattice));
+                    ML_TRY(fine_contract(ctx, nl, blocks, tile0 == 0, K, k_lattice, cur + (size_t)tile0 * GRID_CURRENTS * ps, out, ps,
+                                         nt));
+                }
+            }
+            ML_TRY(fft_cols<true>(ctx, out, nl * nc));
+            ML_TRY(fft_rows<true>(ctx, out, nl * nc, fp.m_cx));
+            hipLaunchKernelGGL(grid_fine_scatter_kernel, dim3((fp.m_cx * fp.m_cy + 255) / 256, nc, nl), dim3(256), 0, ctx->stream, s);
+            ML_HIP(hipGetLastError());
+        }
+    }
+    pp.have_result = true;
+    pp.result_sets = n;
+    return ML_OK;
+}
+
 int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     PropagatePlan &pp = ctx->prop;
     if (pp.method == ML_PROPAGATE_FFT_TILED) return propagate_tile_sets(ctx, Z0, first, n);
+    if (pp.method == ML_PROPAGATE_FFT_FINE) return propagate_fine_sets(ctx, Z0, first, n);
     pp.have_result = false;
     ML_TRY(grid_prepare(ctx));
     const GridPlanFacts &f = pp.grid;
@@ -785,11 +1081,28 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
 
 using namespace ml;
 
-// ml_propagate_plan_grid, ml_propagate_plan_grid_long and ml_propagate_plan_grid_tiled: `entry` is the caller's name,
-// `method` its ML_PROPAGATE_*; tile_lx, tile_ly: the tile lengths of the tiled plan (0: the default)
+// what ml_propagate_plan_grid_fine asks for beyond a tiled plan
+struct FineAsk {
+    const double *tx_first, *ty_first;   // the first min(s, m) coordinates of each fine axis
+    int sx, sy, cache_kernels;
+};
+
+// the origins of an axis' lattices: strictly ascending within one pitch
+static int fine_origins_ok(const char *entry, const char *axis, const double *first, int active, double pitch) {
+    for (int a = 1; a < active; ++a)
+        ML_REQUIRE(first[a] > first[a - 1], "%s: the %s origins of the lattices must ascend strictly: %s_first[%d] = %.17g is not "
+                   "above %s_first[%d] = %.17g", entry, axis, axis, a, first[a], axis, a - 1, first[a - 1]);
+    ML_REQUIRE(first[active - 1] - first[0] < pitch, "%s: the %s origins of the lattices must span less than the aperture's pitch "
+               "%.17g: %s_first[%d] - %s_first[0] = %.17g", entry, axis, pitch, axis, active - 1, axis, first[active - 1] - first[0]);
+    return ML_OK;
+}
+
+// ml_propagate_plan_grid, ml_propagate_plan_grid_long, ml_propagate_plan_grid_tiled and ml_propagate_plan_grid_fine: `entry`
+// is the caller's name, `method` its ML_PROPAGATE_*; tile_lx, tile_ly: the tile lengths of the tiled and the fine plan (0:
+// the default); `fine`: of the fine plan, whose mx, my are the FINE targets and tx0, ty0 its first lattice's origin
 static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, double y0, double dxp, double dyp, double wavelength,
                      double n_glass, double tx0, double ty0, int mx, int my, double z, int want_h, int tile_lx = 0,
-                     int tile_ly = 0) {
+                     int tile_ly = 0, const FineAsk *fine = nullptr) {
     ML_REQUIRE(ctx, "ctx is NULL");
     ML_REQUIRE(ctx->n_ranks <= 1, "%s: this context belongs to a communicator of %d ranks; the "
                "finite-distance propagator sums a whole aperture on one GPU (sharded propagation is not implemented)",
@@ -802,7 +1115,35 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     f.mx = mx;
     f.my = my;
     GridTilePlan tile;
-    if (method == ML_PROPAGATE_FFT_TILED) {   // what is wrong with the targets or the lengths whatever the shape, and
+    GridFinePlan fp;
+    if (fine) {   // as for the tiled plan below
+        char why[480];
+        const bool resident = ctx->fields.nx && ctx->fields.ny;
+        const int bad = resident ? grid_fine_plan(ctx->fields.nx, ctx->fields.ny, mx, my, fine->sx, fine->sy, want_h, tile_lx, tile_ly,
+                                                  fine->cache_kernels, tile_batch_bytes(), &fp, why, sizeof why)
+                                 : (grid_fine_check_axis("x", 0, mx, fine->sx, tile_lx, why, sizeof why) ||
+                                    grid_fine_check_axis("y", 0, my, fine->sy, tile_ly, why, sizeof why));
+        if (bad) {
+            set_error("%s: %s", entry, why);
+            return ML_EINVAL;
+        }
+        fp.sx = fine->sx;   // (what was asked for is known without a shape)
+        fp.sy = fine->sy;
+        fp.mx = mx;
+        fp.my = my;
+        fp.ax = grid_fine_active(mx, fp.sx);
+        fp.ay = grid_fine_active(my, fp.sy);
+        fp.m_cx = grid_fine_count(mx, fp.sx);
+        fp.m_cy = grid_fine_count(my, fp.sy);
+        fp.cache_kernels = fine->cache_kernels != 0;
+        ML_TRY(fine_origins_ok(entry, "tx", fine->tx_first, fp.ax, dxp));
+        ML_TRY(fine_origins_ok(entry, "ty", fine->ty_first, fp.ay, dyp));
+        tile = fp.tile;
+        f.mx = fp.m_cx;   // per lattice: what the launches read
+        f.my = fp.m_cy;
+        f.Lx = resident ? tile.x.L : tile_lx;
+        f.Ly = resident ? tile.y.L : tile_ly;
+    } else if (method == ML_PROPAGATE_FFT_TILED) {   // what is wrong with the targets or the lengths whatever the shape, and
         char why[400];                        // the plan for the shape a pass would meet now
         const bool resident = ctx->fields.nx && ctx->fields.ny;
         const int bad = resident ? grid_tile_plan(ctx->fields.nx, ctx->fields.ny, mx, my, want_h, tile_lx, tile_ly,
@@ -829,6 +1170,9 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     pp.method = method;
     pp.grid = f;
     pp.tile = tile;
+    pp.fine = fp;
+    for (int a = 0; a < fp.ax; ++a) pp.fine_tx[a] = fine->tx_first[a] - x0;
+    for (int b = 0; b < fp.ay; ++b) pp.fine_ty[b] = fine->ty_first[b] - y0;
     pp.tile_lx = tile_lx;
     pp.tile_ly = tile_ly;
     pp.T = mx * my;
@@ -866,10 +1210,40 @@ int ml_propagate_plan_grid_tiled(ml_ctx *ctx, double x0, double y0, double dxp, 
                      mx, my, z, want_h, tile_lx, tile_ly);
 }
 
+int ml_propagate_plan_grid_fine(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                                const double *tx_first, int sx, const double *ty_first, int sy, int mx, int my, double z, int want_h,
+                                int tile_lx, int tile_ly, int cache_kernels) {
+    ML_REQUIRE(tx_first && ty_first, "ml_propagate_plan_grid_fine: NULL argument");
+    const FineAsk fine = {tx_first, ty_first, sx, sy, cache_kernels};
+    const char *entry = "ml_propagate_plan_grid_fine";
+    const int rc = plan_grid(ctx, entry, ML_PROPAGATE_FFT_FINE, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0], ty_first[0], mx,
+                             my, z, want_h, tile_lx, tile_ly, &fine);
+    if (rc != ML_OK && strncmp(ml_last_error(), entry, strlen(entry)) != 0) {   // every refusal names this entry
+        const std::string said = ml_last_error();
+        set_error("%s: %s", entry, said.c_str());
+    }
+    return rc;
+}
+
+int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy, int *cached) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    const PropagatePlan &pp = ctx->prop;
+    if (!pp.ready || pp.method != ML_PROPAGATE_FFT_FINE) {
+        set_error("ml_propagate_plan_lattices: no fine propagation plan is active");
+        return ML_ESTATE;
+    }
+    if (sx) *sx = pp.fine.sx;
+    if (sy) *sy = pp.fine.sy;
+    if (mcx) *mcx = pp.fine.m_cx;
+    if (mcy) *mcy = pp.fine.m_cy;
+    if (cached) *cached = pp.fine.cache_kernels;
+    return ML_OK;
+}
+
 int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch) {
     ML_REQUIRE(ctx, "ctx is NULL");
     const PropagatePlan &pp = ctx->prop;
-    if (!pp.ready || pp.method != ML_PROPAGATE_FFT_TILED) {
+    if (!pp.ready || (pp.method != ML_PROPAGATE_FFT_TILED && pp.method != ML_PROPAGATE_FFT_FINE)) {
         set_error("ml_propagate_plan_tiles: no tiled propagation plan is active");
         return ML_ESTATE;
     }

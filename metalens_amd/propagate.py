@@ -22,6 +22,8 @@ depends on the lag ``(i_t - i_s, j_t - j_s)`` alone, and the same sum runs as a 
 ``method='fft-long'`` is the same with padded axes of up to 16384 instead of 8192 - apertures of 4097 ... 8192 samples a
 side - and a workspace of up to 77 GB.  ``method='fft-tiled'`` cuts the aperture into tiles, convolves each at a short
 padded length ``L >= m`` and adds the tiles' products in the spectral domain (overlap-add): for ``m << n``.
+``method='fft-fine'`` is the tiled form for targets on the pitch divided by integers ``(sx, sy)``: the interleave of
+``sx sy`` lattices on the pitch, convolved with the same current spectra - what resolves a focal spot.
 """
 import numpy as np
 
@@ -46,11 +48,12 @@ def _targets(x, y, z, point_list):
     return x, y, z
 
 
-METHODS = ('direct', 'fft', 'fft-long', 'fft-tiled')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
+METHODS = ('direct', 'fft', 'fft-long', 'fft-tiled', 'fft-fine')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
 GRID_L_MIN, GRID_L_MAX = 16, 8192   # csrc/propagate_grid.h
 GRID_L_LONG_MAX = 16384
 _GRID_CAP = {'fft': GRID_L_MAX, 'fft-long': GRID_L_LONG_MAX}
-_GRID_METHODS = ('fft', 'fft-long', 'fft-tiled')   # a tensor grid of targets on the aperture's pitch
+_GRID_METHODS = ('fft', 'fft-long', 'fft-tiled', 'fft-fine')   # a tensor grid of targets on the aperture's pitch (or a fraction)
+FINE_S_MAX = 8   # csrc/propagate_grid.h GRID_FINE_S_MAX
 
 
 def _padded_length(n, m):
@@ -61,14 +64,19 @@ def _padded_length(n, m):
     return L
 
 
-def _on_pitch(name, t, pitch):
+def _on_pitch(name, t, pitch, s=1):
     """``method='fft'``: the target axis ``t`` must be ``t[0] + i pitch`` to within 4 spacings of its largest value
-    (the deviation changes the phase k x of the direct sum by a few 1e-13 rad at that level)"""
+    (the deviation changes the phase k x of the direct sum by a few 1e-13 rad at that level); ``method='fft-fine'``:
+    ``t[0] + i pitch / s``"""
     tol = 4 * np.spacing(np.abs(t).max())
-    off = np.abs(t - (t[0] + np.arange(t.size) * pitch)) > tol
+    off = np.abs(t - (t[0] + np.arange(t.size) * pitch / s)) > tol
     if off.any():
         i = int(np.argmax(off))
         own = t[1] - t[0]
+        if s != 1:
+            raise ValueError("method='fft-fine' needs the targets on the aperture's pitch / %d: %s[%d] = %.17g is not %s[0] + "
+                             "%d x %.17g / %d (the aperture's pitch along %s; the target axis steps by %.17g)"
+                             % (s, name, i, t[i], name, i, pitch, s, name, own))
         raise ValueError("method='fft' needs the targets on the aperture's pitch: %s[%d] = %.17g is not %s[0] + %d x %.17g "
                          "(the aperture's pitch along %s; the target axis steps by %.17g)"
                          % (name, i, t[i], name, i, pitch, name, own))
@@ -104,19 +112,58 @@ def _check_tile(name, n, m, L):
     return int(L)
 
 
+def _check_subsample(subsample):
+    """-> (sx, sy), integers in [1, 8]; None: (1, 1)"""
+    if subsample is None:
+        return 1, 1
+    try:
+        sx, sy = subsample
+    except (TypeError, ValueError):
+        raise ValueError('subsample must be None or the two pitch ratios (sx, sy), got %r' % (subsample,)) from None
+    for name, v in (('x', sx), ('y', sy)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer, float, np.floating)) or v != int(v) \
+                or not 1 <= v <= FINE_S_MAX:
+            raise ValueError("method='fft-fine' divides the aperture's pitch by an integer in [1, %d]: subsample = %r has "
+                             "s = %r along %s" % (FINE_S_MAX, tuple(subsample), v, name))
+    return int(sx), int(sy)
+
+
+def _check_fine(name, n, m, s, L):
+    """the refusals of ml_propagate_plan_grid_fine for one axis of m fine targets at the ratio s, before a context is
+    touched: at most 8192 targets per lattice, the tile length against ``m_c = ceil(m / s)``; L None: the default"""
+    m_c = -(-m // s)
+    if m_c > GRID_L_MAX:
+        raise ValueError("method='fft-fine' takes at most %d targets per lattice and axis: the %s axis of n = %d samples has "
+                         "m = %d fine targets at s = %d, m_c = %d per lattice; use method='direct' or fewer targets per "
+                         "propagator" % (GRID_L_MAX, name, n, m, s, m_c))
+    if L is None or L == 0:
+        return 0
+    if L != int(L) or not (GRID_L_MIN <= L <= GRID_L_MAX) or int(L) & (int(L) - 1) or L < m_c:
+        raise ValueError("method='fft-fine': the tile length of the %s axis of n = %d samples and m_c = %d targets per "
+                         "lattice (m = %d fine targets at s = %d) is L = %s: it must be a power of two in [%d, %d] and at "
+                         "least m_c (None or 0: the default)"
+                         % (name, n, m_c, m, s, int(L) if L == int(L) else float(L), GRID_L_MIN, GRID_L_MAX))
+    return int(L)
+
+
 def plan_info(ctx):
     """-> ``{'method', 'Lx', 'Ly', 'workspace_bytes'}`` of the context's active propagation plan
     (ml_propagate_plan_info): the padded lengths are 0 for the direct method.  For ``'fft-tiled'`` they are the tile
     lengths, and the dict has ``'tiles': (cx, cy)``, ``'tile_samples': (bx, by)`` and ``'batch'`` as well
-    (ml_propagate_plan_tiles)"""
+    (ml_propagate_plan_tiles); for ``'fft-fine'`` those and ``'subsample': (sx, sy)``, ``'lattice_targets': (m_cx, m_cy)``
+    and ``'cache_kernels'`` (ml_propagate_plan_lattices)"""
     method, lx, ly, ws = _lib.c_int(0), _lib.c_int(0), _lib.c_int(0), _lib.c_int64(0)
     _lib.check(ctx.lib.ml_propagate_plan_info(ctx.handle, _lib.byref(method), _lib.byref(lx), _lib.byref(ly),
                                               _lib.byref(ws)))
     info = {'method': METHODS[method.value], 'Lx': lx.value, 'Ly': ly.value, 'workspace_bytes': ws.value}
-    if info['method'] == 'fft-tiled':
+    if info['method'] in ('fft-tiled', 'fft-fine'):
         t = [_lib.c_int(0) for _ in range(5)]
         _lib.check(ctx.lib.ml_propagate_plan_tiles(ctx.handle, *[_lib.byref(v) for v in t]))
         info.update(tiles=(t[0].value, t[1].value), tile_samples=(t[2].value, t[3].value), batch=t[4].value)
+    if info['method'] == 'fft-fine':
+        t = [_lib.c_int(0) for _ in range(5)]
+        _lib.check(ctx.lib.ml_propagate_plan_lattices(ctx.handle, *[_lib.byref(v) for v in t]))
+        info.update(subsample=(t[0].value, t[1].value), lattice_targets=(t[2].value, t[3].value), cache_kernels=bool(t[4].value))
     return info
 
 
@@ -164,14 +211,34 @@ class PlanePropagator:
     equals.  The same checks as ``'fft'``; at most 8192 targets per axis.  A plan of one tile - the default where a tile
     of at most 512 holds the axis and shorter tiles would pad it no less - has the bits of ``'fft'``.  The workspace is ``(8 cx cy + 4 batch + 6 or 3) Lx Ly`` complex128; ``plan_info()`` reports the tile
     lengths as ``Lx``, ``Ly`` and adds ``'tiles'``, ``'tile_samples'`` and ``'batch'``.
+
+    ``method='fft-fine'`` is the tiled form for a patch FINER than the aperture's pitch (ml_propagate_plan_grid_fine):
+    ``subsample=(sx, sy)``, integers in [1, 8], and ``x``, ``y`` on the pitch divided by them, ``|x[i] - (x[0] + i dxp /
+    sx)| <= 4 spacing(max |x|)``.  Per axis the targets ``a, a + s, a + 2 s, ...`` are lattice ``a``, on the pitch with the
+    origin ``x[a]``; every lattice is the sum of ``'fft-tiled'`` at that origin with ``m_c = ceil(m / s)`` targets per axis
+    - ``tile`` and its default are checked against ``m_c``, at most 8192 - and has its bits where it holds ``m_c`` targets
+    per axis.  One plan serves all lattices: the currents are transformed once per field set, tile by tile, the lattices
+    are contracted two per read of the current spectra, and the result arrives interleaved, shape ``(len(x), len(y))``
+    as for every method, so ``propagate_sets``, ``accumulate``, ``sums`` and ``SourceSweep.run(image=...)`` are unchanged.
+    ``cache_kernels=True`` (default) keeps the kernel spectra of all ``A = min(sx, mx) min(sy, my)`` lattices from the
+    first pass on, a workspace of ``(8 A cx cy + 4 cx cy + 2 (6 or 3)) Lx Ly`` complex128; ``cache_kernels=False`` fills
+    and transforms those of two lattices and one batch of tiles in every pass, ``(16 batch + 4 cx cy + 2 (6 or 3)) Lx
+    Ly``, with the same bits.  The first pass reserves the workspace and raises ``MetalensHipError`` with the bytes asked
+    for (and ``cache_kernels=0``) if the device cannot give them.  ``subsample=(1, 1)`` has the bits of ``'fft-tiled'``.
+    ``plan_info()`` adds ``'subsample'``, ``'lattice_targets'`` and ``'cache_kernels'`` to the keys of ``'fft-tiled'``.
+    ``subsample``, and ``cache_kernels=False``, belong to this method alone.
     """
 
     def __init__(self, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False, want_h=True,
-                 units=None, Z0=None, ctx=None, method='direct', tile=None):
+                 units=None, Z0=None, ctx=None, method='direct', tile=None, subsample=None, cache_kernels=True):
         if method not in METHODS:
             raise ValueError('method must be one of %s, got %r' % (METHODS, method))
-        if tile is not None and method != 'fft-tiled':
+        if tile is not None and method not in ('fft-tiled', 'fft-fine'):
             raise ValueError("tile=%r: the tile lengths belong to method='fft-tiled', not to method=%r" % (tile, method))
+        if subsample is not None and method != 'fft-fine':
+            raise ValueError("subsample=%r: the pitch ratios belong to method='fft-fine', not to method=%r" % (subsample, method))
+        if cache_kernels is not True and method != 'fft-fine':
+            raise ValueError("cache_kernels=%r: the choice belongs to method='fft-fine', not to method=%r" % (cache_kernels, method))
         if tile is not None and len(tile) != 2:
             raise ValueError('tile must be None or the two tile lengths (Lx, Ly), got %r' % (tile,))
         self.method = method
@@ -187,9 +254,14 @@ class PlanePropagator:
         self._geometry = (float(xp_list[0]), float(yp_list[0]), float(xp_list[1] - xp_list[0]),
                           float(yp_list[1] - yp_list[0]), float(wavelength), float(n_glass))
         self.tile = (0, 0)   # 0: the default length
+        self.subsample, self.cache_kernels = _check_subsample(subsample), bool(cache_kernels)
         if method in _GRID_METHODS:
-            _on_pitch('x', self.x, self._geometry[2])
-            _on_pitch('y', self.y, self._geometry[3])
+            _on_pitch('x', self.x, self._geometry[2], self.subsample[0])
+            _on_pitch('y', self.y, self._geometry[3], self.subsample[1])
+        if method == 'fft-fine':
+            Lx, Ly = (None, None) if tile is None else tile   # (None or 0 for an axis: its default)
+            self.tile = (_check_fine('x', self.aperture_shape[0], self.x.size, self.subsample[0], Lx),
+                         _check_fine('y', self.aperture_shape[1], self.y.size, self.subsample[1], Ly))
         if method == 'fft-tiled':
             Lx, Ly = (None, None) if tile is None else tile   # (None or 0 for an axis: its default)
             self.tile = (_check_tile('x', self.aperture_shape[0], self.x.size, Lx),
@@ -209,7 +281,13 @@ class PlanePropagator:
 
     def _plan(self):
         ctx = self.ctx
-        if self.method == 'fft-tiled':
+        if self.method == 'fft-fine':
+            (sx, sy), mx, my = self.subsample, self.x.size, self.y.size
+            first_x, first_y = _lib.f64(self.x[:min(sx, mx)]), _lib.f64(self.y[:min(sy, my)])   # the lattices' origins
+            _lib.check(ctx.lib.ml_propagate_plan_grid_fine(
+                ctx.handle, *self._geometry, _lib.dptr(first_x), sx, _lib.dptr(first_y), sy, mx, my,
+                float(self.z[0]), int(self.want_h), *self.tile, int(self.cache_kernels)))
+        elif self.method == 'fft-tiled':
             _lib.check(ctx.lib.ml_propagate_plan_grid_tiled(
                 ctx.handle, *self._geometry, float(self.x[0]), float(self.y[0]), self.x.size, self.y.size,
                 float(self.z[0]), int(self.want_h), *self.tile))
@@ -303,12 +381,14 @@ class PlanePropagator:
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,
-                   want_h=True, units=None, Z0=None, ctx=None, method='direct', tile=None):
+                   want_h=True, units=None, Z0=None, ctx=None, method='direct', tile=None, subsample=None,
+                   cache_kernels=True):
     """One-shot convenience, modelled on ``farfield_direct``: the field of host arrays ``Ex..Hy`` (or of the
     field set already resident on the GPU if ``Ex is None``, e.g. after ``build_nearfield(..., download=False)``
     or a ``HotPath`` step) at the targets.  Arguments and the returned dict as for ``PlanePropagator``."""
     p = PlanePropagator(xp_list, yp_list, wavelength, n_glass, x, y, z, point_list=point_list, want_h=want_h,
-                        units=units, Z0=Z0, ctx=ctx, method=method, tile=tile)
+                        units=units, Z0=Z0, ctx=ctx, method=method, tile=tile, subsample=subsample,
+                        cache_kernels=cache_kernels)
     ctx = p.ctx
     if Ex is not None:
         arrs = [_lib.c128(a) for a in (Ex, Ey, Hx, Hy)]

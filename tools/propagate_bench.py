@@ -48,7 +48,15 @@ above.  A workspace the device cannot give is reported with the library's messag
 instead of the default), tiles, batch and workspace; --against: the cached pass of that method on the same targets, its
 workspace and max |E_tiled - E_other| / max |E|; --direct T: one direct pass on a T x T corner of the patch, its time per
 target and crossover_targets (for apertures no other FFT form takes).  With a diagnostic build of the library
-(METALENS_HIP_LIB) ML_GRID_TILE_BATCH_MIB sets the bytes of a batch and is reported as batch_MiB."""
+(METALENS_HIP_LIB) ML_GRID_TILE_BATCH_MIB sets the bytes of a batch and is reported as batch_MiB.
+
+    python tools/propagate_bench.py --method fft-fine --case N,M [--subsample S] [--no-direct]
+
+--method fft-fine: ``PlanePropagator(method='fft-fine')`` for one case N^2 -> M^2 fine targets at the pitch / S per process
+(default 4096,64 and 2; --quick: 1024,64), E + H, with the kernel spectra kept and filled in every pass, against the loop
+of S^2 'fft-tiled' propagators that gives the same targets lattice by lattice and against one direct pass on them
+(``fft_fine``).  With a diagnostic build of the library ML_GRID_FINE_PAIR=1 contracts one lattice per read of the current
+spectra instead of two and is reported as lattices_per_contraction."""
 import json
 import os
 import re
@@ -329,6 +337,81 @@ def fft_tiled(n, m, tile=None, other=None, want_hs=(True, False), direct_targets
         print(json.dumps(line), flush=True)
 
 
+def fft_fine(n, m, s, with_direct=True):
+    """``PlanePropagator(method='fft-fine')`` for n^2 -> m^2 fine targets at the pitch / s around the focus, E + H: kernel
+    spectra kept and filled in every pass - ms of a pass (timed as above), ms_first = plan + first pass, the plan's
+    workspace - against the loop of s^2 'fft-tiled' propagators, one per lattice, each planned and run once (what gives
+    the same targets without this method: every plan fills its kernel spectra anew, every pass transforms the currents
+    again; best of two loops), and against one direct pass on the same targets"""
+    import numpy as np
+
+    from metalens_amd import _lib
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl, n_glass = 580e-9, 1.46
+    x, f = converging_wave(ctx, n, wl, n_glass)
+    d = x[1] - x[0]
+    first = (x.size - m // s) // 2
+    tx, ty = x[0] + (first + 0.3) * d + np.arange(m) * d / s, x[0] + (first + 0.6) * d + np.arange(m) * d / s
+    keys = ('Ex', 'Ey', 'Ez')
+    got = {}
+    for cached in (True, False):
+        line = {'case': '%d^2 -> %d^2 at pitch / %d' % (n, m, s), 'fields': 'E+H', 'method': 'fft-fine',
+                'cache_kernels': cached}
+        if os.environ.get('ML_GRID_FINE_PAIR'):
+            line['lattices_per_contraction'] = int(os.environ['ML_GRID_FINE_PAIR'])
+        try:
+            t0 = time.perf_counter()
+            p = PlanePropagator(x, x, wl, n_glass, tx, ty, f, ctx=ctx, method='fft-fine', subsample=(s, s), cache_kernels=cached)
+            _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0))
+            ctx.sync()
+            ms_first = (time.perf_counter() - t0) * 1e3
+        except _lib.MetalensHipError as e:
+            line['error'] = str(e)
+            print(json.dumps(line), flush=True)
+            continue
+        ms = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0)))
+        info = p.plan_info()
+        got[cached] = p._download(None)
+        # (the plan's own bytes: the buffer only grows, and an earlier plan of the process may have left it larger)
+        tiles, lattices = info['tiles'][0] * info['tiles'][1], min(s, m) ** 2
+        planes = (8 * lattices * tiles if cached else 16 * info['batch']) + 4 * tiles + 12
+        line.update(ms=round(ms, 3), ms_first=round(ms_first, 3), L=[info['Lx'], info['Ly']], tiles=list(info['tiles']),
+                    lattices=lattices, lattice_targets=list(info['lattice_targets']), batch=info['batch'],
+                    workspace_MiB=round(planes * info['Lx'] * info['Ly'] * 16 / 2 ** 20, 1))
+        if not cached and True in got:
+            line['same_bits_as_cached'] = all(np.array_equal(got[True][c], got[False][c]) for c in got[True])
+        print(json.dumps(line), flush=True)
+    if not got:
+        return
+    fine = got[True] if True in got else got[False]
+
+    def loop():
+        t0 = time.perf_counter()
+        for a in range(min(s, m)):
+            for b in range(min(s, m)):
+                q = PlanePropagator(x, x, wl, n_glass, tx[a::s], ty[b::s], f, ctx=ctx, method='fft-tiled')
+                _lib.check(ctx.lib.ml_propagate(ctx.handle, q.Z0))
+        ctx.sync()
+        return (time.perf_counter() - t0) * 1e3
+    line = {'case': '%d^2 -> %d^2 at pitch / %d' % (n, m, s), 'fields': 'E+H', 'method': "loop of %d 'fft-tiled' plans" % min(s, m) ** 2,
+            'ms': round(min(loop(), loop()), 3)}
+    print(json.dumps(line), flush=True)
+    if with_direct:
+        pd = PlanePropagator(x, x, wl, n_glass, tx, ty, f, ctx=ctx)
+
+        def one():
+            t0 = time.perf_counter()
+            _lib.check(ctx.lib.ml_propagate(ctx.handle, pd.Z0))
+            ctx.sync()
+            return (time.perf_counter() - t0) * 1e3
+        ms_direct = min(one(), one())
+        want = pd._download(None)
+        diff = max(np.abs(fine[c] - want[c]).max() for c in keys) / max(np.abs(want[c]).max() for c in keys)
+        print(json.dumps({'case': '%d^2 -> %d^2 at pitch / %d' % (n, m, s), 'fields': 'E+H', 'method': 'direct',
+                          'ms': round(ms_direct, 3), 'max_E_difference_to_fft-fine': float('%.3e' % diff)}), flush=True)
+
+
 def fft_three_sets(n=2048, m=64):
     """the three sets of a synthesised x, y, z batch through ONE ml_propagate_sets call of an 'fft' plan"""
     import math
@@ -369,6 +452,10 @@ def _option(name, default=None):
 
 
 def main():
+    if _option('--method') == 'fft-fine':
+        n, m = (int(v) for v in _option('--case', '1024,64' if '--quick' in sys.argv else '4096,64').split(','))
+        fft_fine(n, m, int(_option('--subsample', 2)), with_direct='--no-direct' not in sys.argv)
+        return
     if _option('--method') == 'fft-tiled':
         n, m = (int(v) for v in _option('--case', '1024,64' if '--quick' in sys.argv else '4096,64').split(','))
         tile = int(_option('--tile', 0))
