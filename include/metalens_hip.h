@@ -103,7 +103,9 @@ int ml_upload_layout(ml_ctx *ctx, int n_rings, const double *ring_boundaries,
 
 /* ---- near-field synthesis: nearfield.build_nearfield (nearfield.py:66-480) ---------
  * Scalars are evaluated by the host with the reference's own expressions so that they
- * are bit-identical to what the reference would use.                                   */
+ * are bit-identical to what the reference would use.  A finite source whose largest
+ * distance to a sample of the lens exceeds 1e9 / kvac is refused with ML_EINVAL (the
+ * phase arithmetic covers k R <= 1e9); the plane wave has no such limit.               */
 typedef struct ml_nearfield_params {
     double source_x, source_y;
     double source_z;          /* < 0; -inf selects the normally incident plane wave     */
@@ -445,7 +447,10 @@ int ml_nearfield_kernel_info(ml_ctx *ctx, int *family, int *ring_orders_max, int
  *   point_list == 0  : targets on the tensor grid x[nx_t] x y[ny_t] in the plane z[0] (nz == 1), C-ordered
  *   point_list != 0  : the nx_t points (x[d], y[d], z[d]) (ny_t == nz == nx_t), e.g. a cut through a focus
  *   want_h == 0      : E only (about 40 % less arithmetic)
- * Every z must be > 0 (ML_EINVAL otherwise); |k R| must stay below 1e9.                              */
+ * Every z must be > 0 (ML_EINVAL otherwise).  The phase arithmetic covers k R <= 1e9: a plan whose targets' bounding
+ * box and largest z allow a larger k R over the resident aperture is refused with ML_EINVAL (distance, k R and limit in
+ * ml_last_error; the previous plan stays as it was), and so is a pass that meets such a shape - by ml_propagate /
+ * ml_propagate_sets, for the plans of the ml_propagate_plan_grid* entries below as well.                     */
 int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
                       double wavelength, double n_glass,
                       const double *x, int nx_t, const double *y, int ny_t, const double *z, int nz,
@@ -581,6 +586,33 @@ int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy
  * the first pass on).  ML_ESTATE without a plan.  Any pointer may be NULL.
  * Replaces no reference lines.                                                             */
 int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *workspace_bytes);
+
+/* ---- test surface: the device arithmetic of the hot kernels, one function per lane ----------
+ * csrc/nearfield_math.h is inlined into the synthesis and propagation kernels; this entry applies ONE of its
+ * functions (or a bare hardware estimate) to n arguments of the caller's, with the library's own compiler flags, so
+ * that tests can hold each against an exact reference over its documented range (tests/test_gpu_device_math.py).
+ * No product path calls it.  x, kq, out0, out1, outk are HOST arrays of n entries, 1 <= n <= 2^24.
+ *   op                    reads        writes
+ *   ML_PROBE_SINCOS       x            out0 = sin, out1 = cos          (sincos_cw)
+ *   ML_PROBE_SINCOS_Q     x, kq        out0 = sin, out1 = cos of x + kq pi/2   (sincos_cw_q)
+ *   ML_PROBE_REDUCE       x            out0 = r, outk = k, x = r + k pi/2      (reduce_pio2)
+ *   ML_PROBE_SQRT         x            out0                            (sqrt_exact)
+ *   ML_PROBE_RECIP        x            out0                            (recip)
+ *   ML_PROBE_RSQRT        x            out0                            (rsqrt_fast)
+ *   ML_PROBE_RAW_RCP      x            out0: the hardware's reciprocal estimate alone
+ *   ML_PROBE_RAW_RSQ      x            out0: the hardware's reciprocal-root estimate alone
+ * Pointers an op does not use may be NULL.  An unknown op, a NULL pointer the op needs and n out of range end in
+ * ML_EINVAL.  Synchronises.  Replaces no reference lines.                                                  */
+#define ML_PROBE_SINCOS 0
+#define ML_PROBE_SINCOS_Q 1
+#define ML_PROBE_REDUCE 2
+#define ML_PROBE_SQRT 3
+#define ML_PROBE_RECIP 4
+#define ML_PROBE_RSQRT 5
+#define ML_PROBE_RAW_RCP 6
+#define ML_PROBE_RAW_RSQ 7
+int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq, int n,
+                  double *out0, double *out1, int *outk);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdint>
@@ -289,6 +290,37 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     DeferredUnfold unfold;
 };
 
+// The range the phase arithmetic is tested over and the entries enforce (nearfield_math.h sincos_cw, reduce_pio2): an
+// argument k R of magnitude up to 1e9.  Beyond 2^31 pi/2 = 3.4e9 the quadrant count leaves the int range and the phase
+// is wrong without a sign of it, so a geometry that can reach past the limit is refused where it is set up.
+constexpr double PHASE_LIMIT = 1e9;
+
+// Where the targets of a propagation plan lie: their bounding box minus the aperture's origin (x0, y0), and the
+// largest z
+struct PropExtent {
+    double tx_lo = 0, tx_hi = 0, ty_lo = 0, ty_hi = 0, z_hi = 0;
+};
+
+// the largest distance a pass can meet between a sample (i dxp, j dyp) of an nx x ny aperture and a point of the box
+inline double prop_largest_R(const PropExtent &e, int nx, int ny, double dxp, double dyp) {
+    const double ax = (nx - 1) * dxp, ay = (ny - 1) * dyp;
+    const double dx = std::max(std::max(std::fabs(e.tx_lo), std::fabs(e.tx_hi)),
+                               std::max(std::fabs(e.tx_lo - ax), std::fabs(e.tx_hi - ax)));
+    const double dy = std::max(std::max(std::fabs(e.ty_lo), std::fabs(e.ty_hi)),
+                               std::max(std::fabs(e.ty_lo - ay), std::fabs(e.ty_hi - ay)));
+    return std::sqrt(dx * dx + dy * dy + e.z_hi * e.z_hi);
+}
+
+// ML_EINVAL, with the distance, k R and the limit in the message, unless k R <= PHASE_LIMIT for every pair of such a
+// pass (k = 2 pi n_glass / wavelength); a NaN is refused too
+inline int prop_check_phase(const char *who, const PropExtent &e, int nx, int ny, double dxp, double dyp, double wavelength,
+                            double n_glass) {
+    const double R = prop_largest_R(e, nx, ny, dxp, dyp), kR = 2.0 * M_PI * n_glass / wavelength * R;
+    ML_REQUIRE(kR <= PHASE_LIMIT, "%s: a target can lie %.6g m from a sample of the %d x %d aperture, k R = %.6g: the phase "
+               "arithmetic covers k R up to %g", who, R, nx, ny, kR, PHASE_LIMIT);
+    return ML_OK;
+}
+
 // Targets and buffers of the finite-distance propagator (propagate.hip).  Its own: nothing here is shared with the
 // far-field plan, the radiation vectors or the sweep sums.
 struct PropagatePlan {
@@ -296,6 +328,7 @@ struct PropagatePlan {
     int T = 0, want_h = 1;
     int result_sets = 0;   // field sets in `result`: 1 after ml_propagate, n after ml_propagate_sets
     double x0 = 0, y0 = 0, dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
+    PropExtent extent;   // of the targets: every pass checks it against the shape it meets (prop_check_phase)
     DevBuf targets;   // double [3][T]: x - x0, y - y0, z of every target
     DevBuf partial;   // double [splits][sets][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass

@@ -385,6 +385,15 @@ static int nearfield_prepare(ml_ctx *ctx, const ml_nearfield_params *p, int n, c
         set_error("ml_upload_layout has not been called");
         return ML_ESTATE;
     }
+    // a finite source: the phase k_vac |r - r_source| of a sample inside the lens goes through reduce_pio2 / sincos_cw
+    // (nearfield_math.h), which cover arguments up to PHASE_LIMIT; the plane wave has no such phase
+    for (int m = 0; m < n; ++m) {
+        if (p[m].plane_wave) continue;
+        const double rho = std::hypot(p[m].source_x, p[m].source_y) + ctx->lens.search.r_outer;
+        const double R = std::sqrt(rho * rho + p[m].source_z2), kR = p[m].kvac * R;
+        ML_REQUIRE(kR <= PHASE_LIMIT, "source %d lies up to %.6g m from a sample of the lens, k R = %.6g: the phase arithmetic "
+                   "covers k R up to %g (a plane wave, source_z = -inf, has no such limit)", m, R, kR, PHASE_LIMIT);
+    }
     ML_HIP(hipSetDevice(ctx->device));
     if (ctx->lens.n_cells > 0 && !ctx->lens.center.present) {
         set_error("centre cells present but no HexGridSet table uploaded (slot -1)");

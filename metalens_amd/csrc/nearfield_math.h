@@ -1,14 +1,23 @@
 // Device arithmetic shared by the near-field kernels (nearfield_fast.hip: geometry + general order
-// sets; nearfield_simple.hip: the round-lens order set): Cody-Waite sin / cos with scalar-register
+// sets; nearfield_simple.hip: the round-lens order set) and the propagators (propagate.hip,
+// propagate_grid.hip): Cody-Waite sin / cos with scalar-register
 // coefficients, reciprocal and reciprocal root by one third-order step, an exact square root
 // without range scaling.  Amplitude-type accuracy (a few ulp) unless said otherwise.
+// Every function here is run alone on the GPU over the range its comment states (math_probe.hip,
+// tests/test_gpu_device_math.py); sincos_cw, reduce_pio2 and sincos_cw_q are restated operation by
+// operation for the host in tools/device_math.cpp, which tests/test_device_math_host.py holds against
+// 200-bit arithmetic and the GPU must match bit for bit.  Measured figures: DESIGN.md appendix.
 #pragma once
 #include "nearfield_dev.h"
 
 namespace ml {
 
-// sin and cos of x for |x| < ~1e9: three-constant Cody-Waite reduction with FMA (each step
-// rounds once, relative to the already small remainder), fdlibm kernel polynomials.
+// sin and cos of x for |x| <= 1e9, each within 2^-51 absolute: Cody-Waite reduction by the first two
+// of three constants of pi/2 with FMA (each step rounds once, relative to the already small
+// remainder), fdlibm kernel polynomials.  The budget: two reduction roundings of <= 2^-53 pi/4, the
+// dropped third term (below), <= 2^-52 for the polynomials and the final rounding.  The entries that
+// form such arguments refuse a geometry that can exceed 1e9 (common.h PHASE_LIMIT); (int)k leaves
+// the int range at |x| = 2^31 pi/2 = 3.4e9.
 // Horner step p = z * p + C with the constant in a SCALAR register pair: written as plain C++ the
 // compiler materialises every fp64 coefficient with two v_mov_b32 in front of a v_fmac (3 vector
 // instructions per step, ~100 extra per sample over the four sincos of a sample); an SGPR
@@ -22,7 +31,7 @@ __device__ __forceinline__ void sincos_cw(double x, double &s, double &c) {
     const double k = rint(x * 0.63661977236758138243);          // 2/pi
     double r = fma(-k, 1.57079632679489655800e+00, x);          // pi/2 hi
     r = fma(-k, 6.12323399573676603587e-17, r);                 // pi/2 mid (a third term, 1.5e-33 k, is
-                                                                // below 1e-27 for the |k| < 1e6 met here)
+                                                                // below 1e-24 for the |k| < 6.4e8 of |x| <= 1e9)
     const double z = r * r;
     double ps = horner(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     ps = horner(z, ps, 2.75573137070700676789e-06);
@@ -42,8 +51,8 @@ __device__ __forceinline__ void sincos_cw(double x, double &s, double &c) {
     c = ((q + 1) & 2) ? -b : b;
 }
 
-// x = r + k pi/2 with |r| <= pi/4 (two-constant Cody-Waite, as above); k fits an int for the
-// |x| < ~1e9 this kernel meets
+// x = r + k pi/2 with |r| <= pi/4 (the reduction of sincos_cw, the same bits); |x| <= 1e9 as there,
+// for which |k| < 6.4e8 fits an int
 __device__ __forceinline__ void reduce_pio2(double x, double &r, int &k) {
     const double kd = rint(x * 0.63661977236758138243);
     r = fma(-kd, 1.57079632679489655800e+00, x);
@@ -51,12 +60,13 @@ __device__ __forceinline__ void reduce_pio2(double x, double &r, int &k) {
     k = (int)kd;
 }
 
-// sin and cos of x + kq pi/2 (kq = quadrants already split off a larger angle by reduce_pio2)
+// sin and cos of x + kq pi/2 (kq = quadrants already split off a larger angle by reduce_pio2);
+// x = r + a0 with r of reduce_pio2: within 2^-51 + 2^-53 |x| absolute (the rounding of that sum)
 __device__ __forceinline__ void sincos_cw_q(double x, int kq, double &s, double &c) {
     const double k = rint(x * 0.63661977236758138243);          // 2/pi
     double r = fma(-k, 1.57079632679489655800e+00, x);          // pi/2 hi
     r = fma(-k, 6.12323399573676603587e-17, r);                 // pi/2 mid (a third term, 1.5e-33 k, is
-                                                                // below 1e-27 for the |k| < 1e6 met here)
+                                                                // below 1e-24 for the |k| < 6.4e8 of |x| <= 1e9)
     const double z = r * r;
     double ps = horner(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     ps = horner(z, ps, 2.75573137070700676789e-06);
@@ -76,17 +86,20 @@ __device__ __forceinline__ void sincos_cw_q(double x, int kq, double &s, double 
     c = ((q + 1) & 2) ? -b : b;
 }
 
-// 1 / sqrt(x) to ~1 ulp for well-scaled x (no denormal / overflow handling): hardware estimate
-// (~2^-24) + ONE third-order step, y (1 + e/2 + 3 e^2 / 8) with e = 1 - x y^2 (error ~e^3: five
-// operations where two Newton steps take eight).  Amplitude-type quantities only.
+// 1 / sqrt(x) within 2^-52 relative for 1e-200 < x < 1e200 (no denormal / overflow handling): hardware
+// estimate (v_rsq_f64: measured 2^-24.2 relative on the MI355X and tested to be within 2^-22, the error
+// up to which the sequence is modelled on the host, tools/device_math.cpp model) + ONE third-order step, y (1 + e/2 + 3 e^2 / 8)
+// with e = 1 - x y^2 (error ~e^3: five operations where two Newton steps take eight).
+// Amplitude-type quantities only.
 __device__ __forceinline__ double rsqrt_fast(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     const double e = fma(-x * y, y, 1.0);
     return fma(y, e * fma(e, 0.375, 0.5), y);
 }
 
-// Accurate reciprocal (~1 ulp): hardware estimate (~2^-24) + one third-order step y (1 + e + e^2),
-// e = 1 - x y (three operations where two Newton steps take four).
+// Accurate reciprocal, within 2^-52 relative for 1e-200 < |x| < 1e200 (not always correctly rounded):
+// hardware estimate (v_rcp_f64: measured 2^-24.4, tested to be within 2^-22 relative, as above) + one third-order step
+// y (1 + e + e^2), e = 1 - x y (three operations where two Newton steps take four).
 __device__ __forceinline__ double recip(double x) {
     const double y = __builtin_amdgcn_rcp(x);
     const double e = fma(-x, y, 1.0);
@@ -102,7 +115,8 @@ __device__ __forceinline__ c2 cmulf_conj(c2 a, c2 b) {
 }
 
 // sqrt(x), correctly rounded for well-scaled x (1e-200 < x < 1e200: no denormal / overflow
-// handling): hardware reciprocal root, one coupled Goldschmidt step and two residual corrections -
+// handling; held bit for bit against np.sqrt on the GPU, squares and half-way squares' neighbours
+// included): hardware reciprocal root, one coupled Goldschmidt step and two residual corrections -
 // the sequence the compiler emits for sqrt() minus its range scaling (two ldexp, a class test and
 // six selects).  PHASE-CRITICAL use: the propagation distance of nearfield.py:338-341, 453-461,
 // whose rounding must be the reference's (np.sqrt is correctly rounded).

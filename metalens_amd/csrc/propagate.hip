@@ -27,8 +27,11 @@
 // A synthesised field carries row extents (nearfield.hip row_extent_kernel): samples outside them are
 // exact zeros and are not visited.  The extents are read from the device's own array.  A skipped sample
 // would have added +-0 to every accumulator, so the result has the bits of the whole sum.
-// The phase k R (1.6e4 rad at 1 mm, 1e7 at 1 m) is the accuracy: R by a correctly rounded square root,
-// sin / cos by the three-constant Cody-Waite reduction (nearfield_math.h, |k R| < 1e9).
+// The phase k R (1.6e4 rad at 1 mm, 1e7 at 1 m) is the accuracy: R by a correctly rounded square root (nearfield_math.h
+// sqrt_exact: bit for bit np.sqrt over 1e-200 ... 1e200), sin / cos by the two-constant Cody-Waite reduction with FMA
+// (sincos_cw: within 2^-51 absolute for |k R| <= 1e9) - both held to that on the GPU by tests/test_gpu_device_math.py.
+// k R <= 1e9 is enforced: the plan keeps the targets' bounding box and the largest z, and a plan or a pass whose largest
+// possible k R over the aperture exceeds the limit is refused (common.h prop_check_phase; 1e9 is 92 m at 580 nm in glass).
 #include "nearfield_math.h"
 
 namespace ml {
@@ -217,6 +220,8 @@ static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, in
     ML_REQUIRE(n >= 1 && n <= PROP_MAX_SETS, "%s: a pass takes 1 to %d field sets, got %d", who, PROP_MAX_SETS, n);
     ML_REQUIRE(first >= 0 && first + n <= ctx->fields.n_sets, "%s: field sets %d ... %d asked for, %d resident", who, first,
                first + n - 1, ctx->fields.n_sets);
+    // the shape is known here at the latest: no pair of this pass may leave the range of the phase arithmetic
+    ML_TRY(prop_check_phase(who, pp.extent, ctx->fields.nx, ctx->fields.ny, pp.dxp, pp.dyp, pp.wavelength, pp.n_glass));
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     if (pp.method != ML_PROPAGATE_DIRECT) return propagate_grid_sets(ctx, Z0, first, n);
@@ -278,6 +283,16 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
     const long long T = point_list ? nx_t : (long long)nx_t * ny_t;
     ML_REQUIRE(T <= (1 << 26), "%lld targets: at most 2^26 per plan", T);
     for (int d = 0; d < nz; ++d) ML_REQUIRE(z[d] > 0, "target %d lies at z = %g: the propagator needs z > 0", d, z[d]);
+    // the targets' bounding box and the largest z stay with the plan: with them every pass bounds k R for the shape it
+    // meets (propagate_sets).  A field set resident now is that shape: refuse here, with the previous plan as it was
+    PropExtent ext;
+    ext.tx_lo = *std::min_element(x, x + nx_t) - x0;
+    ext.tx_hi = *std::max_element(x, x + nx_t) - x0;
+    ext.ty_lo = *std::min_element(y, y + ny_t) - y0;
+    ext.ty_hi = *std::max_element(y, y + ny_t) - y0;
+    ext.z_hi = *std::max_element(z, z + nz);
+    if (ctx->fields.nx && ctx->fields.ny)
+        ML_TRY(prop_check_phase("ml_propagate_plan", ext, ctx->fields.nx, ctx->fields.ny, dxp, dyp, wavelength, n_glass));
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
@@ -302,6 +317,7 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
     pp.dyp = dyp;
     pp.wavelength = wavelength;
     pp.n_glass = n_glass;
+    pp.extent = ext;
     pp.ready = true;
     return ML_OK;
 }

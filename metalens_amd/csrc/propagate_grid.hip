@@ -1163,11 +1163,22 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
             return ML_EINVAL;
         }
     }
+    // the largest lag of the plan bounds k R as the direct plan's bounding box does (propagate.hip): checked against the
+    // resident shape here, and by every pass against the shape it meets
+    PropExtent ext;
+    ext.tx_lo = tx0 - x0;
+    ext.tx_hi = ext.tx_lo + (mx - 1) * (dxp / (fine ? fine->sx : 1));
+    ext.ty_lo = ty0 - y0;
+    ext.ty_hi = ext.ty_lo + (my - 1) * (dyp / (fine ? fine->sy : 1));
+    ext.z_hi = z;
+    if (ctx->fields.nx && ctx->fields.ny)
+        ML_TRY(prop_check_phase(entry, ext, ctx->fields.nx, ctx->fields.ny, dxp, dyp, wavelength, n_glass));
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
     pp.spectra_ready = false;
     pp.method = method;
+    pp.extent = ext;
     pp.grid = f;
     pp.tile = tile;
     pp.fine = fp;
