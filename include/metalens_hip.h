@@ -541,8 +541,8 @@ int ml_propagate_plan_grid_tiled(ml_ctx *ctx, double x0, double y0, double dxp, 
                                  double tx0, double ty0, int mx, int my, double z, int want_h,
                                  int tile_lx, int tile_ly);
 /* The tiles of the active tiled plan: tiles per axis cx, cy, samples per tile bx, by and the tiles that go through
- * the transforms together (batch); zeros while the plan has met no resident field set.  ML_ESTATE unless a tiled
- * or a fine plan is active.  Any pointer may be NULL.  Replaces no reference lines.        */
+ * the transforms together (batch); zeros while the plan has met no resident field set.  ML_ESTATE unless a tiled,
+ * a fine or a stack plan is active.  Any pointer may be NULL.  Replaces no reference lines.        */
 int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch);
 /* ml_propagate_plan_grid_tiled for a tensor grid of targets FINER than the aperture's pitch: mx x my targets
  * (tx[0] + i dxp / sx, ty[0] + j dyp / sy, z) with integer ratios sx, sy in [1, 8], target t = i my + j.  Per axis the
@@ -571,14 +571,42 @@ int ml_propagate_plan_grid_fine(ml_ctx *ctx, double x0, double y0, double dxp, d
                                 int mx, int my, double z, int want_h, int tile_lx, int tile_ly,
                                 int cache_kernels);
 /* The lattices of the active fine plan: the ratios sx, sy, the targets per lattice as planned mcx, mcy and whether
- * the kernel spectra are kept (cached).  ML_ESTATE unless a fine plan is active.  Any pointer may be NULL.
+ * the kernel spectra are kept (cached).  ML_ESTATE unless a fine or a stack plan is
+ * active.  Any pointer may be NULL.
  * Replaces no reference lines.                                                             */
 int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy, int *cached);
+/* ml_propagate_plan_grid_fine for a STACK of nz planes z[0 ... nz - 1]: the mx x my fine targets of that entry in every
+ * plane, target t = (p mx + i) my + j, T = nz mx my - a through-focus volume in one plan.  The arguments are those of
+ * ml_propagate_plan_grid_fine with `const double *z, int nz` in place of `double z`; the planes may come in any order and
+ * repeat.  The fine plan does not depend on z: the currents of a field set are padded and transformed ONCE for all
+ * planes, and every (plane, lattice) is one more layer of kernel spectra contracted against them, two per read, in the
+ * order l = p A + a Ay + b (A = Ax Ay active lattices; a pair may straddle two planes).  Plane p has the bits of
+ * ml_propagate_plan_grid_fine planned at z[p].  The result keeps the layout of every other plan - [6 or 3][T] - so
+ * ml_propagate, ml_propagate_sets, ml_propagate_download[_set], ml_propagate_accumulate and ml_propagate_sums serve it
+ * unchanged.  cache_kernels != 0: the kernel spectra of all nz A layers are filled by the first pass and kept while the
+ * plan and the shape stay, a workspace of (8 nz A tiles + 4 tiles + 2 (6 or 3)) Lx Ly complex128; cache_kernels == 0: those
+ * of two layers and one batch of tiles are filled and transformed in every pass, (16 batch + 4 tiles + 2 (6 or 3)) Lx Ly
+ * complex128 whatever nz is; the same bits.  The first pass on a shape reserves the workspace and fails with ML_ENOMEM and
+ * the bytes asked for (and, caching, those of cache_kernels == 0) if the device cannot give them.  nz outside [1, 4096],
+ * nz mx my > 2^26, a z[p] that is not finite or not > 0 (p and the value in the message) and every refusal of
+ * ml_propagate_plan_grid_fine end in ML_EINVAL with this entry's name in ml_last_error; the previous plan stays as it
+ * was.  k R <= 1e9 is checked with the largest z.  ml_propagate_plan_info reports ML_PROPAGATE_FFT_STACK and the TILE
+ * lengths; ml_propagate_plan_tiles and ml_propagate_plan_lattices serve this plan too.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_grid_stack(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
+                                 double wavelength, double n_glass,
+                                 const double *tx_first, int sx, const double *ty_first, int sy,
+                                 int mx, int my, const double *z, int nz, int want_h, int tile_lx, int tile_ly,
+                                 int cache_kernels);
+/* The planes of the active stack plan.  ML_ESTATE unless a stack plan is active.  nz may be NULL.
+ * Replaces no reference lines.                                                             */
+int ml_propagate_plan_planes(ml_ctx *ctx, int *nz);
 #define ML_PROPAGATE_DIRECT 0
 #define ML_PROPAGATE_FFT 1
 #define ML_PROPAGATE_FFT_LONG 2
 #define ML_PROPAGATE_FFT_TILED 3
 #define ML_PROPAGATE_FFT_FINE 4
+#define ML_PROPAGATE_FFT_STACK 5
 /* The active propagation plan: method (ML_PROPAGATE_*), the padded lengths lx, ly (0 for a direct plan, and for
  * an fft plan that has met no resident field set yet; the tile lengths of a tiled or a fine plan) and the bytes of device
  * workspace it holds besides targets,

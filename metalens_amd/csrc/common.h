@@ -334,7 +334,7 @@ struct PropagatePlan {
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
     // the FFT form (propagate_grid.hip, ml_propagate_plan_grid): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
-    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED / ML_PROPAGATE_FFT_FINE
+    int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED / ML_PROPAGATE_FFT_FINE / ML_PROPAGATE_FFT_STACK
     GridPlanFacts grid;   // (propagate_grid.h) for the aperture shape last met; spectra_ready: its kernel spectra are in grid_work
     bool spectra_ready = false;
     double tx_off = 0, ty_off = 0, z = 0;
@@ -347,6 +347,11 @@ struct PropagatePlan {
     // copy of it, for ml_propagate_plan_tiles).  grid.mx, grid.my are then the counts PER LATTICE, T the fine targets
     GridFinePlan fine;
     double fine_tx[GRID_FINE_S_MAX] = {}, fine_ty[GRID_FINE_S_MAX] = {};
+    // the stack plan (ml_propagate_plan_grid_stack; propagate_stack.hip): a fine plan - `fine`, `tile`, the origins above -
+    // in the planes stack_z; T is then planes x fine targets, `z` the largest plane.  stack_layers: the device's table of
+    // the layers (plane, lattice) in contraction order, uploaded by the plan entry
+    std::vector<double> stack_z;
+    DevBuf stack_layers;
     // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; the tiled plan: [tiles][8] kernel spectra,
     // [batch][4] currents, [6 or 3] outputs; the fine plan: [lattices][tiles][8] (or [2][batch][8]) kernel spectra,
     // [tiles][4] currents, [2][6 or 3] outputs; released by a direct plan
@@ -571,6 +576,8 @@ int fields_unmodulate(ml_ctx *ctx);
 int flush_unfold(ml_ctx *ctx);
 // propagate_grid.hip: the pass of propagate.hip's propagate_sets for a plan of ml_propagate_plan_grid (checks done)
 int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n);
+// propagate_stack.hip: the same for a plan of ml_propagate_plan_grid_stack, handed over by propagate_grid_sets
+int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n);
 // in-place sum of `count` doubles over the communicator, queued on `stream` (no-op without one)
 int comm_allreduce_sum(ml_ctx *ctx, double *buf, size_t count, hipStream_t stream);
 // buf = n_ranks chunks of `chunk` doubles: afterwards chunk `rank` holds the sum over the ranks of

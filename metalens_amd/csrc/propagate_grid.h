@@ -266,6 +266,84 @@ inline int grid_fine_plan(int nx, int ny, int mx, int my, int sx, int sy, int wa
     return 0;
 }
 
+// The stack plan (ml_propagate_plan_grid_stack): the fine targets in nz planes z[0 ... nz - 1], any order, equal values
+// allowed.  The fine plan of (nx, ny, mx, my, sx, sy, tile_lx, tile_ly) does not depend on z: a stack has ONE, and the
+// currents of a field set are padded and transformed once for all planes.  A LAYER is (plane p, lattice (a, b)), numbered
+//   l = p A + a Ay + b,  A = Ax Ay,
+// with its own eight kernel spectra - those of the fine plan's lattice (a, b) planned at z[p].  The layers are contracted
+// GRID_FINE_PAIR at a time in that order (a pair may straddle two planes), a single one last if nz A is odd.  The result
+// is plane-major: target t = (p mx + i) my + j, T = nz mx my <= 2^26.
+//   cache_kernels: the kernel spectra of all nz A layers are kept for the life of the plan,
+//                  (8 nz A tiles + 4 tiles + 2 outputs) planes;
+//   otherwise:     the streamed workspace of the fine plan, (16 batch + 4 tiles + 2 outputs) planes, whatever nz is.
+constexpr int GRID_STACK_PLANES_MAX = 4096;
+// The fill kernel takes the kernels of up to GRID_FINE_PAIR layers x GRID_TILE_BATCH_MAX tiles per launch.  What a launch
+// writes is read next by the row pass: all layers of a contraction go into one launch while their planes fit the 256 MiB
+// memory-side cache, else one launch and its transforms per layer.  Measured on an MI355X, 8 planes of 64^2 fine targets at
+// half the pitch behind 4096^2, streamed (a batch of 8 tiles of 512^2: 256 MiB per layer): a launch per layer 111.6 ms,
+// the pair's 512 MiB in one launch 129.3 ms, the loop of eight 'fft-fine' plans 124.2 ms.
+constexpr int64_t GRID_STACK_FILL_BYTES = (int64_t)256 << 20;
+inline int grid_stack_fill_layers(int layers, int tiles, int64_t plane_bytes) {
+    return (int64_t)layers * tiles * GRID_KERNELS * plane_bytes <= GRID_STACK_FILL_BYTES ? layers : 1;
+}
+
+struct GridStackPlan {
+    int nz = 0;
+    int layers = 0;           // nz Ax Ay
+    GridFinePlan fine;        // of one plane
+    int64_t workspace_bytes = 0;
+};
+
+struct GridStackLayer {
+    int p = 0, a = 0, b = 0;   // plane, lattice
+};
+
+inline GridStackLayer grid_stack_layer(int l, int ax, int ay) {
+    GridStackLayer s;
+    const int A = ax * ay, r = l % A;
+    s.p = l / A;
+    s.a = r / ay;
+    s.b = r % ay;
+    return s;
+}
+
+// what is wrong with the planes of a stack of mx x my fine targets, whatever the aperture; -> 0, or -1 with `why` filled
+inline int grid_stack_check_planes(const double *z, int nz, int mx, int my, char *why, size_t why_len) {
+    if (nz < 1 || nz > GRID_STACK_PLANES_MAX) {
+        snprintf(why, why_len, "a stack has 1 to %d planes, got nz = %d", GRID_STACK_PLANES_MAX, nz);
+        return -1;
+    }
+    for (int p = 0; p < nz; ++p)
+        if (!(std::isfinite(z[p]) && z[p] > 0)) {
+            snprintf(why, why_len, "plane %d of the stack lies at z[%d] = %g: the propagator needs a finite z > 0", p, p, z[p]);
+            return -1;
+        }
+    if ((long long)nz * mx * my > (1 << 26)) {
+        snprintf(why, why_len, "%lld targets (%d planes of %d x %d fine targets): at most 2^26 per plan", (long long)nz * mx * my, nz,
+                 mx, my);
+        return -1;
+    }
+    return 0;
+}
+
+// -> 0, or -1 with `why` filled.  z[0 ... nz - 1]: the planes; the other arguments as grid_fine_plan's, whose refusals
+// apply unchanged.
+inline int grid_stack_plan(int nx, int ny, int mx, int my, int sx, int sy, int want_h, int tile_lx, int tile_ly, int cache_kernels,
+                           int64_t batch_bytes, const double *z, int nz, GridStackPlan *s, char *why, size_t why_len) {
+    if (nz < 1 || nz > GRID_STACK_PLANES_MAX) return grid_stack_check_planes(z, nz, mx, my, why, why_len);
+    if (grid_fine_plan(nx, ny, mx, my, sx, sy, want_h, tile_lx, tile_ly, cache_kernels, batch_bytes, &s->fine, why, why_len) != 0)
+        return -1;
+    if (grid_stack_check_planes(z, nz, mx, my, why, why_len) != 0) return -1;
+    const GridFinePlan &f = s->fine;
+    const GridTilePlan &t = f.tile;
+    s->nz = nz;
+    s->layers = nz * f.ax * f.ay;
+    const int64_t kernels = f.cache_kernels ? (int64_t)GRID_KERNELS * s->layers * t.tiles
+                                            : (int64_t)GRID_KERNELS * GRID_FINE_PAIR * t.batch;
+    s->workspace_bytes = (kernels + (int64_t)GRID_CURRENTS * t.tiles + GRID_FINE_PAIR * t.outputs) * t.plane_bytes;
+    return 0;
+}
+
 // cos / sin of 2 pi j / L for j < L / 2, evaluated in long double and rounded once: [L / 2][2]
 inline std::vector<double> grid_twiddles(int L) {
     std::vector<double> t((size_t)L);

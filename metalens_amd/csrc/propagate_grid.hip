@@ -36,7 +36,11 @@
 // transform launches with more planes per launch).
 // The fine plan (ml_propagate_plan_grid_fine) puts targets on the pitch divided by (sx, sy): sx sy lattices on the pitch,
 // each a tiled convolution of the SAME current spectra with its own kernel spectra (the grid_fine_* kernels).
+// The stack plan (ml_propagate_plan_grid_stack) is a fine plan in several planes z; it is planned here, and its pass and
+// kernels are in propagate_stack.hip, which reaches the transform and contraction launchers of this file through
+// propagate_grid_launch.h.
 #include "nearfield_math.h"
+#include "propagate_grid_launch.h"
 
 namespace ml {
 
@@ -1038,6 +1042,7 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     PropagatePlan &pp = ctx->prop;
     if (pp.method == ML_PROPAGATE_FFT_TILED) return propagate_tile_sets(ctx, Z0, first, n);
     if (pp.method == ML_PROPAGATE_FFT_FINE) return propagate_fine_sets(ctx, Z0, first, n);
+    if (pp.method == ML_PROPAGATE_FFT_STACK) return propagate_stack_sets(ctx, Z0, first, n);
     pp.have_result = false;
     ML_TRY(grid_prepare(ctx));
     const GridPlanFacts &f = pp.grid;
@@ -1077,14 +1082,31 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     return ML_OK;
 }
 
+// what propagate_stack.hip goes through (propagate_grid_launch.h)
+int grid_fft_rows(ml_ctx *ctx, double2 *planes, int n_planes, int rows, bool inverse) {
+    return inverse ? fft_rows<true>(ctx, planes, n_planes, rows) : fft_rows<false>(ctx, planes, n_planes, rows);
+}
+int grid_fft_cols(ml_ctx *ctx, double2 *planes, int n_planes, bool inverse) {
+    return inverse ? fft_cols<true>(ctx, planes, n_planes) : fft_cols<false>(ctx, planes, n_planes);
+}
+int grid_fine_contract(ml_ctx *ctx, int lattices, unsigned blocks, bool first, const double2 *K, size_t k_lattice, const double2 *cur,
+                       double2 *out, size_t ps, int n) {
+    return fine_contract(ctx, lattices, blocks, first, K, k_lattice, cur, out, ps, n);
+}
+int grid_upload_twiddles(ml_ctx *ctx, DevBuf &buf, int L) { return upload_twiddles(ctx, buf, L); }
+int64_t grid_tile_batch_bytes() { return tile_batch_bytes(); }
+
 }  // namespace ml
 
 using namespace ml;
 
-// what ml_propagate_plan_grid_fine asks for beyond a tiled plan
+// what ml_propagate_plan_grid_fine asks for beyond a tiled plan; ml_propagate_plan_grid_stack: and the planes (the `z` of
+// plan_grid is then the largest of them, checked by the entry)
 struct FineAsk {
     const double *tx_first, *ty_first;   // the first min(s, m) coordinates of each fine axis
     int sx, sy, cache_kernels;
+    const double *z = nullptr;           // the planes of a stack, or NULL
+    int nz = 0;
 };
 
 // the origins of an axis' lattices: strictly ascending within one pitch
@@ -1097,7 +1119,8 @@ static int fine_origins_ok(const char *entry, const char *axis, const double *fi
     return ML_OK;
 }
 
-// ml_propagate_plan_grid, ml_propagate_plan_grid_long, ml_propagate_plan_grid_tiled and ml_propagate_plan_grid_fine: `entry`
+// ml_propagate_plan_grid, ml_propagate_plan_grid_long, ml_propagate_plan_grid_tiled, ml_propagate_plan_grid_fine and
+// ml_propagate_plan_grid_stack (a fine plan with planes in `fine`; T is then planes x fine targets): `entry`
 // is the caller's name, `method` its ML_PROPAGATE_*; tile_lx, tile_ly: the tile lengths of the tiled and the fine plan (0:
 // the default); `fine`: of the fine plan, whose mx, my are the FINE targets and tx0, ty0 its first lattice's origin
 static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, double y0, double dxp, double dyp, double wavelength,
@@ -1111,6 +1134,8 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     ML_REQUIRE(wavelength > 0 && n_glass > 0 && dxp > 0 && dyp > 0, "bad geometry");
     ML_REQUIRE(z > 0, "the target plane lies at z = %g: the propagator needs z > 0", z);
     ML_REQUIRE((long long)mx * my <= (1 << 26), "%lld targets: at most 2^26 per plan", (long long)mx * my);
+    const bool stack = fine && fine->z;
+    std::vector<GridStackLayerRow> layers;   // of a stack: what the device reads per layer
     GridPlanFacts f;
     f.mx = mx;
     f.my = my;
@@ -1175,6 +1200,17 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
         ML_TRY(prop_check_phase(entry, ext, ctx->fields.nx, ctx->fields.ny, dxp, dyp, wavelength, n_glass));
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
+    if (stack) {   // the layer table, once per plan: layer l = p A + a Ay + b (propagate_grid.h grid_stack_layer)
+        layers.resize((size_t)fine->nz * fp.ax * fp.ay);
+        for (size_t l = 0; l < layers.size(); ++l) {
+            const GridStackLayer s = grid_stack_layer((int)l, fp.ax, fp.ay);
+            layers[l] = {fine->tx_first[s.a] - x0, fine->ty_first[s.b] - y0, fine->z[s.p], s.p, s.a, s.b, 0};
+        }
+        ML_TRY(pp.stack_layers.reserve(layers.size() * sizeof(GridStackLayerRow)));
+        ML_HIP(hipMemcpyAsync(pp.stack_layers.p, layers.data(), layers.size() * sizeof(GridStackLayerRow), hipMemcpyHostToDevice,
+                              ctx->stream));
+        ML_HIP(hipStreamSynchronize(ctx->stream));   // (`layers` goes away)
+    }
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
     pp.spectra_ready = false;
     pp.method = method;
@@ -1186,7 +1222,9 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     for (int b = 0; b < fp.ay; ++b) pp.fine_ty[b] = fine->ty_first[b] - y0;
     pp.tile_lx = tile_lx;
     pp.tile_ly = tile_ly;
-    pp.T = mx * my;
+    pp.T = (stack ? fine->nz : 1) * mx * my;
+    pp.stack_z.clear();
+    if (stack) pp.stack_z.assign(fine->z, fine->z + fine->nz);
     pp.want_h = want_h != 0;
     pp.x0 = x0;
     pp.y0 = y0;
@@ -1236,10 +1274,45 @@ int ml_propagate_plan_grid_fine(ml_ctx *ctx, double x0, double y0, double dxp, d
     return rc;
 }
 
+int ml_propagate_plan_grid_stack(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
+                                 const double *tx_first, int sx, const double *ty_first, int sy, int mx, int my, const double *z,
+                                 int nz, int want_h, int tile_lx, int tile_ly, int cache_kernels) {
+    const char *entry = "ml_propagate_plan_grid_stack";
+    ML_REQUIRE(ctx, "ctx is NULL");
+    ML_REQUIRE(tx_first && ty_first && z, "%s: NULL argument", entry);
+    ML_REQUIRE(mx >= 1 && my >= 1, "%s: no targets", entry);
+    char why[480];
+    if (grid_stack_check_planes(z, nz, mx, my, why, sizeof why) != 0) {
+        set_error("%s: %s", entry, why);
+        return ML_EINVAL;
+    }
+    FineAsk fine = {tx_first, ty_first, sx, sy, cache_kernels};
+    fine.z = z;
+    fine.nz = nz;
+    const int rc = plan_grid(ctx, entry, ML_PROPAGATE_FFT_STACK, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0], ty_first[0], mx,
+                             my, *std::max_element(z, z + nz), want_h, tile_lx, tile_ly, &fine);
+    if (rc != ML_OK && strncmp(ml_last_error(), entry, strlen(entry)) != 0) {   // every refusal names this entry
+        const std::string said = ml_last_error();
+        set_error("%s: %s", entry, said.c_str());
+    }
+    return rc;
+}
+
+int ml_propagate_plan_planes(ml_ctx *ctx, int *nz) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    const PropagatePlan &pp = ctx->prop;
+    if (!pp.ready || pp.method != ML_PROPAGATE_FFT_STACK) {
+        set_error("ml_propagate_plan_planes: no stack propagation plan is active");
+        return ML_ESTATE;
+    }
+    if (nz) *nz = (int)pp.stack_z.size();
+    return ML_OK;
+}
+
 int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy, int *cached) {
     ML_REQUIRE(ctx, "ctx is NULL");
     const PropagatePlan &pp = ctx->prop;
-    if (!pp.ready || pp.method != ML_PROPAGATE_FFT_FINE) {
+    if (!pp.ready || (pp.method != ML_PROPAGATE_FFT_FINE && pp.method != ML_PROPAGATE_FFT_STACK)) {
         set_error("ml_propagate_plan_lattices: no fine propagation plan is active");
         return ML_ESTATE;
     }
@@ -1254,7 +1327,7 @@ int ml_propagate_plan_lattices(ml_ctx *ctx, int *sx, int *sy, int *mcx, int *mcy
 int ml_propagate_plan_tiles(ml_ctx *ctx, int *cx, int *cy, int *bx, int *by, int *batch) {
     ML_REQUIRE(ctx, "ctx is NULL");
     const PropagatePlan &pp = ctx->prop;
-    if (!pp.ready || (pp.method != ML_PROPAGATE_FFT_TILED && pp.method != ML_PROPAGATE_FFT_FINE)) {
+    if (!pp.ready || (pp.method != ML_PROPAGATE_FFT_TILED && pp.method != ML_PROPAGATE_FFT_FINE && pp.method != ML_PROPAGATE_FFT_STACK)) {
         set_error("ml_propagate_plan_tiles: no tiled propagation plan is active");
         return ML_ESTATE;
     }

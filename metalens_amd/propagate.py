@@ -24,6 +24,8 @@ side - and a workspace of up to 77 GB.  ``method='fft-tiled'`` cuts the aperture
 padded length ``L >= m`` and adds the tiles' products in the spectral domain (overlap-add): for ``m << n``.
 ``method='fft-fine'`` is the tiled form for targets on the pitch divided by integers ``(sx, sy)``: the interleave of
 ``sx sy`` lattices on the pitch, convolved with the same current spectra - what resolves a focal spot.
+``method='fft-stack'`` is the fine form for a stack of planes ``z[0], z[1], ...`` (csrc/propagate_stack.hip): one plan, the
+currents transformed once, every plane one more layer of kernel spectra - a through-focus volume.
 """
 import numpy as np
 
@@ -31,10 +33,22 @@ from . import _lib, constants
 from .nearfield_farfield import _check_axis
 
 
-def _targets(x, y, z, point_list):
+def _targets(x, y, z, point_list, stack=False):
     x, y, z = (_lib.f64(np.ravel(np.asarray(v, dtype=float))) for v in (x, y, z))
     if x.size < 1 or y.size < 1 or z.size < 1:
         raise ValueError('no targets: x, y and z need at least one value each')
+    if stack:   # the refusals of ml_propagate_plan_grid_stack for the planes
+        if z.size > STACK_PLANES_MAX:
+            raise ValueError("method='fft-stack' takes 1 to %d planes, got %d" % (STACK_PLANES_MAX, z.size))
+        bad = ~(np.isfinite(z) & (z > 0))
+        if bad.any():
+            p = int(np.argmax(bad))
+            raise ValueError("method='fft-stack': plane %d lies at z[%d] = %g: the propagator needs a finite z > 0 (the "
+                             "aperture is the plane z = 0)" % (p, p, z[p]))
+        if z.size * x.size * y.size > 1 << 26:
+            raise ValueError("method='fft-stack': %d targets (%d planes of %d x %d fine targets): at most 2^26 per propagator"
+                             % (z.size * x.size * y.size, z.size, x.size, y.size))
+        return x, y, z
     if point_list:
         if not x.size == y.size == z.size:
             raise ValueError('a point list needs len(x) == len(y) == len(z), got %d, %d and %d'
@@ -48,12 +62,14 @@ def _targets(x, y, z, point_list):
     return x, y, z
 
 
-METHODS = ('direct', 'fft', 'fft-long', 'fft-tiled', 'fft-fine')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
+METHODS = ('direct', 'fft', 'fft-long', 'fft-tiled', 'fft-fine', 'fft-stack')   # in the order of ML_PROPAGATE_* (include/metalens_hip.h)
 GRID_L_MIN, GRID_L_MAX = 16, 8192   # csrc/propagate_grid.h
 GRID_L_LONG_MAX = 16384
 _GRID_CAP = {'fft': GRID_L_MAX, 'fft-long': GRID_L_LONG_MAX}
-_GRID_METHODS = ('fft', 'fft-long', 'fft-tiled', 'fft-fine')   # a tensor grid of targets on the aperture's pitch (or a fraction)
+_GRID_METHODS = ('fft', 'fft-long', 'fft-tiled', 'fft-fine', 'fft-stack')   # a tensor grid of targets on the aperture's pitch (or a fraction)
+_FINE_METHODS = ('fft-fine', 'fft-stack')   # targets on the pitch divided by `subsample`
 FINE_S_MAX = 8   # csrc/propagate_grid.h GRID_FINE_S_MAX
+STACK_PLANES_MAX = 4096   # csrc/propagate_grid.h GRID_STACK_PLANES_MAX
 
 
 def _padded_length(n, m):
@@ -64,19 +80,19 @@ def _padded_length(n, m):
     return L
 
 
-def _on_pitch(name, t, pitch, s=1):
+def _on_pitch(name, t, pitch, s=1, method='fft-fine'):
     """``method='fft'``: the target axis ``t`` must be ``t[0] + i pitch`` to within 4 spacings of its largest value
     (the deviation changes the phase k x of the direct sum by a few 1e-13 rad at that level); ``method='fft-fine'``:
-    ``t[0] + i pitch / s``"""
+    ``t[0] + i pitch / s`` (``method``: the one of the two fine methods the message names)"""
     tol = 4 * np.spacing(np.abs(t).max())
     off = np.abs(t - (t[0] + np.arange(t.size) * pitch / s)) > tol
     if off.any():
         i = int(np.argmax(off))
         own = t[1] - t[0]
         if s != 1:
-            raise ValueError("method='fft-fine' needs the targets on the aperture's pitch / %d: %s[%d] = %.17g is not %s[0] + "
+            raise ValueError("method=%r needs the targets on the aperture's pitch / %d: %s[%d] = %.17g is not %s[0] + "
                              "%d x %.17g / %d (the aperture's pitch along %s; the target axis steps by %.17g)"
-                             % (s, name, i, t[i], name, i, pitch, s, name, own))
+                             % (method, s, name, i, t[i], name, i, pitch, s, name, own))
         raise ValueError("method='fft' needs the targets on the aperture's pitch: %s[%d] = %.17g is not %s[0] + %d x %.17g "
                          "(the aperture's pitch along %s; the target axis steps by %.17g)"
                          % (name, i, t[i], name, i, pitch, name, own))
@@ -112,7 +128,7 @@ def _check_tile(name, n, m, L):
     return int(L)
 
 
-def _check_subsample(subsample):
+def _check_subsample(subsample, method='fft-fine'):
     """-> (sx, sy), integers in [1, 8]; None: (1, 1)"""
     if subsample is None:
         return 1, 1
@@ -123,26 +139,26 @@ def _check_subsample(subsample):
     for name, v in (('x', sx), ('y', sy)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer, float, np.floating)) or v != int(v) \
                 or not 1 <= v <= FINE_S_MAX:
-            raise ValueError("method='fft-fine' divides the aperture's pitch by an integer in [1, %d]: subsample = %r has "
-                             "s = %r along %s" % (FINE_S_MAX, tuple(subsample), v, name))
+            raise ValueError("method=%r divides the aperture's pitch by an integer in [1, %d]: subsample = %r has "
+                             "s = %r along %s" % (method, FINE_S_MAX, tuple(subsample), v, name))
     return int(sx), int(sy)
 
 
-def _check_fine(name, n, m, s, L):
+def _check_fine(name, n, m, s, L, method='fft-fine'):
     """the refusals of ml_propagate_plan_grid_fine for one axis of m fine targets at the ratio s, before a context is
     touched: at most 8192 targets per lattice, the tile length against ``m_c = ceil(m / s)``; L None: the default"""
     m_c = -(-m // s)
     if m_c > GRID_L_MAX:
-        raise ValueError("method='fft-fine' takes at most %d targets per lattice and axis: the %s axis of n = %d samples has "
+        raise ValueError("method=%r takes at most %d targets per lattice and axis: the %s axis of n = %d samples has "
                          "m = %d fine targets at s = %d, m_c = %d per lattice; use method='direct' or fewer targets per "
-                         "propagator" % (GRID_L_MAX, name, n, m, s, m_c))
+                         "propagator" % (method, GRID_L_MAX, name, n, m, s, m_c))
     if L is None or L == 0:
         return 0
     if L != int(L) or not (GRID_L_MIN <= L <= GRID_L_MAX) or int(L) & (int(L) - 1) or L < m_c:
-        raise ValueError("method='fft-fine': the tile length of the %s axis of n = %d samples and m_c = %d targets per "
+        raise ValueError("method=%r: the tile length of the %s axis of n = %d samples and m_c = %d targets per "
                          "lattice (m = %d fine targets at s = %d) is L = %s: it must be a power of two in [%d, %d] and at "
                          "least m_c (None or 0: the default)"
-                         % (name, n, m_c, m, s, int(L) if L == int(L) else float(L), GRID_L_MIN, GRID_L_MAX))
+                         % (method, name, n, m_c, m, s, int(L) if L == int(L) else float(L), GRID_L_MIN, GRID_L_MAX))
     return int(L)
 
 
@@ -151,19 +167,24 @@ def plan_info(ctx):
     (ml_propagate_plan_info): the padded lengths are 0 for the direct method.  For ``'fft-tiled'`` they are the tile
     lengths, and the dict has ``'tiles': (cx, cy)``, ``'tile_samples': (bx, by)`` and ``'batch'`` as well
     (ml_propagate_plan_tiles); for ``'fft-fine'`` those and ``'subsample': (sx, sy)``, ``'lattice_targets': (m_cx, m_cy)``
-    and ``'cache_kernels'`` (ml_propagate_plan_lattices)"""
+    and ``'cache_kernels'`` (ml_propagate_plan_lattices); for ``'fft-stack'`` those of ``'fft-fine'`` and ``'planes'``
+    (ml_propagate_plan_planes)"""
     method, lx, ly, ws = _lib.c_int(0), _lib.c_int(0), _lib.c_int(0), _lib.c_int64(0)
     _lib.check(ctx.lib.ml_propagate_plan_info(ctx.handle, _lib.byref(method), _lib.byref(lx), _lib.byref(ly),
                                               _lib.byref(ws)))
     info = {'method': METHODS[method.value], 'Lx': lx.value, 'Ly': ly.value, 'workspace_bytes': ws.value}
-    if info['method'] in ('fft-tiled', 'fft-fine'):
+    if info['method'] in ('fft-tiled',) + _FINE_METHODS:
         t = [_lib.c_int(0) for _ in range(5)]
         _lib.check(ctx.lib.ml_propagate_plan_tiles(ctx.handle, *[_lib.byref(v) for v in t]))
         info.update(tiles=(t[0].value, t[1].value), tile_samples=(t[2].value, t[3].value), batch=t[4].value)
-    if info['method'] == 'fft-fine':
+    if info['method'] in _FINE_METHODS:
         t = [_lib.c_int(0) for _ in range(5)]
         _lib.check(ctx.lib.ml_propagate_plan_lattices(ctx.handle, *[_lib.byref(v) for v in t]))
         info.update(subsample=(t[0].value, t[1].value), lattice_targets=(t[2].value, t[3].value), cache_kernels=bool(t[4].value))
+    if info['method'] == 'fft-stack':
+        nz = _lib.c_int(0)
+        _lib.check(ctx.lib.ml_propagate_plan_planes(ctx.handle, _lib.byref(nz)))
+        info['planes'] = nz.value
     return info
 
 
@@ -226,18 +247,31 @@ class PlanePropagator:
     Ly``, with the same bits.  The first pass reserves the workspace and raises ``MetalensHipError`` with the bytes asked
     for (and ``cache_kernels=0``) if the device cannot give them.  ``subsample=(1, 1)`` has the bits of ``'fft-tiled'``.
     ``plan_info()`` adds ``'subsample'``, ``'lattice_targets'`` and ``'cache_kernels'`` to the keys of ``'fft-tiled'``.
-    ``subsample``, and ``cache_kernels=False``, belong to this method alone.
+    ``subsample``, and ``cache_kernels=False``, belong to this method and to ``'fft-stack'``.
+
+    ``method='fft-stack'`` is ``'fft-fine'`` for a STACK of planes (ml_propagate_plan_grid_stack): ``z`` is a sequence of
+    1 to 4096 planes, each finite and > 0, in any order and with repeats allowed; ``x``, ``y``, ``subsample``, ``tile`` and
+    ``cache_kernels`` are those of ``'fft-fine'``, with the same checks.  The fine plan does not depend on z, so one plan
+    serves the volume: the currents are transformed once per field set, and every (plane, lattice) is one more layer of
+    kernel spectra contracted against them, two per read.  Plane ``p`` has the bits of ``'fft-fine'`` planned at ``z[p]``.
+    ``shape`` is ``(len(z), len(x), len(y))`` - 3-D even for one plane - for every returned array, for ``sums()`` and for the
+    ``I_sum``, ``Sz_sum`` and ``image_each`` of ``SourceSweep.run(image=...)``; at most 2^26 targets in all.
+    ``cache_kernels=True`` keeps the kernel spectra of all ``len(z) A`` layers, ``(8 len(z) A cx cy + 4 cx cy + 2 (6 or 3))
+    Lx Ly`` complex128 - 128 B per padded index and layer; ``cache_kernels=False`` takes the streamed workspace of
+    ``'fft-fine'`` whatever ``len(z)`` is and fills the kernels of a pair of layers and a batch of tiles in one launch per
+    pass.  ``plan_info()`` adds ``'planes'`` to the keys of ``'fft-fine'``.  Several z belong to this method alone: every
+    other tensor grid lies in one plane.
     """
 
     def __init__(self, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False, want_h=True,
                  units=None, Z0=None, ctx=None, method='direct', tile=None, subsample=None, cache_kernels=True):
         if method not in METHODS:
             raise ValueError('method must be one of %s, got %r' % (METHODS, method))
-        if tile is not None and method not in ('fft-tiled', 'fft-fine'):
+        if tile is not None and method not in ('fft-tiled',) + _FINE_METHODS:
             raise ValueError("tile=%r: the tile lengths belong to method='fft-tiled', not to method=%r" % (tile, method))
-        if subsample is not None and method != 'fft-fine':
+        if subsample is not None and method not in _FINE_METHODS:
             raise ValueError("subsample=%r: the pitch ratios belong to method='fft-fine', not to method=%r" % (subsample, method))
-        if cache_kernels is not True and method != 'fft-fine':
+        if cache_kernels is not True and method not in _FINE_METHODS:
             raise ValueError("cache_kernels=%r: the choice belongs to method='fft-fine', not to method=%r" % (cache_kernels, method))
         if tile is not None and len(tile) != 2:
             raise ValueError('tile must be None or the two tile lengths (Lx, Ly), got %r' % (tile,))
@@ -248,20 +282,23 @@ class PlanePropagator:
         self.point_list, self.want_h = bool(point_list), bool(want_h)
         if method in _GRID_METHODS and self.point_list:
             raise ValueError("method=%r takes a tensor grid of targets on the aperture's pitch, not a point list" % method)
-        self.x, self.y, self.z = _targets(x, y, z, self.point_list)
+        self.x, self.y, self.z = _targets(x, y, z, self.point_list, stack=method == 'fft-stack')
         self.shape = (self.x.size,) if self.point_list else (self.x.size, self.y.size)
+        if method == 'fft-stack':
+            self.shape = (self.z.size,) + self.shape   # 3-D even for one plane
         self.aperture_shape = (len(xp_list), len(yp_list))
         self._geometry = (float(xp_list[0]), float(yp_list[0]), float(xp_list[1] - xp_list[0]),
                           float(yp_list[1] - yp_list[0]), float(wavelength), float(n_glass))
         self.tile = (0, 0)   # 0: the default length
-        self.subsample, self.cache_kernels = _check_subsample(subsample), bool(cache_kernels)
+        fine = method if method in _FINE_METHODS else 'fft-fine'   # (the fine method the messages name)
+        self.subsample, self.cache_kernels = _check_subsample(subsample, fine), bool(cache_kernels)
         if method in _GRID_METHODS:
-            _on_pitch('x', self.x, self._geometry[2], self.subsample[0])
-            _on_pitch('y', self.y, self._geometry[3], self.subsample[1])
-        if method == 'fft-fine':
+            _on_pitch('x', self.x, self._geometry[2], self.subsample[0], fine)
+            _on_pitch('y', self.y, self._geometry[3], self.subsample[1], fine)
+        if method in _FINE_METHODS:
             Lx, Ly = (None, None) if tile is None else tile   # (None or 0 for an axis: its default)
-            self.tile = (_check_fine('x', self.aperture_shape[0], self.x.size, self.subsample[0], Lx),
-                         _check_fine('y', self.aperture_shape[1], self.y.size, self.subsample[1], Ly))
+            self.tile = (_check_fine('x', self.aperture_shape[0], self.x.size, self.subsample[0], Lx, method),
+                         _check_fine('y', self.aperture_shape[1], self.y.size, self.subsample[1], Ly, method))
         if method == 'fft-tiled':
             Lx, Ly = (None, None) if tile is None else tile   # (None or 0 for an axis: its default)
             self.tile = (_check_tile('x', self.aperture_shape[0], self.x.size, Lx),
@@ -281,7 +318,13 @@ class PlanePropagator:
 
     def _plan(self):
         ctx = self.ctx
-        if self.method == 'fft-fine':
+        if self.method == 'fft-stack':
+            (sx, sy), mx, my = self.subsample, self.x.size, self.y.size
+            first_x, first_y = _lib.f64(self.x[:min(sx, mx)]), _lib.f64(self.y[:min(sy, my)])   # the lattices' origins
+            _lib.check(ctx.lib.ml_propagate_plan_grid_stack(
+                ctx.handle, *self._geometry, _lib.dptr(first_x), sx, _lib.dptr(first_y), sy, mx, my,
+                _lib.dptr(self.z), self.z.size, int(self.want_h), *self.tile, int(self.cache_kernels)))
+        elif self.method == 'fft-fine':
             (sx, sy), mx, my = self.subsample, self.x.size, self.y.size
             first_x, first_y = _lib.f64(self.x[:min(sx, mx)]), _lib.f64(self.y[:min(sy, my)])   # the lattices' origins
             _lib.check(ctx.lib.ml_propagate_plan_grid_fine(

@@ -190,7 +190,8 @@ class SourceSweep:
 
         ``image`` = a ``PlanePropagator`` built on this sweep's context and axes: the result gains ``I_sum`` =
         ``sum_k weights[k] |E_k|^2`` at its targets and, if it has ``want_h``, ``Sz_sum`` = ``sum_k weights[k]
-        Sz_k`` (shape ``image.shape``; summed on the GPU), and with ``keep_each`` ``image_each``, the dicts of
+        Sz_k`` (shape ``image.shape`` - ``(len(z), len(x), len(y))`` for a ``method='fft-stack'`` propagator, a through-focus
+        volume; summed on the GPU), and with ``keep_each`` ``image_each``, the dicts of
         ``PlanePropagator.propagate()`` per source - bit for bit those of ``build_nearfield`` + ``field_at_plane`` of
         the source alone.  ``P_sum``, ``total_P``, ``power_in`` and ``cone_P`` are not touched by it (``P_each`` of
         a polarisation group is then projected from the group's re-synthesised field sets)."""

@@ -56,7 +56,16 @@ target and crossover_targets (for apertures no other FFT form takes).  With a di
 (default 4096,64 and 2; --quick: 1024,64), E + H, with the kernel spectra kept and filled in every pass, against the loop
 of S^2 'fft-tiled' propagators that gives the same targets lattice by lattice and against one direct pass on them
 (``fft_fine``).  With a diagnostic build of the library ML_GRID_FINE_PAIR=1 contracts one lattice per read of the current
-spectra instead of two and is reported as lattices_per_contraction."""
+spectra instead of two and is reported as lattices_per_contraction.
+
+    python tools/propagate_bench.py --method fft-stack --planes N [--case N,M] [--subsample S] [--row ROW]
+
+--method fft-stack: ``PlanePropagator(method='fft-stack')`` for N planes of M^2 fine targets at the pitch / S around the focus
+(default 4096,64 and 2; --quick: 1024,64), E + H (``fft_stack``).  --row picks ONE row, so that every row can have a process
+of its own: ``stack-streamed``, ``stack-cached`` (a pass on the plan; ms_first = plan + first pass; the workspace),
+``loop`` (what gives the same volume without this method: one 'fft-fine' propagator per z, each planned and passed once,
+with the default cache_kernels=True), ``loop-streamed`` (the same with cache_kernels=False)
+and ``fine`` (one cached 'fft-fine' pass at the first z: the yardstick of N = 1).  Without --row: all four."""
 import json
 import os
 import re
@@ -412,6 +421,70 @@ def fft_fine(n, m, s, with_direct=True):
                           'ms': round(ms_direct, 3), 'max_E_difference_to_fft-fine': float('%.3e' % diff)}), flush=True)
 
 
+def fft_stack(n, m, s, nz, rows):
+    """``PlanePropagator(method='fft-stack')`` for nz planes of m^2 fine targets at the pitch / s around the focus of the
+    converging wave, E + H, planes 16 wavelengths around the focal length.  Rows (each timed by ``best_ms`` after a
+    priming pass): 'stack-streamed' and 'stack-cached' - a pass on the plan, ms_first = plan + first pass, the plan's
+    workspace; 'loop' - one 'fft-fine' propagator per z, planned and passed, with the default cache_kernels=True - the way
+    the volume is computed without this method - and 'loop-streamed', the same with cache_kernels=False; 'fine' - a pass of
+    one cached 'fft-fine' plan at the first z"""
+    import numpy as np
+
+    from metalens_amd import _lib
+    from metalens_amd.propagate import PlanePropagator
+    ctx = _lib.default_context()
+    wl, n_glass = 580e-9, 1.46
+    x, f = converging_wave(ctx, n, wl, n_glass)
+    d = x[1] - x[0]
+    first = (x.size - m // s) // 2
+    tx, ty = x[0] + (first + 0.3) * d + np.arange(m) * d / s, x[0] + (first + 0.6) * d + np.arange(m) * d / s
+    z = f + (np.linspace(-8, 8, nz) if nz > 1 else np.zeros(1)) * wl
+    case = '%d^2 -> %d x %d^2 at pitch / %d' % (n, nz, m, s)
+    for row in rows:
+        line = {'case': case, 'fields': 'E+H', 'row': row}
+        if row in ('stack-streamed', 'stack-cached'):
+            cached = row == 'stack-cached'
+            try:
+                t0 = time.perf_counter()
+                p = PlanePropagator(x, x, wl, n_glass, tx, ty, z, ctx=ctx, method='fft-stack', subsample=(s, s), cache_kernels=cached)
+                _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0))
+                ctx.sync()
+                ms_first = (time.perf_counter() - t0) * 1e3
+            except _lib.MetalensHipError as e:
+                line['error'] = str(e)
+                print(json.dumps(line), flush=True)
+                continue
+            ms = best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, p.Z0)))
+            info = p.plan_info()
+            out = p._download(None)
+            I = sum(np.abs(out[c]) ** 2 for c in ('Ex', 'Ey', 'Ez'))
+            tiles, layers = info['tiles'][0] * info['tiles'][1], nz * min(s, m) ** 2
+            planes = (8 * layers * tiles if cached else 16 * info['batch']) + 4 * tiles + 12   # (the plan's own bytes)
+            line.update(ms=round(ms, 3), ms_first=round(ms_first, 3), L=[info['Lx'], info['Ly']], tiles=list(info['tiles']),
+                        layers=layers, batch=info['batch'], workspace_MiB=round(planes * info['Lx'] * info['Ly'] * 16 / 2 ** 20, 1),
+                        brightest_plane=int(np.argmax(I.reshape(nz, -1).max(axis=1))))
+        elif row in ('loop', 'loop-streamed'):
+            def loop():
+                for zp in z:
+                    q = PlanePropagator(x, x, wl, n_glass, tx, ty, zp, ctx=ctx, method='fft-fine', subsample=(s, s),
+                                        cache_kernels=row == 'loop')
+                    _lib.check(ctx.lib.ml_propagate(ctx.handle, q.Z0))
+            line.update(method="loop of %d 'fft-fine' plans, planned and passed" % nz, cache_kernels=row == 'loop',
+                        ms=round(best_ms(ctx, loop), 3))
+        elif row == 'fine':
+            q = PlanePropagator(x, x, wl, n_glass, tx, ty, z[0], ctx=ctx, method='fft-fine', subsample=(s, s))
+            line.update(method="one cached 'fft-fine' pass", ms=round(best_ms(ctx, lambda: _lib.check(ctx.lib.ml_propagate(ctx.handle, q.Z0))), 3))
+            # at this size a streamed pair is filled a layer per launch (csrc/propagate_grid.h grid_stack_fill_layers), which
+            # no case of the tests reaches: plane 0 of a streamed stack of two planes against this plan, bit for bit
+            fine = q._download(None)
+            two = PlanePropagator(x, x, wl, n_glass, tx, ty, [z[0], z[0] + wl], ctx=ctx, method='fft-stack', subsample=(s, s),
+                                  cache_kernels=False).propagate()
+            line['same_bits_as_plane_0_of_a_streamed_stack'] = all(np.array_equal(two[c][0], fine[c]) for c in fine)
+        else:
+            raise SystemExit('--row: stack-streamed, stack-cached, loop, loop-streamed or fine, got %r' % row)
+        print(json.dumps(line), flush=True)
+
+
 def fft_three_sets(n=2048, m=64):
     """the three sets of a synthesised x, y, z batch through ONE ml_propagate_sets call of an 'fft' plan"""
     import math
@@ -452,6 +525,12 @@ def _option(name, default=None):
 
 
 def main():
+    if _option('--method') == 'fft-stack':
+        n, m = (int(v) for v in _option('--case', '1024,64' if '--quick' in sys.argv else '4096,64').split(','))
+        row = _option('--row')
+        fft_stack(n, m, int(_option('--subsample', 2)), int(_option('--planes', 8)),
+                  (row,) if row else ('stack-streamed', 'stack-cached', 'loop', 'fine'))
+        return
     if _option('--method') == 'fft-fine':
         n, m = (int(v) for v in _option('--case', '1024,64' if '--quick' in sys.argv else '4096,64').split(','))
         fft_fine(n, m, int(_option('--subsample', 2)), with_direct='--no-direct' not in sys.argv)
