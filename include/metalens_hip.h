@@ -490,6 +490,34 @@ int ml_propagate_accumulate(ml_ctx *ctx, const double *weights, int n, int reset
  * want_h == 0.  ML_ESTATE if no accumulation has run on the active propagation plan.  Synchronises.
  * Replaces no reference lines.                                                            */
 int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
+/* Focus metrics of the resident image, reduced on the GPU (csrc/propagate_focus.hip): per plane the peak of |E|^2 and its
+ * place, the zeroth to second moments of |E|^2 and of Sz, and the sums of both inside n_radii radii about a centre - what
+ * a focusing efficiency, a centroid, a spot size or a depth of focus are made of, without the image crossing PCIe.
+ *   source           : >= 0: member `source` of the last pass (ml_propagate: 0), weights I = (|Ex|^2 + |Ey|^2) + |Ez|^2 and
+ *                      Sz = 0.5 (Re Ex Hy* - Re Ey Hx*) as ml_propagate_accumulate forms them; -1: the sums of
+ *                      ml_propagate_accumulate as they are stored
+ *   mx, my, planes   : the targets as `planes` planes of mx x my, target (i, j) of plane p at (p mx + i) my + j; mx my planes
+ *                      must be the plan's targets (planes = 1 unless the plan is a stack)
+ *   dx, dy           : the targets' pitch, in the unit of the radii
+ *   centre           : [planes][2], (ci, cj) in INDEX units, fractions allowed; NULL: every plane's own peak, read on the
+ *                      device
+ *   radii, n_radii   : 0 <= n_radii <= 32 radii, finite, >= 0 and not decreasing.  Target (i, j) is inside radius R iff
+ *                      fx fx + fy fy <= R R with fx = dx (i - ci), fy = dy (j - cj), every operation rounded on its own
+ *   records          : HOST, [planes][record_doubles], record_doubles >= 16 + 2 n_radii.  A record, K = n_radii:
+ *                      [0] peak_I  [1] peak_index = i my + j, the lowest of equals
+ *                      [2 ... 7] sum w, sum w i, sum w j, sum w i^2, sum w j^2, sum w i j with w = I  [8 ... 13] with w = Sz
+ *                      [14] ci [15] cj, the centre used  [16 + r] sum of I inside radii[r]  [16 + K + r] sum of Sz inside it
+ *                      (csrc/propagate_focus.h FOCUS_*; the Sz entries are 0 for a plan with want_h == 0)
+ * ML_ESTATE with the wording of ml_propagate_download if no pass has run on the active plan, with that of
+ * ml_propagate_sums if source = -1 and nothing has been accumulated; ML_EINVAL with the numbers in ml_last_error for a
+ * member the last pass does not hold, mx my planes != targets, a pitch that is not > 0, more than 32 radii, a radius that
+ * is negative, not finite or below the one before it, a centre that is not finite, record_doubles too small.  A
+ * refused call leaves result, sums and plan as they were; so does an accepted one.  fp64, no atomics: chunks of a plane
+ * are reduced by a workgroup each in a fixed order and added in index order by a second launch; the cut depends on
+ * (mx, my) alone, so a record is repeatable bit for bit and plane p of a stack has the record of that plane planned
+ * alone.  Synchronises.  Replaces no reference lines; the far-field counterpart is ml_farfield_accumulate. */
+int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, double dx, double dy,
+                       const double *centre, const double *radii, int n_radii, double *records, int record_doubles);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
  * (csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the

@@ -51,7 +51,7 @@ SYMBOLS = (
     'ml_fields_sets', 'ml_nearfield_members_async', 'ml_propagate_plan_grid', 'ml_propagate_plan_info',
     'ml_propagate_plan_grid_long', 'ml_propagate_plan_grid_tiled', 'ml_propagate_plan_tiles',
     'ml_propagate_plan_grid_fine', 'ml_propagate_plan_lattices', 'ml_math_probe',
-    'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes',
+    'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes', 'ml_propagate_focus',
 )
 
 
@@ -182,6 +182,8 @@ def load():
         lib.ml_propagate_plan_grid_stack.argtypes = [c_void_p] + [c_double] * 6 + [_dp, c_int, _dp, c_int, c_int, c_int, _dp, c_int,
                                                                                   c_int, c_int, c_int, c_int]
         lib.ml_propagate_plan_planes.argtypes = [c_void_p, POINTER(c_int)]
+    if hasattr(lib, 'ml_propagate_focus'):
+        lib.ml_propagate_focus.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, _dp, _dp, c_int, _dp, c_int]
     if hasattr(lib, 'ml_math_probe'):   # (test surface: tests/test_gpu_device_math.py)
         lib.ml_math_probe.argtypes = [c_void_p, c_int, _dp, _ip, c_int, _dp, _dp, _ip]
     lib.ml_propagate_plan_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]

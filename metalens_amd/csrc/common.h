@@ -357,6 +357,9 @@ struct PropagatePlan {
     // [tiles][4] currents, [2][6 or 3] outputs; released by a direct plan
     DevBuf grid_work;
     DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
+    // the focus metrics (propagate_focus.hip, ml_propagate_focus): the chunks' partial records [planes][chunks][FOCUS_PARTIAL],
+    // the planes' records and the centres [planes][2] the radii are taken about; they read result and sums and change neither
+    DevBuf focus_partial, focus_records, focus_centre;
 };
 
 // What the kernels read about the lens (lens_pack.h lays it out, ctx.hip uploads it): the tables, the layout and what is

@@ -162,6 +162,72 @@ def _check_fine(name, n, m, s, L, method='fft-fine'):
     return int(L)
 
 
+FOCUS_RADII_MAX = 32   # csrc/propagate_focus.h
+# the record of a plane (csrc/propagate_focus.h FOCUS_*): peak, its index, the moments of I and of Sz, the centre, the radii's sums
+_FOCUS_MOM_I, _FOCUS_MOM_SZ, _FOCUS_CENTRE, _FOCUS_ENC = 2, 8, 14, 16
+
+
+def _focus_axis(name, t):
+    """-> (pitch, tolerance in index units) of a target axis of ``focus()``: ``(t[-1] - t[0]) / (len(t) - 1)``, with every
+    target within ``4 spacing(max |t|)`` of ``t[0] + i pitch`` (the rule of ``_on_pitch``)"""
+    if t.size < 2:
+        raise ValueError('focus() needs at least 2 targets along %s to know their pitch, the axis has %d' % (name, t.size))
+    pitch = (t[-1] - t[0]) / (t.size - 1)
+    if not (np.isfinite(pitch) and pitch > 0):
+        raise ValueError('focus() needs an ascending target axis: %s runs from %.17g to %.17g' % (name, t[0], t[-1]))
+    tol = 4 * np.spacing(np.abs(t).max())
+    off = np.abs(t - (t[0] + np.arange(t.size) * pitch)) > tol
+    if off.any():
+        i = int(np.argmax(off))
+        raise ValueError('focus() needs uniform target axes: %s[%d] = %.17g is not %s[0] + %d x %.17g (the moments and the '
+                         'radii are taken on the lattice of the targets)' % (name, i, t[i], name, i, pitch))
+    return float(pitch), tol / pitch
+
+
+def _check_focus(p, radii, centre, of):
+    """the argument checks of ``PlanePropagator.focus`` (and of ``SourceSweep.run(image_radii=...)``), before any device
+    call -> (radii ascending, the caller's order as indices into them, centres (planes, 2) in index units or None for
+    ``'peak'``, planes, dx, dy)"""
+    if of not in ('fields', 'sums'):
+        raise ValueError("of must be 'fields' or 'sums', got %r" % (of,))
+    if p.point_list:
+        raise ValueError('focus() takes a tensor grid of targets, not a point list: moments and radii need the lattice')
+    dx, tol_i = _focus_axis('x', p.x)
+    dy, tol_j = _focus_axis('y', p.y)
+    planes = p.z.size if p.method == 'fft-stack' else 1
+    r = np.asarray(radii, dtype=float)
+    if r.ndim != 1:
+        raise ValueError('radii must be a sequence of numbers, got an array of shape %s' % (r.shape,))
+    if r.size > FOCUS_RADII_MAX:
+        raise ValueError('focus() takes at most %d radii, got %d' % (FOCUS_RADII_MAX, r.size))
+    bad = ~(np.isfinite(r) & (r >= 0))
+    if bad.any():
+        raise ValueError('a radius must be finite and >= 0: radii[%d] = %g' % (int(np.argmax(bad)), r[np.argmax(bad)]))
+    order = np.argsort(r, kind='stable')
+    back = np.empty(r.size, dtype=int)
+    back[order] = np.arange(r.size)
+    if isinstance(centre, str):
+        if centre != 'peak':
+            raise ValueError("centre must be 'peak', one (xc, yc) or an array (planes, 2), got %r" % (centre,))
+        return _lib.f64(r[order]), back, None, planes, dx, dy
+    try:
+        c = np.asarray(centre, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError("centre must be 'peak', one (xc, yc) or an array (planes, 2), got %r" % (centre,)) from None
+    if c.shape == (2,):
+        c = np.broadcast_to(c, (planes, 2))
+    if c.shape != (planes, 2):
+        raise ValueError("centre must be 'peak', one (xc, yc) or an array (%d, 2) - one centre per plane -, got shape %s"
+                         % (planes, np.shape(centre)))
+    if not np.isfinite(c).all():
+        raise ValueError('a centre must be finite, got %r' % (centre,))
+    # index units; a centre within the axes' own tolerance of a target IS that target (a radius of 0 then holds it)
+    ci, cj = (c[:, 0] - p.x[0]) / dx, (c[:, 1] - p.y[0]) / dy
+    ci = np.where(np.abs(ci - np.rint(ci)) <= tol_i, np.rint(ci), ci)
+    cj = np.where(np.abs(cj - np.rint(cj)) <= tol_j, np.rint(cj), cj)
+    return _lib.f64(r[order]), back, _lib.f64(np.stack([ci, cj], axis=1)), planes, dx, dy
+
+
 def plan_info(ctx):
     """-> ``{'method', 'Lx', 'Ly', 'workspace_bytes'}`` of the context's active propagation plan
     (ml_propagate_plan_info): the padded lengths are 0 for the direct method.  For ``'fft-tiled'`` they are the tile
@@ -198,6 +264,8 @@ class PlanePropagator:
 
     ``propagate_sets()`` does the same for all field sets of a synthesis batch (the x, y, z dipoles of an emitter)
     in one pass and ``accumulate()`` keeps their weighted intensity sums on the GPU (``SourceSweep.run(image=...)``).
+    ``focus()`` reduces the resident image - a field set or the sums - to its focus metrics on the GPU: peak, moments,
+    the power inside up to 32 radii, per plane (csrc/propagate_focus.hip).
 
     ``propagate()`` sums the field set resident on the GPU (the selected one of a batch) and returns a dict
     with ``Ex, Ey, Ez, Hx, Hy, Hz`` (complex128, shape ``(len(x), len(y))`` or ``(len(x),)``) and
@@ -421,6 +489,54 @@ class PlanePropagator:
         Sz = np.empty(self.shape) if self.want_h else None
         _lib.check(ctx.lib.ml_propagate_sums(ctx.handle, _lib.dptr(I), _lib.dptr(Sz)))
         return I, Sz
+
+    def focus(self, radii=(), centre='peak', member=0, of='fields'):
+        """The focus metrics of the image that is resident on the GPU, reduced there (``ml_propagate_focus``,
+        csrc/propagate_focus.hip): nothing but a record of ``16 + 2 len(radii)`` doubles per plane crosses PCIe.
+
+        ``of='fields'``: of member ``member`` of the last ``propagate()`` / ``queue_sets()`` / ``propagate_sets()`` pass,
+        with ``I = |E|^2`` and ``Sz = Re(E x H*)_z / 2``; ``of='sums'``: of the sums of ``accumulate()`` as they are stored
+        (``member`` is ignored).  ``radii``: up to 32 radii in the targets' length unit, in any order; ``centre``: ``'peak'``
+        (every plane's own peak, read on the device), one ``(xc, yc)`` in the targets' frame, or an array ``(planes, 2)``.
+        A target is inside radius ``R`` iff ``(dx (i - ci))^2 + (dy (j - cj))^2 <= R^2`` in index units about the centre
+        ``(ci, cj) = ((xc - x[0]) / dx, (yc - y[0]) / dy)`` - a centre within the axes' tolerance of a target is that
+        target.  The targets must be a tensor grid with uniform ascending axes of at least 2 targets each,
+        ``|x[i] - (x[0] + i dx)| <= 4 spacing(max |x|)`` with ``dx = (x[-1] - x[0]) / (len(x) - 1)``.
+
+        -> dict of arrays whose leading axis is the planes (1 unless ``method='fft-stack'``): ``peak_I``, ``peak_index``
+        (``(planes, 2)`` ints, the lowest flat index of equals) and ``peak_xy``; ``I_dA = sum I dx dy``; ``centroid_I =
+        (x[0] + dx sum I i / sum I, ...)`` (NaN where the sum is 0) and ``second_moments_I``, central, in length^2, as ``(xx,
+        yy, xy)``; ``centre_index`` and ``centre_xy``, the centre used; ``encircled_I`` of shape ``(planes, len(radii))``,
+        ``sum I dx dy`` inside each radius, in the caller's order.  With ``want_h``: ``P = sum Sz dx dy``, ``centroid_Sz``,
+        ``second_moments_Sz`` and ``encircled_P`` as well.  Bit for bit repeatable; plane ``p`` of a stack has the numbers
+        of that plane planned alone.  Synchronises."""
+        r, back, c, planes, dx, dy = _check_focus(self, radii, centre, of)
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        K, mx, my = r.size, self.x.size, self.y.size
+        rd = _FOCUS_ENC + 2 * K
+        rec = np.empty((planes, rd))
+        _lib.check(ctx.lib.ml_propagate_focus(ctx.handle, -1 if of == 'sums' else int(member), mx, my, planes, dx, dy,
+                                              _lib.dptr(c), _lib.dptr(r) if K else None, K, _lib.dptr(rec), rd))
+        flat = rec[:, 1].astype(np.int64)
+        out = {'peak_I': rec[:, 0].copy(), 'peak_index': np.stack([flat // my, flat % my], axis=1)}
+        out['peak_xy'] = np.stack([self.x[out['peak_index'][:, 0]], self.y[out['peak_index'][:, 1]]], axis=1)
+        out['centre_index'] = rec[:, _FOCUS_CENTRE:_FOCUS_CENTRE + 2].copy()
+        out['centre_xy'] = np.stack([self.x[0] + dx * rec[:, _FOCUS_CENTRE], self.y[0] + dy * rec[:, _FOCUS_CENTRE + 1]], axis=1)
+        for name, total, at, enc, e_at in (('I', 'I_dA', _FOCUS_MOM_I, 'encircled_I', _FOCUS_ENC),
+                                           ('Sz', 'P', _FOCUS_MOM_SZ, 'encircled_P', _FOCUS_ENC + K)):
+            if name == 'Sz' and not self.want_h:
+                continue
+            s, si, sj, sii, sjj, sij = (rec[:, at + q] for q in range(6))
+            with np.errstate(divide='ignore', invalid='ignore'):
+                mi, mj = np.where(s != 0, si / s, np.nan), np.where(s != 0, sj / s, np.nan)
+                out['second_moments_' + name] = np.stack([dx * dx * (sii / s - mi * mi), dy * dy * (sjj / s - mj * mj),
+                                                          dx * dy * (sij / s - mi * mj)], axis=1)
+            out[total] = s * dx * dy
+            out['centroid_' + name] = np.stack([self.x[0] + dx * mi, self.y[0] + dy * mj], axis=1)
+            out[enc] = rec[:, e_at:e_at + K][:, back] * dx * dy
+        return out
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,

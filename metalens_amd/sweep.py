@@ -19,7 +19,9 @@ What a sweep shares:
 * with ``image=`` (a ``PlanePropagator``): the image of the emitter at finite distance.  The field sets of a
   group are propagated to the image plane in ONE pass (``ml_propagate_sets``: the geometry of a (sample, target)
   pair serves all members) and their weighted ``|E|^2`` and ``Sz`` are summed on the GPU
-  (``ml_propagate_accumulate``); two real maps cross PCIe at the end.
+  (``ml_propagate_accumulate``); two real maps cross PCIe at the end.  With ``image_radii=`` the sums are reduced
+  further on the GPU (``ml_propagate_focus``): peak, moments and the power inside each radius, and from it the focusing
+  efficiency ``encircled power / incident power``.
 """
 import numpy as np
 
@@ -175,7 +177,20 @@ class SourceSweep:
             image.accumulate([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
         return n
 
-    def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None):
+    def _check_image_focus(self, image, image_radii, image_centre):
+        """argument errors of ``image_radii=``, before any device call"""
+        if image_radii is None:
+            return
+        if image is None:
+            raise ValueError('image_radii= needs image=, the PlanePropagator whose sums the radii are taken in')
+        if not image.want_h:
+            raise ValueError('image_radii= needs an image with want_h=True: the focusing efficiency is the power sum Sz dx dy '
+                             'inside a radius over the incident power')
+        from .propagate import _check_focus
+        _check_focus(image, image_radii, image_centre, 'sums')
+
+    def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
+            image_radii=None, image_centre='peak'):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -194,8 +209,15 @@ class SourceSweep:
         volume; summed on the GPU), and with ``keep_each`` ``image_each``, the dicts of
         ``PlanePropagator.propagate()`` per source - bit for bit those of ``build_nearfield`` + ``field_at_plane`` of
         the source alone.  ``P_sum``, ``total_P``, ``power_in`` and ``cone_P`` are not touched by it (``P_each`` of
-        a polarisation group is then projected from the group's re-synthesised field sets)."""
+        a polarisation group is then projected from the group's re-synthesised field sets).
+
+        ``image_radii`` = up to 32 radii in the image (needs ``image`` with ``want_h``): the result gains ``image_focus`` =
+        ``image.focus(image_radii, image_centre, of='sums')`` - peak, moments and encircled sums of ``I_sum`` and ``Sz_sum``,
+        reduced on the GPU (``ml_propagate_focus``) - and ``focus_efficiency`` = ``encircled_P / sum_k weights[k]
+        power_in[k]``, shape ``(planes, len(image_radii))``: the power through a disc in the image plane over the incident
+        power (NaN where that is 0).  ``image_centre``: ``'peak'`` (default), one ``(xc, yc)`` or ``(planes, 2)``."""
         self._check_image(image)
+        self._check_image_focus(image, image_radii, image_centre)
         sources = list(sources)
         if not 1 <= len(sources) <= MAX_SLOTS:
             raise ValueError('a sweep takes 1 to %d sources, got %d' % (MAX_SLOTS, len(sources)))
@@ -266,6 +288,11 @@ class SourceSweep:
                 out['Sz_sum'] = Sz_sum
             if keep_each:
                 out['image_each'] = image_each
+            if image_radii is not None:
+                out['image_focus'] = image.focus(image_radii, image_centre, of='sums')
+                incident = float((weights * power_in).sum())
+                enc = out['image_focus']['encircled_P']
+                out['focus_efficiency'] = enc / incident if incident else np.full(enc.shape, np.nan)
         return out
 
 
