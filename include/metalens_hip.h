@@ -518,6 +518,31 @@ int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
  * alone.  Synchronises.  Replaces no reference lines; the far-field counterpart is ml_farfield_accumulate. */
 int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, double dx, double dy,
                        const double *centre, const double *radii, int n_radii, double *records, int record_doubles);
+/* The transfer function of the resident image, contracted on the GPU (csrc/propagate_otf.hip): per plane and per weight
+ * w (0: I = |E|^2, 1: Sz, formed as ml_propagate_focus forms them)
+ *     O_w[p][a][b] = sum_i sum_j w(p, i, j) exp(-2 pi i (u[a] i + v[b] j)),   a < nu, b < nv
+ * - the Fourier transform of the point-spread function at chosen frequencies, whose modulus over O_w(0, 0) is the
+ * modulation transfer function -, without the image crossing PCIe.
+ *   source, mx, my, planes : as for ml_propagate_focus; mx, my >= 1, no pitch enters ((i, j) are target indices)
+ *   u, nu, v, nv           : 1 <= nu, nv <= ML_OTF_FREQ_MAX frequencies per axis in CYCLES PER TARGET SAMPLE, finite,
+ *                            |u|, |v| <= 0.5 (Nyquist included), in any order, repeats allowed
+ *   otf                    : HOST, complex128 [planes][2][nu][nv] as (re, im) pairs; the blocks of weight 1 are zeros for
+ *                            a plan with want_h == 0
+ * The phase 2 pi frac(u i) is formed so that the rounding of u i does not reach it (csrc/propagate_otf.h
+ * otf_phase_fraction: an FMA takes the product's rounding error) and the quarter turns come off the fraction exactly, so a
+ * phasor at a fraction of 0, +-1/4, +-1/2 is exactly 0 or +-1; each component of a phasor is within 16 x 2^-53 of the exact
+ * one.  fp64, no atomics: rows, then columns, each in segments of 32 indices added in ascending order; the order
+ * depends on (mx, my) alone, so an entry is repeatable bit for bit, plane p of a stack has the bits of that plane
+ * planned alone, and an entry does not depend on nu, nv, the other frequencies or their order.
+ * ML_ESTATE with the wording of ml_propagate_download if no pass has run on the active plan, with that of
+ * ml_propagate_sums if source = -1 and nothing has been accumulated; ML_EINVAL with the numbers in ml_last_error for a
+ * member the last pass does not hold, mx my planes != targets, more than 65535 planes, nu or nv outside [1, 64], a NULL pointer, a frequency
+ * that is not finite or beyond +-0.5 (axis, index and value), more than 2^24 = mx nu + my nv tabulated phasors, more than
+ * 2^26 = planes mx nv row sums per weight, a context of more than one rank.  A refused call leaves result, sums, plan and
+ * focus records as they were; so does an accepted one.  Synchronises.  Replaces no reference lines.  */
+#define ML_OTF_FREQ_MAX 64
+int ml_propagate_otf(ml_ctx *ctx, int source, int mx, int my, int planes, const double *u, int nu, const double *v,
+                     int nv, double *otf);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
  * (csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the
@@ -657,6 +682,9 @@ int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *
  *   ML_PROBE_RSQRT        x            out0                            (rsqrt_fast)
  *   ML_PROBE_RAW_RCP      x            out0: the hardware's reciprocal estimate alone
  *   ML_PROBE_RAW_RSQ      x            out0: the hardware's reciprocal-root estimate alone
+ *   ML_PROBE_OTF_PHASOR   x, kq        out0 = sin, out1 = cos of 2 pi frac(x kq), x = a frequency (|x| <= 0.5), kq = an
+ *                                      index >= 0, as the kernels of ml_propagate_otf form them (csrc/propagate_otf.h)
+ * (op 8 is reserved.)
  * Pointers an op does not use may be NULL.  An unknown op, a NULL pointer the op needs and n out of range end in
  * ML_EINVAL.  Synchronises.  Replaces no reference lines.                                                  */
 #define ML_PROBE_SINCOS 0
@@ -667,6 +695,7 @@ int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *
 #define ML_PROBE_RSQRT 5
 #define ML_PROBE_RAW_RCP 6
 #define ML_PROBE_RAW_RSQ 7
+#define ML_PROBE_OTF_PHASOR 9
 int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq, int n,
                   double *out0, double *out1, int *outk);
 

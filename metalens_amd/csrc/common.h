@@ -360,6 +360,9 @@ struct PropagatePlan {
     // the focus metrics (propagate_focus.hip, ml_propagate_focus): the chunks' partial records [planes][chunks][FOCUS_PARTIAL],
     // the planes' records and the centres [planes][2] the radii are taken about; they read result and sums and change neither
     DevBuf focus_partial, focus_records, focus_centre;
+    // the transfer function (propagate_otf.hip, ml_propagate_otf): the phasor tables Tx[mx][nu], Ty[my][nv], the row sums
+    // R[2][planes][mx][nv] and the device copy of the output [planes][2][nu][nv]; it reads result and sums and changes neither
+    DevBuf otf_tables, otf_rows, otf_out;
 };
 
 // What the kernels read about the lens (lens_pack.h lays it out, ctx.hip uploads it): the tables, the layout and what is

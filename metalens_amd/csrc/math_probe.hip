@@ -5,6 +5,7 @@
 // No product code calls this entry.
 #include "common.h"
 #include "nearfield_math.h"
+#include "propagate_otf.h"
 
 namespace ml {
 
@@ -26,6 +27,12 @@ __global__ __launch_bounds__(256) void math_probe_kernel(int op, const double *x
     case ML_PROBE_RSQRT: a = rsqrt_fast(v); break;
     case ML_PROBE_RAW_RCP: a = __builtin_amdgcn_rcp(v); break;
     case ML_PROBE_RAW_RSQ: a = __builtin_amdgcn_rsq(v); break;
+    case ML_PROBE_OTF_PHASOR: {   // propagate_otf.hip otf_phasor_sincos
+        double rest;
+        const int q = otf_phase_quarters(otf_phase_fraction(v, (double)kq[i]), rest);
+        sincos_cw_q(OTF_TWO_PI * rest, q, a, b);
+        break;
+    }
     }
     out0[i] = a;
     if (out1) out1[i] = b;
@@ -39,11 +46,12 @@ using namespace ml;
 extern "C" int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq, int n, double *out0, double *out1,
                              int *outk) {
     ML_REQUIRE(ctx && x && out0, "ml_math_probe: NULL argument");
-    ML_REQUIRE(op >= ML_PROBE_SINCOS && op <= ML_PROBE_RAW_RSQ, "ml_math_probe: unknown op %d (0 ... %d)", op,
-               ML_PROBE_RAW_RSQ);
+    ML_REQUIRE((op >= ML_PROBE_SINCOS && op <= ML_PROBE_RAW_RSQ) || op == ML_PROBE_OTF_PHASOR,
+               "ml_math_probe: unknown op %d (0 ... %d, %d)", op, ML_PROBE_RAW_RSQ, ML_PROBE_OTF_PHASOR);
     ML_REQUIRE(n >= 1 && n <= PROBE_MAX_N, "ml_math_probe: n = %d values, 1 ... 2^24 are taken", n);
     ML_REQUIRE(op != ML_PROBE_SINCOS_Q || kq, "ml_math_probe: op %d (sincos_cw_q) needs the quadrants kq", op);
-    const bool two = op == ML_PROBE_SINCOS || op == ML_PROBE_SINCOS_Q;
+    ML_REQUIRE(op != ML_PROBE_OTF_PHASOR || kq, "ml_math_probe: op %d (the phasor of ml_propagate_otf) needs the indices kq", op);
+    const bool two = op == ML_PROBE_SINCOS || op == ML_PROBE_SINCOS_Q || op == ML_PROBE_OTF_PHASOR;
     ML_REQUIRE(!two || out1, "ml_math_probe: op %d returns sin and cos: out1 is NULL", op);
     ML_REQUIRE(op != ML_PROBE_REDUCE || outk, "ml_math_probe: op %d (reduce_pio2) returns the quadrants: outk is NULL", op);
     ML_HIP(hipSetDevice(ctx->device));
@@ -54,7 +62,7 @@ extern "C" int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq
     double *dx = buf.as<double>(), *d0 = dx + n, *d1 = dx + 2 * (size_t)n;
     int *dkq = reinterpret_cast<int *>(dx + 3 * (size_t)n), *dk = dkq + n;
     ML_HIP(hipMemcpyAsync(dx, x, nd, hipMemcpyHostToDevice, ctx->stream));
-    if (op == ML_PROBE_SINCOS_Q) ML_HIP(hipMemcpyAsync(dkq, kq, ni, hipMemcpyHostToDevice, ctx->stream));
+    if (op == ML_PROBE_SINCOS_Q || op == ML_PROBE_OTF_PHASOR) ML_HIP(hipMemcpyAsync(dkq, kq, ni, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, op, dx, dkq, n, d0,
                        two ? d1 : nullptr, op == ML_PROBE_REDUCE ? dk : nullptr);
     ML_HIP(hipGetLastError());

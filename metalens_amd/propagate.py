@@ -206,10 +206,15 @@ def _check_focus(p, radii, centre, of):
     order = np.argsort(r, kind='stable')
     back = np.empty(r.size, dtype=int)
     back[order] = np.arange(r.size)
+    return _lib.f64(r[order]), back, _centre_index(p, centre, planes, dx, dy, tol_i, tol_j), planes, dx, dy
+
+
+def _centre_index(p, centre, planes, dx, dy, tol_i, tol_j):
+    """a centre of ``focus()`` / ``otf()`` -> (planes, 2) in index units, None for ``'peak'``"""
     if isinstance(centre, str):
         if centre != 'peak':
             raise ValueError("centre must be 'peak', one (xc, yc) or an array (planes, 2), got %r" % (centre,))
-        return _lib.f64(r[order]), back, None, planes, dx, dy
+        return None
     try:
         c = np.asarray(centre, dtype=float)
     except (TypeError, ValueError):
@@ -225,7 +230,55 @@ def _check_focus(p, radii, centre, of):
     ci, cj = (c[:, 0] - p.x[0]) / dx, (c[:, 1] - p.y[0]) / dy
     ci = np.where(np.abs(ci - np.rint(ci)) <= tol_i, np.rint(ci), ci)
     cj = np.where(np.abs(cj - np.rint(cj)) <= tol_j, np.rint(cj), cj)
-    return _lib.f64(r[order]), back, _lib.f64(np.stack([ci, cj], axis=1)), planes, dx, dy
+    return _lib.f64(np.stack([ci, cj], axis=1))
+
+
+OTF_FREQ_MAX = 64   # csrc/propagate_otf.h, ML_OTF_FREQ_MAX
+
+
+def _otf_axis(name, f, pitch):
+    """one frequency axis of ``otf()``: cycles per length -> (cycles per target sample for the device, frequency 0 put in
+    front where the caller has none; where the caller's frequencies lie in that array)"""
+    f = np.asarray(f, dtype=float)
+    if f.ndim != 1 or f.size < 1:
+        raise ValueError('f%s must be a sequence of at least one frequency, got an array of shape %s' % (name, f.shape))
+    if not np.isfinite(f).all():
+        i = int(np.argmax(~np.isfinite(f)))
+        raise ValueError('a frequency must be finite: f%s[%d] = %g' % (name, i, f[i]))
+    u = f * pitch
+    # 1 / (2 pitch) times the pitch may round to the double above 1/2: that is Nyquist
+    u = np.where(np.abs(np.abs(u) - 0.5) <= 4 * np.spacing(0.5), np.copysign(0.5, u), u)
+    beyond = np.abs(u) > 0.5
+    if beyond.any():
+        i = int(np.argmax(beyond))
+        raise ValueError('f%s[%d] = %.17g lies beyond the Nyquist frequency 1 / (2 d%s) = %.17g of targets %.17g apart'
+                         % (name, i, f[i], name, 0.5 / pitch, pitch))
+    has_zero = bool((u == 0).any())
+    if u.size + (not has_zero) > OTF_FREQ_MAX:
+        raise ValueError('otf() takes at most %d frequencies per axis, %d when 0 is not among them (it is added for the '
+                         'normalisation): f%s has %d' % (OTF_FREQ_MAX, OTF_FREQ_MAX - 1, name, u.size))
+    if has_zero:
+        return _lib.f64(u), np.arange(u.size), int(np.argmax(u == 0))
+    return _lib.f64(np.concatenate([[0.0], u])), 1 + np.arange(u.size), 0
+
+
+def _check_otf(p, fx, fy, centre, of):
+    """the argument checks of ``PlanePropagator.otf`` (and of ``SourceSweep.run(image_freqs=...)``), before any device call
+    -> ((u, the caller's entries, where 0 lies), the same for v, centres (planes, 2) in index units / ``'peak'`` / None, planes,
+    dx, dy)"""
+    if of not in ('fields', 'sums'):
+        raise ValueError("of must be 'fields' or 'sums', got %r" % (of,))
+    if p.point_list:
+        raise ValueError('otf() takes a tensor grid of targets, not a point list: the transform needs the lattice')
+    dx, tol_i = _focus_axis('x', p.x)
+    dy, tol_j = _focus_axis('y', p.y)
+    planes = p.z.size if p.method == 'fft-stack' else 1
+    ax, ay = _otf_axis('x', fx, dx), _otf_axis('y', fy, dy)
+    if centre is not None:
+        centre = _centre_index(p, centre, planes, dx, dy, tol_i, tol_j)
+        if centre is None:
+            centre = 'peak'
+    return ax, ay, centre, planes, dx, dy
 
 
 def plan_info(ctx):
@@ -536,6 +589,44 @@ class PlanePropagator:
             out[total] = s * dx * dy
             out['centroid_' + name] = np.stack([self.x[0] + dx * mi, self.y[0] + dy * mj], axis=1)
             out[enc] = rec[:, e_at:e_at + K][:, back] * dx * dy
+        return out
+
+    def otf(self, fx, fy, member=0, of='fields', centre=None):
+        """The transfer function of the image that is resident on the GPU - the Fourier transform of ``I = |E|^2`` (and of
+        ``Sz`` with ``want_h``) at the frequencies ``fx`` x ``fy`` -, contracted there (``ml_propagate_otf``,
+        csrc/propagate_otf.hip): ``2 len(fx) len(fy)`` complex numbers per plane cross PCIe, not the image.
+
+        ``fx``, ``fy``: 1-D sequences in cycles per length unit of the targets, in any order, repeats allowed, none beyond
+        the Nyquist frequency ``1 / (2 dx)``; at most 64 per axis, 63 when 0 is not among them (it is added for the
+        normalisation and stripped again; an entry does not depend on the other frequencies of a call).  ``member``, ``of``
+        and the conditions on the targets are those of ``focus()``.  ``centre`` is the phase reference: None - the first
+        target, ``(x[0], y[0])`` -, ``'peak'`` - every plane's own peak, from ``focus()`` -, one ``(xc, yc)`` in the targets'
+        frame or an array ``(planes, 2)``; it is applied on the host as ``exp(+2 pi i (fx (xc - x[0]) + fy (yc - y[0])))``.
+
+        -> dict of arrays whose leading axis is the planes (1 unless ``method='fft-stack'``): ``otf_I`` of shape ``(planes,
+        len(fx), len(fy))``, ``sum_ij I exp(-2 pi i (fx (x_i - xc) + fy (y_j - yc))) dx dy``; ``mtf_I = |otf_I| / otf_I(0, 0)``
+        (NaN where that is 0); with ``want_h`` ``otf_Sz`` and ``mtf_Sz``; ``fx`` and ``fy`` as given.  Repeatable bit for bit;
+        plane ``p`` of a stack has the numbers of that plane planned alone.  Synchronises."""
+        (u, iu, u0), (v, iv, v0), c, planes, dx, dy = _check_otf(self, fx, fy, centre, of)
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        if isinstance(c, str):
+            c = self.focus(member=member, of=of)['peak_index'].astype(float)
+        raw = np.empty((planes, 2, u.size, v.size), dtype=np.complex128)
+        _lib.check(ctx.lib.ml_propagate_otf(ctx.handle, -1 if of == 'sums' else int(member), self.x.size, self.y.size, planes,
+                                            _lib.dptr(u), u.size, _lib.dptr(v), v.size, _lib.dptr(raw)))
+        turn = 1.0
+        if c is not None:   # the phase reference, with u ci reduced to its fraction first
+            px, py = u[None, :] * c[:, :1], v[None, :] * c[:, 1:]
+            turn = np.exp(2j * np.pi * (px - np.rint(px)))[:, :, None] * np.exp(2j * np.pi * (py - np.rint(py)))[:, None, :]
+        out = {}
+        for w, name in enumerate(('I', 'Sz')[:2 if self.want_h else 1]):
+            zero = raw[:, w, u0, v0].real[:, None, None]
+            with np.errstate(divide='ignore', invalid='ignore'):   # (the modulus is the device's own: no phase reference moves it)
+                out['mtf_' + name] = np.where(zero != 0, np.abs(raw[:, w]) / zero, np.nan)[:, iu][:, :, iv]
+            out['otf_' + name] = (raw[:, w] * turn)[:, iu][:, :, iv] * (dx * dy)
+        out['fx'], out['fy'] = np.array(fx, dtype=float), np.array(fy, dtype=float)
         return out
 
 

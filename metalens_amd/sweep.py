@@ -189,8 +189,23 @@ class SourceSweep:
         from .propagate import _check_focus
         _check_focus(image, image_radii, image_centre, 'sums')
 
+    def _check_image_otf(self, image, image_freqs, image_centre):
+        """argument errors of ``image_freqs=``, before any device call -> (fx, fy) as arrays, or None"""
+        if image_freqs is None:
+            return None
+        if image is None:
+            raise ValueError('image_freqs= needs image=, the PlanePropagator whose sums are transformed')
+        try:
+            fx, fy = image_freqs
+        except (TypeError, ValueError):
+            raise ValueError('image_freqs must be a pair (fx, fy) of frequency axes, got %r' % (image_freqs,)) from None
+        from .propagate import _check_otf
+        fx, fy = np.array(fx, dtype=float), np.array(fy, dtype=float)   # (taken once: the pair may be a one-shot iterable)
+        _check_otf(image, fx, fy, image_centre, 'sums')
+        return fx, fy
+
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
-            image_radii=None, image_centre='peak'):
+            image_radii=None, image_centre='peak', image_freqs=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -215,9 +230,14 @@ class SourceSweep:
         ``image.focus(image_radii, image_centre, of='sums')`` - peak, moments and encircled sums of ``I_sum`` and ``Sz_sum``,
         reduced on the GPU (``ml_propagate_focus``) - and ``focus_efficiency`` = ``encircled_P / sum_k weights[k]
         power_in[k]``, shape ``(planes, len(image_radii))``: the power through a disc in the image plane over the incident
-        power (NaN where that is 0).  ``image_centre``: ``'peak'`` (default), one ``(xc, yc)`` or ``(planes, 2)``."""
+        power (NaN where that is 0).  ``image_centre``: ``'peak'`` (default), one ``(xc, yc)`` or ``(planes, 2)``.
+
+        ``image_freqs`` = ``(fx, fy)``, frequency axes in cycles per length (needs ``image``): the result gains ``image_otf`` =
+        ``image.otf(fx, fy, of='sums', centre=image_centre)`` - the transfer function of the field of view, the transform of
+        ``I_sum`` (and ``Sz_sum``) contracted on the GPU (``ml_propagate_otf``), and its modulus, the MTF."""
         self._check_image(image)
         self._check_image_focus(image, image_radii, image_centre)
+        image_freqs = self._check_image_otf(image, image_freqs, image_centre)
         sources = list(sources)
         if not 1 <= len(sources) <= MAX_SLOTS:
             raise ValueError('a sweep takes 1 to %d sources, got %d' % (MAX_SLOTS, len(sources)))
@@ -293,6 +313,8 @@ class SourceSweep:
                 incident = float((weights * power_in).sum())
                 enc = out['image_focus']['encircled_P']
                 out['focus_efficiency'] = enc / incident if incident else np.full(enc.shape, np.nan)
+            if image_freqs is not None:
+                out['image_otf'] = image.otf(*image_freqs, of='sums', centre=image_centre)
         return out
 
 
