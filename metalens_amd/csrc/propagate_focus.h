@@ -26,11 +26,21 @@
 // A partial record of a chunk has FOCUS_PARTIAL doubles: the chunk's peak and its index, the twelve sums, and behind
 // them [annulus][I, Sz] for FOCUS_RADII_MAX annuli: annulus a holds the targets inside radius a that are outside every
 // radius before it (the radii are sorted: disjoint sets, summed one by one and accumulated by the second launch).
+//
+// The second launch takes the chunks' partial records through the LDS FOCUS_FINISH_TILE = 32 at a time, in index order:
+// focus_finish_tiles(P) tiles, the last of focus_finish_tile_chunks(chunks, tiles - 1) records.  The sums and the peak
+// are carried from tile to tile, so the tiles change no order.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+
+#if defined(__HIPCC__)
+#define ML_FOCUS_HD __host__ __device__
+#else
+#define ML_FOCUS_HD
+#endif
 
 namespace ml {
 
@@ -39,6 +49,8 @@ constexpr int FOCUS_STEP = 2 * FOCUS_THREADS;   // targets a workgroup takes per
 constexpr int FOCUS_CHUNK_MIN = 1024;     // targets of the shortest chunk
 constexpr int FOCUS_CHUNKS_MAX = 1024;    // chunks of a plane at the most
 constexpr int FOCUS_RADII_MAX = 32;
+constexpr int FOCUS_FINISH_THREADS = 256; // lanes of the second launch's workgroup, one per plane
+constexpr int FOCUS_FINISH_TILE = 32;     // partial records that lie in its LDS at once
 
 constexpr int FOCUS_PEAK_I = 0, FOCUS_PEAK_INDEX = 1, FOCUS_MOM_I = 2, FOCUS_MOM_SZ = 8, FOCUS_CENTRE = 14, FOCUS_ENC = 16;
 constexpr int FOCUS_MOMENTS = 6;
@@ -58,6 +70,16 @@ inline int focus_chunks(long long P) {
     const long long c = focus_chunk_targets(P);
     return (int)((P + c - 1) / c);
 }
+
+// the tiles the second launch takes `chunks` partial records in, and the records of tile t of them
+ML_FOCUS_HD inline int focus_finish_tiles_of(int chunks) { return (chunks + FOCUS_FINISH_TILE - 1) / FOCUS_FINISH_TILE; }
+
+ML_FOCUS_HD inline int focus_finish_tile_chunks(int chunks, int t) {
+    const int left = chunks - t * FOCUS_FINISH_TILE;
+    return left < FOCUS_FINISH_TILE ? left : FOCUS_FINISH_TILE;
+}
+
+inline int focus_finish_tiles(long long P) { return focus_finish_tiles_of(focus_chunks(P)); }
 
 // What the entry knows of the active plan when it checks a call.
 struct FocusState {

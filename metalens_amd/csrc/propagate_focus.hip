@@ -240,8 +240,7 @@ __global__ __launch_bounds__(FOCUS_THREADS) void focus_chunk_kernel(const FocusA
 // per sum that adds them in their order waits for the LDS and not for a load from memory per chunk.
 // moments: the peak (of equals the lowest chunk, which holds the lowest index), the twelve sums and the centre - the
 // peak's (i, j), written to the centre buffer too, or the one the buffer holds; radii: the annuli, then accumulated
-constexpr int FOCUS_FINISH_THREADS = 256, FOCUS_FINISH_TILE = 32;
-
+// (FOCUS_FINISH_THREADS, FOCUS_FINISH_TILE and the tiles of a plane: propagate_focus.h)
 __global__ __launch_bounds__(FOCUS_FINISH_THREADS) void focus_finish_kernel(const double *partial, double *records, double *centre,
                                                                             int chunks, int my, int K, int rd, int moments,
                                                                             int radii, int centre_is_peak) {
@@ -254,8 +253,9 @@ __global__ __launch_bounds__(FOCUS_FINISH_THREADS) void focus_finish_kernel(cons
     const bool sum = (moments && tid >= FOCUS_MOM_I && tid < FOCUS_PARTIAL_ANNULI) ||
                      (radii && tid >= FOCUS_PARTIAL_ANNULI && tid < FOCUS_PARTIAL_ANNULI + 2 * K);
     double s = 0.0, bv = -INFINITY, bi = 0.0;
-    for (int c0 = 0; c0 < chunks; c0 += FOCUS_FINISH_TILE) {
-        const int n = min(FOCUS_FINISH_TILE, chunks - c0);
+    const int tiles = focus_finish_tiles_of(chunks);
+    for (int t = 0; t < tiles; ++t) {
+        const int c0 = t * FOCUS_FINISH_TILE, n = focus_finish_tile_chunks(chunks, t);
         __syncthreads();   // the previous tile has been added
         for (int f = tid; f < n * FOCUS_PARTIAL; f += FOCUS_FINISH_THREADS) (&s_tile[0][0])[f] = p[(size_t)c0 * FOCUS_PARTIAL + f];
         __syncthreads();

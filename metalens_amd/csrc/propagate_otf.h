@@ -63,7 +63,70 @@ ML_OTF_HD inline double otf_phase_fraction_naive(double u, double i) {
     return t - rint(t);
 }
 
-inline int otf_segments(int n) { return (n + OTF_SEGMENT - 1) / OTF_SEGMENT; }
+ML_OTF_HD inline int otf_segments(int n) { return (n + OTF_SEGMENT - 1) / OTF_SEGMENT; }
+
+// The launch shapes of the two passes (the kernels and launchers of propagate_otf.hip call these; tools/
+// propagate_otf_plan.cpp prints them).  The row pass takes a row in tiles of OTF_TILE targets whose weights lie in the
+// LDS at once - or, above OTF_FEW frequencies nv, OTF_ROWS_MANY rows in tiles of OTF_TILE / OTF_ROWS_MANY of each -, the
+// column pass takes the rows in tiles of OTF_TILE.  A tile is whole segments but for the last one of an axis, so the
+// tiles cut no segment and change no order.
+constexpr int OTF_TILE = 1024;                    // targets whose weights lie in the LDS at once
+constexpr int OTF_FEW = 8, OTF_ROWS_MANY = 4;     // above OTF_FEW frequencies nv a workgroup takes 4 rows
+constexpr int OTF_BATCH = 16;                     // frequencies whose segment sums lie in the LDS at once (four rows: 32)
+static_assert(OTF_TILE % (OTF_ROWS_MANY * OTF_SEGMENT) == 0, "whole segments per tile in either row kernel");
+
+ML_OTF_HD inline int otf_rows_per_group(int nv) { return nv <= OTF_FEW ? 1 : OTF_ROWS_MANY; }
+
+// tiles of `tile` indices that hold n, and the indices of tile t of them
+ML_OTF_HD inline int otf_tiles(int n, int tile) { return (n + tile - 1) / tile; }
+
+ML_OTF_HD inline int otf_tile_len(int n, int tile, int t) {
+    const int left = n - t * tile;
+    return left < tile ? left : tile;
+}
+
+// the live rows of workgroup g of the row pass (rows behind the plane's last are zeros, never written out)
+ML_OTF_HD inline int otf_live_rows(int mx, int rows, int g) { return otf_tile_len(mx, rows, g); }
+
+struct OtfRowsShape {
+    int rows;            // rows of a plane per workgroup: 1 or OTF_ROWS_MANY
+    int tile;            // targets of each row per tile
+    int tiles;           // tiles per row
+    int batch;           // frequencies per batch
+    int last_segments;   // segments of the last tile
+    int last_segment;    // indices of its last segment
+    int groups;          // workgroups along x
+    int last_rows;       // live rows of the last of them
+};
+
+inline OtfRowsShape otf_rows_shape(int mx, int my, int nv) {
+    OtfRowsShape s;
+    s.rows = otf_rows_per_group(nv);
+    s.tile = OTF_TILE / s.rows;
+    s.tiles = otf_tiles(my, s.tile);
+    s.batch = s.rows == 1 ? OTF_BATCH : 2 * OTF_BATCH;
+    const int last = otf_tile_len(my, s.tile, s.tiles - 1);
+    s.last_segments = otf_segments(last);
+    s.last_segment = last - (s.last_segments - 1) * OTF_SEGMENT;
+    s.groups = otf_tiles(mx, s.rows);
+    s.last_rows = otf_live_rows(mx, s.rows, s.groups - 1);
+    return s;
+}
+
+struct OtfColumnsShape {
+    int tiles;           // tiles of OTF_TILE rows
+    int last_segments;   // segments of the last tile
+    int last_segment;    // indices of its last segment
+};
+
+inline OtfColumnsShape otf_columns_shape(int mx) {
+    OtfColumnsShape s;
+    s.tiles = otf_tiles(mx, OTF_TILE);
+    const int last = otf_tile_len(mx, OTF_TILE, s.tiles - 1);
+    s.last_segments = otf_segments(last);
+    s.last_segment = last - (s.last_segments - 1) * OTF_SEGMENT;
+    return s;
+}
 
 // The argument checks of ml_propagate_otf.  -> 0; -1: an argument error, -2: the state does not allow the call; `why` is
 // filled then.  source >= 0: member of the last pass, -1: the sums.

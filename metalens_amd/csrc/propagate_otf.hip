@@ -34,11 +34,9 @@
 namespace ml {
 
 constexpr int OTF_THREADS = 256;
-constexpr int OTF_TILE = 1024;                              // targets of a row whose weights lie in the LDS at once
+// (OTF_TILE, OTF_BATCH, OTF_FEW, OTF_ROWS_MANY and the tiles they give: propagate_otf.h)
 constexpr int OTF_TILE_SEGS = OTF_TILE / OTF_SEGMENT;       // 32
 constexpr int OTF_SEG_PITCH = OTF_SEGMENT + 1;              // doubles between two segments' weights in the LDS
-constexpr int OTF_BATCH = 16;                               // frequencies whose segment sums lie in the LDS at once
-constexpr int OTF_FEW = 8, OTF_ROWS_MANY = 4;               // above OTF_FEW frequencies nv a workgroup takes 4 rows
 static_assert(OTF_FREQ_MAX * 4 <= OTF_THREADS, "a lane per (frequency, weight, component) keeps a running sum");
 static_assert(OTF_TILE % OTF_THREADS == 0 && OTF_TILE % OTF_SEGMENT == 0, "whole steps and whole segments per tile");
 
@@ -90,12 +88,13 @@ __global__ __launch_bounds__(OTF_THREADS) void otf_rows_kernel(const OtfRowArgs 
     __shared__ double s_part[TILE_SEGS][BATCH][ROWS][4];   // (re, im) with I, (re, im) with Sz
     __shared__ double s_run[ROWS][OTF_FREQ_MAX][4];
     const int tid = threadIdx.x, i0 = blockIdx.x * ROWS, plane = blockIdx.y;
-    const int rows = min(ROWS, a.mx - i0);
+    const int rows = otf_live_rows(a.mx, ROWS, blockIdx.x);
     const size_t row0 = ((size_t)plane * a.mx + i0) * a.my;   // the first row's first target
     const size_t T = (size_t)a.T;
     for (int e = tid; e < ROWS * OTF_FREQ_MAX * 4; e += OTF_THREADS) (&s_run[0][0][0])[e] = 0.0;
-    for (int t0 = 0; t0 < a.my; t0 += TILE) {
-        const int n = min(TILE, a.my - t0), segs = (n + OTF_SEGMENT - 1) / OTF_SEGMENT;
+    const int tiles = otf_tiles(a.my, TILE);
+    for (int tile = 0; tile < tiles; ++tile) {
+        const int t0 = tile * TILE, n = otf_tile_len(a.my, TILE, tile), segs = otf_segments(n);
         // the weights of the tile, once per target (a row behind the plane's last: zeros, never written out)
 #pragma unroll
         for (int k = 0; k < OTF_TILE / OTF_THREADS; ++k) {
@@ -174,11 +173,12 @@ __global__ __launch_bounds__(OTF_THREADS) void otf_rows_kernel(const OtfRowArgs 
 
 template <bool FIELDS, bool WANT_H>
 static void otf_rows_launch(hipStream_t stream, const OtfRowArgs &a) {
-    if (a.nv <= OTF_FEW)
-        hipLaunchKernelGGL((otf_rows_kernel<FIELDS, WANT_H, 1>), dim3(a.mx, a.planes), dim3(OTF_THREADS), 0, stream, a);
+    const int rows = otf_rows_per_group(a.nv);
+    const dim3 grid(otf_tiles(a.mx, rows), a.planes);
+    if (rows == 1)
+        hipLaunchKernelGGL((otf_rows_kernel<FIELDS, WANT_H, 1>), grid, dim3(OTF_THREADS), 0, stream, a);
     else
-        hipLaunchKernelGGL((otf_rows_kernel<FIELDS, WANT_H, OTF_ROWS_MANY>), dim3((a.mx + OTF_ROWS_MANY - 1) / OTF_ROWS_MANY, a.planes),
-                           dim3(OTF_THREADS), 0, stream, a);
+        hipLaunchKernelGGL((otf_rows_kernel<FIELDS, WANT_H, OTF_ROWS_MANY>), grid, dim3(OTF_THREADS), 0, stream, a);
 }
 
 // O_w[p][a][b] = sum_i Tx(i, a) R_w(p, i, b): a workgroup per (a, w, p), tiles of 1024 rows, a lane per (segment, b), then a
@@ -190,8 +190,9 @@ __global__ __launch_bounds__(OTF_THREADS) void otf_columns_kernel(const double2 
     const int tid = threadIdx.x, a = blockIdx.x, w = blockIdx.y, plane = blockIdx.z;
     const double2 *R = rows + ((size_t)w * planes + plane) * mx * nv;
     double run = 0.0;
-    for (int t0 = 0; t0 < mx; t0 += OTF_TILE) {
-        const int n = min(OTF_TILE, mx - t0), segs = (n + OTF_SEGMENT - 1) / OTF_SEGMENT;
+    const int tiles = otf_tiles(mx, OTF_TILE);
+    for (int tile = 0; tile < tiles; ++tile) {
+        const int t0 = tile * OTF_TILE, n = otf_tile_len(mx, OTF_TILE, tile), segs = otf_segments(n);
         for (int item = tid; item < segs * nv; item += OTF_THREADS) {
             const int s = item / nv, b = item - s * nv;
             const int i0 = t0 + s * OTF_SEGMENT, cnt = min(OTF_SEGMENT, n - s * OTF_SEGMENT);

@@ -15,7 +15,7 @@ import math
 import numpy as np
 
 U = 2.0 ** -53
-RADII_MAX, CHUNK_MIN, CHUNKS_MAX, STEP = 32, 1024, 1024, 512        # csrc/propagate_focus.h
+RADII_MAX, CHUNK_MIN, CHUNKS_MAX, STEP, FINISH_TILE = 32, 1024, 1024, 512, 32        # csrc/propagate_focus.h
 PEAK_I, PEAK_INDEX, MOM_I, MOM_SZ, CENTRE, ENC, PARTIAL = 0, 1, 2, 8, 14, 16, 14 + 2 * 32
 
 
@@ -37,6 +37,14 @@ def plan(mx, my, K):
     chunks = -(-P // c)
     return dict(mx=mx, my=my, P=P, chunk=c, chunks=chunks, steps=c // STEP, last=P - (chunks - 1) * c,
                 record_doubles=record_doubles(K), partial_doubles=PARTIAL)
+
+
+def finish(mx, my):
+    """the tiles of the second launch, which takes the chunks' partial records 32 at a time (focus_finish_tiles): what
+    ``propagate_focus_plan finish`` prints"""
+    chunks = plan(mx, my, 0)['chunks']
+    tiles = -(-chunks // FINISH_TILE)
+    return dict(mx=mx, my=my, chunks=chunks, finish_tile=FINISH_TILE, finish_tiles=tiles, last_tile=chunks - (tiles - 1) * FINISH_TILE)
 
 
 def weights(d, want_h):

@@ -22,6 +22,28 @@ import numpy as np
 
 U = 2.0 ** -53
 FREQ_MAX, SEGMENT = 64, 32        # csrc/propagate_otf.h
+TILE, FEW, ROWS_MANY, BATCH = 1024, 8, 4, 16
+
+
+def _last(n, tile):
+    """n indices in tiles of ``tile``: -> tiles, segments of the last tile, indices of its last segment"""
+    tiles = -(-n // tile)
+    last = n - (tiles - 1) * tile
+    segments = -(-last // SEGMENT)
+    return tiles, segments, last - (segments - 1) * SEGMENT
+
+
+def plan(mx, my, nv):
+    """the launch shapes of the row and the column pass (otf_rows_shape, otf_columns_shape): what ``propagate_otf_plan shape``
+    prints"""
+    rows = 1 if nv <= FEW else ROWS_MANY
+    tile = TILE // rows
+    tiles, last_segments, last_segment = _last(my, tile)
+    groups = -(-mx // rows)
+    col_tiles, col_last_segments, col_last_segment = _last(mx, TILE)
+    return dict(rows=rows, tile=tile, tiles=tiles, batch=BATCH if rows == 1 else 2 * BATCH, last_segments=last_segments,
+                last_segment=last_segment, groups=groups, last_rows=mx - (groups - 1) * rows, col_tile=TILE, col_tiles=col_tiles,
+                col_last_segments=col_last_segments, col_last_segment=col_last_segment)
 
 
 def _over_power_of_two(freqs):

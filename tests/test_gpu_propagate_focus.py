@@ -68,22 +68,24 @@ def _wave():
     return x, y, f, (Ex, Ey, -Ey / Z, Ex / Z)
 
 
-def _make(ma, ctx, name, F=None, method=None, z=None):
-    """upload the wave (or F), plan the case -> the propagator; its axis targets lie on the wave's axis"""
+def _make(ma, ctx, name, F=None, method=None, z=None, case=None, peak_at=None):
+    """upload the wave (or F), plan the case -> the propagator; target ``peak_at`` (default: the middle one, (mx // 2,
+    my // 2)) lies on the wave's axis.  ``case``: (method, mx, my, want_h) in place of ``CASES[name]``"""
     from test_gpu_fft_mixed import _upload
     from metalens_amd import _lib
     x, y, f, wave = _wave()
-    case_method, mx, my, want_h = CASES[name]
+    case_method, mx, my, want_h = CASES[name] if case is None else case
+    pi, pj = (mx // 2, my // 2) if peak_at is None else peak_at
     _upload(ctx, [_lib.c128(a) for a in (wave if F is None else F)])
     ctx.fields_owner = None
     if case_method == 'fft-stack':
-        tx, ty = fine_ref.fine_axis(x, (NX - 1) / 2 - 3, mx, 2), fine_ref.fine_axis(y, (NY - 1) / 2 - 2.5, my, 2)
+        tx, ty = fine_ref.fine_axis(x, (NX - 1) / 2 - pi / 2, mx, 2), fine_ref.fine_axis(y, (NY - 1) / 2 - pj / 2, my, 2)
         planes = f + np.array([-1.0, 0.0, 1.5]) * WL / N_GLASS
         more = dict(subsample=(2, 2))
         if method == 'fft-fine':
             planes = planes[z]
     else:
-        tx, ty = gref.target_axis(x, (NX - 1) / 2 - mx // 2, mx), gref.target_axis(y, (NY - 1) / 2 - my // 2, my)
+        tx, ty = gref.target_axis(x, (NX - 1) / 2 - pi, mx), gref.target_axis(y, (NY - 1) / 2 - pj, my)
         planes, more = f, {}
     return ma.PlanePropagator(x, y, WL, N_GLASS, tx, ty, planes, want_h=want_h, ctx=ctx, method=method or case_method, **more)
 
@@ -451,6 +453,15 @@ def test_through_the_sweep(ma, ctx):
     # a given centre, in the caller's frame
     given = sw.run(sources, weights=weights, image=p, image_radii=radii, image_centre=(tx[9], ty[8]))
     assert np.array_equal(given['image_focus']['centre_index'], [[9.0, 8.0]])
+    # ... and the record behind it - moments and radii of the sums in one pass about a given centre - against the yardstick
+    # on the returned maps
+    rec = _raw(p, np.sort(radii), (9.0, 8.0), source=-1)
+    want = fref.record(given['I_sum'], given['Sz_sum'], dx, dy, np.sort(radii), centre=(9.0, 8.0))
+    assert len(set(want['n_inside'])) == 4 and want['n_inside'][0] == 1          # whole discs about target (9, 8)
+    _check_peak(rec[0], given['I_sum'], from_sums=True)
+    print('PARITY focus sweep sums, given centre: worst error / bound %.4f' % _check_record(rec[0], want, 4, True, from_sums=True))
+    assert np.array_equal(given['image_focus']['encircled_P'][0], rec[0, fref.ENC + 4:fref.ENC + 8][[1, 0, 3, 2]] * dx * dy)
+    assert np.array_equal(given['image_focus']['encircled_I'][0], rec[0, fref.ENC:fref.ENC + 4][[1, 0, 3, 2]] * dx * dy)
 
 
 # ---- the example ----------------------------------------------------------------------------------------------

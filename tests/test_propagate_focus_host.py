@@ -101,6 +101,27 @@ def test_plan_of_the_shapes(tool):
     assert fref.plan(30, 50, 4)['chunk'] == fref.plan(50, 30, 4)['chunk']
 
 
+# mx, my: planes around the tiles of 32 partial records of the second launch - 1, 5, 32, 33, 64, 65, 513, 1024 chunks
+FINISH_SHAPES = [(21, 17), (70, 61), (128, 256), (182, 181), (256, 256), (65, 1024), (1025, 1024), (4096, 4096), (8192, 8192), (1, 1)]
+
+
+def test_finish_tiles_of_the_shapes(tool):
+    """focus_finish_tiles and focus_finish_tile_chunks - what focus_finish_kernel calls - against the Python restatement"""
+    lines = tool('finish', *[v for s in FINISH_SHAPES for v in s]).splitlines()
+    assert len(lines) == len(FINISH_SHAPES)
+    tiles = {}
+    for (mx, my), line in zip(FINISH_SHAPES, lines):
+        want = fref.finish(mx, my)
+        assert _facts(line) == want, (mx, my)
+        assert want['chunks'] == fref.plan(mx, my, 0)['chunks'] and want['finish_tile'] == fref.FINISH_TILE == 32
+        # the tiles cover the chunks: full tiles of 32 records and a last one of 1 ... 32
+        assert 1 <= want['last_tile'] <= fref.FINISH_TILE and (want['finish_tiles'] - 1) * fref.FINISH_TILE + want['last_tile'] == want['chunks']
+        tiles[(mx, my)] = (want['chunks'], want['finish_tiles'], want['last_tile'])
+    assert tiles[(128, 256)] == (32, 1, 32) and tiles[(182, 181)] == (33, 2, 1) and tiles[(256, 256)] == (64, 2, 32)
+    assert tiles[(65, 1024)] == (65, 3, 1) and tiles[(21, 17)] == (1, 1, 1) and tiles[(4096, 4096)] == (1024, 32, 32)
+    assert tiles[(1025, 1024)] == (513, 17, 1) and tiles[(70, 61)] == (5, 1, 5) and tiles[(8192, 8192)] == (1024, 32, 32)
+
+
 def test_record_layout(tool):
     for K in (0, 5, 32):
         f = _facts(tool('layout', K))
@@ -147,6 +168,8 @@ def test_under_sanitizers(tool):
     shapes = [v for s in SHAPES for v in s]
     assert tool(*shapes, exe='propagate_focus_plan_san') == tool(*shapes)
     assert tool('layout', 32, exe='propagate_focus_plan_san') == tool('layout', 32)
+    finish = [v for s in FINISH_SHAPES for v in s]
+    assert tool('finish', *finish, exe='propagate_focus_plan_san') == tool('finish', *finish)
     for args, code, said in REFUSALS:
         assert tool('check', *args, exe='propagate_focus_plan_san') == tool('check', *args)
 

@@ -166,8 +166,44 @@ def test_refusals_name_the_numbers(tool):
     assert (oref.FREQ_MAX, oref.SEGMENT) == (64, 32)
 
 
+# mx, my, nv: the shapes of tests/test_gpu_propagate_otf.py, rows and columns either side of a tile of 1024 (256 for four
+# rows), the frequencies either side of the two row kernels, live rows 1 to 4 of the last workgroup
+LAUNCH_SHAPES = [(21, 17, 1), (21, 17, 64), (70, 61, 8), (70, 61, 9), (13, 11, 64), (3, 1100, 7), (3, 1100, 8), (3, 1100, 33),
+                 (3, 1100, 64), (1100, 3, 1), (1100, 3, 64), (5, 300, 64), (6, 256, 9), (7, 257, 9), (8, 1024, 8), (8, 1025, 8),
+                 (1024, 1, 1), (1025, 1, 1), (2048, 32, 16), (4096, 4096, 64), (1, 1, 1)]
+
+
+def _shape(tool, mx, my, nv, exe='propagate_otf_plan'):
+    return {k: int(v) for k, v in (kv.split('=') for kv in tool('shape', mx, my, nv, exe=exe).split())}
+
+
+def test_launch_shapes(tool):
+    """otf_rows_shape and otf_columns_shape - what the kernels and launchers of propagate_otf.hip call - against the Python
+    restatement, and the cover they promise: whole tiles and a last one, whole segments and a last one"""
+    for mx, my, nv in LAUNCH_SHAPES:
+        got = _shape(tool, mx, my, nv)
+        assert got == oref.plan(mx, my, nv), (mx, my, nv)
+        assert got['rows'] == (1 if nv <= 8 else 4) and got['rows'] * got['tile'] == got['col_tile'] == 1024
+        assert got['batch'] == 16 * (1 if got['rows'] == 1 else 2) and oref.FREQ_MAX % got['batch'] == 0
+        assert got['tile'] % oref.SEGMENT == 0          # a tile cuts no segment
+        for n, tile, tiles, segs, seg in ((my, got['tile'], got['tiles'], got['last_segments'], got['last_segment']),
+                                          (mx, 1024, got['col_tiles'], got['col_last_segments'], got['col_last_segment'])):
+            assert 1 <= seg <= oref.SEGMENT and 1 <= segs <= tile // oref.SEGMENT
+            assert (tiles - 1) * tile + (segs - 1) * oref.SEGMENT + seg == n
+        assert 1 <= got['last_rows'] <= got['rows'] and (got['groups'] - 1) * got['rows'] + got['last_rows'] == mx
+    s = oref.plan(3, 1100, 7)
+    assert (s['tiles'], s['last_segments'], s['last_segment'], s['groups'], s['last_rows']) == (2, 3, 12, 3, 1)
+    s = oref.plan(3, 1100, 64)
+    assert (s['tile'], s['tiles'], s['last_segments'], s['last_segment'], s['groups'], s['last_rows']) == (256, 5, 3, 12, 1, 3)
+    s = oref.plan(1100, 3, 64)
+    assert (s['col_tiles'], s['col_last_segments'], s['col_last_segment'], s['groups'], s['last_rows']) == (2, 3, 12, 275, 4)
+    assert {oref.plan(mx, 17, 9)['last_rows'] for mx in (13, 21, 70, 3)} == {1, 2, 3}          # 13 and 21 leave one row, 70 two
+
+
 def test_under_sanitizers(tool):
     """the same program under the address and undefined-behaviour sanitizers: same output, nothing reported"""
+    for mx, my, nv in LAUNCH_SHAPES:
+        assert tool('shape', mx, my, nv, exe='propagate_otf_plan_san') == tool('shape', mx, my, nv)
     for more, code, said in REFUSALS:
         assert tool(*_check_args(**more), exe='propagate_otf_plan_san') == tool(*_check_args(**more))
     for more in ACCEPTED:

@@ -3,6 +3,9 @@
 //        -> per shape a line  mx=... my=... P=... chunk=... chunks=... steps=... last=... record_doubles=... partial_doubles=...
 //           (chunk: targets per chunk; steps: steps of 512 targets a workgroup takes in a full chunk; last: targets of the
 //           plane's last chunk)
+//   propagate_focus_plan finish mx my [mx my ...]
+//        -> per shape a line  mx=... my=... chunks=... finish_tile=... finish_tiles=... last_tile=...
+//           (of the second launch: partial records per tile, tiles, records of the last tile)
 //   propagate_focus_plan layout n_radii
 //        -> peak_i=... peak_index=... mom_i=... mom_sz=... centre=... enc_i=... enc_sz=... record_doubles=... radii_max=...
 //   propagate_focus_plan check have_result have_sums T sets source mx my planes dx dy record_doubles centre [radius ...]
@@ -25,6 +28,20 @@ int main(int argc, char **argv) {
         printf("peak_i=%d peak_index=%d mom_i=%d mom_sz=%d centre=%d enc_i=%d enc_sz=%d record_doubles=%d radii_max=%d\n",
                FOCUS_PEAK_I, FOCUS_PEAK_INDEX, FOCUS_MOM_I, FOCUS_MOM_SZ, FOCUS_CENTRE, FOCUS_ENC, FOCUS_ENC + K,
                focus_record_doubles(K), FOCUS_RADII_MAX);
+        return 0;
+    }
+    if (argc >= 4 && argc % 2 == 0 && !strcmp(argv[1], "finish")) {
+        for (int i = 2; i + 1 < argc; i += 2) {
+            const int mx = atoi(argv[i]), my = atoi(argv[i + 1]);
+            if (mx < 1 || my < 1 || (long long)mx * my > (1 << 26)) {
+                fprintf(stderr, "finish: mx, my >= 1, mx my <= 2^26\n");
+                return 2;
+            }
+            const long long P = (long long)mx * my;
+            const int chunks = focus_chunks(P), tiles = focus_finish_tiles(P);
+            printf("mx=%d my=%d chunks=%d finish_tile=%d finish_tiles=%d last_tile=%d\n", mx, my, chunks, FOCUS_FINISH_TILE, tiles,
+                   focus_finish_tile_chunks(chunks, tiles - 1));
+        }
         return 0;
     }
     if (argc >= 14 && !strcmp(argv[1], "check")) {
@@ -59,7 +76,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc < 4 || (argc - 1) % 3 != 0) {
-        fprintf(stderr, "usage: propagate_focus_plan mx my n_radii [...] | layout n_radii | check have_result have_sums T sets "
+        fprintf(stderr, "usage: propagate_focus_plan mx my n_radii [...] | finish mx my [...] | layout n_radii | check have_result have_sums T sets "
                         "source mx my planes dx dy record_doubles centre [radius ...]\n");
         return 2;
     }

@@ -6,6 +6,12 @@
 //   propagate_otf_plan plan mx my planes nu nv
 //        -> table=... rows=... segments_x=... segments_y=... segment=... freq_max=...  (phasors tabulated, row sums per
 //           weight, segments of 32 indices along either axis)
+//   propagate_otf_plan shape mx my nv
+//        -> rows=... tile=... tiles=... batch=... last_segments=... last_segment=... groups=... last_rows=... col_tile=...
+//           col_tiles=... col_last_segments=... col_last_segment=...  (the row pass: rows of a plane per workgroup, targets
+//           of each per tile, tiles per row, frequencies per batch, segments of the last tile and indices of its last
+//           segment, workgroups along x and live rows of the last; the column pass: rows per tile, tiles, the last tile's
+//           segments and the indices of its last segment)
 //   propagate_otf_plan check have_result have_sums T sets source mx my planes null nu nv ku kv [u ... v ...]
 //        -> ok=1, or refused=-1 (an argument) / refused=-2 (the state) followed by the message on a line of its own;
 //           null: 1 = u is NULL, 2 = v, 4 = otf (added up); ku and kv values follow, nu and nv are what the call claims
@@ -36,6 +42,19 @@ int main(int argc, char **argv) {
                (long long)planes * mx * nv, otf_segments(mx), otf_segments(my), OTF_SEGMENT, OTF_FREQ_MAX);
         return 0;
     }
+    if (argc == 5 && !strcmp(argv[1], "shape")) {
+        const int mx = atoi(argv[2]), my = atoi(argv[3]), nv = atoi(argv[4]);
+        if (mx < 1 || my < 1 || nv < 1 || nv > OTF_FREQ_MAX) {
+            fprintf(stderr, "shape: mx, my >= 1, 1 <= nv <= %d\n", OTF_FREQ_MAX);
+            return 2;
+        }
+        const OtfRowsShape r = otf_rows_shape(mx, my, nv);
+        const OtfColumnsShape c = otf_columns_shape(mx);
+        printf("rows=%d tile=%d tiles=%d batch=%d last_segments=%d last_segment=%d groups=%d last_rows=%d col_tile=%d col_tiles=%d "
+               "col_last_segments=%d col_last_segment=%d\n", r.rows, r.tile, r.tiles, r.batch, r.last_segments, r.last_segment,
+               r.groups, r.last_rows, OTF_TILE, c.tiles, c.last_segments, c.last_segment);
+        return 0;
+    }
     if (argc >= 15 && !strcmp(argv[1], "check")) {
         FocusState s;
         s.have_result = atoi(argv[2]) != 0;
@@ -63,7 +82,7 @@ int main(int argc, char **argv) {
             printf("ok=1\n");
         return 0;
     }
-    fprintf(stderr, "usage: propagate_otf_plan fraction u i [...] | plan mx my planes nu nv | check have_result have_sums T sets source "
+    fprintf(stderr, "usage: propagate_otf_plan fraction u i [...] | plan mx my planes nu nv | shape mx my nv | check have_result have_sums T sets source "
                     "mx my planes null nu nv ku kv [u ... v ...]\n");
     return 2;
 }
