@@ -427,6 +427,18 @@ int ml_nearfield_result(ml_ctx *ctx, double *power, ml_bound_violation *violatio
  * Any pointer may be NULL.                                                                       */
 int ml_nearfield_kernel_info(ml_ctx *ctx, int *family, int *ring_orders_max, int *centre_orders);
 
+/* Which FORM of the family-1 kernels the last synthesis launched (after a batch of members at different
+ * positions: for its last member).  Tables of exactly three present order slots on uniform axes, lit by one
+ * dipole without premodulation, have fixed-shape kernels for the steady-state launch from the patch lists;
+ * their results are bit-identical to the general form's, which takes every other launch - the first
+ * synthesis into a buffer, polarisation batches, plane waves, any other table.  METALENS_HIP_FIXED_SYNTH=0
+ * in the environment (read once per process) keeps the general form for every call.
+ *   *ring_form     the ring samples of collections of up to four order slots: 0 no such launch, 1 general,
+ *                  2 fixed-shape
+ *   *centre_form   the centre samples, likewise
+ * Either pointer may be NULL.                                                                    */
+int ml_nearfield_synth_info(ml_ctx *ctx, int *ring_form, int *centre_form);
+
 /* ---- propagation to points at finite distance ---------------------------------------------
  * The field at targets r = (x, y, z), z > 0, behind the aperture plane z = 0: the Stratton-Chu / Franz
  * sum over the equivalent currents of the SELECTED resident field set (ml_fields_select),

@@ -52,7 +52,7 @@ SYMBOLS = (
     'ml_propagate_plan_grid_long', 'ml_propagate_plan_grid_tiled', 'ml_propagate_plan_tiles',
     'ml_propagate_plan_grid_fine', 'ml_propagate_plan_lattices', 'ml_math_probe',
     'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes', 'ml_propagate_focus',
-    'ml_propagate_otf',
+    'ml_propagate_otf', 'ml_nearfield_synth_info',
 )
 
 
@@ -159,6 +159,8 @@ def load():
         lib.ml_comm_set_max_channels.argtypes = [c_void_p, c_int]
     if hasattr(lib, 'ml_nearfield_kernel_info'):
         lib.ml_nearfield_kernel_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
+    if hasattr(lib, 'ml_nearfield_synth_info'):
+        lib.ml_nearfield_synth_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int)]
     lib.ml_propagate_plan.argtypes = [c_void_p, c_double, c_double, c_double, c_double, c_double, c_double,
                                       _dp, c_int, _dp, c_int, _dp, c_int, c_int, c_int]
     lib.ml_propagate.argtypes = [c_void_p, c_double]
@@ -391,6 +393,17 @@ class Context:
         check(self.lib.ml_nearfield_kernel_info(self.handle, byref(fam), byref(ring), byref(cen)))
         return {'family': ('general', 'orders-along-x', 'mixed')[fam.value], 'ring_orders_max': ring.value,
                 'centre_orders': cen.value}
+
+    def synth_forms(self):
+        """which form of the ring kernel (narrow collections) and of the centre kernel the last synthesis launched:
+        {'ring': None (no such launch), 'general' or 'fixed3' (the fixed-shape kernels of three-order tables,
+        bit-identical to the general ones; METALENS_HIP_FIXED_SYNTH=0 turns them off), 'centre': likewise}"""
+        if not hasattr(self.lib, 'ml_nearfield_synth_info'):   # (A/B runs against an older build)
+            return {'ring': 'unknown', 'centre': 'unknown'}
+        ring, cen = c_int(0), c_int(0)
+        check(self.lib.ml_nearfield_synth_info(self.handle, byref(ring), byref(cen)))
+        names = (None, 'general', 'fixed3')
+        return {'ring': names[ring.value], 'centre': names[cen.value]}
 
     def profile(self, on=True, kernels=None, every=1):
         """time kernel launches with HIP events; ``kernels`` = names to time (default all),

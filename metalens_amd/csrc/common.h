@@ -445,6 +445,9 @@ struct SynthOut {
     // the projection kernel does it in a spare block, ml_nearfield_result otherwise
     bool power_pending = false;
     int n_partials = 0;
+    // which instantiation the last synthesis launched for the ring samples of narrow collections and for the centre
+    // samples (ml_nearfield_synth_info): 0 none, 1 general, 2 fixed-shape (nearfield_simple.hip FIXED3)
+    int ring_form = 0, centre_form = 0;
 };
 
 }  // namespace ml

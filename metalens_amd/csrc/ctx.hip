@@ -608,6 +608,13 @@ int ml_nearfield_kernel_info(ml_ctx *ctx, int *family, int *ring_orders_max, int
     return ML_OK;
 }
 
+int ml_nearfield_synth_info(ml_ctx *ctx, int *ring_form, int *centre_form) {
+    ML_REQUIRE(ctx, "ctx is NULL");
+    if (ring_form) *ring_form = ctx->out.ring_form;
+    if (centre_form) *centre_form = ctx->out.centre_form;
+    return ML_OK;
+}
+
 int ml_nearfield(ml_ctx *ctx, const ml_nearfield_params *p, const double *x_pts, int nx,
                  const double *y_pts, int ny, double *power, ml_bound_violation *violations,
                  int max_violations, int *n_violations) {

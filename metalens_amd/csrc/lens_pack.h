@@ -320,6 +320,43 @@ inline LensClass classify_lens(const HostTable *const *colls, int n_colls, const
     return K;
 }
 
+// The FIXED-SHAPE synthesis kernels (nearfield_simple.hip, FIXED3): the narrow ring instantiation and the centre kernel
+// compiled for tables of exactly three present order slots on uniform axes - the three-order tables of SURVEY.md 8(d),
+// the outer collections of a real lens - lit by one dipole.  Same arithmetic in the same order as the general
+// instantiations, which keep everything else; which one a launch takes is decided here, from facts alone.
+struct Fixed3Facts {
+    const CollDesc *coll;   // the lens' dense collections (RingTables::coll)
+    int narrow_mask;        // LensClass::narrow_mask: the collections of the narrow ring instantiation
+    int center_n_slots, center_present, center_uniform;   // centre table: CentreSlots, TableDesc::uniform (0, 0, 0: none)
+    // the launch
+    int n_pol;              // members of the polarisation batch
+    int use_active, first_pass;   // from the patch lists with their lengths known on the host; the first synthesis into a buffer
+    int plane_wave, premod;       // the source is a plane wave; the fields are stored premodulated
+};
+struct Fixed3 {
+    bool ring = false, centre = false;   // the ring launch over list 1, the centre launch over list 2
+};
+// the lens' part: what its tables allow
+inline Fixed3 fixed3_lens(const Fixed3Facts &f) {
+    Fixed3 t;
+    t.ring = f.narrow_mask != 0;
+    for (int c = 0; c < MAX_RING_COLLS; ++c)
+        if ((f.narrow_mask >> c) & 1)
+            t.ring = t.ring && f.coll[c].n_slots == 3 && f.coll[c].present == 7 && (f.coll[c].flags & 1) != 0;
+    // (ox_lo may differ between the collections: it stays a wave-uniform scalar of the kernel)
+    t.centre = f.center_n_slots == 3 && f.center_present == 7 && f.center_uniform != 0;
+    return t;
+}
+inline Fixed3 fixed3_takes(const Fixed3Facts &f) {
+    Fixed3 t = fixed3_lens(f);
+    const bool launch = f.n_pol == 1 && f.use_active && !f.first_pass && !f.plane_wave && !f.premod;
+    t.ring = t.ring && launch;
+    t.centre = t.centre && launch;
+    return t;
+}
+// (three slots per collection: the narrow instantiation's pitch and capacity are then synth_staging.h's
+// narrow_pitch(3) = 49 and narrow_cap(49) = 8, asserted where the kernel names them)
+
 // the collections the rings use, numbered densely in slot order: what the geometry records
 // carry and the field kernel's CollDesc array is indexed by
 struct DenseColls {

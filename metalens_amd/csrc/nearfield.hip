@@ -222,6 +222,15 @@ void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int 
                         pl.fold_y.has_E && pl.ny == ny;
     a.premod = premod ? pl.fold_y.E.as<double2>() : nullptr;
     ctx->fields.premod_serial = premod ? pl.serial : -1;
+    // Three-order tables on uniform axes lit by one dipole have kernels of their own with the same arithmetic
+    // (nearfield_simple.hip FIXED3; lens_pack.h fixed3_takes): what a listed steady-state launch of these arguments
+    // may take - bit 0 the ring launch, bit 1 the centre launch; the launch code knows whether it is one.
+    // METALENS_HIP_FIXED_SYNTH=0 in the environment, read once: the general kernels for every call
+    static const bool fixed_off = [] { const char *e = getenv("METALENS_HIP_FIXED_SYNTH"); return e && e[0] == '0'; }();
+    const Fixed3Facts facts = {a.coll, a.narrow_mask, a.center_n_slots, a.center_present, a.center_desc.uniform,
+                               n, 1, 0, a.p.plane_wave, a.premod != nullptr};
+    const Fixed3 fixed = fixed3_takes(facts);
+    a.fixed3 = fixed_off ? 0 : (fixed.ring ? 1 : 0) | (fixed.centre ? 2 : 0);
 }
 
 // ---- the steps of a synthesis (nearfield_launch), each named for what it ensures; synth_caches.h says what each
@@ -355,6 +364,7 @@ int nearfield_launch(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, i
         }
     }
     int n_partials = 0;
+    ctx->out.ring_form = ctx->out.centre_form = 0;   // (set by the launch code of the kernels that have two forms)
     ML_TRY(launch_members(ctx, p, n, members_alone, a, &n_partials));
     ctx->caches.zeros.set(zeros.v);
     ML_HIP(hipGetLastError());

@@ -116,6 +116,9 @@ struct NfArgs {
     int general_mask, centre_general;
     int narrow_pitch, narrow_cap;   // narrow ring instantiation: complex between staged blocks (16 x its widest collection's orders + 1), blocks per round
     int center_n_slots, center_lo, center_present;   // centre table, simple order sets: as CollDesc::n_slots / ox_lo / present
+    // a listed steady-state launch of these arguments takes the fixed-shape kernels of three-order tables: bit 0 the
+    // ring launch, bit 1 the centre launch (lens_pack.h fixed3_takes; read by the launch code, not by a kernel)
+    int fixed3;
     // the (ux', uy') range every ring table covers (intersection of their bounds: lo0, hi0, lo1, hi1);
     // a sample inside it cannot trip a table bound, and only the others read their ring's own bounds
     double ring_bounds_all[4];

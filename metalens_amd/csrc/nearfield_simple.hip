@@ -76,6 +76,9 @@ struct Consts {
     int plane_wave, patches_x, n_rings, outside_is_zero, nx, ny, n_partials;
     double hcoef, pcoef, pol[3];   // member 0 of the batch (what a single source reads)
 };
+// FIXED3 (the fixed-shape kernels, below): a dipole and no premodulation by construction - two scalars fewer to pin,
+// and every test of them folds
+template <bool FIXED3>
 __device__ __forceinline__ void load_consts(const NfArgs &a, Consts &K) {
     K.kvac = a.p.kvac;
     K.kvac2 = a.p.kvac2;
@@ -89,12 +92,12 @@ __device__ __forceinline__ void load_consts(const NfArgs &a, Consts &K) {
     K.ring_rec = (const ML_GLOBAL double2 *)a.ring_rec;
     K.rot_table = (const ML_GLOBAL double2 *)a.rot_table;
     K.ring_tab = (const ML_GLOBAL double2 *)a.ring_tab;
-    K.plane_wave = a.p.plane_wave;
+    K.plane_wave = FIXED3 ? 0 : a.p.plane_wave;
     K.b0 = a.ring_bounds_all[0];
     K.b1 = a.ring_bounds_all[1];
     K.b2 = a.ring_bounds_all[2];
     K.b3 = a.ring_bounds_all[3];
-    K.premod = (const ML_GLOBAL double2 *)a.premod;
+    K.premod = FIXED3 ? nullptr : (const ML_GLOBAL double2 *)a.premod;
     K.geo_ix = (const ML_GLOBAL int2 *)a.geo_ix;
     K.fields = (ML_GLOBAL double *)a.fields;
     K.patches_x = a.patches_x;
@@ -102,8 +105,12 @@ __device__ __forceinline__ void load_consts(const NfArgs &a, Consts &K) {
     K.outside_is_zero = a.outside_is_zero;
     K.nx = a.nx;
     K.ny = a.ny;
-    asm volatile("" : "+s"(K.kvac), "+s"(K.kvac2), "+s"(K.kg2), "+s"(K.efh), "+s"(K.sx), "+s"(K.sy), "+s"(K.dz), "+s"(K.dz2),
-                 "+s"(K.z2), "+s"(K.ring_rec), "+s"(K.rot_table), "+s"(K.ring_tab), "+s"(K.plane_wave));
+    if (FIXED3)
+        asm volatile("" : "+s"(K.kvac), "+s"(K.kvac2), "+s"(K.kg2), "+s"(K.efh), "+s"(K.sx), "+s"(K.sy), "+s"(K.dz), "+s"(K.dz2),
+                     "+s"(K.z2), "+s"(K.ring_rec), "+s"(K.rot_table), "+s"(K.ring_tab));
+    else
+        asm volatile("" : "+s"(K.kvac), "+s"(K.kvac2), "+s"(K.kg2), "+s"(K.efh), "+s"(K.sx), "+s"(K.sy), "+s"(K.dz), "+s"(K.dz2),
+                     "+s"(K.z2), "+s"(K.ring_rec), "+s"(K.rot_table), "+s"(K.ring_tab), "+s"(K.plane_wave));
     K.partial_power = (ML_GLOBAL double *)a.partial_power;
     K.n_partials = a.n_partials;
     K.hcoef = a.hcoef[0];
@@ -111,8 +118,12 @@ __device__ __forceinline__ void load_consts(const NfArgs &a, Consts &K) {
     K.pol[0] = a.pol[0][0];
     K.pol[1] = a.pol[0][1];
     K.pol[2] = a.pol[0][2];
-    asm volatile("" : "+s"(K.b0), "+s"(K.b1), "+s"(K.b2), "+s"(K.b3), "+s"(K.premod), "+s"(K.geo_ix), "+s"(K.fields),
-                 "+s"(K.patches_x), "+s"(K.n_rings), "+s"(K.outside_is_zero), "+s"(K.nx), "+s"(K.ny));
+    if (FIXED3)
+        asm volatile("" : "+s"(K.b0), "+s"(K.b1), "+s"(K.b2), "+s"(K.b3), "+s"(K.geo_ix), "+s"(K.fields),
+                     "+s"(K.patches_x), "+s"(K.n_rings), "+s"(K.outside_is_zero), "+s"(K.nx), "+s"(K.ny));
+    else
+        asm volatile("" : "+s"(K.b0), "+s"(K.b1), "+s"(K.b2), "+s"(K.b3), "+s"(K.premod), "+s"(K.geo_ix), "+s"(K.fields),
+                     "+s"(K.patches_x), "+s"(K.n_rings), "+s"(K.outside_is_zero), "+s"(K.nx), "+s"(K.ny));
     asm volatile("" : "+s"(K.partial_power), "+s"(K.n_partials), "+s"(K.hcoef), "+s"(K.pcoef), "+s"(K.pol[0]), "+s"(K.pol[1]),
                  "+s"(K.pol[2]));
 }
@@ -416,13 +427,23 @@ enum { PART_RING = 1, PART_CENTRE = 2 };
 #define ML_NF_KEEP_ROT 0
 #endif
 
-template <int NP, int PART, bool LISTED, bool WIDE>
+// FIXED3: the FIXED-SHAPE form of the listed single-source kernels for what the flagship lens and the outer, narrow
+// collections of a real lens hold - every narrow collection (ring kernel), the centre table (centre kernel) exactly
+// three present order slots on uniform axes, the source one dipole, no premodulation (lens_pack.h fixed3_takes decides
+// on the host).  Slot count, presence mask, LDS pitch (49) and capacity (8), the staging lane bound and the source kind
+// are constants then, the order loop three straight-line slots; the lowest order of a collection stays a wave-uniform
+// scalar.  The arithmetic and its order are the general instantiation's, so the result is bit-identical.
+constexpr int FIXED3_SLOTS = 3, FIXED3_PRESENT = 7;
+static_assert(narrow_pitch(FIXED3_SLOTS) == 49 && narrow_cap(narrow_pitch(FIXED3_SLOTS)) == SK_SLOTS_NARROW && FIXED3_SLOTS * UNIT == 48,
+              "the fixed-shape ring kernel's pitch, capacity and staging lanes");
+template <int NP, int PART, bool LISTED, bool WIDE, bool FIXED3 = false>
 __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab, double2 *s_tab1, int bx, int by) {
+    static_assert(!FIXED3 || (NP == 1 && LISTED && !WIDE), "fixed-shape kernels: one source, from the lists, narrow");
     const int lane = threadIdx.x;
     const unsigned lane_off = (unsigned)lane * 16u;
     ML_PRIO_AT(0, 3);
     Consts K;
-    load_consts(a, K);
+    load_consts<FIXED3>(a, K);
     const int i = by * 8 + (lane >> 3);   // x index
     const int j = bx * 8 + (lane & 7);    // y index (fastest in memory)
     const bool inb = j < K.ny && i < K.nx;
@@ -499,7 +520,7 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     // - the narrow one if the lens has narrow collections - runs over the whole grid and does it for every patch)
     // (mixed lens: ... else the general kernel's where it has samples of a general table, else the centre kernel's)
     const bool mine_too = PART == PART_RING ? (!WIDE || !a.narrow_exists || (LISTED && !a.first_pass && !__ballot(peri_any && ((a.narrow_mask >> cell_type) & 1))))
-                                            : (LISTED && !a.first_pass && !__ballot(peri_any));   // wave-uniform
+                                            : (LISTED && (FIXED3 || !a.first_pass) && !__ballot(peri_any));   // wave-uniform
     if (mine_too) {
 #pragma unroll
         for (int m = 0; m < NP; ++m) wave_power_k(a, K, lens ? power_in[m] : 0.0, bx, by, m);
@@ -529,7 +550,7 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     const TableDesc &T = a.center_desc;
     int i0, i1;
     double t0, t1;
-    if (T.uniform) {   // (every lane: ux, uy are defined for all of them)
+    if (FIXED3 || T.uniform) {   // (every lane: ux, uy are defined for all of them)
         locate_uniform(T.uni_ax, (double)(T.n0 - 2), (double)(T.n1 - 2), ux, uy, i0, t0, i1, t1);
     } else {
         locate_axis(T.axis0, T.n0, ux, i0, t0);
@@ -589,6 +610,25 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
         asm volatile("" : "+v"(R.kx0));   // (see the ring samples' order loop)
         OrderWalk W;
         walk_start(W, R, a.center_lo);
+        if constexpr (FIXED3) {
+            // three orders, straight-line: the two buffers alternate statically, no presence test
+            const double2 *next = src;
+#pragma unroll
+            for (int oc = 0; oc < FIXED3_SLOTS; ++oc) {
+                const double2 *cur = (oc & 1) ? s_tab1 : s_tab;
+                if (oc + 1 < FIXED3_SLOTS) {
+                    next += order_blocks * CB;
+                    stage_block<CB / 64>(next, (oc & 1) ? s_tab : s_tab1, lane_off);
+                    staged_wait<CB / 64>();
+                } else {
+                    staged_wait<0>();
+                }
+                order_simple<NP, SK_TYPES>(acc, cur + mine_off, wa, wb, Hy_i, Hx_i, R, K, W, mine);
+                if (oc + 1 < FIXED3_SLOTS) walk_step(W, R);
+                __builtin_amdgcn_sched_barrier(0);   // (as below)
+            }
+            continue;
+        }
 #pragma nounroll
         for (int oc = 0; oc < n_slots; ++oc) {   // wave-uniform
             const double2 *cur = (oc & 1) ? s_tab1 : s_tab;
@@ -668,9 +708,14 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
         // (the whole descriptor in ONE round of scalar loads, pinned: fetched where it is used, the flag
         // test, the axes and the order list each wait for a round trip of their own)
         double ax0 = C.uni_ax[0], ax2 = C.uni_ax[2], ax3 = C.uni_ax[3], ax5 = C.uni_ax[5], lim0 = C.lim0, lim1 = C.lim1;
-        int flags = C.flags, n1m1 = C.n1 - 1, c_ns = C.n_slots, c_lo = C.ox_lo, c_present = C.present;
-        asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(flags), "+s"(n1m1),
-                     "+s"(c_ns), "+s"(c_lo), "+s"(c_present));
+        int flags = 1, n1m1 = C.n1 - 1, c_ns = FIXED3_SLOTS, c_lo = C.ox_lo, c_present = FIXED3_PRESENT;
+        if constexpr (FIXED3) {   // (uniform axes, three slots, all present: three scalars fewer)
+            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(n1m1), "+s"(c_lo));
+        } else {
+            flags = C.flags, c_ns = C.n_slots, c_present = C.present;
+            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(flags), "+s"(n1m1),
+                         "+s"(c_ns), "+s"(c_lo), "+s"(c_present));
+        }
         if (c_cur < 0) {
             c_cur = c0;
             ns = c_ns;
@@ -692,7 +737,10 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
             // (i0 (n1 - 1) + i1) n_slots, in units of 16 complex; 24-bit products (full rate): tables of
             // up to 4096 x 4096 cells
             asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(cell) : "v"(i0), "s"(n1m1), "v"(i1));
-            asm("v_mul_u32_u24 %0, %1, %2" : "=v"(cell) : "v"(cell), "s"(c_ns));
+            if constexpr (FIXED3)
+                cell *= FIXED3_SLOTS;   // (the same 24-bit product, exact; a shift-and-add)
+            else
+                asm("v_mul_u32_u24 %0, %1, %2" : "=v"(cell) : "v"(cell), "s"(c_ns));
         }
     }
     // the sample's (ring, table cell) block, by its first unit: what the lanes of the wave are matched by
@@ -735,7 +783,8 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     constexpr int NSLOT = WIDE ? SK_SLOTS : SK_SLOTS_NARROW;
     int lead[NSLOT];
     constexpr int SMALL_SLOTS = SIMPLE_NARROW_SLOTS;
-    const int small_pitch = a.narrow_pitch, small_cap = a.narrow_cap;   // (narrow instantiation: see RING_LDS_NARROW)
+    // (narrow instantiation: see RING_LDS_NARROW; fixed-shape: three slots in every narrow collection)
+    const int small_pitch = FIXED3 ? narrow_pitch(FIXED3_SLOTS) : a.narrow_pitch, small_cap = FIXED3 ? SK_SLOTS_NARROW : a.narrow_cap;
     auto match = [&]() {
         myslot = -1;
         n_blocks = 0;
@@ -773,7 +822,7 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     auto begin_round = [&](auto small) {
         match();
         if constexpr (decltype(small)::value) {
-            if (lane < ns * UNIT) {
+            if (lane < (FIXED3 ? FIXED3_SLOTS : ns) * UNIT) {
 #pragma unroll
                 for (int s = 0; s < NSLOT; ++s)
                     if (lead[s] >= 0)
@@ -841,7 +890,20 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
         OrderWalk W;
         walk_start(W, R, lo);
         const bool mine = myslot >= 0;
-        if constexpr (decltype(small)::value) {
+        if constexpr (FIXED3) {
+            // three present slots, straight-line: the steps of the general loop below for ns = 3, present = 0b111
+            const double2 *b = s_tab + max(myslot, 0) * narrow_pitch(FIXED3_SLOTS);
+            staged_wait<0>();
+#pragma unroll
+            for (int sl = 0; sl < FIXED3_SLOTS; ++sl) {
+                if (sl) {
+                    walk_step(W, R);
+                    asm volatile("" : "+v"(W.ph.r), "+v"(W.ph.i), "+v"(W.kx));   // (as below)
+                }
+                order_simple<NP, 1>(pr, b + sl * UNIT, wa, wb, Hw_x, Hw_y, R, K, W, mine);
+                __builtin_amdgcn_sched_barrier(0);   // (as below)
+            }
+        } else if constexpr (decltype(small)::value) {
             int boff;   // the lane's block in the buffer (complex)
             asm("v_mul_u32_u24 %0, %1, %2" : "=v"(boff) : "v"(max(myslot, 0)), "s"(small_pitch));
             const double2 *b = s_tab + boff;
@@ -889,9 +951,9 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
             // the next collection among the wave's lanes: its list by scalar loads
             c_cur = __builtin_amdgcn_readlane(cell_type, __ffsll((long long)later) - 1);
             coll_done |= 1u << c_cur;
-            ns = a.coll[c_cur].n_slots;
+            if (!FIXED3) ns = a.coll[c_cur].n_slots;   // (fixed-shape: three slots, all present, in every collection)
             lo = a.coll[c_cur].ox_lo;
-            present = (unsigned)a.coll[c_cur].present;
+            if (!FIXED3) present = (unsigned)a.coll[c_cur].present;
             todo = __ballot(peri && cell_type == c_cur);
         }
         __builtin_amdgcn_sched_barrier(0);   // (this round's LDS reads are done before the next round's loads go out)
@@ -952,33 +1014,35 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
 // pointer can arrive in scalar registers with the wave - kernarg preload, see the Makefile - and the
 // list entry is the FIRST load of the wave, not the third of a dependent chain); else the whole grid
 // WIDE: the instantiation for the ring collections of more than SIMPLE_NARROW_SLOTS = 4 orders (NfArgs::wide_mask)
-template <int NP, bool LISTED, bool WIDE>
+// FIXED3: the fixed-shape form (synthesize_patch) - of <1, true, false> and of the centre kernel's <1, true> only
+template <int NP, bool LISTED, bool WIDE, bool FIXED3 = false>
 __global__ __launch_bounds__(64, NP == 1 ? ML_NF_RING_MINW : 3) void nearfield_ring_kernel(const int2 *list, const NfArgs a) {
     __shared__ double2 s_tab[WIDE ? RING_LDS : RING_LDS_NARROW];
     int bx = blockIdx.x, by = blockIdx.y;
     if (LISTED) {
         // (first pass: the launch covers every patch number, the list's length is on the device)
-        if (a.list_count && (int)blockIdx.x >= *a.list_count) return;
+        // (fixed-shape: steady state only, the list's length is the grid)
+        if (!FIXED3 && a.list_count && (int)blockIdx.x >= *a.list_count) return;
         const int2 pb = list[blockIdx.x];
         bx = pb.x;
         by = pb.y;
     }
-    synthesize_patch<NP, PART_RING, LISTED, WIDE>(a, s_tab, s_tab, bx, by);
+    synthesize_patch<NP, PART_RING, LISTED, WIDE, FIXED3>(a, s_tab, s_tab, bx, by);
 }
 
-template <int NP, bool LISTED>
+template <int NP, bool LISTED, bool FIXED3 = false>
 __global__ __launch_bounds__(64, 3) void nearfield_centre_kernel(const int2 *list, const NfArgs a) {
     // two buffers: order o + 1's block is on its way while order o is evaluated
     __shared__ double2 s_tab[CB], s_tab1[CB];
     int bx = blockIdx.x, by = blockIdx.y;
     if (LISTED) {
         // (first pass: the launch covers every patch number, the list's length is on the device)
-        if (a.list_count && (int)blockIdx.x >= *a.list_count) return;
+        if (!FIXED3 && a.list_count && (int)blockIdx.x >= *a.list_count) return;
         const int2 pb = list[blockIdx.x];
         bx = pb.x;
         by = pb.y;
     }
-    synthesize_patch<NP, PART_CENTRE, LISTED, false>(a, s_tab, s_tab1, bx, by);
+    synthesize_patch<NP, PART_CENTRE, LISTED, false, FIXED3>(a, s_tab, s_tab1, bx, by);
 }
 
 #ifdef ML_PHASE_TIMERS
@@ -1019,6 +1083,8 @@ static int launch_parts(ml_ctx *ctx, const NfArgs &a) {
         if (centre_grid > 0 && !a.centre_general)
             hipLaunchKernelGGL((nearfield_centre_kernel<NP, true>), dim3(centre_grid), dim3(64), 0, ctx->stream,
                                a.active_list + (size_t)2 * a.list_stride, c);
+        ctx->out.ring_form = narrow ? 1 : 0;
+        ctx->out.centre_form = centre_grid > 0 && !a.centre_general ? 1 : 0;
         // a mixed lens: the samples of the tables that are not simple, from list 0 (the same trick: every patch
         // number, the surplus workgroups leave at once)
         if (a.general_mask || a.centre_general) {
@@ -1033,15 +1099,39 @@ static int launch_parts(ml_ctx *ctx, const NfArgs &a) {
         // at the end of its patch, restores the registers a fresh wave arrives with and branches to the kernel's own
         // entry point: no loop the compiler sees, no spills - and it still lost: two entries per workgroup equal to
         // noise, 5120 resident workgroups 0.265-0.27 against 0.25.  The empty wave slots are not what the kernel waits for.)
-        if (a.n_active[1] > 0)
-            hipLaunchKernelGGL((nearfield_ring_kernel<NP, true, false>), dim3(a.n_active[1]), dim3(64), 0, ctx->stream,
-                               a.active_list + (size_t)1 * a.list_stride, a);
+        // three-order tables lit by one dipole: the fixed-shape kernels (NfArgs::fixed3, from lens_pack.h fixed3_takes;
+        // this branch is the listed steady-state launch that predicate asks for)
+        const bool listed = a.use_active && !a.first_pass;
+        bool ring_fixed = false, centre_fixed = false;
+        if constexpr (NP == 1) {
+            ring_fixed = listed && (a.fixed3 & 1) != 0;
+            centre_fixed = listed && (a.fixed3 & 2) != 0;
+        }
+        if (a.n_active[1] > 0) {
+            if constexpr (NP == 1) {
+                if (ring_fixed)
+                    hipLaunchKernelGGL((nearfield_ring_kernel<1, true, false, true>), dim3(a.n_active[1]), dim3(64), 0, ctx->stream,
+                                       a.active_list + (size_t)1 * a.list_stride, a);
+            }
+            if (!ring_fixed)
+                hipLaunchKernelGGL((nearfield_ring_kernel<NP, true, false>), dim3(a.n_active[1]), dim3(64), 0, ctx->stream,
+                                   a.active_list + (size_t)1 * a.list_stride, a);
+        }
         if (a.n_active[3] > 0)
             hipLaunchKernelGGL((nearfield_ring_kernel<NP, true, true>), dim3(a.n_active[3]), dim3(64), 0, ctx->stream,
                                a.active_list + (size_t)3 * a.list_stride, a);
-        if (a.n_active[2] > 0)
-            hipLaunchKernelGGL((nearfield_centre_kernel<NP, true>), dim3(a.n_active[2]), dim3(64), 0, ctx->stream,
-                               a.active_list + (size_t)2 * a.list_stride, a);
+        if (a.n_active[2] > 0) {
+            if constexpr (NP == 1) {
+                if (centre_fixed)
+                    hipLaunchKernelGGL((nearfield_centre_kernel<1, true, true>), dim3(a.n_active[2]), dim3(64), 0, ctx->stream,
+                                       a.active_list + (size_t)2 * a.list_stride, a);
+            }
+            if (!centre_fixed)
+                hipLaunchKernelGGL((nearfield_centre_kernel<NP, true>), dim3(a.n_active[2]), dim3(64), 0, ctx->stream,
+                                   a.active_list + (size_t)2 * a.list_stride, a);
+        }
+        ctx->out.ring_form = a.n_active[1] > 0 ? (ring_fixed ? 2 : 1) : 0;
+        ctx->out.centre_form = a.n_active[2] > 0 ? (centre_fixed ? 2 : 1) : 0;
         if ((a.general_mask || a.centre_general) && a.n_active[0] > 0)
             ML_TRY(nearfield_general_listed_launch(ctx, a, a.n_active[0]));
     }

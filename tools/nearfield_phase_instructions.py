@@ -19,7 +19,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'metalens_amd', 'csrc')
-KERNEL = '_ZN2ml21nearfield_ring_kernelILi1ELb1ELb0EEEvPK15HIP_vector_typeIiLj2EENS_6NfArgsE'
+# (<NP = 1, LISTED, !WIDE, !FIXED3>: the general narrow instantiation, whose order loop unrolls four slots)
+KERNEL = '_ZN2ml21nearfield_ring_kernelILi1ELb1ELb0ELb0EEEvPK15HIP_vector_typeIiLj2EENS_6NfArgsE'
 # program order of the stamps (nearfield_simple.hip ML_MARK) and what ends at each
 PHASES = ['prologue: constants pinned, coordinates, record load issued',
           'record arrives (incident direction, field and power worked meanwhile)',
