@@ -377,7 +377,12 @@ int ml_nearfield_powers(ml_ctx *ctx, double *power, int n);
  *   slot's total_P = sum of finite P * dux * duy       (nearfield_farfield.py:74)
  *   slot's cone_P  = the same over (ux - cone_ux0)^2 + (uy - cone_uy0)^2 <= cone_u^2  (encircled power)
  * asynchronous; ml_farfield_sums downloads P_sum [mx][my] (or NULL) and the first n_slots pairs.
- * Only P_sum and two scalars per source cross PCIe, whatever the sweep's length.             */
+ * Only P_sum and two scalars per source cross PCIe, whatever the sweep's length.
+ * P_sum belongs to the plan it was started on (its direction count, and tensor grid or pair list):
+ * ml_farfield_accumulate with reset == 0 is refused with ML_ESTATE when the context has no sums yet
+ * (the first call needs reset != 0) or when the active plan's direction count or kind differs, and
+ * ml_farfield_sums with P_sum != NULL is refused likewise under such a plan; the slot scalars stay
+ * readable (P_sum == NULL).  A refused call leaves the sums as they were.                    */
 #define ML_MAX_SWEEP_SLOTS 4096
 int ml_farfield_accumulate(ml_ctx *ctx, double weight, double cone_u, double cone_ux0, double cone_uy0,
                            int slot, int reset);

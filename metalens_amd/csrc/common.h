@@ -472,6 +472,10 @@ struct ml_ctx {
 
     // far-field sums kept on the GPU across the sources of a sweep (farfield.hip, ml_farfield_accumulate)
     ml::DevBuf acc_P, acc_partials, acc_sums;
+    // the plan P_sum was accumulated on: its direction count and kind (0 directions: nothing accumulated yet).  acc_P is
+    // sized by it, so adding onto it or reading it under a plan of another size or kind is refused
+    size_t acc_n = 0;
+    int acc_pair_list = 0;
     ml::DevBuf lattice_in;   // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only

@@ -1419,11 +1419,29 @@ static int accumulate_impl(ml_ctx *ctx, double weight, double cone_u, double con
         set_error("the power map is reduce-scattered over the ranks: call ml_farfield_gather before summing it");
         return ML_ESTATE;
     }
+    const size_t n = (size_t)pl.mx * (pl.pair_list ? 1 : pl.my);
+    if (into_sum && !reset) {
+        // P_sum is sized by the plan it was started on: adding onto it needs that plan's directions
+        if (!ctx->acc_n) {
+            set_error("ml_farfield_accumulate: this context has no sums yet (the first call needs reset = 1)");
+            return ML_ESTATE;
+        }
+        if (ctx->acc_n != n || ctx->acc_pair_list != pl.pair_list) {
+            set_error("ml_farfield_accumulate: the sums were started on a plan of %zu directions (%s), the active plan "
+                      "has %zu (%s): start a new sum with reset = 1", ctx->acc_n,
+                      ctx->acc_pair_list ? "pair list" : "tensor grid", n, pl.pair_list ? "pair list" : "tensor grid");
+            return ML_ESTATE;
+        }
+    }
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(comm_join(ctx, false));
-    const size_t n = (size_t)pl.mx * (pl.pair_list ? 1 : pl.my);
     const int blocks = (int)((n + 255) / 256);
-    if (into_sum) ML_TRY(ctx->acc_P.reserve(n * sizeof(double)));
+    if (into_sum) {
+        ctx->acc_n = 0;   // (a reserve that fails has let go of the old sum)
+        ML_TRY(ctx->acc_P.reserve(n * sizeof(double)));
+        ctx->acc_n = n;
+        ctx->acc_pair_list = pl.pair_list;
+    }
     ML_TRY(ctx->acc_partials.reserve((size_t)blocks * 2 * sizeof(double)));
     if (!ctx->acc_sums.p) {
         const size_t bytes = (size_t)(ML_MAX_SWEEP_SLOTS + 1) * 2 * sizeof(double);
@@ -1484,6 +1502,13 @@ int ml_farfield_sums(ml_ctx *ctx, double *P_sum, double *total_P, double *cone_P
     ML_TRY(comm_join(ctx, false));
     FarfieldPlan &pl = ctx->plan;
     const size_t n = (size_t)pl.mx * (pl.pair_list ? 1 : pl.my);
+    if (P_sum && (!pl.ready || ctx->acc_n != n || ctx->acc_pair_list != pl.pair_list)) {
+        // P_sum has the size of the plan it was accumulated on; the slot scalars do not depend on it (P_sum = NULL)
+        set_error("ml_farfield_sums: P_sum was accumulated on a plan of %zu directions (%s), the active plan has %zu "
+                  "(%s)", ctx->acc_n, ctx->acc_pair_list ? "pair list" : "tensor grid", pl.ready ? n : (size_t)0,
+                  pl.pair_list ? "pair list" : "tensor grid");
+        return ML_ESTATE;
+    }
     std::vector<double> sums((size_t)2 * std::max(n_slots, 1));
     if (P_sum)
         ML_HIP(hipMemcpyAsync(P_sum, ctx->acc_P.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
