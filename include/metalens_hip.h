@@ -391,6 +391,45 @@ int ml_farfield_sums(ml_ctx *ctx, double *P_sum, double *total_P, double *cone_P
  * touching P_sum or any sweep slot: a one-off far field on a context that is also running a sweep
  * leaves the sweep's sums as they were.  Synchronises.                                          */
 int ml_farfield_total_power(ml_ctx *ctx, double *total_P);
+/* Beam metrics of a far-field map, reduced on the GPU (csrc/farfield_beam.hip): where the beam points, how wide it is and
+ * how much power falls inside n_cones cones - one record per call, queued into a slot of the context, so that a sweep reads
+ * a record per source at its end instead of downloading a map per source.  The far-field counterpart of ml_propagate_focus.
+ *   source           : 0: the active plan's current projection (after ml_farfield_project[_async]); -1: the P_sum of
+ *                      ml_farfield_accumulate as it is stored
+ *   centre           : {cx, cy}, direction cosines; NULL: the map's own peak direction, read on the device
+ *   cones, n_cones   : 0 <= n_cones <= ML_BEAM_CONES_MAX sines of half-angles, finite, >= 0 and not decreasing
+ *   slot             : in [0, ML_MAX_SWEEP_SLOTS); the records are a buffer of their own, not the slots of
+ *                      ml_farfield_accumulate, released with the context
+ * The map has n directions - mx my of a tensor grid, direction (i, j) at i my + j, or mx of a pair list, i = j - and is NaN
+ * outside the unit circle: every sum and the peak run over the finite P only.  With dx = ux[i] - cx, dy = uy[j] - cy and
+ * cell = dux duy as ml_farfield_accumulate takes it (the axes' first steps, 1 for an axis of one direction, 1 for a pair
+ * list) the terms of a direction are t0 = P cell, t1 = t0 dx, t2 = t0 dy, t3 = t0 (dx dx), t4 = t0 (dy dy), t5 = t0 (dx dy),
+ * and it is inside cone c iff dx dx + dy dy <= c c - every operation rounded on its own, what NumPy computes from the same
+ * doubles.  A record has ML_BEAM_RECORD doubles, K = n_cones:
+ *   [0] peak_P, the largest finite P (NaN if no direction is finite)  [1] its flat index, the lowest of equals (-1 if none)
+ *   [2] the number of finite directions  [3 ... 8] sum t0, t1, t2, t3, t4, t5  [9] cx [10] cy, the centre used (NaN if it is
+ *   the peak and nothing is finite; the sums are then 0)  [11] K  [12 + r] sum of t0 inside cones[r], r < K; zeros behind K
+ * (csrc/farfield_beam.h BEAM_*).  The moments are taken about the centre, so the central second moment of a narrow beam
+ * far off axis does not cancel.
+ * Order of summation: fp64, no atomics.  Chunks of the map (1024 directions, doubled until there are at most 1024 chunks:
+ * of n alone) are reduced by a workgroup each - a lane adds every 256th direction in ascending order, a butterfly over the
+ * wave, the four waves in their order -, and a last launch adds the chunks' partials in index order in two levels, tiles of
+ * 32 chunks and then the tiles.  Every cone has a sum of its own.  So a record is repeatable bit for bit, does not depend
+ * on the slot or on the other cones, and the record of source k of a sweep is that of the same map reduced alone.
+ * ML_ESTATE with the wording of ml_farfield_accumulate if nothing is projected or the power map is reduce-scattered and
+ * not gathered, and for source = -1 if the context has no sums or they were started on a plan of another direction count or
+ * kind; ML_EINVAL with the numbers in ml_last_error for a source other than 0 or -1, a slot out of range, more than 32
+ * cones, cones == NULL with n_cones > 0, a cone that is negative, not finite or below the one before it, a centre that is
+ * not finite.  A refused call leaves every slot, P_sum, the sweep's scalars and the plan as they were; an accepted one
+ * writes its own slot and nothing else of those.  Asynchronous.  Replaces no reference lines (the reference's callers
+ * form these from the downloaded P).
+ * ml_farfield_beams: records = HOST, [n_slots][ML_BEAM_RECORD], the slots first_slot ... first_slot + n_slots - 1; a slot
+ * never written reads zeros.  ML_EINVAL for first_slot outside [0, ML_MAX_SWEEP_SLOTS), n_slots < 0 or first_slot +
+ * n_slots > ML_MAX_SWEEP_SLOTS, records == NULL with n_slots > 0.  Synchronises.  Replaces no reference lines.          */
+#define ML_BEAM_CONES_MAX 32
+#define ML_BEAM_RECORD (12 + ML_BEAM_CONES_MAX)
+int ml_farfield_beam(ml_ctx *ctx, int source, const double *centre, const double *cones, int n_cones, int slot);
+int ml_farfield_beams(ml_ctx *ctx, int first_slot, int n_slots, double *records);
 
 /* Exact ties of the nearest-cell search.  A centre-region sample that is exactly equidistant
  * from two cells (it sits on a mirror line of the cell lattice: the x = 0 row of a symmetric
@@ -532,7 +571,8 @@ int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
  * refused call leaves result, sums and plan as they were; so does an accepted one.  fp64, no atomics: chunks of a plane
  * are reduced by a workgroup each in a fixed order and added in index order by a second launch; the cut depends on
  * (mx, my) alone, so a record is repeatable bit for bit and plane p of a stack has the record of that plane planned
- * alone.  Synchronises.  Replaces no reference lines; the far-field counterpart is ml_farfield_accumulate. */
+ * alone.  Synchronises.  Replaces no reference lines; the far-field counterparts are ml_farfield_accumulate and
+ * ml_farfield_beam. */
 int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, double dx, double dy,
                        const double *centre, const double *radii, int n_radii, double *records, int record_doubles);
 /* The transfer function of the resident image, contracted on the GPU (csrc/propagate_otf.hip): per plane and per weight

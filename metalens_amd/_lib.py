@@ -52,7 +52,7 @@ SYMBOLS = (
     'ml_propagate_plan_grid_long', 'ml_propagate_plan_grid_tiled', 'ml_propagate_plan_tiles',
     'ml_propagate_plan_grid_fine', 'ml_propagate_plan_lattices', 'ml_math_probe',
     'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes', 'ml_propagate_focus',
-    'ml_propagate_otf', 'ml_nearfield_synth_info',
+    'ml_propagate_otf', 'ml_nearfield_synth_info', 'ml_farfield_beam', 'ml_farfield_beams',
 )
 
 
@@ -189,6 +189,9 @@ def load():
         lib.ml_propagate_focus.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, _dp, _dp, c_int, _dp, c_int]
     if hasattr(lib, 'ml_propagate_otf'):
         lib.ml_propagate_otf.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp]
+    if hasattr(lib, 'ml_farfield_beam'):
+        lib.ml_farfield_beam.argtypes = [c_void_p, c_int, _dp, _dp, c_int, c_int]
+        lib.ml_farfield_beams.argtypes = [c_void_p, c_int, c_int, _dp]
     if hasattr(lib, 'ml_math_probe'):   # (test surface: tests/test_gpu_device_math.py)
         lib.ml_math_probe.argtypes = [c_void_p, c_int, _dp, _ip, c_int, _dp, _dp, _ip]
     lib.ml_propagate_plan_info.argtypes = [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int64)]

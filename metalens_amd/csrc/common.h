@@ -476,7 +476,10 @@ struct ml_ctx {
     // sized by it, so adding onto it or reading it under a plan of another size or kind is refused
     size_t acc_n = 0;
     int acc_pair_list = 0;
-    ml::DevBuf lattice_in;   // staging for ml_farfield_lattice_power
+    // beam metrics of the far field (farfield_beam.hip, ml_farfield_beam): the chunks' partial records of the call in flight,
+    // and the slots' records - a buffer of its own, not acc_sums
+    ml::DevBuf beam_partials, beam_records;
+    ml::DevBuf lattice_in;  // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only
     bool premod_enabled = false;   // ml_nearfield_premodulate: the synthesis applies the active plan's stage-1 input modulation

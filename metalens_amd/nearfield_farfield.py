@@ -22,6 +22,7 @@ all-reduce.  On FFT-lattice directions the result equals the reference's
 import numpy as np
 
 from . import _lib, constants
+from .postprocess import BEAM_RECORD, _beam_dict, _beam_single, _check_beam
 
 
 def _check_axis(pts, wavelength):
@@ -219,6 +220,32 @@ class FarfieldTransform:
         _lib.check(self.ctx.lib.ml_farfield_project(self.ctx.handle, Z0, _lib.dptr(P),
                                                     _lib.dptr(a_theta), _lib.dptr(a_phi)))
         return P, a_theta, a_phi
+
+    def beam(self, cones=(), centre='peak', of='projection', slot=0):
+        """The beam metrics of the far-field map that is resident on the GPU, reduced there (``ml_farfield_beam``,
+        csrc/farfield_beam.hip): a record of 44 doubles crosses PCIe, not the map.
+
+        ``of='projection'``: of the current projection (``project()`` or ``ml_farfield_project_async`` has run);
+        ``of='sums'``: of the ``P_sum`` of ``ml_farfield_accumulate`` as it is stored.  ``cones``: up to 32 sines of
+        half-angles, in any order; ``centre``: ``'peak'`` (the map's own peak direction, read on the device) or one ``(ux0,
+        uy0)``.  NaN (outside the unit circle) is left out of every sum and of the peak.  A direction is inside cone ``c``
+        iff ``dx dx + dy dy <= c c`` with ``dx = ux - cx``, ``dy = uy - cy``, every operation rounded on its own.  ``slot``:
+        the record slot of the context the call uses (a sweep on the same context fills slots ``0 ... len(sources)``).
+
+        -> dict: ``peak_P``; ``peak_index`` (``(i, j)``, or ``i`` for a pair list; the lowest of equals, -1 if nothing is
+        finite) and ``peak_u``; ``finite``, the number of finite directions; ``total_P = sum P dux duy``; ``centre_u``, the
+        centre used; ``centroid_u = centre + (sum t1, sum t2) / sum t0``, where the beam points (NaN where the sum is 0);
+        ``second_moments_u = (xx, yy, xy)``, central, in direction cosines squared; ``cone_P``, the power inside each
+        cone, in the caller's order (``postprocess.beam_metrics`` is the same in NumPy).  Bit for bit repeatable.
+        Synchronises."""
+        c, back, ce = _check_beam(cones, centre, of)
+        self._check_owner()
+        ctx = self.ctx
+        _lib.check(ctx.lib.ml_farfield_beam(ctx.handle, -1 if of == 'sums' else 0, _lib.dptr(ce), _lib.dptr(c) if c.size else None,
+                                            c.size, int(slot)))
+        rec = np.empty(BEAM_RECORD)
+        _lib.check(ctx.lib.ml_farfield_beams(ctx.handle, int(slot), 1, _lib.dptr(rec)))
+        return _beam_single(_beam_dict(rec, self.ux, self.uy, self.pair_list, back), self.pair_list)
 
 
 def farfield_direct(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, ux, uy,

@@ -69,3 +69,125 @@ def efficiency(P, ux, uy, dux, duy, power_in, half_angle=None, sin_max=None, cen
     else:
         out = encircled_power(P, ux, uy, dux, duy, half_angle, sin_max, center)
     return out / power_in if power_in else float('nan')
+
+
+BEAM_CONES_MAX = 32     # csrc/farfield_beam.h, ML_BEAM_CONES_MAX
+# the record of ml_farfield_beam (csrc/farfield_beam.h BEAM_*)
+_BEAM_PEAK_P, _BEAM_PEAK_INDEX, _BEAM_FINITE, _BEAM_MOM, _BEAM_CENTRE, _BEAM_K, _BEAM_CONE = 0, 1, 2, 3, 9, 11, 12
+BEAM_RECORD = _BEAM_CONE + BEAM_CONES_MAX
+
+
+def _check_beam(cones, centre, of='projection'):
+    """the argument checks of ``FarfieldTransform.beam``, ``SourceSweep.run(beam_cones=...)`` and ``beam_metrics``, before
+    any device call -> (cones ascending as float64, the caller's order as indices into them, the centre as a float64
+    pair or None for ``'peak'``)"""
+    if of not in ('projection', 'sums'):
+        raise ValueError("of must be 'projection' or 'sums', got %r" % (of,))
+    try:
+        c = np.asarray(cones, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('cones must be a sequence of numbers, got %r' % (cones,)) from None
+    if c.ndim != 1:
+        raise ValueError('cones must be a sequence of numbers, got an array of shape %s' % (c.shape,))
+    if c.size > BEAM_CONES_MAX:
+        raise ValueError('beam() takes at most %d cones, got %d' % (BEAM_CONES_MAX, c.size))
+    bad = ~(np.isfinite(c) & (c >= 0))
+    if bad.any():
+        raise ValueError('a cone is the sine of a half-angle, finite and >= 0: cones[%d] = %g' % (int(np.argmax(bad)), c[np.argmax(bad)]))
+    order = np.argsort(c, kind='stable')
+    back = np.empty(c.size, dtype=int)
+    back[order] = np.arange(c.size)
+    said = "centre must be 'peak' or one (ux0, uy0), got %r" % (centre,)
+    if isinstance(centre, str):
+        if centre != 'peak':
+            raise ValueError(said)
+        return np.ascontiguousarray(c[order]), back, None
+    try:
+        ce = np.asarray(centre, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError(said) from None
+    if ce.shape != (2,):
+        raise ValueError(said)
+    if not np.isfinite(ce).all():
+        raise ValueError('a centre must be finite, got %r' % (centre,))
+    return np.ascontiguousarray(c[order]), back, np.ascontiguousarray(ce)
+
+
+def _beam_dict(rec, ux, uy, pair_list, back):
+    """records of ml_farfield_beam, shape ``(..., BEAM_RECORD)`` with the cones ascending -> the dict of ``beam()``, every
+    entry with the records' leading axes; ``back``: the caller's order of the cones"""
+    rec = np.asarray(rec, dtype=float)
+    ux, uy = np.asarray(ux, dtype=float).ravel(), np.asarray(uy, dtype=float).ravel()
+    flat = rec[..., _BEAM_PEAK_INDEX].astype(np.int64)
+    none = flat < 0
+    at = np.where(none, 0, flat)
+    i, j = (at, at) if pair_list else (at // uy.size, at % uy.size)
+    out = {'peak_P': rec[..., _BEAM_PEAK_P].copy()}
+    out['peak_index'] = np.where(none, -1, i) if pair_list else np.stack([np.where(none, -1, i), np.where(none, -1, j)], axis=-1)
+    out['peak_u'] = np.stack([np.where(none, np.nan, ux[i]), np.where(none, np.nan, uy[j])], axis=-1)
+    out['finite'] = rec[..., _BEAM_FINITE].astype(np.int64)
+    s, sx, sy, sxx, syy, sxy = (rec[..., _BEAM_MOM + q] for q in range(6))
+    out['total_P'] = s.copy()
+    out['centre_u'] = rec[..., _BEAM_CENTRE:_BEAM_CENTRE + 2].copy()
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mx, my = np.where(s != 0, sx / s, np.nan), np.where(s != 0, sy / s, np.nan)
+        out['centroid_u'] = out['centre_u'] + np.stack([mx, my], axis=-1)
+        out['second_moments_u'] = np.stack([sxx / s - mx * mx, syy / s - my * my, sxy / s - mx * my], axis=-1)
+    out['cone_P'] = rec[..., _BEAM_CONE:_BEAM_CONE + back.size][..., back]
+    return out
+
+
+def _beam_single(d, pair_list):
+    """the dict of one record: plain numbers where ``_beam_dict`` left arrays of no axis, ``peak_index`` an ``(i, j)`` tuple"""
+    d['peak_P'], d['total_P'], d['finite'] = float(d['peak_P']), float(d['total_P']), int(d['finite'])
+    d['peak_index'] = int(d['peak_index']) if pair_list else tuple(int(v) for v in d['peak_index'])
+    return d
+
+
+def beam_metrics(P, ux, uy, cones=(), centre='peak', pair_list=False):
+    """The beam metrics of a far-field map on the host: what ``FarfieldTransform.beam`` and ``SourceSweep.run(beam_cones=...)``
+    reduce on the GPU (``ml_farfield_beam``), for an arbitrary map in NumPy.  ``P``: shape ``(len(ux), len(uy))``, or
+    ``(len(ux),)`` at the directions ``(ux[d], uy[d])`` with ``pair_list``; NaN (outside the unit circle) and infinities
+    are left out of every sum and of the peak.  ``cones``: up to 32 sines of half-angles in any order; ``centre``:
+    ``'peak'`` (the map's own peak direction) or one ``(ux0, uy0)``.
+
+    With ``dx = ux - cx``, ``dy = uy - cy`` and ``cell = dux duy`` (the axes' first steps, 1 for an axis of one direction,
+    1 for a pair list) the terms are ``t0 = P cell`` and ``t0 dx``, ``t0 dy``, ``t0 (dx dx)``, ``t0 (dy dy)``, ``t0 (dx dy)``;
+    a direction is inside cone ``c`` iff ``dx dx + dy dy <= c c``.  -> dict: ``peak_P``; ``peak_index`` (``(i, j)``, ``i`` of a
+    pair list; the lowest of equals, -1 if nothing is finite) and ``peak_u``, its direction; ``finite``, the number of
+    finite directions; ``total_P = sum t0``; ``centre_u``, the centre used; ``centroid_u = centre + (sum t1, sum t2) / sum
+    t0`` (NaN where the sum is 0) - where the beam points; ``second_moments_u = (xx, yy, xy)``, central - ``xx + yy`` is the
+    squared RMS half-width of the beam in direction cosines; ``cone_P``, the power inside each cone, in the caller's order."""
+    c, back, ce = _check_beam(cones, centre)
+    ux, uy = np.asarray(ux, dtype=float).ravel(), np.asarray(uy, dtype=float).ravel()
+    P = np.asarray(P, dtype=float)
+    want = (ux.size,) if pair_list else (ux.size, uy.size)
+    if P.shape != want or (pair_list and uy.size != ux.size):
+        raise ValueError('P has shape %s, the directions give %s' % (P.shape, want))
+    cell = 1.0
+    if not pair_list:
+        cell = (ux[1] - ux[0] if ux.size > 1 else 1.0) * (uy[1] - uy[0] if uy.size > 1 else 1.0)
+    ok = np.isfinite(P)
+    rec = np.zeros(BEAM_RECORD)
+    rec[_BEAM_PEAK_P], rec[_BEAM_PEAK_INDEX], rec[_BEAM_K] = np.nan, -1.0, c.size
+    rec[_BEAM_FINITE] = int(ok.sum())
+    if ok.any():
+        at = int(np.argmax(np.where(ok, P, -np.inf)))           # (the first of equals)
+        rec[_BEAM_PEAK_P], rec[_BEAM_PEAK_INDEX] = P.flat[at], at
+        if ce is None:
+            ce = np.array([ux[at] if pair_list else ux[at // uy.size], uy[at] if pair_list else uy[at % uy.size]])
+    elif ce is None:
+        ce = np.array([np.nan, np.nan])
+    rec[_BEAM_CENTRE:_BEAM_CENTRE + 2] = ce
+    if ok.any():
+        dx, dy = ux - ce[0], uy - ce[1]
+        if not pair_list:
+            dx, dy = np.broadcast_to(dx[:, None], P.shape), np.broadcast_to(dy[None, :], P.shape)
+        dx, dy, t0 = dx[ok], dy[ok], (P * cell)[ok]
+        xx, yy = dx * dx, dy * dy
+        for q, t in enumerate((t0, t0 * dx, t0 * dy, t0 * xx, t0 * yy, t0 * (dx * dy))):
+            rec[_BEAM_MOM + q] = t.sum()
+        rho2 = xx + yy
+        for r in range(c.size):
+            rec[_BEAM_CONE + r] = t0[rho2 <= c[r] * c[r]].sum()
+    return _beam_single(_beam_dict(rec, ux, uy, pair_list, back), pair_list)

@@ -29,6 +29,7 @@ from . import _lib, constants, packing, ties
 from .grating import n_glass as tabulated_n_glass
 from .nearfield import _check_axis, _raise_violation, nearfield_params
 from .pipeline import _check_source
+from .postprocess import BEAM_RECORD, _beam_dict, _beam_single, _check_beam
 
 MAX_BATCH = 3          # members of a polarisation batch (csrc/nearfield_dev.h MAX_POL)
 MAX_SLOTS = 4096       # ML_MAX_SWEEP_SLOTS
@@ -95,7 +96,7 @@ class SourceSweep:
             raise ValueError('image= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
                              % (tuple(image.aperture_shape) + (self.x.size, self.y.size)))
 
-    def queue(self, sources, image=None):
+    def queue(self, sources, image=None, beam_cones=None, beam_centre='peak'):
         """queue the whole sweep on the GPU and return without synchronising (benchmarks);
         tie settlement and the downloads are ``run``'s business.
 
@@ -105,12 +106,17 @@ class SourceSweep:
         ``run``) after editing.  Another object replacing the context's tables or layout IS
         noticed (the context's tokens change) and triggers a full re-check.
 
-        ``image``: as for ``run``; its sums stay on the GPU (``image.sums()``)."""
+        ``image``: as for ``run``; its sums stay on the GPU (``image.sums()``).  ``beam_cones``, ``beam_centre``: as for
+        ``run``; the records stay in the sources' slots (``ml_farfield_beams``)."""
+        beam = None
+        if beam_cones is not None:
+            beam_c, _back, beam_ce = _check_beam(beam_cones, beam_centre)
+            beam = (beam_c, beam_ce)
         self._check_image(image)
         self.prepare(check_content=False)
         weights = np.ones(len(sources))
         for g in self._group(sources):
-            self._pass(g, None, (0.0, 0.0, 0.0), weights, image)
+            self._pass(g, None, (0.0, 0.0, 0.0), weights, image, beam)
 
     def _group(self, sources):
         """consecutive sources at one position -> batches of up to MAX_BATCH polarisations (one
@@ -141,9 +147,10 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights, image=None):
+    def _pass(self, group, slots_done, cone, weights, image=None, beam=None):
         """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
-        group's field sets are then propagated to its targets in one pass and added to the image sums"""
+        group's field sets are then propagated to its targets in one pass and added to the image sums; with ``beam`` =
+        (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -164,6 +171,9 @@ class SourceSweep:
             _lib.check(lib.ml_farfield_project_async(ctx.handle, self.Z0))
             _lib.check(lib.ml_farfield_accumulate(ctx.handle, float(weights[k]), cone[0], cone[1],
                                                   cone[2], k, int(k == 0)))
+            if beam is not None:
+                _lib.check(lib.ml_farfield_beam(ctx.handle, 0, _lib.dptr(beam[1]), _lib.dptr(beam[0]) if beam[0].size else None,
+                                                beam[0].size, k))
         if image is not None:
             # the sums start over with the group that holds source 0 (as int(k == 0) above: the first pass is
             # repeated after tie settlement and must not count twice)
@@ -205,7 +215,7 @@ class SourceSweep:
         return fx, fy
 
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
-            image_radii=None, image_centre='peak', image_freqs=None):
+            image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak'):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -234,13 +244,29 @@ class SourceSweep:
 
         ``image_freqs`` = ``(fx, fy)``, frequency axes in cycles per length (needs ``image``): the result gains ``image_otf`` =
         ``image.otf(fx, fy, of='sums', centre=image_centre)`` - the transfer function of the field of view, the transform of
-        ``I_sum`` (and ``Sz_sum``) contracted on the GPU (``ml_propagate_otf``), and its modulus, the MTF."""
+        ``I_sum`` (and ``Sz_sum``) contracted on the GPU (``ml_propagate_otf``), and its modulus, the MTF.
+
+        ``beam_cones`` = up to 32 sines of half-angles (an empty tuple is allowed): the beam metrics of every source's far
+        field, reduced on the GPU right behind its projection (``ml_farfield_beam``, one asynchronous call per source into
+        the source's slot - no map is downloaded and nothing synchronises).  The result gains ``beam``, the dict of
+        ``FarfieldTransform.beam`` with a leading axis over the sources - ``peak_u`` and ``centroid_u`` (where each beam
+        points), ``second_moments_u`` (how wide it is), ``cone_P`` of shape ``(len(sources), len(beam_cones))``, ... -,
+        ``beam_sum``, the same of ``P_sum`` (no leading axis), and ``beam_efficiency = beam['cone_P'] / power_in[:, None]``.
+        ``beam_centre``: ``'peak'`` (each map's own peak direction) or one ``(ux0, uy0)``.  Takes 1 to 4095 sources (one
+        slot is ``P_sum``'s)."""
+        beam = None
+        if beam_cones is not None:
+            beam_c, beam_back, beam_ce = _check_beam(beam_cones, beam_centre)
+            beam = (beam_c, beam_ce)
         self._check_image(image)
         self._check_image_focus(image, image_radii, image_centre)
         image_freqs = self._check_image_otf(image, image_freqs, image_centre)
         sources = list(sources)
         if not 1 <= len(sources) <= MAX_SLOTS:
             raise ValueError('a sweep takes 1 to %d sources, got %d' % (MAX_SLOTS, len(sources)))
+        if beam is not None and len(sources) > MAX_SLOTS - 1:
+            raise ValueError('a sweep with beam_cones= takes 1 to %d sources (one record slot is P_sum\'s), got %d'
+                             % (MAX_SLOTS - 1, len(sources)))
         weights = np.ones(len(sources)) if weights is None else np.asarray(weights, dtype=float)
         if weights.shape != (len(sources),):
             raise ValueError('weights must have one entry per source: got shape %s for %d sources'
@@ -254,7 +280,7 @@ class SourceSweep:
         image_each = [None] * len(sources)
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights, image)
+            n = self._pass(g, None, cone3, weights, image, beam)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -266,7 +292,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights, image)
+                    n = self._pass(g, None, cone3, weights, image, beam)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:
@@ -302,6 +328,16 @@ class SourceSweep:
             out['cone_efficiency'] = cone_P.sum() / power_in.sum() if power_in.sum() else np.nan
         if keep_each:
             out['P_each'] = each
+        if beam is not None:
+            S = len(sources)
+            _lib.check(lib.ml_farfield_beam(ctx.handle, -1, _lib.dptr(beam_ce), _lib.dptr(beam_c) if beam_c.size else None,
+                                            beam_c.size, S))
+            rec = np.empty((S + 1, BEAM_RECORD))
+            _lib.check(lib.ml_farfield_beams(ctx.handle, 0, S + 1, _lib.dptr(rec)))
+            out['beam'] = _beam_dict(rec[:S], self.ux, self.uy, False, beam_back)
+            out['beam_sum'] = _beam_single(_beam_dict(rec[S], self.ux, self.uy, False, beam_back), False)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                out['beam_efficiency'] = np.where(power_in[:, None] != 0, out['beam']['cone_P'] / power_in[:, None], np.nan)
         if image is not None:
             out['I_sum'], Sz_sum = image.sums()
             if image.want_h:
