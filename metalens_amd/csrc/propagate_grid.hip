@@ -8,8 +8,9 @@
 //   Cx = w (i - q) ux        Cy = w (i - q) uy    Cz = w (i - q) uz
 //   E / scale_e:  Ex = Kxx Jx + Kxy Jy + Cz my     Ey = Kxy Jx + Kyy Jy - Cz mx     Ez = Kzx Jx + Kzy Jy + Cy mx - Cx my
 //   H / scale_h:  Hx = Kxx mx + Kxy my - Cz Jy     Hy = Kxy mx + Kyy my + Cz Jx     Hz = Kzx mx + Kzy my + Cx Jy - Cy Jx
-// each product a convolution over the aperture.  R, 1 / R, the sincos of k R, q, w, a, b and Rhat of a lag are the
-// inlined functions of propagate_kernel in its order.
+// each product a convolution over the aperture.  The kernels of a lag (grid_green), a field sample as a current
+// (grid_current), this term table (grid_products) and the scaled store of a target (grid_store_scaled) are stated once,
+// in propagate_grid_dev.h; the kernels below find the lag, the sample and the pointer and call them.
 //
 // A pass: pad the four currents of a set into Lx x Ly planes (zeros outside the aperture and outside the row extents
 // of a synthesised field), transform them, contract bin by bin with the eight kernel spectra into 6 (3) output
@@ -37,9 +38,9 @@
 // The fine plan (ml_propagate_plan_grid_fine) puts targets on the pitch divided by (sx, sy): sx sy lattices on the pitch,
 // each a tiled convolution of the SAME current spectra with its own kernel spectra (the grid_fine_* kernels).
 // The stack plan (ml_propagate_plan_grid_stack) is a fine plan in several planes z; it is planned here, and its pass and
-// kernels are in propagate_stack.hip, which reaches the transform and contraction launchers of this file through
-// propagate_grid_launch.h.
-#include "nearfield_math.h"
+// its fill and scatter kernels are in propagate_stack.hip, which reaches the transform and contraction launchers of this
+// file, the currents of a batch of tiles (grid_tile_currents) and the host helpers through propagate_grid_launch.h.
+#include "propagate_grid_dev.h"
 #include "propagate_grid_launch.h"
 
 namespace ml {
@@ -209,107 +210,40 @@ __global__ __launch_bounds__(1024) void grid_rows_block_kernel(const GridFftArgs
     for (int p = threadIdx.x; p < len; p += blockDim.x) g[p] = s[grid_lds_slot(p)];
 }
 
-struct GridGeoArgs {
-    d2 *out;               // kernel planes [8][Lx][Ly]
-    size_t plane_stride;
-    int Lx, Ly, mx, my;
-    double tx_off, ty_off, dxp, dyp, z, k, inv_k;
-};
-
-// the eight kernels at every index of the padded grid: index p holds lag p (p < m) or p - L
+// the eight kernels at every index of the padded grid: index p holds lag p (p < m) or p - L (GridGeoArgs:
+// propagate_grid_launch.h)
 __global__ __launch_bounds__(256) void grid_fill_kernel(const GridGeoArgs a) {
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly (a multiple of 256)
     const int p = (int)(id / a.Ly), r = (int)(id - (size_t)p * a.Ly);
     const int lx = p < a.mx ? p : p - a.Lx, ly = r < a.my ? r : r - a.Ly;
-    const double dx = fma((double)lx, a.dxp, a.tx_off), dy = fma((double)ly, a.dyp, a.ty_off);
-    const double s_row = fma(dx, dx, a.z * a.z);
-    const double R = sqrt_exact(fma(dy, dy, s_row));
-    const double iR = recip(R);
-    const double ux = dx * iR, uy = dy * iR, uz = a.z * iR;
-    const double q = iR * a.inv_k, q2 = q * q;
-    double sn, cs;
-    sincos_cw(a.k * R, sn, cs);
-    const c2 w = {cs * q, sn * q};
-    const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
-    const c2 wb = cmulf(w, cb);
-    const c2 txx = {fma(-(ux * ux), cb.r, ca.r), fma(-(ux * ux), cb.i, ca.i)};
-    const c2 tyy = {fma(-(uy * uy), cb.r, ca.r), fma(-(uy * uy), cb.i, ca.i)};
-    const c2 wxx = cmulf(w, txx), wyy = cmulf(w, tyy);
-    const c2 ci = {fma(-q, w.r, -w.i), fma(-q, w.i, w.r)};   // w (i - q)
-    const double gxy = ux * uy, gzx = uz * ux, gzy = uz * uy;
-    d2 *o = a.out + id;
-    o[0] = make_double2(-wxx.i, wxx.r);                  // i w (a - b ux^2)
-    o[a.plane_stride] = make_double2(wb.i * gxy, -(wb.r * gxy));   // -i w b ux uy
-    o[2 * a.plane_stride] = make_double2(-wyy.i, wyy.r);
-    o[3 * a.plane_stride] = make_double2(wb.i * gzx, -(wb.r * gzx));
-    o[4 * a.plane_stride] = make_double2(wb.i * gzy, -(wb.r * gzy));
-    o[5 * a.plane_stride] = make_double2(ci.r * ux, ci.i * ux);
-    o[6 * a.plane_stride] = make_double2(ci.r * uy, ci.i * uy);
-    o[7 * a.plane_stride] = make_double2(ci.r * uz, ci.i * uz);
+    grid_green(lx, ly, a.dxp, a.dyp, a.tx_off, a.ty_off, a.z, a.k, a.inv_k, a.out + id, a.plane_stride);
 }
 
-// current c = blockIdx.y of one field set into its padded plane: Jx = -Hy, Jy = Hx, Mx / Z = Ey / Z, My / Z = -Ex / Z
-// (the conversion of propagate_kernel's staging: field f = 3 - c, the same signs, the same division)
+// current c = blockIdx.y of one field set into its padded plane (grid_current)
 __global__ __launch_bounds__(256) void grid_pad_kernel(const d2 *fields, const int *row_first, d2 *cur, size_t plane_stride,
                                                        int nx, int ny, int Lx, int Ly, double Z) {
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
     const int i = (int)(id / Ly), j = (int)(id - (size_t)i * Ly);
-    const int c = blockIdx.y, f = 3 - c;
-    d2 v = make_double2(0.0, 0.0);
-    if (i < nx && j < ny) {
-        const int first = row_first ? row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
-        if (j >= first && j < ny - first) {
-            const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? Z : 1.0;
-            const d2 s = fields[((size_t)f * nx + i) * ny + j];
-            v = make_double2(sg * s.x / den, sg * s.y / den);
-        }
-    }
-    cur[c * plane_stride + id] = v;
+    const int c = blockIdx.y;
+    cur[c * plane_stride + id] = grid_current(fields, row_first, nx, ny, i, j, c, Z);
 }
 
-// acc += k v
-__device__ __forceinline__ void zfma(d2 &acc, d2 k, d2 v) {
-    acc.x = fma(-k.y, v.y, fma(k.x, v.x, acc.x));
-    acc.y = fma(k.y, v.x, fma(k.x, v.y, acc.y));
-}
-__device__ __forceinline__ d2 zmul(d2 k, d2 v) { return make_double2(fma(k.x, v.x, -(k.y * v.y)), fma(k.x, v.y, k.y * v.x)); }
-__device__ __forceinline__ d2 zneg(d2 v) { return make_double2(-v.x, -v.y); }
-
-// per bin: the 6 (3) output spectra from the 4 current spectra and the 8 kernel spectra (the table on top)
+// per bin: the 6 (3) output spectra from the 4 current spectra and the 8 kernel spectra (grid_products); the kernel
+// spectra by plain loads, here and not through a function (propagate_grid_dev.h grid_load_kernels)
 template <bool WANT_H>
 __global__ __launch_bounds__(256) void grid_contract_kernel(const d2 *K, const d2 *cur, d2 *out, size_t ps) {
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
-    const d2 Kxx = K[id], Kxy = K[ps + id], Kyy = K[2 * ps + id], Kzx = K[3 * ps + id], Kzy = K[4 * ps + id];
-    const d2 Cx = K[5 * ps + id], Cy = K[6 * ps + id], Cz = K[7 * ps + id];
-    const d2 Jx = cur[id], Jy = cur[ps + id], mx = cur[2 * ps + id], my = cur[3 * ps + id];
-    d2 e;
-    e = zmul(Kxx, Jx);
-    zfma(e, Kxy, Jy);
-    zfma(e, Cz, my);
-    out[id] = e;
-    e = zmul(Kxy, Jx);
-    zfma(e, Kyy, Jy);
-    zfma(e, zneg(Cz), mx);
-    out[ps + id] = e;
-    e = zmul(Kzx, Jx);
-    zfma(e, Kzy, Jy);
-    zfma(e, Cy, mx);
-    zfma(e, zneg(Cx), my);
-    out[2 * ps + id] = e;
+    d2 e[6];
+    const GridKernels8 k8 = {K[id],          K[ps + id],     K[2 * ps + id], K[3 * ps + id],
+                             K[4 * ps + id], K[5 * ps + id], K[6 * ps + id], K[7 * ps + id]};
+    grid_products<WANT_H, true>(e, k8, cur[id], cur[ps + id], cur[2 * ps + id], cur[3 * ps + id]);
+    out[id] = e[0];
+    out[ps + id] = e[1];
+    out[2 * ps + id] = e[2];
     if (WANT_H) {
-        e = zmul(Kxx, mx);
-        zfma(e, Kxy, my);
-        zfma(e, zneg(Cz), Jy);
-        out[3 * ps + id] = e;
-        e = zmul(Kxy, mx);
-        zfma(e, Kyy, my);
-        zfma(e, Cz, Jx);
-        out[4 * ps + id] = e;
-        e = zmul(Kzx, mx);
-        zfma(e, Kzy, my);
-        zfma(e, Cx, Jy);
-        zfma(e, zneg(Cy), Jx);
-        out[5 * ps + id] = e;
+        out[3 * ps + id] = e[3];
+        out[4 * ps + id] = e[4];
+        out[5 * ps + id] = e[5];
     }
 }
 
@@ -319,9 +253,7 @@ __global__ __launch_bounds__(256) void grid_crop_kernel(const d2 *out, size_t ps
     const int t = blockIdx.x * 256 + threadIdx.x, T = mx * my;
     if (t >= T) return;
     const int i = t / my, j = t - i * my, m = blockIdx.y;
-    const double scale = m < 3 ? scale_e : scale_h;
-    const d2 v = out[m * ps + (size_t)i * Ly + j];
-    result[(size_t)m * T + t] = make_double2(scale * v.x, scale * v.y);
+    grid_store_scaled(&result[(size_t)m * T + t], out[m * ps + (size_t)i * Ly + j], m, scale_e, scale_h);
 }
 
 template <typename Kern>
@@ -443,6 +375,23 @@ static int upload_twiddles(ml_ctx *ctx, DevBuf &buf, int L) {
 
 static int grid_cap(int method) { return method == ML_PROPAGATE_FFT_LONG ? GRID_L_LONG_MAX : GRID_L_MAX; }
 
+GridGeoArgs grid_geo(const PropagatePlan &pp, double tx_off, double ty_off, double z) {
+    const GridPlanFacts &f = pp.grid;
+    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
+    return {nullptr, (size_t)f.Lx * f.Ly, f.Lx, f.Ly, f.mx, f.my, tx_off, ty_off, pp.dxp, pp.dyp, z, k, 1.0 / k};
+}
+
+GridScales grid_scales(const PropagatePlan &pp, const GridPlanFacts &f, double Z0) {
+    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
+    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
+    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    return {Z, Z * scale_h * inv_n, scale_h * inv_n};
+}
+
+void grid_facts_of_tile(GridPlanFacts &f, const GridTilePlan &t, int m_x, int m_y, int64_t workspace_bytes) {
+    f = {t.nx, t.ny, m_x, m_y, t.x.L, t.y.L, t.outputs, t.plane_bytes, workspace_bytes};
+}
+
 // the workspace and the kernel spectra for the resident field's shape (kept while the shape stays)
 static int grid_prepare(ml_ctx *ctx) {
     PropagatePlan &pp = ctx->prop;
@@ -459,20 +408,8 @@ static int grid_prepare(ml_ctx *ctx) {
     ML_TRY(pp.grid_work.reserve((size_t)f.workspace_bytes));
     ML_TRY(upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
     ML_TRY(upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
-    GridGeoArgs g;
+    GridGeoArgs g = grid_geo(pp, pp.tx_off, pp.ty_off, pp.z);
     g.out = pp.grid_work.as<d2>();
-    g.plane_stride = (size_t)f.Lx * f.Ly;
-    g.Lx = f.Lx;
-    g.Ly = f.Ly;
-    g.mx = mx;
-    g.my = my;
-    g.tx_off = pp.tx_off;
-    g.ty_off = pp.ty_off;
-    g.dxp = pp.dxp;
-    g.dyp = pp.dyp;
-    g.z = pp.z;
-    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
-    g.inv_k = 1.0 / g.k;
     hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)(g.plane_stride / 256)), dim3(256), 0, ctx->stream, g);
     ML_HIP(hipGetLastError());
     ML_TRY(fft_rows<false>(ctx, g.out, GRID_KERNELS, f.Lx));
@@ -494,38 +431,15 @@ struct GridTileGeoArgs {
 };
 
 // the eight kernels of tile tile0 + blockIdx.y at every index of the tile's padded grid: index p holds the lag
-// (p < m ? p : p - L) - a B, which goes into the arithmetic of grid_fill_kernel unchanged
+// (p < m ? p : p - L) - a B, which goes into grid_green as grid_fill_kernel's lag does
 __global__ __launch_bounds__(256) void grid_tile_fill_kernel(const GridTileGeoArgs t) {
     const GridGeoArgs &a = t.g;
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly (a multiple of 256)
     const int tile = t.tile0 + blockIdx.y, ta = tile / t.cy, tb = tile - ta * t.cy;
     const int p = (int)(id / a.Ly), r = (int)(id - (size_t)p * a.Ly);
     const int lx = (p < a.mx ? p : p - a.Lx) - ta * t.Bx, ly = (r < a.my ? r : r - a.Ly) - tb * t.By;
-    const double dx = fma((double)lx, a.dxp, a.tx_off), dy = fma((double)ly, a.dyp, a.ty_off);
-    const double s_row = fma(dx, dx, a.z * a.z);
-    const double R = sqrt_exact(fma(dy, dy, s_row));
-    const double iR = recip(R);
-    const double ux = dx * iR, uy = dy * iR, uz = a.z * iR;
-    const double q = iR * a.inv_k, q2 = q * q;
-    double sn, cs;
-    sincos_cw(a.k * R, sn, cs);
-    const c2 w = {cs * q, sn * q};
-    const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
-    const c2 wb = cmulf(w, cb);
-    const c2 txx = {fma(-(ux * ux), cb.r, ca.r), fma(-(ux * ux), cb.i, ca.i)};
-    const c2 tyy = {fma(-(uy * uy), cb.r, ca.r), fma(-(uy * uy), cb.i, ca.i)};
-    const c2 wxx = cmulf(w, txx), wyy = cmulf(w, tyy);
-    const c2 ci = {fma(-q, w.r, -w.i), fma(-q, w.i, w.r)};   // w (i - q)
-    const double gxy = ux * uy, gzx = uz * ux, gzy = uz * uy;
-    d2 *o = a.out + (size_t)blockIdx.y * GRID_KERNELS * a.plane_stride + id;
-    o[0] = make_double2(-wxx.i, wxx.r);
-    o[a.plane_stride] = make_double2(wb.i * gxy, -(wb.r * gxy));
-    o[2 * a.plane_stride] = make_double2(-wyy.i, wyy.r);
-    o[3 * a.plane_stride] = make_double2(wb.i * gzx, -(wb.r * gzx));
-    o[4 * a.plane_stride] = make_double2(wb.i * gzy, -(wb.r * gzy));
-    o[5 * a.plane_stride] = make_double2(ci.r * ux, ci.i * ux);
-    o[6 * a.plane_stride] = make_double2(ci.r * uy, ci.i * uy);
-    o[7 * a.plane_stride] = make_double2(ci.r * uz, ci.i * uz);
+    grid_green(lx, ly, a.dxp, a.dyp, a.tx_off, a.ty_off, a.z, a.k, a.inv_k,
+               a.out + (size_t)blockIdx.y * GRID_KERNELS * a.plane_stride + id, a.plane_stride);
 }
 
 struct GridTilePadArgs {
@@ -537,71 +451,25 @@ struct GridTilePadArgs {
     double Z;
 };
 
-// current c = blockIdx.y of tile tile0 + blockIdx.z into its padded plane (the conversion of grid_pad_kernel): zeros
-// beyond the tile's samples, beyond the aperture and outside the row extents of a synthesised field
+// current c = blockIdx.y of tile tile0 + blockIdx.z into its padded plane (grid_current): zeros beyond the tile's samples,
+// beyond the aperture and outside the row extents of a synthesised field
 __global__ __launch_bounds__(256) void grid_tile_pad_kernel(const GridTilePadArgs a) {
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
     const int il = (int)(id / a.Ly), jl = (int)(id - (size_t)il * a.Ly);
     const int tile = a.tile0 + blockIdx.z, ta = tile / a.cy, tb = tile - ta * a.cy;
     const int i = ta * a.Bx + il, j = tb * a.By + jl;
-    const int c = blockIdx.y, f = 3 - c;
+    const int c = blockIdx.y;
     d2 v = make_double2(0.0, 0.0);
-    if (il < a.Bx && jl < a.By && i < a.nx && j < a.ny) {
-        const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
-        if (j >= first && j < a.ny - first) {
-            const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? a.Z : 1.0;
-            const d2 s = a.fields[((size_t)f * a.nx + i) * a.ny + j];
-            v = make_double2(sg * s.x / den, sg * s.y / den);
-        }
-    }
+    if (il < a.Bx && jl < a.By) v = grid_current(a.fields, a.row_first, a.nx, a.ny, i, j, c, a.Z);
     a.cur[((size_t)blockIdx.z * GRID_CURRENTS + c) * a.plane_stride + id] = v;
 }
 
-// a kernel spectrum is read once per pass: a streaming load
-__device__ __forceinline__ d2 ld_stream(const d2 *p) {
-    typedef double double2v __attribute__((ext_vector_type(2)));
-    const double2v t = __builtin_nontemporal_load(reinterpret_cast<const double2v *>(p));
-    return make_double2(t.x, t.y);
-}
-
-// e = k v (START) or e += k v
-template <bool START>
-__device__ __forceinline__ void zterm(d2 &e, d2 k, d2 v) {
-    if (START)
-        e = zmul(k, v);
-    else
-        zfma(e, k, v);
-}
-
-// the products of one tile in the term order of grid_contract_kernel (the table on top)
+// the products of one tile: its four currents, its kernel spectra by streaming loads, the term table
 template <bool WANT_H, bool START>
 __device__ __forceinline__ void tile_products(d2 (&e)[6], const d2 *K, const d2 *cur, size_t ps, size_t id) {
-    const d2 Kxx = ld_stream(K + id), Kxy = ld_stream(K + ps + id), Kyy = ld_stream(K + 2 * ps + id);
-    const d2 Kzx = ld_stream(K + 3 * ps + id), Kzy = ld_stream(K + 4 * ps + id);
-    const d2 Cx = ld_stream(K + 5 * ps + id), Cy = ld_stream(K + 6 * ps + id), Cz = ld_stream(K + 7 * ps + id);
+    const GridKernels8 k8 = grid_load_kernels(K, ps, id);
     const d2 Jx = cur[id], Jy = cur[ps + id], mx = cur[2 * ps + id], my = cur[3 * ps + id];
-    zterm<START>(e[0], Kxx, Jx);
-    zfma(e[0], Kxy, Jy);
-    zfma(e[0], Cz, my);
-    zterm<START>(e[1], Kxy, Jx);
-    zfma(e[1], Kyy, Jy);
-    zfma(e[1], zneg(Cz), mx);
-    zterm<START>(e[2], Kzx, Jx);
-    zfma(e[2], Kzy, Jy);
-    zfma(e[2], Cy, mx);
-    zfma(e[2], zneg(Cx), my);
-    if (WANT_H) {
-        zterm<START>(e[3], Kxx, mx);
-        zfma(e[3], Kxy, my);
-        zfma(e[3], zneg(Cz), Jy);
-        zterm<START>(e[4], Kxy, mx);
-        zfma(e[4], Kyy, my);
-        zfma(e[4], Cz, Jx);
-        zterm<START>(e[5], Kzx, mx);
-        zfma(e[5], Kzy, my);
-        zfma(e[5], Cx, Jy);
-        zfma(e[5], zneg(Cy), Jx);
-    }
+    grid_products<WANT_H, START>(e, k8, Jx, Jy, mx, my);
 }
 
 // per bin: the n tiles of a batch (K: the batch's first tile's spectra, cur: its currents) added in ascending order to
@@ -642,31 +510,13 @@ static int tile_prepare(ml_ctx *ctx) {
         return ML_EINVAL;
     }
     pp.tile = t;
-    GridPlanFacts &f = pp.grid;   // what the transform launchers read: the tile's lengths
-    f.nx = t.nx;
-    f.ny = t.ny;
-    f.Lx = t.x.L;
-    f.Ly = t.y.L;
-    f.outputs = t.outputs;
-    f.plane_bytes = t.plane_bytes;
-    f.workspace_bytes = t.workspace_bytes;
+    GridPlanFacts &f = pp.grid;
+    grid_facts_of_tile(f, t, f.mx, f.my, t.workspace_bytes);
     ML_TRY(pp.grid_work.reserve((size_t)t.workspace_bytes));
     ML_TRY(upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
     ML_TRY(upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
     GridTileGeoArgs a;
-    GridGeoArgs &g = a.g;
-    g.plane_stride = (size_t)f.Lx * f.Ly;
-    g.Lx = f.Lx;
-    g.Ly = f.Ly;
-    g.mx = f.mx;
-    g.my = f.my;
-    g.tx_off = pp.tx_off;
-    g.ty_off = pp.ty_off;
-    g.dxp = pp.dxp;
-    g.dyp = pp.dyp;
-    g.z = pp.z;
-    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
-    g.inv_k = 1.0 / g.k;
+    GridGeoArgs &g = a.g = grid_geo(pp, pp.tx_off, pp.ty_off, pp.z);
     a.cy = t.y.c;
     a.Bx = t.x.B;
     a.By = t.y.B;
@@ -691,6 +541,20 @@ static void launch_tile_contract(ml_ctx *ctx, unsigned blocks, bool first, const
         hipLaunchKernelGGL((grid_tile_contract_kernel<WANT_H, false>), dim3(blocks), dim3(256), 0, ctx->stream, K, cur, out, ps, n);
 }
 
+// the currents of the tiles [tile0, tile0 + nt) of the active plan (pp.tile, pp.grid) and their forward transforms: what the
+// tiled, the fine and the stack pass do with a batch of tiles of a field set
+int grid_tile_currents(ml_ctx *ctx, const double2 *fields, double Z, double2 *cur, int tile0, int nt, int rows_fwd) {
+    const PropagatePlan &pp = ctx->prop;
+    const GridPlanFacts &f = pp.grid;
+    const GridTilePlan &t = pp.tile;
+    const int *row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
+    const GridTilePadArgs p = {fields, row_first, cur, (size_t)f.Lx * f.Ly, t.nx, t.ny, f.Lx, f.Ly, t.x.B, t.y.B, tile0, t.y.c, Z};
+    hipLaunchKernelGGL(grid_tile_pad_kernel, dim3((unsigned)(p.plane_stride / 256), GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
+    ML_HIP(hipGetLastError());
+    ML_TRY(fft_rows<false>(ctx, cur, nt * GRID_CURRENTS, rows_fwd));
+    return fft_cols<false>(ctx, cur, nt * GRID_CURRENTS);
+}
+
 static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
     PropagatePlan &pp = ctx->prop;
     pp.have_result = false;
@@ -701,32 +565,14 @@ static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
     ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
     const size_t ps = (size_t)f.Lx * f.Ly;
     d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)t.tiles * GRID_KERNELS * ps, *out = cur + (size_t)t.batch * GRID_CURRENTS * ps;
-    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
-    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
-    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const GridScales sc = grid_scales(pp, f, Z0);
     const unsigned blocks = (unsigned)(ps / 256);
     const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
-    GridTilePadArgs p;
-    p.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
-    p.cur = cur;
-    p.plane_stride = ps;
-    p.nx = t.nx;
-    p.ny = t.ny;
-    p.Lx = f.Lx;
-    p.Ly = f.Ly;
-    p.Bx = t.x.B;
-    p.By = t.y.B;
-    p.cy = t.y.c;
-    p.Z = Z;
     for (int m = 0; m < n; ++m) {
-        p.fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
+        const d2 *fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
         for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {
             const int nt = std::min(t.batch, t.tiles - tile0);
-            p.tile0 = tile0;
-            hipLaunchKernelGGL(grid_tile_pad_kernel, dim3(blocks, GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
-            ML_HIP(hipGetLastError());
-            ML_TRY(fft_rows<false>(ctx, cur, nt * GRID_CURRENTS, rows_fwd));
-            ML_TRY(fft_cols<false>(ctx, cur, nt * GRID_CURRENTS));
+            ML_TRY(grid_tile_currents(ctx, fields, sc.Z, cur, tile0, nt, rows_fwd));
             const d2 *Kt = K + (size_t)tile0 * GRID_KERNELS * ps;
             if (pp.want_h)
                 launch_tile_contract<true>(ctx, blocks, tile0 == 0, Kt, cur, out, ps, nt);
@@ -737,7 +583,7 @@ static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
         ML_TRY(fft_cols<true>(ctx, out, nc));
         ML_TRY(fft_rows<true>(ctx, out, nc, f.mx));
         hipLaunchKernelGGL(grid_crop_kernel, dim3((T + 255) / 256, nc), dim3(256), 0, ctx->stream, out, ps,
-                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, Z * scale_h * inv_n, scale_h * inv_n);
+                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, sc.scale_e, sc.scale_h);
         ML_HIP(hipGetLastError());
     }
     pp.have_result = true;
@@ -753,34 +599,10 @@ static int propagate_tile_sets(ml_ctx *ctx, double Z0, int first, int n) {
 // pass; outputs [2][6 or 3].  Then lattice by lattice, in pairs (a single one last if Ax Ay is odd): contraction over
 // all tiles in ascending order, ONE inverse transform of the pair's planes, scatter into the interleaved result.
 
-// the products of one tile and one lattice from currents already loaded: tile_products, term by term
+// the products of one tile and one lattice from currents already loaded
 template <bool WANT_H, bool START>
 __device__ __forceinline__ void fine_products(d2 (&e)[6], const d2 *K, size_t ps, size_t id, d2 Jx, d2 Jy, d2 mx, d2 my) {
-    const d2 Kxx = ld_stream(K + id), Kxy = ld_stream(K + ps + id), Kyy = ld_stream(K + 2 * ps + id);
-    const d2 Kzx = ld_stream(K + 3 * ps + id), Kzy = ld_stream(K + 4 * ps + id);
-    const d2 Cx = ld_stream(K + 5 * ps + id), Cy = ld_stream(K + 6 * ps + id), Cz = ld_stream(K + 7 * ps + id);
-    zterm<START>(e[0], Kxx, Jx);
-    zfma(e[0], Kxy, Jy);
-    zfma(e[0], Cz, my);
-    zterm<START>(e[1], Kxy, Jx);
-    zfma(e[1], Kyy, Jy);
-    zfma(e[1], zneg(Cz), mx);
-    zterm<START>(e[2], Kzx, Jx);
-    zfma(e[2], Kzy, Jy);
-    zfma(e[2], Cy, mx);
-    zfma(e[2], zneg(Cx), my);
-    if (WANT_H) {
-        zterm<START>(e[3], Kxx, mx);
-        zfma(e[3], Kxy, my);
-        zfma(e[3], zneg(Cz), Jy);
-        zterm<START>(e[4], Kxy, mx);
-        zfma(e[4], Kyy, my);
-        zfma(e[4], Cz, Jx);
-        zterm<START>(e[5], Kzx, mx);
-        zfma(e[5], Kzy, my);
-        zfma(e[5], Cx, Jy);
-        zfma(e[5], zneg(Cy), Jx);
-    }
+    grid_products<WANT_H, START>(e, grid_load_kernels(K, ps, id), Jx, Jy, mx, my);
 }
 
 // per bin: the n tiles of a launch (cur: the first one's currents) added in ascending order to the 6 (3) output spectra
@@ -838,9 +660,8 @@ __global__ __launch_bounds__(256) void grid_fine_scatter_kernel(const GridFineSc
     const int i = t / s.m_cy, j = t - i * s.m_cy, m = blockIdx.y, l = blockIdx.z;
     const int fi = s.a[l] + s.sx * i, fj = s.b[l] + s.sy * j;
     if (fi >= s.mx || fj >= s.my) return;
-    const double scale = m < 3 ? s.scale_e : s.scale_h;
-    const d2 v = s.out[((size_t)l * s.nc + m) * s.plane_stride + (size_t)i * s.Ly + j];
-    s.result[(size_t)m * s.mx * s.my + (size_t)fi * s.my + fj] = make_double2(scale * v.x, scale * v.y);
+    grid_store_scaled(&s.result[(size_t)m * s.mx * s.my + (size_t)fi * s.my + fj],
+                      s.out[((size_t)l * s.nc + m) * s.plane_stride + (size_t)i * s.Ly + j], m, s.scale_e, s.scale_h);
 }
 
 // (diagnostic build: ML_GRID_FINE_PAIR=1 contracts one lattice per read of the currents, for timing)
@@ -853,19 +674,7 @@ static int fine_kernels(ml_ctx *ctx, int a, int b, int tile0, int nt, d2 *K) {
     const GridPlanFacts &f = pp.grid;
     const GridTilePlan &t = pp.fine.tile;
     GridTileGeoArgs ta;
-    GridGeoArgs &g = ta.g;
-    g.plane_stride = (size_t)f.Lx * f.Ly;
-    g.Lx = f.Lx;
-    g.Ly = f.Ly;
-    g.mx = f.mx;
-    g.my = f.my;
-    g.tx_off = pp.fine_tx[a];
-    g.ty_off = pp.fine_ty[b];
-    g.dxp = pp.dxp;
-    g.dyp = pp.dyp;
-    g.z = pp.z;
-    g.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
-    g.inv_k = 1.0 / g.k;
+    GridGeoArgs &g = ta.g = grid_geo(pp, pp.fine_tx[a], pp.fine_ty[b], pp.z);
     ta.cy = t.y.c;
     ta.Bx = t.x.B;
     ta.By = t.y.B;
@@ -896,16 +705,8 @@ static int fine_prepare(ml_ctx *ctx) {
     }
     pp.fine = p;
     const GridTilePlan &t = pp.tile = p.tile;
-    GridPlanFacts &f = pp.grid;   // what the transform launchers read: the tile's lengths
-    f.nx = t.nx;
-    f.ny = t.ny;
-    f.mx = p.m_cx;
-    f.my = p.m_cy;
-    f.Lx = t.x.L;
-    f.Ly = t.y.L;
-    f.outputs = t.outputs;
-    f.plane_bytes = t.plane_bytes;
-    f.workspace_bytes = p.workspace_bytes;
+    GridPlanFacts &f = pp.grid;
+    grid_facts_of_tile(f, t, p.m_cx, p.m_cy, p.workspace_bytes);
     if (pp.grid_work.reserve((size_t)p.workspace_bytes) != ML_OK) {
         if (p.cache_kernels) {
             GridFinePlan streamed;
@@ -970,22 +771,9 @@ static int propagate_fine_sets(ml_ctx *ctx, double Z0, int first, int n) {
     const size_t k_lattice = (size_t)(fp.cache_kernels ? t.tiles : t.batch) * GRID_KERNELS * ps;
     d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)(fp.cache_kernels ? lattices : GRID_FINE_PAIR) * k_lattice;
     d2 *out = cur + (size_t)t.tiles * GRID_CURRENTS * ps;
-    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
-    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
-    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const GridScales sc = grid_scales(pp, f, Z0);
     const unsigned blocks = (unsigned)(ps / 256);
     const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
-    GridTilePadArgs p;
-    p.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
-    p.plane_stride = ps;
-    p.nx = t.nx;
-    p.ny = t.ny;
-    p.Lx = f.Lx;
-    p.Ly = f.Ly;
-    p.Bx = t.x.B;
-    p.By = t.y.B;
-    p.cy = t.y.c;
-    p.Z = Z;
     GridFineScatterArgs s;
     s.out = out;
     s.plane_stride = ps;
@@ -997,19 +785,13 @@ static int propagate_fine_sets(ml_ctx *ctx, double Z0, int first, int n) {
     s.my = fp.my;
     s.sx = fp.sx;
     s.sy = fp.sy;
-    s.scale_e = Z * scale_h * inv_n;
-    s.scale_h = scale_h * inv_n;
+    s.scale_e = sc.scale_e;
+    s.scale_h = sc.scale_h;
     for (int m = 0; m < n; ++m) {
-        p.fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
-        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {   // the current spectra of every tile, once per set
-            const int nt = std::min(t.batch, t.tiles - tile0);
-            p.tile0 = tile0;
-            p.cur = cur + (size_t)tile0 * GRID_CURRENTS * ps;
-            hipLaunchKernelGGL(grid_tile_pad_kernel, dim3(blocks, GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
-            ML_HIP(hipGetLastError());
-            ML_TRY(fft_rows<false>(ctx, p.cur, nt * GRID_CURRENTS, rows_fwd));
-            ML_TRY(fft_cols<false>(ctx, p.cur, nt * GRID_CURRENTS));
-        }
+        const d2 *fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
+        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch)   // the current spectra of every tile, once per set
+            ML_TRY(grid_tile_currents(ctx, fields, sc.Z, cur + (size_t)tile0 * GRID_CURRENTS * ps, tile0,
+                                      std::min(t.batch, t.tiles - tile0), rows_fwd));
         s.result = pp.result.as<d2>() + (size_t)m * nc * T;
         for (int l0 = 0; l0 < lattices; l0 += pair) {
             const int nl = std::min(pair, lattices - l0);
@@ -1050,9 +832,7 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
     const size_t ps = (size_t)f.Lx * f.Ly;
     d2 *K = pp.grid_work.as<d2>(), *cur = K + GRID_KERNELS * ps, *out = cur + GRID_CURRENTS * ps;
-    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
-    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
-    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const GridScales sc = grid_scales(pp, f, Z0);
     const unsigned blocks = (unsigned)(ps / 256);
     // rows that are zero need no transform (diagnostic build: ML_GRID_ALL_ROWS=1 transforms them all, for timing)
     const bool all_rows = diag_int("ML_GRID_ALL_ROWS", 0) != 0;
@@ -1062,7 +842,7 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
         hipLaunchKernelGGL(grid_pad_kernel, dim3(blocks, GRID_CURRENTS), dim3(256), 0, ctx->stream, fields,
                            ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr, cur, ps,
                            ctx->fields.nx, ctx->fields.ny,
-                           f.Lx, f.Ly, Z);
+                           f.Lx, f.Ly, sc.Z);
         ML_HIP(hipGetLastError());
         ML_TRY(fft_rows<false>(ctx, cur, GRID_CURRENTS, rows_fwd));
         ML_TRY(fft_cols<false>(ctx, cur, GRID_CURRENTS));
@@ -1074,7 +854,7 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
         ML_TRY(fft_cols<true>(ctx, out, nc));
         ML_TRY(fft_rows<true>(ctx, out, nc, rows_inv));
         hipLaunchKernelGGL(grid_crop_kernel, dim3((T + 255) / 256, nc), dim3(256), 0, ctx->stream, out, ps,
-                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, Z * scale_h * inv_n, scale_h * inv_n);
+                           pp.result.as<d2>() + (size_t)m * nc * T, f.mx, f.my, f.Ly, sc.scale_e, sc.scale_h);
         ML_HIP(hipGetLastError());
     }
     pp.have_result = true;
@@ -1082,7 +862,7 @@ int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n) {
     return ML_OK;
 }
 
-// what propagate_stack.hip goes through (propagate_grid_launch.h)
+// what propagate_stack.hip goes through (propagate_grid_launch.h) beside grid_tile_currents and the helpers above
 int grid_fft_rows(ml_ctx *ctx, double2 *planes, int n_planes, int rows, bool inverse) {
     return inverse ? fft_rows<true>(ctx, planes, n_planes, rows) : fft_rows<false>(ctx, planes, n_planes, rows);
 }
@@ -1117,6 +897,15 @@ static int fine_origins_ok(const char *entry, const char *axis, const double *fi
     ML_REQUIRE(first[active - 1] - first[0] < pitch, "%s: the %s origins of the lattices must span less than the aperture's pitch "
                "%.17g: %s_first[%d] - %s_first[0] = %.17g", entry, axis, pitch, axis, active - 1, axis, first[active - 1] - first[0]);
     return ML_OK;
+}
+
+// every refusal of an entry names it: the name in front of a message that lacks it; -> rc
+static int named_refusal(const char *entry, int rc) {
+    if (rc != ML_OK && strncmp(ml_last_error(), entry, strlen(entry)) != 0) {
+        const std::string said = ml_last_error();
+        set_error("%s: %s", entry, said.c_str());
+    }
+    return rc;
 }
 
 // ml_propagate_plan_grid, ml_propagate_plan_grid_long, ml_propagate_plan_grid_tiled, ml_propagate_plan_grid_fine and
@@ -1265,13 +1054,8 @@ int ml_propagate_plan_grid_fine(ml_ctx *ctx, double x0, double y0, double dxp, d
     ML_REQUIRE(tx_first && ty_first, "ml_propagate_plan_grid_fine: NULL argument");
     const FineAsk fine = {tx_first, ty_first, sx, sy, cache_kernels};
     const char *entry = "ml_propagate_plan_grid_fine";
-    const int rc = plan_grid(ctx, entry, ML_PROPAGATE_FFT_FINE, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0], ty_first[0], mx,
-                             my, z, want_h, tile_lx, tile_ly, &fine);
-    if (rc != ML_OK && strncmp(ml_last_error(), entry, strlen(entry)) != 0) {   // every refusal names this entry
-        const std::string said = ml_last_error();
-        set_error("%s: %s", entry, said.c_str());
-    }
-    return rc;
+    return named_refusal(entry, plan_grid(ctx, entry, ML_PROPAGATE_FFT_FINE, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0],
+                                          ty_first[0], mx, my, z, want_h, tile_lx, tile_ly, &fine));
 }
 
 int ml_propagate_plan_grid_stack(ml_ctx *ctx, double x0, double y0, double dxp, double dyp, double wavelength, double n_glass,
@@ -1289,13 +1073,8 @@ int ml_propagate_plan_grid_stack(ml_ctx *ctx, double x0, double y0, double dxp, 
     FineAsk fine = {tx_first, ty_first, sx, sy, cache_kernels};
     fine.z = z;
     fine.nz = nz;
-    const int rc = plan_grid(ctx, entry, ML_PROPAGATE_FFT_STACK, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0], ty_first[0], mx,
-                             my, *std::max_element(z, z + nz), want_h, tile_lx, tile_ly, &fine);
-    if (rc != ML_OK && strncmp(ml_last_error(), entry, strlen(entry)) != 0) {   // every refusal names this entry
-        const std::string said = ml_last_error();
-        set_error("%s: %s", entry, said.c_str());
-    }
-    return rc;
+    return named_refusal(entry, plan_grid(ctx, entry, ML_PROPAGATE_FFT_STACK, x0, y0, dxp, dyp, wavelength, n_glass, tx_first[0],
+                                          ty_first[0], mx, my, *std::max_element(z, z + nz), want_h, tile_lx, tile_ly, &fine));
 }
 
 int ml_propagate_plan_planes(ml_ctx *ctx, int *nz) {

@@ -5,7 +5,8 @@
 // (a, b), an origin (tx_off, ty_off) on the pitch.  A plane at another z is one more such set of kernels: here a LAYER is
 // (plane p, lattice (a, b)), l = p Ax Ay + a Ay + b, and its (tx_off, ty_off, z) come from a table in device memory that
 // the plan entry uploads once (GridStackLayerRow).  Per field set:
-//   1. the currents of every tile are padded and transformed once, in the batches of the tiled plan, and kept;
+//   1. the currents of every tile are padded and transformed once, in the batches of the tiled plan, and kept
+//      (grid_tile_currents: the tiled plan's own pad kernel and launch);
 //   2. the layers go GRID_FINE_PAIR at a time, a single one last if their number is odd - a pair may straddle two planes:
 //        cached:    one contraction over all tiles (the kernel spectra [layers][tiles][8] are filled by the first pass on a
 //                   shape and kept while the plan and the shape stay);
@@ -14,12 +15,12 @@
 //                   contraction - FIRST on the first batch only;
 //   3. one inverse transform of the pair's 2 x (6 or 3) planes, rows [0, m_cx);
 //   4. the scatter into result[component][(p mx + a + sx i) my + b + sy j].
-// The transforms and the contraction are propagate_grid.hip's own kernels through its launchers
-// (propagate_grid_launch.h); the fill has the arithmetic of grid_tile_fill_kernel operation for operation, the pad that
-// of grid_tile_pad_kernel and the scatter the scales of grid_fine_scatter_kernel, so plane p of a stack has the bits of
-// the fine plan planned at z[p].  The result is [set][6 or 3][T], T = nz mx my, plane-major: ml_propagate,
-// ml_propagate_sets, the downloads, ml_propagate_accumulate and ml_propagate_sums read T alone and serve it unchanged.
-#include "nearfield_math.h"
+// The transforms, the pad and the contraction are propagate_grid.hip's own kernels through its launchers
+// (propagate_grid_launch.h); the fill calls the grid_green of grid_tile_fill_kernel and the scatter the grid_store_scaled
+// of grid_fine_scatter_kernel (propagate_grid_dev.h), so plane p of a stack has the bits of the fine plan planned at z[p].
+// The result is [set][6 or 3][T], T = nz mx my, plane-major: ml_propagate, ml_propagate_sets, the downloads,
+// ml_propagate_accumulate and ml_propagate_sums read T alone and serve it unchanged.
+#include "propagate_grid_dev.h"
 #include "propagate_grid_launch.h"
 
 namespace ml {
@@ -37,8 +38,8 @@ struct GridStackFillArgs {
 };
 
 // the eight kernels of tile tile0 + blockIdx.y and layer blockIdx.z of the launch at every index of the tile's padded
-// grid: index p holds the lag (p < m ? p : p - L) - a B; the layer's origin and plane are uniform loads from the table.
-// From the lag on, grid_tile_fill_kernel operation for operation.
+// grid: index p holds the lag (p < m ? p : p - L) - a B, as in grid_tile_fill_kernel; the layer's origin and plane are
+// uniform loads from the table
 __global__ __launch_bounds__(256) void grid_stack_fill_kernel(const GridStackFillArgs t) {
     const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly (a multiple of 256)
     const GridStackLayerRow &layer = t.layers[blockIdx.z];
@@ -46,60 +47,8 @@ __global__ __launch_bounds__(256) void grid_stack_fill_kernel(const GridStackFil
     const int tile = t.tile0 + blockIdx.y, ta = tile / t.cy, tb = tile - ta * t.cy;
     const int p = (int)(id / t.Ly), r = (int)(id - (size_t)p * t.Ly);
     const int lx = (p < t.mx ? p : p - t.Lx) - ta * t.Bx, ly = (r < t.my ? r : r - t.Ly) - tb * t.By;
-    const double dx = fma((double)lx, t.dxp, tx_off), dy = fma((double)ly, t.dyp, ty_off);
-    const double s_row = fma(dx, dx, z * z);
-    const double R = sqrt_exact(fma(dy, dy, s_row));
-    const double iR = recip(R);
-    const double ux = dx * iR, uy = dy * iR, uz = z * iR;
-    const double q = iR * t.inv_k, q2 = q * q;
-    double sn, cs;
-    sincos_cw(t.k * R, sn, cs);
-    const c2 w = {cs * q, sn * q};
-    const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
-    const c2 wb = cmulf(w, cb);
-    const c2 txx = {fma(-(ux * ux), cb.r, ca.r), fma(-(ux * ux), cb.i, ca.i)};
-    const c2 tyy = {fma(-(uy * uy), cb.r, ca.r), fma(-(uy * uy), cb.i, ca.i)};
-    const c2 wxx = cmulf(w, txx), wyy = cmulf(w, tyy);
-    const c2 ci = {fma(-q, w.r, -w.i), fma(-q, w.i, w.r)};   // w (i - q)
-    const double gxy = ux * uy, gzx = uz * ux, gzy = uz * uy;
-    d2 *o = t.out + (size_t)blockIdx.z * t.layer_stride + (size_t)blockIdx.y * GRID_KERNELS * t.plane_stride + id;
-    o[0] = make_double2(-wxx.i, wxx.r);
-    o[t.plane_stride] = make_double2(wb.i * gxy, -(wb.r * gxy));
-    o[2 * t.plane_stride] = make_double2(-wyy.i, wyy.r);
-    o[3 * t.plane_stride] = make_double2(wb.i * gzx, -(wb.r * gzx));
-    o[4 * t.plane_stride] = make_double2(wb.i * gzy, -(wb.r * gzy));
-    o[5 * t.plane_stride] = make_double2(ci.r * ux, ci.i * ux);
-    o[6 * t.plane_stride] = make_double2(ci.r * uy, ci.i * uy);
-    o[7 * t.plane_stride] = make_double2(ci.r * uz, ci.i * uz);
-}
-
-struct GridStackPadArgs {
-    const d2 *fields;       // one field set [4][nx][ny]
-    const int *row_first;   // of a synthesised field, or NULL
-    d2 *cur;                // [tiles of the launch][4][Lx][Ly]
-    size_t plane_stride;
-    int nx, ny, Lx, Ly, Bx, By, tile0, cy;
-    double Z;
-};
-
-// current c = blockIdx.y of tile tile0 + blockIdx.z into its padded plane: grid_tile_pad_kernel, the same conversion, the
-// same zeros (that kernel and its launch stay in propagate_grid.hip, whose launches its tests pin)
-__global__ __launch_bounds__(256) void grid_stack_pad_kernel(const GridStackPadArgs a) {
-    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;   // < Lx Ly
-    const int il = (int)(id / a.Ly), jl = (int)(id - (size_t)il * a.Ly);
-    const int tile = a.tile0 + blockIdx.z, ta = tile / a.cy, tb = tile - ta * a.cy;
-    const int i = ta * a.Bx + il, j = tb * a.By + jl;
-    const int c = blockIdx.y, f = 3 - c;
-    d2 v = make_double2(0.0, 0.0);
-    if (il < a.Bx && jl < a.By && i < a.nx && j < a.ny) {
-        const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
-        if (j >= first && j < a.ny - first) {
-            const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? a.Z : 1.0;
-            const d2 s = a.fields[((size_t)f * a.nx + i) * a.ny + j];
-            v = make_double2(sg * s.x / den, sg * s.y / den);
-        }
-    }
-    a.cur[((size_t)blockIdx.z * GRID_CURRENTS + c) * a.plane_stride + id] = v;
+    grid_green(lx, ly, t.dxp, t.dyp, tx_off, ty_off, z, t.k, t.inv_k,
+               t.out + (size_t)blockIdx.z * t.layer_stride + (size_t)blockIdx.y * GRID_KERNELS * t.plane_stride + id, t.plane_stride);
 }
 
 struct GridStackScatterArgs {
@@ -123,9 +72,8 @@ __global__ __launch_bounds__(256) void grid_stack_scatter_kernel(const GridStack
     const GridStackLayerRow &layer = s.layers[l];
     const int fi = layer.a + s.sx * i, fj = layer.b + s.sy * j;
     if (fi >= s.mx || fj >= s.my) return;
-    const double scale = m < 3 ? s.scale_e : s.scale_h;
-    const d2 v = s.out[((size_t)l * s.nc + m) * s.plane_stride + (size_t)i * s.Ly + j];
-    s.result[(size_t)m * s.T + ((size_t)layer.p * s.mx + fi) * s.my + fj] = make_double2(scale * v.x, scale * v.y);
+    grid_store_scaled(&s.result[(size_t)m * s.T + ((size_t)layer.p * s.mx + fi) * s.my + fj],
+                      s.out[((size_t)l * s.nc + m) * s.plane_stride + (size_t)i * s.Ly + j], m, s.scale_e, s.scale_h);
 }
 
 // the eight kernels of the tiles [tile0, tile0 + nt), nt <= GRID_TILE_BATCH_MAX, of the nl layers from l0 on into K
@@ -134,23 +82,9 @@ static int stack_kernels(ml_ctx *ctx, int l0, int nl, int tile0, int nt, d2 *K, 
     const PropagatePlan &pp = ctx->prop;
     const GridPlanFacts &f = pp.grid;
     const GridTilePlan &t = pp.fine.tile;
-    GridStackFillArgs a;
-    a.out = K;
-    a.plane_stride = (size_t)f.Lx * f.Ly;
-    a.layer_stride = layer_stride;
-    a.layers = pp.stack_layers.as<GridStackLayerRow>() + l0;
-    a.Lx = f.Lx;
-    a.Ly = f.Ly;
-    a.mx = f.mx;
-    a.my = f.my;
-    a.tile0 = tile0;
-    a.cy = t.y.c;
-    a.Bx = t.x.B;
-    a.By = t.y.B;
-    a.dxp = pp.dxp;
-    a.dyp = pp.dyp;
-    a.k = 2.0 * M_PI * pp.n_glass / pp.wavelength;
-    a.inv_k = 1.0 / a.k;
+    const GridGeoArgs g = grid_geo(pp, 0.0, 0.0, 0.0);   // (the origin and the plane: per layer, from the table)
+    GridStackFillArgs a = {nullptr, g.plane_stride, layer_stride, nullptr, g.Lx, g.Ly, g.mx, g.my, tile0, t.y.c, t.x.B, t.y.B,
+                           g.dxp, g.dyp, g.k, g.inv_k};   // (out, layers: per launch)
     // what a launch fills goes through the row pass next: all nl layers in one launch where that fits the memory-side
     // cache, else layer by layer (propagate_grid.h grid_stack_fill_layers)
     const int per_launch = grid_stack_fill_layers(nl, nt, f.plane_bytes);
@@ -185,16 +119,8 @@ static int stack_prepare(ml_ctx *ctx) {
     }
     const GridFinePlan &p = pp.fine = s.fine;
     const GridTilePlan &t = pp.tile = p.tile;
-    GridPlanFacts &f = pp.grid;   // what the transform launchers read: the tile's lengths
-    f.nx = t.nx;
-    f.ny = t.ny;
-    f.mx = p.m_cx;
-    f.my = p.m_cy;
-    f.Lx = t.x.L;
-    f.Ly = t.y.L;
-    f.outputs = t.outputs;
-    f.plane_bytes = t.plane_bytes;
-    f.workspace_bytes = s.workspace_bytes;
+    GridPlanFacts &f = pp.grid;
+    grid_facts_of_tile(f, t, p.m_cx, p.m_cy, s.workspace_bytes);
     if (pp.grid_work.reserve((size_t)s.workspace_bytes) != ML_OK) {
         if (p.cache_kernels) {
             GridStackPlan streamed;
@@ -240,22 +166,9 @@ int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n) {
     const size_t k_layer = (size_t)(fp.cache_kernels ? t.tiles : t.batch) * GRID_KERNELS * ps;
     d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)(fp.cache_kernels ? layers : GRID_FINE_PAIR) * k_layer;
     d2 *out = cur + (size_t)t.tiles * GRID_CURRENTS * ps;
-    const double k = 2.0 * M_PI * pp.n_glass / pp.wavelength, Z = Z0 / pp.n_glass;
-    const double scale_h = k * k / (4.0 * M_PI) * pp.dxp * pp.dyp;
-    const double inv_n = 1.0 / ((double)f.Lx * (double)f.Ly);   // a power of two
+    const GridScales sc = grid_scales(pp, f, Z0);
     const unsigned blocks = (unsigned)(ps / 256);
     const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
-    GridStackPadArgs p;
-    p.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : (const int *)nullptr;
-    p.plane_stride = ps;
-    p.nx = t.nx;
-    p.ny = t.ny;
-    p.Lx = f.Lx;
-    p.Ly = f.Ly;
-    p.Bx = t.x.B;
-    p.By = t.y.B;
-    p.cy = t.y.c;
-    p.Z = Z;
     GridStackScatterArgs s;
     s.out = out;
     s.plane_stride = ps;
@@ -268,19 +181,13 @@ int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n) {
     s.my = fp.my;
     s.sx = fp.sx;
     s.sy = fp.sy;
-    s.scale_e = Z * scale_h * inv_n;
-    s.scale_h = scale_h * inv_n;
+    s.scale_e = sc.scale_e;
+    s.scale_h = sc.scale_h;
     for (int m = 0; m < n; ++m) {
-        p.fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
-        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {   // the current spectra of every tile, once per set
-            const int nt = std::min(t.batch, t.tiles - tile0);
-            p.tile0 = tile0;
-            p.cur = cur + (size_t)tile0 * GRID_CURRENTS * ps;
-            hipLaunchKernelGGL(grid_stack_pad_kernel, dim3(blocks, GRID_CURRENTS, nt), dim3(256), 0, ctx->stream, p);
-            ML_HIP(hipGetLastError());
-            ML_TRY(grid_fft_rows(ctx, p.cur, nt * GRID_CURRENTS, rows_fwd, false));
-            ML_TRY(grid_fft_cols(ctx, p.cur, nt * GRID_CURRENTS, false));
-        }
+        const d2 *fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
+        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch)   // the current spectra of every tile, once per set
+            ML_TRY(grid_tile_currents(ctx, fields, sc.Z, cur + (size_t)tile0 * GRID_CURRENTS * ps, tile0,
+                                      std::min(t.batch, t.tiles - tile0), rows_fwd));
         s.result = pp.result.as<d2>() + (size_t)m * nc * T;
         for (int l0 = 0; l0 < layers; l0 += GRID_FINE_PAIR) {
             const int nl = std::min(GRID_FINE_PAIR, layers - l0);

@@ -98,7 +98,9 @@ DIAGNOSTIC = frozenset(['grid_rows_top_kernel<1>'])
 RESIDENT = {
     'grid_pad_kernel/row-extents': (('test_gpu_propagate_grid', 'test_resident_equals_uploaded'),),
     'grid_tile_pad_kernel/row-extents': (('test_gpu_propagate_grid_tiled', 'test_resident_equals_uploaded'),
-                                         ('test_gpu_propagate_grid_fine', 'test_resident_equals_uploaded')),
+                                         ('test_gpu_propagate_grid_fine', 'test_resident_equals_uploaded'),
+                                         # the stack pads through the tiled plan's kernel and launch
+                                         ('test_gpu_propagate_grid_stack', 'test_resident_equals_uploaded')),
 }
 
 # ---- the existing cases ----------------------------------------------------------------------------------------------
