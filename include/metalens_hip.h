@@ -600,6 +600,48 @@ int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, doub
 #define ML_OTF_FREQ_MAX 64
 int ml_propagate_otf(ml_ctx *ctx, int source, int mx, int my, int planes, const double *u, int nu, const double *v,
                      int nv, double *otf);
+/* Per-zone power and wavefront overlap of the resident near field, reduced on the GPU (csrc/fields_zones.hip): for every
+ * zone of a list of ring edges about a centre - with the edges of a lens layout, zone 0 is the centre and zone z ring
+ * z - 1 - and for n_sets field sets in one pass the members, the sums of Sz, |Ex|^2, |Ey|^2 and the overlaps sum Ex conj(w),
+ * sum Ey conj(w) with a reference wave w = exp(i phi): which rings lose power or sit off phase, without the fields
+ * crossing PCIe.
+ *   first_set, n_sets : the resident sets first_set ... first_set + n_sets - 1, 1 <= n_sets <= 3 (a synthesis batch); zone,
+ *                       phase and sincos of a sample are computed once for all of them
+ *   x2, nx, y2, ny    : X2[i] = (x[i] - xc)^2 and Y2[j] = (y[j] - yc)^2 as the host formed them; nx, ny must be the resident
+ *                       shape; finite, >= 0, and y2 must fall to its minimum and rise again (an axis in order)
+ *   e2, n_edges       : 1 <= n_edges <= ML_ZONES_EDGES_MAX squared edges, finite, >= 0, not decreasing.  Sample (i, j) has
+ *                       r2 = X2[i] + Y2[j] (one rounded addition) and lies in zone searchsorted(e2, r2, side = 'left'): zone 0
+ *                       is the disc r2 <= e2[0], zone z the ring e2[z - 1] < r2 <= e2[z], a sample on an edge belongs to
+ *                       the inner zone, a sample beyond the last edge to none
+ *   ref_mode, ra, rb, ref_c, k : the reference phase from two per-axis arrays [nx], [ny] and two scalars.
+ *                       ML_ZONES_REF_PLANE: phi = ra[i] + rb[j] (ref_c and k are not read).  ML_ZONES_REF_FOCUS:
+ *                       phi = -sign(ref_c) (k sqrt((ra[i] + rb[j]) + ref_c ref_c)) with ra, rb >= 0 the squared distances to the
+ *                       focus per axis, ref_c = zf != 0 its distance behind (> 0) or in front of the aperture, k > 0; the
+ *                       square root is correctly rounded.  (cos phi, sin phi) by the Cody-Waite reduction of the propagators
+ *   records           : HOST, [n_sets][n_edges][record_doubles], record_doubles >= ML_ZONES_RECORD.  A record:
+ *                       [0] the members  [1] sum S, S = 0.5 ((Ex.r Hy.r + Ex.i Hy.i) - (Ey.r Hx.r + Ey.i Hx.i))
+ *                       [2] sum Ex.r^2 + Ex.i^2  [3] the same of Ey  [4] [5] Re, Im of sum Cx, Cx = (Ex.r c + Ex.i s,
+ *                       Ex.i c - Ex.r s)  [6] [7] the same of Ey - every operation rounded on its own (csrc/fields_zones.h ZONES_*)
+ * Undoes ml_nearfield_premodulate first, as ml_fields_download does.  fp64, no atomics.  A wave walks a line of contiguous
+ * samples in blocks of 64 and leaves one partial record per run of samples of one zone on one side of the line's vertex; a
+ * second launch adds the runs of a zone in the order of (line, side).  The sum of a zone is a fixed tree over the grid
+ * positions, of (nx, ny) and the vertex alone, in which the other samples add +0.0: a record is repeatable bit for bit, the
+ * record of a set does not depend on the other sets of the call, and the record of zone (e_a, e_b] does not depend on the
+ * other edges.  Scratch: at most n_sets nx min(ny + 2, 2 n_edges + 2) 64 bytes, reserved on first use; ML_ENOMEM with the
+ * bytes asked for in ml_last_error if the device cannot give them.
+ * ML_ESTATE if no field set is resident; ML_EINVAL with the numbers in ml_last_error for a context of more than one rank,
+ * n_sets outside [1, 3], sets that are not resident, axes that differ from the resident shape, n_edges outside [1, 4096], an
+ * entry of x2, y2, e2 that is negative or not finite, edges that decrease, a y2 with more than one valley, an unknown
+ * ref_mode, ra or rb not finite (focus: or negative), ref_c = 0 or k <= 0 for a focus, a reference phase beyond 1e9 rad on
+ * the grid (the value is named), record_doubles < 8, a NULL pointer.  A refused call changes nothing.  Synchronises.
+ * Replaces no reference lines (phase continuity is "checked by eye").                   */
+#define ML_ZONES_EDGES_MAX 4096
+#define ML_ZONES_RECORD 8
+#define ML_ZONES_REF_PLANE 0
+#define ML_ZONES_REF_FOCUS 1
+int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, int nx, const double *y2, int ny,
+                    const double *e2, int n_edges, int ref_mode, const double *ra, const double *rb, double ref_c,
+                    double k, double *records, int record_doubles);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
  * (csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the

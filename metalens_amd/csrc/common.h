@@ -479,6 +479,9 @@ struct ml_ctx {
     // beam metrics of the far field (farfield_beam.hip, ml_farfield_beam): the chunks' partial records of the call in flight,
     // and the slots' records - a buffer of its own, not acc_sums
     ml::DevBuf beam_partials, beam_records;
+    // per-zone sums of the resident near field (fields_zones.hip, ml_fields_zones): the call's axis arrays and edges, the
+    // lines' run lists with their counts, and the device copy of the records
+    ml::DevBuf zones_in, zones_runs, zones_records;
     ml::DevBuf lattice_in;  // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only

@@ -191,3 +191,151 @@ def beam_metrics(P, ux, uy, cones=(), centre='peak', pair_list=False):
         for r in range(c.size):
             rec[_BEAM_CONE + r] = t0[rho2 <= c[r] * c[r]].sum()
     return _beam_single(_beam_dict(rec, ux, uy, pair_list, back), pair_list)
+
+
+ZONES_EDGES_MAX = 4096   # csrc/fields_zones.h, ML_ZONES_EDGES_MAX
+# the record of ml_fields_zones per (field set, zone) (csrc/fields_zones.h ZONES_*)
+_ZONES_N, _ZONES_S, _ZONES_IX, _ZONES_IY, _ZONES_CX, _ZONES_CY = 0, 1, 2, 3, 4, 6
+ZONES_RECORD = 8
+ZONES_REF_PLANE, ZONES_REF_FOCUS = 0, 1
+
+
+def _zones_axis(name, t):
+    try:
+        t = np.asarray(t, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a sequence of numbers, got %r' % (name, t)) from None
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError('%s must be a sequence of at least one number, got an array of shape %s' % (name, t.shape))
+    if not np.isfinite(t).all():
+        i = int(np.argmin(np.isfinite(t)))
+        raise ValueError('%s must be finite: %s[%d] = %g' % (name, name, i, t[i]))
+    return t
+
+
+def _check_zones(x, y, wavelength, n_glass, edges, centre=(0.0, 0.0), reference=('plane', 0.0, 0.0)):
+    """the argument checks of ``ApertureZones``, ``aperture_zones`` and ``zone_metrics``, before any device call, and what the
+    host forms for ml_fields_zones -> dict: ``x2 = (x - xc)**2``, ``y2``, ``e2 = edges * edges``, ``mode``, the reference's
+    per-axis arrays ``ra``, ``rb`` and scalars ``ref_c``, ``k``, and ``dA``, the area of a sample (an axis of one sample
+    counts 1)"""
+    x, y = _zones_axis('xp_list', x), _zones_axis('yp_list', y)
+    if not (np.isfinite(wavelength) and wavelength > 0 and np.isfinite(n_glass) and n_glass > 0):
+        raise ValueError('wavelength and n_glass must be finite and > 0, got %r and %r' % (wavelength, n_glass))
+    try:
+        e = np.asarray(edges, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('edges must be a sequence of numbers, got %r' % (edges,)) from None
+    if e.ndim != 1:
+        raise ValueError('edges must be a sequence of numbers, got an array of shape %s' % (e.shape,))
+    if not 1 <= e.size <= ZONES_EDGES_MAX:
+        raise ValueError('zones take 1 to %d edges, got %d' % (ZONES_EDGES_MAX, e.size))
+    bad = ~(np.isfinite(e) & (e >= 0))
+    if bad.any():
+        raise ValueError('an edge must be finite and >= 0: edges[%d] = %g' % (int(np.argmax(bad)), e[np.argmax(bad)]))
+    down = np.diff(e) < 0
+    if down.any():
+        z = int(np.argmax(down)) + 1
+        raise ValueError('the edges must not decrease: edges[%d] = %g < edges[%d] = %g' % (z, e[z], z - 1, e[z - 1]))
+    said = 'centre must be one (xc, yc), got %r' % (centre,)
+    try:
+        c = np.asarray(centre, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError(said) from None
+    if c.shape != (2,):
+        raise ValueError(said)
+    if not np.isfinite(c).all():
+        raise ValueError('a centre must be finite, got %r' % (centre,))
+    said = "reference must be ('plane', ux, uy) or ('focus', xf, yf, zf), got %r" % (reference,)
+    try:
+        kind, r = reference[0], np.asarray(reference[1:], dtype=float)
+    except (TypeError, ValueError, IndexError, KeyError):
+        raise ValueError(said) from None
+    if not isinstance(kind, str) or kind not in ('plane', 'focus') or r.shape != ((2,) if kind == 'plane' else (3,)):
+        raise ValueError(said)
+    k = 2 * np.pi * n_glass / wavelength
+    if kind == 'plane':
+        if not (np.isfinite(r).all() and r[0] * r[0] + r[1] * r[1] <= 1):
+            raise ValueError('a plane-wave reference needs ux^2 + uy^2 <= 1, got (%g, %g)' % (r[0], r[1]))
+        mode, ra, rb, ref_c = ZONES_REF_PLANE, k * (r[0] * x), k * (r[1] * y), 0.0
+    else:
+        if not (np.isfinite(r).all() and r[2] != 0):
+            raise ValueError('a focus reference needs a finite focus (xf, yf, zf) with zf != 0, got (%g, %g, %g)' % tuple(r))
+        mode, ra, rb, ref_c = ZONES_REF_FOCUS, (x - r[0]) ** 2, (y - r[1]) ** 2, float(r[2])
+    x2, y2 = (x - c[0]) ** 2, (y - c[1]) ** 2
+    jv = int(np.argmin(y2))
+    step = np.diff(y2)
+    wrong = np.concatenate((step[:jv] > 0, step[jv:] < 0))
+    if wrong.any():
+        j = int(np.argmax(wrong)) + 1
+        raise ValueError('yp_list must be in ascending or descending order - (y - yc)^2 has to fall to one minimum and rise '
+                         'again: yp_list[%d] = %.17g follows yp_list[%d] = %.17g' % (j, y[j], j - 1, y[j - 1]))
+    dA = (abs(x[1] - x[0]) if x.size > 1 else 1.0) * (abs(y[1] - y[0]) if y.size > 1 else 1.0)
+    return dict(x2=x2, y2=y2, e2=e * e, mode=mode, ra=ra, rb=rb, ref_c=ref_c, k=float(k), dA=float(dA))
+
+
+def _zones_dict(rec, dA, total):
+    """records of ml_fields_zones, shape ``(sets, K, ZONES_RECORD)`` -> the dict of ``ApertureZones.analyse``; ``total``: the
+    samples of the aperture"""
+    rec = np.asarray(rec, dtype=float)
+    n = rec[0, :, _ZONES_N]
+    out = {'samples': n.astype(np.int64)}
+    out['area'] = n * dA
+    out['P'] = rec[:, :, _ZONES_S] * dA
+    raw_I = rec[:, :, _ZONES_IX:_ZONES_IY + 1]
+    raw_C = np.stack([rec[:, :, _ZONES_CX] + 1j * rec[:, :, _ZONES_CX + 1], rec[:, :, _ZONES_CY] + 1j * rec[:, :, _ZONES_CY + 1]], axis=-1)
+    out['I'] = raw_I * dA
+    out['overlap'] = raw_C * dA
+    out['phase'] = np.angle(out['overlap'])
+    den = n[None, :, None] * raw_I
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out['coherence'] = np.where(den != 0, (raw_C.real ** 2 + raw_C.imag ** 2) / den, np.nan)
+    out['outside'] = int(total - out['samples'].sum())
+    return out
+
+
+def _zones_phase(z):
+    """the reference phase on the grid from the arrays of ``_check_zones``, every operation rounded on its own"""
+    u = z['ra'][:, None] + z['rb'][None, :]
+    if z['mode'] == ZONES_REF_PLANE:
+        return u
+    return -np.sign(z['ref_c']) * (z['k'] * np.sqrt(u + z['ref_c'] * z['ref_c']))
+
+
+def zone_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, edges, centre=(0.0, 0.0), reference=('plane', 0.0, 0.0)):
+    """Per-zone power and wavefront overlap of a near field on the host: what ``ApertureZones.analyse`` reduces on the GPU
+    (``ml_fields_zones``), for host arrays in NumPy.  ``Ex, Ey, Hx, Hy``: complex, shape ``(len(x), len(y))`` or
+    ``(sets, len(x), len(y))``; ``edges``: 1 to 4096 radii, ascending; ``centre = (xc, yc)``; ``reference``: ``('plane', ux,
+    uy)``, the wave ``exp(i k (ux x + uy y))``, or ``('focus', xf, yf, zf)``, the spherical wave that converges on the point
+    ``zf > 0`` behind the aperture (diverges from one in front of it for ``zf < 0``), ``k = 2 pi n_glass / wavelength``.
+
+    Sample ``(i, j)`` has ``r2 = (x[i] - xc)**2 + (y[j] - yc)**2`` and lies in zone ``searchsorted(edges * edges, r2, 'left')``:
+    zone 0 is the disc inside ``edges[0]``, zone ``z`` the ring ``edges[z - 1] < r <= edges[z]``; a sample on an edge belongs
+    to the inner zone.  With ``edges = zones.zone_edges(lens_periphery_summary)`` zone 0 is the lens centre and zone ``z``
+    ring ``z - 1``.  -> dict, the leading axis of every entry but ``samples``, ``area`` and ``outside`` the sets: ``samples``
+    ``(K,)``; ``area = samples dx dy``; ``P = sum S dA``, ``S = Re(Ex Hy* - Ey Hx*) / 2``; ``I`` ``(sets, K, 2)``, ``sum |Ex|^2
+    dA`` and ``sum |Ey|^2 dA``; ``overlap`` ``(sets, K, 2)``, ``sum E conj(w) dA`` of Ex and Ey; ``phase = angle(overlap)``, the
+    piston of the zone against the reference; ``coherence = |sum E conj(w)|^2 / (n sum |E|^2)``, in [0, 1], 1 for a zone
+    that follows the reference, NaN for a zone without samples or field; ``outside``, the samples in no zone."""
+    z = _check_zones(x, y, wavelength, n_glass, edges, centre, reference)
+    F = [np.asarray(a, dtype=np.complex128) for a in (Ex, Ey, Hx, Hy)]
+    F = [a[None] if a.ndim == 2 else a for a in F]
+    shape = (z['x2'].size, z['y2'].size)
+    for name, a in zip(('Ex', 'Ey', 'Hx', 'Hy'), F):
+        if a.ndim != 3 or a.shape[1:] != shape or a.shape[0] != F[0].shape[0]:
+            raise ValueError('%s has shape %s, the axes give %s' % (name, a.shape[-2:] if a.ndim == 3 else a.shape, shape))
+    K = z['e2'].size
+    zone = np.searchsorted(z['e2'], z['x2'][:, None] + z['y2'][None, :], side='left')
+    inside = zone < K
+    zi = zone[inside]
+    phi = _zones_phase(z)[inside]
+    c, s = np.cos(phi), np.sin(phi)
+    rec = np.zeros((F[0].shape[0], K, ZONES_RECORD))
+    rec[:, :, _ZONES_N] = np.bincount(zi, minlength=K)
+    for m in range(F[0].shape[0]):
+        ex, ey, hx, hy = (a[m][inside] for a in F)
+        terms = (0.5 * ((ex.real * hy.real + ex.imag * hy.imag) - (ey.real * hx.real + ey.imag * hx.imag)),
+                 ex.real * ex.real + ex.imag * ex.imag, ey.real * ey.real + ey.imag * ey.imag,
+                 ex.real * c + ex.imag * s, ex.imag * c - ex.real * s, ey.real * c + ey.imag * s, ey.imag * c - ey.real * s)
+        for q, t in enumerate(terms):
+            rec[m, :, 1 + q] = np.bincount(zi, weights=t, minlength=K)
+    return _zones_dict(rec, z['dA'], shape[0] * shape[1])
