@@ -798,6 +798,33 @@ int ml_propagate_plan_info(ml_ctx *ctx, int *method, int *lx, int *ly, int64_t *
 int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq, int n,
                   double *out0, double *out1, int *outk);
 
+/* ---- test surface: the discrete decisions of the synthesis, one point per lane ---------------
+ * Which ring a sample lies in, which sector of the ring, which centre cell: sample_geometry (csrc/nearfield_fast.hip)
+ * decides them once per (grid, layout) and every synthesis reuses the records.  This entry runs the same function on n
+ * points (x[i], y[i]) of the caller's against the layout now on the context (ml_upload_layout; no tables, grid or source
+ * are needed), so that tests can place points on every edge of every decision (tests/test_gpu_geometry_cases.py).
+ * No product path calls it.  x, y, ring, pick, path are HOST arrays of n entries, 1 <= n <= 2^20.
+ *   ring[i]   0: the centre disc, 1 ... n_rings: a ring, n_rings + 1: outside the lens
+ *   pick[i]   ring sample: the sector (round(arctan2(y, x) / dphi) of the ring); centre sample: the ORIGINAL index of the
+ *             nearest cell, the lowest among equidistant ones, -1 for a layout without cells; outside: -1
+ *   path[i]   the stages that decided, ML_GEO_* below.  Exactly one of the two RING bits is set.
+ * The probe keeps tie scratch of its own and takes no tie answers: pending ties, tie answers, geometry records, patch
+ * lists and caches of the context stay as they are.  A NULL argument, n out of range and a coordinate that is not
+ * finite end in ML_EINVAL, a context without a layout in ML_ESTATE, each with a message and without a launch.
+ * Synchronises.  Replaces no reference lines.                                                              */
+#define ML_GEO_RING_RECORD 1      /* ring settled by the bucket record (or r beyond the outer radius) */
+#define ML_GEO_RING_SEARCH 2      /* ring by the search from the uniform table */
+#define ML_GEO_SECTOR_EXACT 4     /* sector: the near-tie recomputation from the extended table was taken */
+#define ML_GEO_SECTOR_CLAMPED 8   /* sector: a clamp to the tabulated range acted */
+#define ML_GEO_CELL_NODE 16       /* cell accepted from the lattice node the sample is nearest to */
+#define ML_GEO_CELL_FOUR 32       /* cell among the four nodes around the sample */
+#define ML_GEO_CELL_BINS 64       /* cell from the 3 x 3 bin runs */
+#define ML_GEO_CELL_MORE 128      /* ... a run longer than one batch of candidates was finished one by one */
+#define ML_GEO_CELL_GROW 256      /* the ring-growing search over the bins was entered */
+#define ML_GEO_TIE 512            /* the nearest cell shares its distance with another */
+int ml_geometry_probe(ml_ctx *ctx, const double *x, const double *y, int n,
+                      int32_t *ring, int32_t *pick, int32_t *path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,43 +94,7 @@ static int centre_patch_bound(const ml_ctx *ctx, int nx, int ny) {
     return span(ctx->grid.h_x_pts, nx) * span(ctx->grid.h_y_pts, ny);
 }
 
-void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny, NfArgs &a) {
-    a.p = p[0];
-    a.n_pol = n;
-    a.e_from_h = p[0].Z0 * (1.0 / p[0].n_glass) * (1.0 / p[0].k_glass);
-    a.n_partials = 4 * ((ny + 7) / 8) * ((nx + 7) / 8);   // four per 8 x 8 patch (wave_power)
-    for (int m = 0; m < MAX_POL; ++m) {
-        const ml_nearfield_params &q = p[m < n ? m : 0];
-        for (int k = 0; k < 3; ++k) a.pol[m][k] = q.pol[k];
-        a.hcoef[m] = q.H_coef;
-        a.dmom[m] = q.dipole_moment;
-        // nearfield.py:225-228, the reference's own expressions (this file is compiled without contraction)
-        const double Ex_i = q.pol[0] * q.dipole_moment, Ey_i = q.pol[1] * q.dipole_moment;
-        a.pw_Hx[m] = -q.pol[1] * q.dipole_moment / q.Z0;
-        a.pw_Hy[m] = q.pol[0] * q.dipole_moment / q.Z0;
-        a.pw_power[m] = Ex_i * a.pw_Hy[m] - Ey_i * a.pw_Hx[m];
-        a.pcoef[m] = q.Z0 * q.H_coef * q.H_coef;
-    }
-    a.nx = nx;
-    a.ny = ny;
-    a.patches_x = (ny + 7) / 8;
-
-    const SynthGrid &grid = ctx->grid;
-    a.x_pts = grid.x_pts.as<double>();
-    a.y_pts = grid.y_pts.as<double>();
-    a.row_first = grid.row_first.as<int>();
-    a.geo_ix = grid.geo_ix.as<int2>();
-    a.active_list = grid.active_list.as<int2>();
-    a.active_count = grid.active_count.as<int>();
-    a.active_flag = grid.active_flag.as<int>();
-    a.list_stride = a.n_partials / 4;
-    a.count_stride = a.n_partials / 4 / 1024 + 4;
-    a.use_active = 0;
-    a.list_count = nullptr;
-    a.first_pass = 0;
-    a.centre_patch_bound = 0;   // (launch_members: first pass only)
-    for (int k = 0; k < 4; ++k) a.n_active[k] = 0;
-
+void fill_layout_args(const ml_ctx *ctx, NfArgs &a) {
     const Lens &lens = ctx->lens;
     a.n_rings = lens.n_rings;
     a.B = lens.ring_boundaries.as<double>();
@@ -178,6 +142,48 @@ void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int 
     a.lat_bmin = L.bmin;
     a.lat_na = L.na;
     a.lat_nb = L.nb;
+}
+
+void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny, NfArgs &a) {
+    a.p = p[0];
+    a.n_pol = n;
+    a.e_from_h = p[0].Z0 * (1.0 / p[0].n_glass) * (1.0 / p[0].k_glass);
+    a.n_partials = 4 * ((ny + 7) / 8) * ((nx + 7) / 8);   // four per 8 x 8 patch (wave_power)
+    for (int m = 0; m < MAX_POL; ++m) {
+        const ml_nearfield_params &q = p[m < n ? m : 0];
+        for (int k = 0; k < 3; ++k) a.pol[m][k] = q.pol[k];
+        a.hcoef[m] = q.H_coef;
+        a.dmom[m] = q.dipole_moment;
+        // nearfield.py:225-228, the reference's own expressions (this file is compiled without contraction)
+        const double Ex_i = q.pol[0] * q.dipole_moment, Ey_i = q.pol[1] * q.dipole_moment;
+        a.pw_Hx[m] = -q.pol[1] * q.dipole_moment / q.Z0;
+        a.pw_Hy[m] = q.pol[0] * q.dipole_moment / q.Z0;
+        a.pw_power[m] = Ex_i * a.pw_Hy[m] - Ey_i * a.pw_Hx[m];
+        a.pcoef[m] = q.Z0 * q.H_coef * q.H_coef;
+    }
+    a.nx = nx;
+    a.ny = ny;
+    a.patches_x = (ny + 7) / 8;
+
+    const SynthGrid &grid = ctx->grid;
+    a.x_pts = grid.x_pts.as<double>();
+    a.y_pts = grid.y_pts.as<double>();
+    a.row_first = grid.row_first.as<int>();
+    a.geo_ix = grid.geo_ix.as<int2>();
+    a.active_list = grid.active_list.as<int2>();
+    a.active_count = grid.active_count.as<int>();
+    a.active_flag = grid.active_flag.as<int>();
+    a.list_stride = a.n_partials / 4;
+    a.count_stride = a.n_partials / 4 / 1024 + 4;
+    a.use_active = 0;
+    a.list_count = nullptr;
+    a.first_pass = 0;
+    a.centre_patch_bound = 0;   // (launch_members: first pass only)
+    for (int k = 0; k < 4; ++k) a.n_active[k] = 0;
+
+    fill_layout_args(ctx, a);
+    const Lens &lens = ctx->lens;
+
     a.tables = lens.table_desc.as<TableDesc>();
     a.center_desc = lens.h_center_desc;
     a.ring_rec = lens.ring_rec.as<double2>();

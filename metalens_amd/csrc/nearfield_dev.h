@@ -183,7 +183,10 @@ __device__ __forceinline__ void consider_cell(const NfArgs &a, double d2, int s,
 
 // the winner shared its distance with another cell: take the host's answer if there is one,
 // else keep the provisional winner and report the sample
-__device__ __forceinline__ int settle_tie(const NfArgs &a, long long sample_id, int best_slot) {
+// (`trace`, here and below: where a decision was made, for ml_geometry_probe - ML_GEO_* of metalens_hip.h; the product's
+// call sites leave it at nullptr and every mention of it folds away)
+__device__ __forceinline__ int settle_tie(const NfArgs &a, long long sample_id, int best_slot, int *trace = nullptr) {
+    if (trace) *trace |= ML_GEO_TIE;
     int lo = 0, hi = a.n_ovr;
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -200,7 +203,7 @@ __device__ __forceinline__ int settle_tie(const NfArgs &a, long long sample_id, 
 
 // exact nearest centre cell (nearfield.py:363-364) through a uniform grid of bins
 __device__ __forceinline__ int nearest_cell(const NfArgs &a, double x, double y,
-                                            long long sample_id) {
+                                            long long sample_id, int *trace = nullptr) {
     int bx = (int)floor((x - a.bx0) / a.bh);
     int by = (int)floor((y - a.by0) / a.bh);
     bx = min(max(bx, 0), a.bins_x - 1);
@@ -227,7 +230,7 @@ __device__ __forceinline__ int nearest_cell(const NfArgs &a, double x, double y,
         const double reach = k * a.bh;
         if (best_slot >= 0 && best <= reach * reach) break;
     }
-    return tied ? settle_tie(a, sample_id, best_slot) : best_slot;
+    return tied ? settle_tie(a, sample_id, best_slot, trace) : best_slot;
 }
 
 
@@ -268,7 +271,7 @@ __device__ __forceinline__ int lattice_pick(const NfArgs &a, double x, double y,
 // same rule as nearest_cell), otherwise the ring-growing search runs; ties resolve to the
 // lowest original index.
 __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, double y,
-                                                 long long sample_id) {
+                                                 long long sample_id, int *trace = nullptr) {
     // Lattice shortcut: the sample lies in (or within rounding of) the lattice parallelogram
     // (a0, b0); its four corner nodes are the candidates.  Every cell that is NOT one of them
     // sits on another node, i.e. at least lat_accept_r away from anywhere in that parallelogram
@@ -283,7 +286,10 @@ __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, doub
             if (s >= 0) {
                 const double2 q = a.cxy[s];
                 const double ex = x - q.x, ey = y - q.y;
-                if (ex * ex + ey * ey <= a.lat_accept_r2) return s;
+                if (ex * ex + ey * ey <= a.lat_accept_r2) {
+                    if (trace) *trace |= ML_GEO_CELL_NODE;
+                    return s;
+                }
             }
         }
         int cand[4];
@@ -305,8 +311,10 @@ __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, doub
             const double ex = x - p[k].x, ey = y - p[k].y;
             consider_cell(a, ex * ex + ey * ey, cand[k], best, best_slot, tied);
         }
-        if (best_slot >= 0 && best <= a.lat_accept_r2)
-            return tied ? settle_tie(a, sample_id, best_slot) : best_slot;
+        if (best_slot >= 0 && best <= a.lat_accept_r2) {
+            if (trace) *trace |= ML_GEO_CELL_FOUR;
+            return tied ? settle_tie(a, sample_id, best_slot, trace) : best_slot;
+        }
     }
     // bin of the sample by multiplication with 1/bh (two fp64 divisions saved).  A sample within
     // an ulp of a bin edge may land in the neighbouring bin; the acceptance test below allows
@@ -353,6 +361,7 @@ __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, doub
         }
     }
     if (more) {   // denser bins than usual: finish the runs one by one
+        if (trace) *trace |= ML_GEO_CELL_MORE;
         for (int c = 0; c < 3; ++c)
             for (int s = lo[c] + BATCH; s < hi[c]; ++s) {
                 const double2 q = a.cxy[s];
@@ -361,8 +370,12 @@ __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, doub
             }
     }
     const double reach = a.bh * (1.0 - 1e-9);
-    if (best_slot < 0 || !(best <= reach * reach)) return nearest_cell(a, x, y, sample_id);
-    return tied ? settle_tie(a, sample_id, best_slot) : best_slot;
+    if (best_slot < 0 || !(best <= reach * reach)) {
+        if (trace) *trace |= ML_GEO_CELL_GROW;
+        return nearest_cell(a, x, y, sample_id, trace);
+    }
+    if (trace) *trace |= ML_GEO_CELL_BINS;
+    return tied ? settle_tie(a, sample_id, best_slot, trace) : best_slot;
 }
 
 // Sector of a sample: round(arctan2(y, x) / dphi) (nearfield.py:119,169), clamped to the
@@ -371,7 +384,10 @@ __device__ __forceinline__ int nearest_cell_fast(const NfArgs &a, double x, doub
 // num_around_circle = 4 mod 8), so phi is then recomputed to ~1e-19 about the boundary angle
 // theta = (k + 1/2) dphi from the host's extended-precision table,
 //   phi = theta + atan((y cos theta - x sin theta) / (x cos theta + y sin theta)),
-// and rounded: the correctly rounded arctan2, which is what NumPy returns on these arguments.
+// and rounded: the kernel follows the CORRECTLY ROUNDED arctan2.  NumPy's agrees with it on the diagonals and axes
+// and wherever a sample lies 1e-12 sectors or more from a tie; closer than that it may differ in its last bit and
+// so in the sector (counted in profiles/geometry_probe.txt; tests/test_gpu_geometry_cases.py holds the kernel to
+// the correctly rounded decision at such points through ml_geometry_probe).
 // `inv_dphi` != 0 (fast kernel): the first quotient is phi * inv_dphi; it differs from phi / dphi by
 // ~1e-16 relative, 1e7 times less than the width of the tie window, so the decision is the same.
 __device__ __forceinline__ int sector_of(const NfArgs &a, int ring, double x, double y,
@@ -407,7 +423,8 @@ __device__ __forceinline__ int boundaries_below(const NfArgs &a, double r) {
 
 // the same answer from one 32-byte bucket record whenever the record settles it (at most one
 // boundary inside the bucket below r), else by the search above
-__device__ __forceinline__ int boundaries_below_fast(const NfArgs &a, double r) {
+__device__ __forceinline__ int boundaries_below_fast(const NfArgs &a, double r, int *trace = nullptr) {
+    if (trace) *trace |= ML_GEO_RING_RECORD;   // (r_outer is the record table's too; the search below takes the bit back)
     if (r > a.r_outer) return a.n_rings + 1;
     int bucket = (int)(r * a.lutrec_inv_h);
     bucket = min(max(bucket, 0), a.lutrec_buckets - 1);
@@ -418,6 +435,7 @@ __device__ __forceinline__ int boundaries_below_fast(const NfArgs &a, double r) 
     const int first = (int)(__double_as_longlong(q.w) & 0xffffffffll);
     const bool below0 = q.y < r, below1 = q.z < r;
     if (q.x < r && !below1) return first + (below0 ? 1 : 0);
+    if (trace) *trace ^= ML_GEO_RING_RECORD | ML_GEO_RING_SEARCH;
     return boundaries_below(a, r);
 }
 
@@ -469,6 +487,8 @@ __device__ __forceinline__ void store_fields(const NfArgs &a, int member, int i,
 }
 
 void fill_nf_args(ml_ctx *ctx, const ml_nearfield_params *p, int n, int nx, int ny, NfArgs &a);
+// the part of it that states the uploaded LAYOUT (rings, sectors, cells): all that sample_geometry reads
+void fill_layout_args(const ml_ctx *ctx, NfArgs &a);
 // writes the number of per-block power partials it produces to *n_partials
 int nearfield_fast_launch(ml_ctx *ctx, const NfArgs &a, int *n_partials);
 // nearfield_simple.hip: the kernels of a round lens' order sets (orders (ox, 0), |ox| <= 5, per collection)

@@ -61,17 +61,19 @@ __device__ __forceinline__ double atan2_fast(double y, double x) {
     double r = fma(t * z, q, t);
     r = ay > ax ? 1.57079632679489655800e+00 - r : r;
     r = x < 0.0 ? 3.14159265358979311600e+00 - r : r;
-    return y < 0.0 ? -r : r;
+    // the sign as atan2 takes it: y = -0.0 with x < 0 is -pi, a different sector from +pi when num_around_circle is odd
+    return copysign(r, y);
 }
 
 // sector_of (nearfield_dev.h) with the ring's constants already in registers and the fast
 // arctangent; the near-tie branch is the same exact recomputation
 __device__ __forceinline__ int sector_of_fast(const NfArgs &a, int half, int rot_center, double x,
-                                              double y, double dphi, double inv_dphi) {
+                                              double y, double dphi, double inv_dphi, int *trace = nullptr) {
     double q = atan2_fast(y, x) * inv_dphi;
     const double fl = floor(q);
     if (fabs((q - fl) - 0.5) < 1e-9) {
         const int k = min(max((int)fl, -half - 1), half);
+        if (trace) *trace |= ML_GEO_SECTOR_EXACT | (k != (int)fl ? ML_GEO_SECTOR_CLAMPED : 0);
         const double *e = a.tie_table + (size_t)(rot_center + k) * 6;
         const double th_hi = e[0], th_lo = e[1], c_hi = e[2], c_lo = e[3], s_hi = e[4], s_lo = e[5];
         const double p1 = y * c_hi, e1 = fma(y, c_hi, -p1);
@@ -81,6 +83,7 @@ __device__ __forceinline__ int sector_of_fast(const NfArgs &a, int half, int rot
         const double phi = th_hi + (th_lo + num / den);
         q = phi / dphi;
     }
+    if (trace && ((int)rint(q) < -half || (int)rint(q) > half)) *trace |= ML_GEO_SECTOR_CLAMPED;
     return min(max((int)rint(q), -half), half);
 }
 
@@ -241,16 +244,16 @@ __device__ __forceinline__ void order_apply(Acc &acc, const OrderCommon &oc, dou
 // from the records (kernel 2).  Same thread -> sample map as kernel 2 (8 x 8 patch per wave).
 // the decisions of one sample (see the geometry kernel below): idx, aux
 __device__ __forceinline__ void sample_geometry(const NfArgs &a, double x, double y, long long sample_id,
-                                                int &idx, int &aux) {
+                                                int &idx, int &aux, int *trace = nullptr) {
     const double r = sqrt(x * x + y * y);
-    idx = boundaries_below_fast(a, r);
+    idx = boundaries_below_fast(a, r, trace);
     aux = -1;
     if (idx >= 1 && idx <= a.n_rings) {
         const int ring = idx - 1;
         const double dphi = a.dphi[ring];
         const int rot_half = a.rot_half[ring], rot_center = a.rot_center[ring];
         // sector decision: exact (nearfield.py:169)
-        const int sector = sector_of_fast(a, rot_half, rot_center, x, y, dphi, recip(dphi));
+        const int sector = sector_of_fast(a, rot_half, rot_center, x, y, dphi, recip(dphi), trace);
         aux = rot_center + sector;
     } else if (idx == 0 && a.n_cells > 0) {
         // nearest cell: the lattice shortcut settles almost every sample from the node map (two
@@ -266,10 +269,11 @@ __device__ __forceinline__ void sample_geometry(const NfArgs &a, double x, doubl
                 if (ex * ex + ey * ey <= a.lat_accept_r2) {   // false for a NaN (empty) node
                     aux = a.lat_map[node];
                     have_cell = true;
+                    if (trace) *trace |= ML_GEO_CELL_NODE;
                 }
             }
         }
-        if (!have_cell) aux = nearest_cell_fast(a, x, y, sample_id);
+        if (!have_cell) aux = nearest_cell_fast(a, x, y, sample_id, trace);
         aux = max(aux, 0);   // a (never produced) negative slot would read as "no cells"
     }
 }
@@ -871,4 +875,64 @@ int nearfield_fast_launch(ml_ctx *ctx, const NfArgs &a, int *n_partials) {
     return ML_OK;
 }
 
+// ---- test surface (ml_geometry_probe): the decisions of sample_geometry at points of the caller's ------------------
+// One lane per point, against the layout on the context, with the trace the product's instantiation compiles out.
+// Down here so that no product kernel of this file moves.  No product code launches it.
+constexpr int GEO_PROBE_MAX_N = 1 << 20;
+constexpr int GEO_PROBE_TIES = 4096;   // entries of the probe's own tie list (the count goes on beyond it)
+
+__global__ __launch_bounds__(64) void geometry_probe_kernel(const NfArgs a, const double *x, const double *y, int n, int *ring,
+                                                            int *pick, int *path) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int idx, aux, trace = 0;
+    sample_geometry(a, x[i], y[i], (long long)i, idx, aux, &trace);
+    int p = -1;
+    if (idx >= 1 && idx <= a.n_rings)
+        p = aux - a.rot_center[idx - 1];
+    else if (idx == 0 && a.n_cells > 0)
+        p = a.cindex[aux];
+    ring[i] = idx;
+    pick[i] = p;
+    path[i] = trace;
+}
+
 }  // namespace ml
+
+using namespace ml;
+
+extern "C" int ml_geometry_probe(ml_ctx *ctx, const double *x, const double *y, int n, int32_t *ring, int32_t *pick,
+                                 int32_t *path) {
+    ML_REQUIRE(ctx && x && y && ring && pick && path, "ml_geometry_probe: NULL argument");
+    ML_REQUIRE(n >= 1 && n <= GEO_PROBE_MAX_N, "ml_geometry_probe: n = %d points, 1 ... 2^20 are taken", n);
+    for (int i = 0; i < n; ++i)
+        ML_REQUIRE(std::isfinite(x[i]) && std::isfinite(y[i]), "ml_geometry_probe: point %d is not finite (%g, %g)", i, x[i], y[i]);
+    if (!ctx->lens.have_layout) {
+        set_error("ml_geometry_probe: ml_upload_layout has not been called");
+        return ML_ESTATE;
+    }
+    ML_HIP(hipSetDevice(ctx->device));
+    const size_t nd = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
+    // [x][y] doubles, [tie list] 64-bit integers, [ring][pick][path][tie count] integers - all the probe's own
+    DevBuf buf;
+    ML_TRY(buf.reserve(2 * nd + GEO_PROBE_TIES * sizeof(long long) + 3 * ni + sizeof(int)));
+    double *dx = buf.as<double>(), *dy = dx + n;
+    long long *tie_list = reinterpret_cast<long long *>(dy + n);
+    int *dring = reinterpret_cast<int *>(tie_list + GEO_PROBE_TIES), *dpick = dring + n, *dpath = dpick + n, *tie_count = dpath + n;
+    NfArgs a{};
+    fill_layout_args(ctx, a);
+    a.tie_count = tie_count;
+    a.tie_list = tie_list;
+    a.tie_cap = GEO_PROBE_TIES;
+    a.n_ovr = 0;   // no answers: every tie keeps the lowest original index
+    ML_HIP(hipMemcpyAsync(dx, x, nd, hipMemcpyHostToDevice, ctx->stream));
+    ML_HIP(hipMemcpyAsync(dy, y, nd, hipMemcpyHostToDevice, ctx->stream));
+    ML_HIP(hipMemsetAsync(tie_count, 0, sizeof(int), ctx->stream));
+    hipLaunchKernelGGL(geometry_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a, dx, dy, n, dring, dpick, dpath);
+    ML_HIP(hipGetLastError());
+    ML_HIP(hipMemcpyAsync(ring, dring, ni, hipMemcpyDeviceToHost, ctx->stream));
+    ML_HIP(hipMemcpyAsync(pick, dpick, ni, hipMemcpyDeviceToHost, ctx->stream));
+    ML_HIP(hipMemcpyAsync(path, dpath, ni, hipMemcpyDeviceToHost, ctx->stream));
+    ML_HIP(hipStreamSynchronize(ctx->stream));
+    return ML_OK;
+}

@@ -220,8 +220,10 @@ def pack_layout(lens_periphery_summary, lens_center_summary):
     # (or one ulp off) the diagonals, where phi / dphi can be an exact tie, and then the decision
     # hangs on the last bit of arctan2.  For such near-tie samples the kernel recomputes phi to
     # ~1e-19 from the boundary angle (k + 1/2) * dphi, whose value, cosine and sine are tabulated
-    # here in extended precision, and rounds it - i.e. it uses the correctly rounded arctan2,
-    # which is what NumPy returns on these arguments.
+    # here in extended precision, and rounds it - i.e. it follows the CORRECTLY ROUNDED arctan2.  NumPy's
+    # agrees with that on the diagonals and the axes, and wherever a sample lies 1e-12 sectors or more from a
+    # tie; closer than that its last bit may differ and with it the sector (1 - 3 % of the points built within
+    # 1e-14 sectors of a tie at generic angles: profiles/geometry_probe.txt, tests/test_geometry_cases.py).
     rot_center = np.zeros(r_center.size, dtype=np.int32)
     rot_half = np.zeros(r_center.size, dtype=np.int32)
     runs, ties, at = [], [], 0
