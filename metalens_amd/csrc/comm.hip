@@ -302,7 +302,7 @@ int ml_farfield_allreduce(ml_ctx *ctx) {
     // one communicator must not be in flight on two streams (the ranks could enqueue them in
     // different orders)
     ML_TRY(comm_join(ctx, false));
-    const size_t n = (size_t)pl.mx * (pl.pair_list ? 1 : pl.my);
+    const size_t n = pl.directions();
     pl.amplitudes_reduced = false;
     return allreduce_dev(ctx, pl.vectors.as<double>(), 4 * n * 2, 0, ctx->stream);
 }

@@ -93,7 +93,7 @@ struct DevBuf {
 
 // A device allocation that only grows, made of PHYSICAL pieces of `piece` bytes, each an allocation of its own
 // (hipMemCreate), mapped side by side into one reserved address range (hipMemMap).  What that is for: how fast 16-byte
-// stores a fixed large stride apart go (the row transform's transposed result, farfield.hip) depends on the physical
+// stores a fixed large stride apart go (the row transform's transposed result, farfield.hip stage1_fft) depends on the physical
 // layout behind the buffer, which hipMalloc leaves to the driver's free lists - measured at 4096^2 -> 512^2, stage 1
 // (profiles/r06_ab_runs.txt): one physically contiguous allocation 0.33 ms, pieces of 16 KB 1.28, 512 KB 0.8-1.0, 1 MB
 // 0.51 (address translation: the 2 MB fragment is lost), 2 / 4 / 8 MB 0.178-0.190 in three processes of four (else
@@ -226,7 +226,7 @@ struct ZfftAxis : ZfftAxisGeo {   // (transform_route.h: the axis' facts)
 };
 
 // The tables of the folded (even/odd) GEMM along one centre-symmetric direction axis (zfold.hip), over the S half-
-// directions of the plan's facts: farfield.hip plan_fold_axis uploads v, fold_tables fills the rest.
+// directions of the plan's facts: farfield_plan.hip plan_fold_axis uploads v, fold_tables fills the rest.
 struct FoldAxis {
     bool has_E = false;        // u_c != 0: the input modulation E exists
     DevBuf v;                  // the split directions (transform_route.h FoldSplit::v) ...
@@ -237,8 +237,8 @@ struct FoldAxis {
 };
 
 // the folded stage 2 leaves its split-K slabs in fold2_ot; they are summed, transposed and signed into `vectors` by
-// whoever needs the vectors next - the projection does it in the same kernel (farfield.hip flush_unfold /
-// unfold_project_kernel).  What that consumer needs to know:
+// whoever needs the vectors next - the projection does it in the same kernel (farfield_project.hip flush_unfold /
+// unfold_project_kernel); the transform only records it here.  What that consumer needs to know:
 struct DeferredUnfold {
     bool pending = false;
     int splits = 1, accumulate = 0;
@@ -257,7 +257,7 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     long serial = 0;   // incremented by every ml_farfield_plan call
     bool amplitudes_reduced = false;   // ml_farfield_project_reduce ran on the current vectors
     // ... and left the amplitudes RANK-BLOCKED when amp_rows > 0: blocks of amp_rows direction rows, both
-    // planes of a block contiguous (what a reduce-scatter deals to the ranks; farfield.hip ProjArgs);
+    // planes of a block contiguous (what a reduce-scatter deals to the ranks; farfield_project.hip ProjArgs);
     // amp_gathered: every rank holds every block's sum (and the whole power map), not only its own
     int amp_rows = 0;
     bool amp_gathered = true;
@@ -274,7 +274,7 @@ struct FarfieldPlan : PlanFacts {   // (transform_route.h: the facts a call's ro
     // and projects into the other slot (ml_farfield_project_reduce)
     DevBuf amplitudes;
     int amp_slot = 0;
-    double *amp_ptr() const { return reinterpret_cast<double *>(amplitudes.p) + (size_t)amp_slot * 4 * mx * (pair_list ? 1 : my); }
+    double *amp_ptr() const { return reinterpret_cast<double *>(amplitudes.p) + (size_t)amp_slot * 4 * directions(); }
     bool have_vectors = false;
     bool tw_x_ready = false;  // complex x twiddles built for the current plan
     int stage1_splits = 1;   // split-K slabs currently held in `stage1`
@@ -411,7 +411,7 @@ struct SynthGrid {
     DevBuf x_pts, y_pts;
     std::vector<double> h_x_pts, h_y_pts;   // what x_pts / y_pts hold (re-uploaded only on change)
     DevBuf row_first;                       // see row_extent_kernel
-    int trim_rows[2] = {0, 0};              // rows of the local aperture that meet the lens circle, [lo, hi) - farfield.hip
+    int trim_rows[2] = {0, 0};              // rows of the local aperture that meet the lens circle, [lo, hi) - farfield.hip trim_rows_of
     // per-sample geometry records and the four patch lists (nearfield_fast.hip; NfArgs::active_list)
     DevBuf geo_ix, active_list, active_count, active_flag;
     int n_active[4] = {0, 0, 0, 0};         // the lists' lengths, once SynthCaches::lengths == KNOWN
@@ -470,7 +470,7 @@ struct ml_ctx {
     int *counts_pinned = nullptr;
     hipEvent_t counts_ready = nullptr;
 
-    // far-field sums kept on the GPU across the sources of a sweep (farfield.hip, ml_farfield_accumulate)
+    // far-field sums kept on the GPU across the sources of a sweep (farfield_sums.hip, ml_farfield_accumulate)
     ml::DevBuf acc_P, acc_partials, acc_sums;
     // the plan P_sum was accumulated on: its direction count and kind (0 directions: nothing accumulated yet).  acc_P is
     // sized by it, so adding onto it or reading it under a plan of another size or kind is refused
@@ -589,10 +589,17 @@ int zfft_build_interleave_tables(hipStream_t stream, double *wk, double *pj, int
 int zfft_run(hipStream_t stream, const ZfftCall &c);
 // comm.hip
 void comm_release(ml_ctx *ctx);
-// farfield.hip: undo ml_nearfield_premodulate on the resident fields (no-op if plain)
+// farfield_plan.hip: undo ml_nearfield_premodulate on the resident fields (no-op if plain)
 int fields_unmodulate(ml_ctx *ctx);
-// farfield.hip: write the radiation vectors a folded stage 2 left in split-K slabs (no-op if none)
+// farfield_plan.hip, plan tables the transform builds on first use: the folded stage 2's phase tables for the resident
+// rows (the split-K factor through *want_split), and the complex x twiddles of the generic stage 2 / the column dot
+int stage2_tables(ml_ctx *ctx, int row0, int mirrored, int *want_split);
+int need_tw_x(ml_ctx *ctx);
+// farfield_project.hip: write the radiation vectors a folded stage 2 left in split-K slabs (no-op if none)
 int flush_unfold(ml_ctx *ctx);
+// farfield_beam.hip: what the checks of farfield_beam.h read of a context (ml_farfield_beam, the sweep sums)
+struct BeamState;
+BeamState beam_state(const ml_ctx *ctx);
 // propagate_grid.hip: the pass of propagate.hip's propagate_sets for a plan of ml_propagate_plan_grid (checks done)
 int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n);
 // propagate_stack.hip: the same for a plan of ml_propagate_plan_grid_stack, handed over by propagate_grid_sets

@@ -10,8 +10,8 @@
 // The terms of a finite direction, every operation rounded on its own (nothing is contracted into an FMA):
 //   dx = ux[i] - cx, dy = uy[j] - cy;  t0 = P cell;  t1 = t0 dx;  t2 = t0 dy;  t3 = t0 (dx dx);  t4 = t0 (dy dy);
 //   t5 = t0 (dx dy);  inside cone r iff dx dx + dy dy <= c_r c_r.
-// cell = dux duy as ml_farfield_accumulate takes it: the axes' first steps, a factor 1 for an axis of one direction,
-// 1 for a pair list.
+// cell = dux duy (beam_cell below, the one statement of it; ml_farfield_accumulate is its other user): the axes' first
+// steps, a factor 1 for an axis of one direction, 1 for a pair list.
 //
 // The cut.  A chunk is beam_chunk_directions(n) consecutive directions: BEAM_CHUNK_MIN = 1024, doubled until the map
 // has at most BEAM_CHUNKS_MAX = 1024 chunks.  It depends on n alone - not on the slot, the source, the centre or the
@@ -108,7 +108,8 @@ inline int beam_bound_roundings(long long n) {
     return (beam_steps(n) - 1) + 6 + 3 + (in_tile - 1) + (tiles - 1);
 }
 
-// dux duy of a map: the axes' first steps, 1 for an axis of one direction, 1 for a pair list
+// dux duy of a map as the reference takes them (nearfield_farfield.py:71-74): the axes' first steps, 1 for an axis of
+// one direction, 1 for a pair list (it has no cell).  Taken by ml_farfield_beam and by ml_farfield_accumulate
 inline double beam_cell(const double *ux, int mx, const double *uy, int my, bool pair_list) {
     double cell = 1.0;
     if (!pair_list) {
@@ -118,15 +119,31 @@ inline double beam_cell(const double *ux, int mx, const double *uy, int my, bool
     return cell;
 }
 
-// What the entry knows of the context when it checks a call.
+// What an entry that reads the power map knows of the context when it checks a call (farfield_beam.hip beam_state fills
+// it, for ml_farfield_beam and for the sweep sums of farfield_sums.hip).
 struct BeamState {
-    bool projected = false;    // the active plan holds radiation vectors (as ml_farfield_accumulate asks)
+    bool projected = false;    // the active plan holds radiation vectors
     bool scattered = false;    // its power map is reduce-scattered over the ranks and not gathered
     long long n = 0;           // directions of the active plan
     bool pair_list = false;
     long long acc_n = 0;       // directions of the plan P_sum was started on, 0: no sums
     bool acc_pair_list = false;
 };
+
+// Can the power map be read whole?  The two refusals every such entry shares.  -> 0, or -2 with `why` filled.
+inline int beam_check_map(const BeamState &s, char *why, size_t why_len) {
+    if (!s.projected) {
+        snprintf(why, why_len, "nothing projected: call ml_farfield_transform and ml_farfield_project first");
+        return -2;
+    }
+    if (s.scattered) {
+        // after a reduce-scatter a rank holds the power of ITS block of direction rows only: sums over the whole map
+        // would mix it with stale rows
+        snprintf(why, why_len, "the power map is reduce-scattered over the ranks: call ml_farfield_gather before summing it");
+        return -2;
+    }
+    return 0;
+}
 
 // The argument checks of ml_farfield_beam.  -> 0; -1: an argument error, -2: the state does not allow the call; `why`
 // is filled then.  source 0: the current projection, -1: P_sum.  centre: {cx, cy} or NULL (the map's peak).
@@ -163,14 +180,7 @@ inline int beam_check(const BeamState &s, int source, const double *centre, cons
         snprintf(why, why_len, "ml_farfield_beam: the centre is (%g, %g): it must be finite", centre[0], centre[1]);
         return -1;
     }
-    if (!s.projected) {
-        snprintf(why, why_len, "nothing projected: call ml_farfield_transform and ml_farfield_project first");
-        return -2;
-    }
-    if (s.scattered) {
-        snprintf(why, why_len, "the power map is reduce-scattered over the ranks: call ml_farfield_gather before summing it");
-        return -2;
-    }
+    if (beam_check_map(s, why, why_len) != 0) return -2;
     if (s.n < 1 || s.n > BEAM_DIRECTIONS_MAX) {
         snprintf(why, why_len, "ml_farfield_beam: the active plan has %lld directions: 1 to %lld are taken", s.n, BEAM_DIRECTIONS_MAX);
         return -1;

@@ -271,6 +271,19 @@ __global__ __launch_bounds__(BEAM_FINISH_THREADS) void beam_finish_kernel(const 
     }
 }
 
+// what the checks of farfield_beam.h read of a context
+BeamState beam_state(const ml_ctx *ctx) {
+    const FarfieldPlan &pl = ctx->plan;
+    BeamState st;
+    st.projected = pl.ready && pl.have_vectors;
+    st.scattered = pl.amp_rows && !pl.amp_gathered;
+    st.n = pl.ready ? (long long)pl.directions() : 0;
+    st.pair_list = pl.pair_list != 0;
+    st.acc_n = (long long)ctx->acc_n;
+    st.acc_pair_list = ctx->acc_pair_list != 0;
+    return st;
+}
+
 }  // namespace ml
 
 using namespace ml;
@@ -280,13 +293,7 @@ extern "C" {
 int ml_farfield_beam(ml_ctx *ctx, int source, const double *centre, const double *cones, int n_cones, int slot) {
     ML_REQUIRE(ctx, "ctx is NULL");
     FarfieldPlan &pl = ctx->plan;
-    BeamState st;
-    st.projected = pl.ready && pl.have_vectors;
-    st.scattered = pl.amp_rows && !pl.amp_gathered;
-    st.n = pl.ready ? (long long)pl.mx * (pl.pair_list ? 1 : pl.my) : 0;
-    st.pair_list = pl.pair_list != 0;
-    st.acc_n = (long long)ctx->acc_n;
-    st.acc_pair_list = ctx->acc_pair_list != 0;
+    const BeamState st = beam_state(ctx);
     char why[320];
     const int rc = beam_check(st, source, centre, cones, n_cones, slot, why, sizeof why);
     if (rc != 0) {
@@ -309,8 +316,8 @@ int ml_farfield_beam(ml_ctx *ctx, int source, const double *centre, const double
     a.partial = ctx->beam_partials.as<double>();
     a.peaks = a.partial + (size_t)chunks * BEAM_PARTIAL;
     a.n = n;
-    a.my = pl.pair_list ? 1 : pl.my;
-    a.pair_list = pl.pair_list ? 1 : 0;
+    a.my = pl.out_my();
+    a.pair_list = pl.pair_list != 0;
     a.chunk = chunk;
     a.chunks = chunks;
     a.K = n_cones;

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void row_extent_kernel(const NfArgs a) {
 }
 
 // deterministic tree sum of the per-block partials (the same routine runs as a spare block of
-// the projection kernel when a transform follows, farfield.hip)
+// the projection kernel when a transform follows, farfield_project.hip)
 __global__ __launch_bounds__(256) void sum_partials_kernel(const double *partial, int n,
                                                            double *groups) {
     // blockIdx.y = field set (member of a polarisation batch)

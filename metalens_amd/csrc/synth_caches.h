@@ -1,7 +1,7 @@
 // What the synthesis keeps from call to call and when it is dropped: the serials of the three things a synthesis'
 // geometry depends on, a stamp per cache (the key it was built for), and the events that drop them, each a member
 // function that states what it drops.  DESIGN.md 3.1 holds the table; tests/test_synth_caches.py pins it.
-// The callers (ctx.hip, nearfield.hip, farfield.hip) build a key, ask the stamp, do the work, set the stamp; none of
+// The callers (ctx.hip, nearfield.hip, farfield.hip, farfield_plan.hip) build a key, ask the stamp, do the work, set the stamp; none of
 // them looks inside a key.
 //
 // Host code without HIP types: compiled by hipcc into the library and by the host compiler into

@@ -2,7 +2,7 @@
 // stage 1's result G, the allocator that backs it and the rows both stages work on - decided here, as a value, from
 // plain facts; farfield.hip's stage functions consume it.
 //
-// Host code without HIP types: compiled by hipcc into farfield.hip and by the host compiler into
+// Host code without HIP types: compiled by hipcc into the library (common.h) and by the host compiler into
 // tools/transform_route.cpp, which prints the route of given plan facts (tests/test_transform_route.py).
 #pragma once
 #include <stddef.h>
@@ -42,11 +42,14 @@ struct ZfftAxisGeo {
     int A = 0, B = 0, R = 0;
 };
 
-// the facts of a FarfieldPlan (common.h adds its tables and buffers).  Set in farfield.hip: method and the sizes by
+// the facts of a FarfieldPlan (common.h adds its tables and buffers).  Set in farfield_plan.hip: method and the sizes by
 // ml_farfield_plan, fold / fold_S and fold2 / fold2_S by plan_fold_axis from fold_split (ZfftAxisGeo: plan_fft_axis)
 struct PlanFacts {
     int method = 0;    // ml_farfield_set_method value the plan was made under
     int nx_total = 0, ny = 0, mx = 0, my = 0, pair_list = 0;
+    // the directions of the plan: mx x my of a tensor grid, direction (i, j) at i my + j; mx of a pair list (one column)
+    int out_my() const { return pair_list ? 1 : my; }
+    size_t directions() const { return (size_t)mx * out_my(); }
     // centre-symmetric uy / ux: the folded (even/odd) GEMM exists for stage 1 / stage 2, over S half-directions
     bool fold = false, fold2 = false;
     int fold_S = 0, fold2_S = 0;
@@ -215,7 +218,7 @@ inline TransformRoute transform_route(const PlanFacts &pl, const ZfftAxisGeo &ff
 }
 
 // ---- The launch shapes of the GEMM-path stage kernels: which tile and how many split-K slabs a stage takes for its
-// sizes, as the launchers apply them (zfold.hip zfold_stage1, farfield.hip stage2_tables, zgemm.hip pick_tile; the
+// sizes, as the launchers apply them (zfold.hip zfold_stage1, farfield_plan.hip stage2_tables, zgemm.hip pick_tile; the
 // reasons and measurements stand there).  Pure arithmetic, so that tools/transform_route.cpp can name the kernel of
 // each stage (tests/gemm_cases.py).  The forcing knobs of a diagnostic build (ML_ZFOLD_TILE, ML_STAGE2_SPLIT,
 // ML_ZGEMM_TILE) stay with the launchers.
@@ -254,7 +257,7 @@ inline int zgemm_tile(int M, int N, int batch) {
 }
 
 // ---- The launch rules of the pruned FFT on lattices of 256 R3 samples (zfft.hip): how an axis is cut
-// into launches (farfield.hip plan_fft_axis), the block of an interleaved shard (farfield.hip interleave_block) and
+// into launches (farfield_plan.hip plan_fft_axis), the block of an interleaved shard (farfield.hip interleave_block) and
 // which kernel instantiation a call launches (zfft.hip zfft_run, zfft_run_tiles, zfft_run_interleaved) - pure
 // arithmetic over the call's facts, applied by those launchers and printed by tools/transform_route.cpp
 // (tests/fft_cases.py).  The reasons and measurements stand with the kernels.
@@ -359,7 +362,7 @@ inline long double symmetry_tolerance(long double kappa, long double p_max, cons
 // Does the axis of m direction cosines u fold - is it centre-symmetric to symmetry_tolerance at the edge of an aperture
 // axis of n samples `step` apart?  If so the folded (even/odd) GEMM (zfold.hip) runs over S = ceil(m / 2) half-
 // directions v_s = (u[m-1-s] - u[s]) / 2 about the centre u_c = (u[0] + u[m-1]) / 2, both computed in long double and
-// split into (hi, lo) doubles for the phase tables (farfield.hip fold_tables).  m < 2 or n < 2: does not fold.
+// split into (hi, lo) doubles for the phase tables (farfield_plan.hip fold_tables).  m < 2 or n < 2: does not fold.
 struct FoldSplit {
     bool ok = false;
     int S = 0;

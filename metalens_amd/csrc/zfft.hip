@@ -59,7 +59,7 @@ struct FftArgs {
     // min(n, n_valid - 1 - n) < row_first[r % rf_mod] are not read (nullptr: read everything)
     const int *row_first;
     int rf_mod;
-    // two-level transforms (lattices beyond 8192 samples, farfield.hip plan_fft_axis): this launch
+    // two-level transforms (lattices beyond 8192 samples, farfield_plan.hip plan_fft_axis): this launch
     // transforms the sub-sequence sub_i, sub_i + sub_s, sub_i + 2 sub_s, ... of the axis; sample n
     // of the transform is sample n sub_s + sub_i of the axis (1, 0: the whole axis)
     int sub_s, sub_i;

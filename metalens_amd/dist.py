@@ -89,7 +89,7 @@ def interleaved_rows(n_rows, world, rank, block):
 
 def block_amplitudes(a_theta, a_phi, world):
     """the two projected amplitudes [mx][my] in the RANK-BLOCKED order the GPU path reduces them in
-    (csrc/farfield.hip ProjArgs::blk_rows): block b = direction rows [b R, (b + 1) R), R = mx / world,
+    (csrc/farfield_project.hip ProjArgs::blk_rows): block b = direction rows [b R, (b + 1) R), R = mx / world,
     of BOTH planes, contiguous - what a reduce-scatter hands rank b.  Returns a float64 vector (RCCL has
     no complex type) of world equal chunks."""
     a_theta, a_phi = np.asarray(a_theta, dtype=np.complex128), np.asarray(a_phi, dtype=np.complex128)

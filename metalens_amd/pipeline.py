@@ -88,7 +88,7 @@ class HotPath:
         # of the whole aperture's and the ranks' loads balance by construction (metalens_hip.h
         # ml_farfield_interleave_block); else mirrored row pairs when the aperture has an even number
         # of rows (both far-field stages fold), one contiguous block otherwise (pair lists have no
-        # folded form: csrc/farfield.hip rejects mirrored shards for them)
+        # folded form: csrc/farfield.hip validate_shard rejects mirrored shards for them)
         self.interleave = 0
         if world > 1 and not self.pair_list and sharding in ('auto', 'interleaved'):
             self._plan()

@@ -1,5 +1,5 @@
-"""The cases of the far-field back end (csrc/farfield.hip: project_kernel, unfold_project_kernel, accumulate_kernel,
-accumulate_finish_kernel behind ml_farfield_project[_async], ml_farfield_project_reduce, ml_farfield_lattice_power,
+"""The cases of the far-field back end (csrc/farfield_project.hip: project_kernel, unfold_project_kernel;
+csrc/farfield_sums.hip: accumulate_kernel, accumulate_finish_kernel; behind ml_farfield_project[_async], ml_farfield_project_reduce, ml_farfield_lattice_power,
 ml_farfield_accumulate, ml_farfield_sums, ml_farfield_total_power) in one table: the directions at which a nearly
 faithful projection differs from a faithful one, the tensor grid that reaches the fused unfold + projection kernel,
 and the sweep-sum rows that reach every branch and loop edge of the two summing kernels.

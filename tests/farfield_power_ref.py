@@ -1,5 +1,5 @@
-"""Yardsticks of the far-field back end (csrc/farfield.hip project_point, accumulate_kernel,
-accumulate_finish_kernel) for tests/farfield_power_cases.py: the projection of the four radiation vectors onto the
+"""Yardsticks of the far-field back end (csrc/farfield_project.hip project_point, csrc/farfield_sums.hip
+accumulate_kernel, accumulate_finish_kernel) for tests/farfield_power_cases.py: the projection of the four radiation vectors onto the
 two amplitudes and the power P, ELEMENTWISE - so that it serves a pair list as well as a tensor grid - and the sums
 of P over a source sweep.  NumPy and math only, float64, in the reference's order of operations
 (oracle/farfield_oracle.py project, nearfield_farfield.py:153-189): test_farfield_power_cases.py holds

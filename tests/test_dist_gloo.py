@@ -176,7 +176,7 @@ def test_rank_blocked_amplitudes_round_trip():
 
 
 def _scatter_worker(rank, world, port, out_dir):
-    """the step's collective as the GPU path runs it (csrc/farfield.hip ml_farfield_project_reduce /
+    """the step's collective as the GPU path runs it (csrc/farfield_project.hip ml_farfield_project_reduce /
     ml_farfield_gather), with gloo standing in for RCCL: every rank projects ITS partial amplitudes into
     the rank-blocked buffer, a reduce-scatter leaves rank r with the sum of block r (gloo has no
     reduce-scatter: one reduce per root), each rank takes the power of its block, an all-gather of

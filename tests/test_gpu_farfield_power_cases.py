@@ -1,8 +1,8 @@
 """The far-field back end on the GPU, every row of tests/farfield_power_cases.py against the yardsticks of
-tests/farfield_power_ref.py: the projection (csrc/farfield.hip project_point in project_kernel and in the fused
+tests/farfield_power_ref.py: the projection (csrc/farfield_project.hip project_point in project_kernel and in the fused
 unfold_project_kernel) POINTWISE - never relative to the brightest direction of the map - at the directions on and
-next to the rim of the unit circle and the axis, and the sweep sums (accumulate_kernel, accumulate_finish_kernel) at
-every loop and branch edge.  To isolate the projection from the transform in front of it the yardstick is fed the
+next to the rim of the unit circle and the axis, and the sweep sums (csrc/farfield_sums.hip accumulate_kernel,
+accumulate_finish_kernel) at every loop and branch edge.  To isolate the projection from the transform in front of it the yardstick is fed the
 GPU's OWN downloaded radiation vectors; the transform rows also hold those vectors against the oracle at the
 project's TOL.  What each row is chosen for is the table's claim, held without a GPU by
 test_farfield_power_cases.py.  Needs an MI355X.

@@ -1445,7 +1445,7 @@ def test_north_star_size_properties(ma, side, M, diameter, na, precision, method
 def test_large_aperture_plans_take_the_folded_path(ma, N, M):
     """A direction grid computed as (k - M/2) * du in floating point is centre-symmetric only to
     about one ulp; for large apertures that is more than 1e-13 rad of phase at the aperture edge.
-    The symmetry test scales with the grid's own rounding (farfield.hip symmetry_tolerance), so
+    The symmetry test scales with the grid's own rounding (transform_route.h symmetry_tolerance), so
     such grids must still plan the folded kernel (the generic complex GEMM is ~5x slower), while
     a grid perturbed well above its rounding must not."""
     from metalens_amd import _lib
