@@ -644,7 +644,7 @@ int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, in
                     double k, double *records, int record_doubles);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
- * (csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the
+ * (csrc/propagate_grid_plan.hip; the pass: csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the
  * origin (tx0 - x0, ty0 - y0) is arbitrary.  Every factor of a (sample, target) pair of the direct sum depends on
  * the lag (i_t - i_s, j_t - j_s) alone, so the sum is a discrete convolution of the four currents with eight
  * kernels; it is computed as a zero-padded circular convolution of Lx x Ly points, L = the smallest power of two

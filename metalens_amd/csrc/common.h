@@ -333,7 +333,8 @@ struct PropagatePlan {
     DevBuf partial;   // double [splits][sets][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)
-    // the FFT form (propagate_grid.hip, ml_propagate_plan_grid): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
+    // the FFT form (propagate_grid_plan.hip ml_propagate_plan_grid*; passes: propagate_grid.hip and the files it hands
+    // over to): targets (x0 + tx_off + i dxp, y0 + ty_off + j dyp, z)
     int method = 0;   // ML_PROPAGATE_DIRECT / ML_PROPAGATE_FFT / ML_PROPAGATE_FFT_LONG / ML_PROPAGATE_FFT_TILED / ML_PROPAGATE_FFT_FINE / ML_PROPAGATE_FFT_STACK
     GridPlanFacts grid;   // (propagate_grid.h) for the aperture shape last met; spectra_ready: its kernel spectra are in grid_work
     bool spectra_ready = false;
@@ -354,7 +355,8 @@ struct PropagatePlan {
     DevBuf stack_layers;
     // complex [8 kernel spectra + 4 currents + 6 or 3 outputs][Lx][Ly]; the tiled plan: [tiles][8] kernel spectra,
     // [batch][4] currents, [6 or 3] outputs; the fine plan: [lattices][tiles][8] (or [2][batch][8]) kernel spectra,
-    // [tiles][4] currents, [2][6 or 3] outputs; released by a direct plan
+    // [tiles][4] currents, [2][6 or 3] outputs, and the stack plan the same with its layers for the lattices; released by
+    // a direct plan.  Where the parts begin: grid_work_plain, grid_work_tiled, grid_work_layered below
     DevBuf grid_work;
     DevBuf grid_tw_x, grid_tw_y;   // (cos, sin) of 2 pi j / L, j < L / 2, per axis
     // the focus metrics (propagate_focus.hip, ml_propagate_focus): the chunks' partial records [planes][chunks][FOCUS_PARTIAL],
@@ -364,6 +366,32 @@ struct PropagatePlan {
     // R[2][planes][mx][nv] and the device copy of the output [planes][2][nu][nv]; it reads result and sums and changes neither
     DevBuf otf_tables, otf_rows, otf_out;
 };
+
+// The parts of PropagatePlan::grid_work in planes of ps = grid.Lx grid.Ly elements, one function per layout: what a
+// prepare fills and what its pass reads.  k_layer: the elements from a lattice's (a layer's) kernel spectra to the next.
+struct GridWork {
+    double2 *K, *cur, *out;
+    size_t k_layer;
+};
+inline GridWork grid_work_at(const PropagatePlan &pp, size_t k_layer, size_t k_layers, size_t cur_tiles) {
+    const size_t ps = (size_t)pp.grid.Lx * pp.grid.Ly;
+    double2 *K = pp.grid_work.as<double2>(), *cur = K + k_layers * k_layer;
+    return {K, cur, cur + cur_tiles * GRID_CURRENTS * ps, k_layer};
+}
+inline GridWork grid_work_plain(const PropagatePlan &pp) {   // [8][4][6 or 3]
+    return grid_work_at(pp, (size_t)GRID_KERNELS * pp.grid.Lx * pp.grid.Ly, 1, 1);
+}
+inline GridWork grid_work_tiled(const PropagatePlan &pp) {   // [tiles][8], [batch][4], [6 or 3]
+    return grid_work_at(pp, (size_t)pp.tile.tiles * GRID_KERNELS * pp.grid.Lx * pp.grid.Ly, 1, pp.tile.batch);
+}
+// `layers`: the lattices of a fine plan, planes x lattices of a stack plan.  cached: [layers][tiles][8]; streamed:
+// [2][batch][8]; then [tiles][4], [2][6 or 3]
+inline GridWork grid_work_layered(const PropagatePlan &pp, int layers) {
+    const GridTilePlan &t = pp.fine.tile;
+    const bool cached = pp.fine.cache_kernels;
+    return grid_work_at(pp, (size_t)(cached ? t.tiles : t.batch) * GRID_KERNELS * pp.grid.Lx * pp.grid.Ly,
+                        cached ? layers : GRID_FINE_PAIR, t.tiles);
+}
 
 // What the kernels read about the lens (lens_pack.h lays it out, ctx.hip uploads it): the tables, the layout and what is
 // packed from both.  The scalars are held as the packers return them.
@@ -600,10 +628,9 @@ int flush_unfold(ml_ctx *ctx);
 // farfield_beam.hip: what the checks of farfield_beam.h read of a context (ml_farfield_beam, the sweep sums)
 struct BeamState;
 BeamState beam_state(const ml_ctx *ctx);
-// propagate_grid.hip: the pass of propagate.hip's propagate_sets for a plan of ml_propagate_plan_grid (checks done)
+// propagate_grid.hip: the pass of propagate.hip's propagate_sets for a plan of ml_propagate_plan_grid* (checks done); it
+// hands the tiled, the fine and the stack plan over to their files (propagate_grid_launch.h)
 int propagate_grid_sets(ml_ctx *ctx, double Z0, int first, int n);
-// propagate_stack.hip: the same for a plan of ml_propagate_plan_grid_stack, handed over by propagate_grid_sets
-int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n);
 // in-place sum of `count` doubles over the communicator, queued on `stream` (no-op without one)
 int comm_allreduce_sum(ml_ctx *ctx, double *buf, size_t count, hipStream_t stream);
 // buf = n_ranks chunks of `chunk` doubles: afterwards chunk `rank` holds the sum over the ranks of

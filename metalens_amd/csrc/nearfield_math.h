@@ -1,6 +1,6 @@
 // Device arithmetic shared by the near-field kernels (nearfield_fast.hip: geometry + general order
 // sets; nearfield_simple.hip: the round-lens order set) and the propagators (propagate.hip,
-// propagate_grid.hip): Cody-Waite sin / cos with scalar-register
+// propagate_grid*.hip): Cody-Waite sin / cos with scalar-register
 // coefficients, reciprocal and reciprocal root by one third-order step, an exact square root
 // without range scaling.  Amplitude-type accuracy (a few ulp) unless said otherwise.
 // Every function here is run alone on the GPU over the range its comment states (math_probe.hip,

@@ -1,4 +1,4 @@
-// Plan arithmetic of the FFT form of the finite-distance propagator (propagate_grid.hip), on the host and free of
+// Plan arithmetic of the FFT form of the finite-distance propagator (propagate_grid*.hip, propagate_stack.hip), on the host and free of
 // HIP types (as transform_route.h): tools/propagate_grid.cpp and tests/test_propagate_grid_host.py run it without
 // a GPU.
 //
@@ -356,7 +356,7 @@ inline std::vector<double> grid_twiddles(int L) {
     return t;
 }
 
-// How an axis of length L is transformed (propagate_grid.hip).  A transform is log2 L radix-2 stages, decimation in
+// How an axis of length L is transformed (propagate_grid_fft.hip).  A transform is log2 L radix-2 stages, decimation in
 // frequency forward (natural order in, bit-reversed out) and decimation in time back (bit-reversed in, natural out):
 // the contraction is bin by bin, so no pass reorders.  The stage of block size B pairs the elements p and p + B / 2
 // of every block of B.  Up to three stages run in registers between two exchanges (groups).

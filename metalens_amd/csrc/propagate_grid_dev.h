@@ -1,6 +1,6 @@
 // The device arithmetic that every FFT form of the finite-distance propagator shares, stated once: the eight kernels of a
 // lag, a field sample as a padded current, the contraction's term table, the scaled store of a target.  Functions only -
-// the kernels that call them, their index arithmetic and their launches are in propagate_grid.hip and propagate_stack.hip.
+// the kernels that call them, their index arithmetic and their launches are in propagate_grid.hip, propagate_grid_tiled.hip, propagate_grid_fine.hip and propagate_stack.hip.
 // The cross-method equalities of the suite (a one-tile plan and 'fft', a full lattice and 'fft-tiled', a plane of a stack
 // and 'fft-fine', kept and streamed spectra) hold because both sides run these functions.
 #pragma once

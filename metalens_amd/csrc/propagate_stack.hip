@@ -1,10 +1,11 @@
 // The finite-distance propagator for a STACK of planes of fine targets (ml_propagate_plan_grid_stack; plan arithmetic:
 // propagate_grid.h GridStackPlan).  fp64 throughout, no atomics.
 //
-// The fine plan of propagate_grid.hip contracts ONE set of current spectra with the kernel spectra of every lattice
+// The fine plan of propagate_grid_fine.hip contracts ONE set of current spectra with the kernel spectra of every lattice
 // (a, b), an origin (tx_off, ty_off) on the pitch.  A plane at another z is one more such set of kernels: here a LAYER is
 // (plane p, lattice (a, b)), l = p Ax Ay + a Ay + b, and its (tx_off, ty_off, z) come from a table in device memory that
-// the plan entry uploads once (GridStackLayerRow).  Per field set:
+// the plan entry uploads once (GridStackLayerRow).  The pass is the layered driver of propagate_grid_fine.hip
+// (grid_layered_sets) with this file's fill and scatter (stack_ops).  Per field set:
 //   1. the currents of every tile are padded and transformed once, in the batches of the tiled plan, and kept
 //      (grid_tile_currents: the tiled plan's own pad kernel and launch);
 //   2. the layers go GRID_FINE_PAIR at a time, a single one last if their number is odd - a pair may straddle two planes:
@@ -15,9 +16,11 @@
 //                   contraction - FIRST on the first batch only;
 //   3. one inverse transform of the pair's 2 x (6 or 3) planes, rows [0, m_cx);
 //   4. the scatter into result[component][(p mx + a + sx i) my + b + sy j].
-// The transforms, the pad and the contraction are propagate_grid.hip's own kernels through its launchers
-// (propagate_grid_launch.h); the fill calls the grid_green of grid_tile_fill_kernel and the scatter the grid_store_scaled
-// of grid_fine_scatter_kernel (propagate_grid_dev.h), so plane p of a stack has the bits of the fine plan planned at z[p].
+// The transforms, the pad and the contraction are the kernels of propagate_grid_fft.hip, propagate_grid_tiled.hip and
+// propagate_grid_fine.hip through their launchers (propagate_grid_launch.h); the fill calls the grid_green of
+// grid_tile_fill_kernel and the scatter the grid_store_scaled of grid_fine_scatter_kernel (propagate_grid_dev.h), so plane
+// p of a stack has the bits of the fine plan planned at z[p].
+// Layouts: the workspace in PropagatePlan::grid_work (common.h grid_work_layered), the layer table in GridStackLayerRow.
 // The result is [set][6 or 3][T], T = nz mx my, plane-major: ml_propagate, ml_propagate_sets, the downloads,
 // ml_propagate_accumulate and ml_propagate_sums read T alone and serve it unchanged.
 #include "propagate_grid_dev.h"
@@ -103,114 +106,64 @@ static int stack_kernels(ml_ctx *ctx, int l0, int nl, int tile0, int nt, d2 *K, 
     return ML_OK;
 }
 
-// the plan and the workspace for the resident field's shape and, with cache_kernels, every layer's kernel spectra (kept
-// while the shape stays)
-static int stack_prepare(ml_ctx *ctx) {
-    PropagatePlan &pp = ctx->prop;
-    if (pp.spectra_ready && pp.grid.nx == ctx->fields.nx && pp.grid.ny == ctx->fields.ny) return ML_OK;
-    pp.spectra_ready = false;
-    char why[480];
-    GridStackPlan s;
-    const int nz = (int)pp.stack_z.size();
-    if (grid_stack_plan(ctx->fields.nx, ctx->fields.ny, pp.fine.mx, pp.fine.my, pp.fine.sx, pp.fine.sy, pp.want_h, pp.tile_lx,
-                        pp.tile_ly, pp.fine.cache_kernels, grid_tile_batch_bytes(), pp.stack_z.data(), nz, &s, why, sizeof why) != 0) {
-        set_error("%s", why);
-        return ML_EINVAL;
-    }
-    const GridFinePlan &p = pp.fine = s.fine;
-    const GridTilePlan &t = pp.tile = p.tile;
-    GridPlanFacts &f = pp.grid;
-    grid_facts_of_tile(f, t, p.m_cx, p.m_cy, s.workspace_bytes);
-    if (pp.grid_work.reserve((size_t)s.workspace_bytes) != ML_OK) {
-        if (p.cache_kernels) {
-            GridStackPlan streamed;
-            grid_stack_plan(t.nx, t.ny, p.mx, p.my, p.sx, p.sy, pp.want_h, pp.tile_lx, pp.tile_ly, 0, grid_tile_batch_bytes(),
-                            pp.stack_z.data(), nz, &streamed, why, sizeof why);
-            set_error("the stack FFT form keeps the kernel spectra of %d planes x %d x %d lattices and %d tiles: the device did not "
-                      "give the %lld bytes of its workspace; cache_kernels=0 fills them in every pass and takes %lld bytes",
-                      nz, p.ax, p.ay, t.tiles, (long long)s.workspace_bytes, (long long)streamed.workspace_bytes);
-        } else {
-            set_error("the stack FFT form: the device did not give the %lld bytes of its workspace (%d tiles; the current spectra "
-                      "of all tiles are kept for a pass)", (long long)s.workspace_bytes, t.tiles);
-        }
-        return ML_ENOMEM;
-    }
-    ML_TRY(grid_upload_twiddles(ctx, pp.grid_tw_x, f.Lx));
-    ML_TRY(grid_upload_twiddles(ctx, pp.grid_tw_y, f.Ly));
-    if (p.cache_kernels) {   // [layers][tiles][8]
-        const size_t ps = (size_t)f.Lx * f.Ly, per_layer = (size_t)t.tiles * GRID_KERNELS * ps;
-        for (int l0 = 0; l0 < s.layers; l0 += GRID_FINE_PAIR) {
-            const int nl = std::min(GRID_FINE_PAIR, s.layers - l0);
-            for (int tile0 = 0; tile0 < t.tiles; tile0 += GRID_TILE_BATCH_MAX) {   // 512 planes per layer and launch at the most
-                const int nt = std::min(GRID_TILE_BATCH_MAX, t.tiles - tile0);
-                ML_TRY(stack_kernels(ctx, l0, nl, tile0, nt,
-                                     pp.grid_work.as<d2>() + l0 * per_layer + (size_t)tile0 * GRID_KERNELS * ps, per_layer));
-            }
-        }
-    }
-    pp.spectra_ready = true;
+// GridLayeredOps::fill: a launch takes GRID_TILE_BATCH_MAX tiles per layer (512 planes) at the most
+static int stack_fill(ml_ctx *ctx, int l0, int nl, int tile0, int nt, d2 *K, size_t k_layer) {
+    const size_t tile_stride = (size_t)GRID_KERNELS * ctx->prop.grid.Lx * ctx->prop.grid.Ly;
+    for (int done = 0; done < nt; done += GRID_TILE_BATCH_MAX)
+        ML_TRY(stack_kernels(ctx, l0, nl, tile0 + done, std::min(GRID_TILE_BATCH_MAX, nt - done), K + done * tile_stride, k_layer));
     return ML_OK;
 }
 
-int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n) {
-    PropagatePlan &pp = ctx->prop;
-    pp.have_result = false;
-    ML_TRY(stack_prepare(ctx));
-    const GridPlanFacts &f = pp.grid;
+static int stack_scatter(ml_ctx *ctx, const GridPass &p, const d2 *out, d2 *result, int l0, int nl) {
+    const PropagatePlan &pp = ctx->prop;
     const GridFinePlan &fp = pp.fine;
-    const GridTilePlan &t = fp.tile;
-    const int T = pp.T, nc = f.outputs, layers = (int)pp.stack_z.size() * fp.ax * fp.ay;
-    ML_TRY(pp.result.reserve((size_t)n * nc * T * sizeof(d2)));
-    const size_t ps = (size_t)f.Lx * f.Ly;
-    // cached: [layers][tiles][8]; streamed: [2][batch][8]
-    const size_t k_layer = (size_t)(fp.cache_kernels ? t.tiles : t.batch) * GRID_KERNELS * ps;
-    d2 *K = pp.grid_work.as<d2>(), *cur = K + (size_t)(fp.cache_kernels ? layers : GRID_FINE_PAIR) * k_layer;
-    d2 *out = cur + (size_t)t.tiles * GRID_CURRENTS * ps;
-    const GridScales sc = grid_scales(pp, f, Z0);
-    const unsigned blocks = (unsigned)(ps / 256);
-    const int rows_fwd = std::min(t.x.B, t.nx);   // the rows below hold no sample of any tile
-    GridStackScatterArgs s;
-    s.out = out;
-    s.plane_stride = ps;
-    s.T = (size_t)T;
-    s.nc = nc;
-    s.Ly = f.Ly;
-    s.m_cx = fp.m_cx;
-    s.m_cy = fp.m_cy;
-    s.mx = fp.mx;
-    s.my = fp.my;
-    s.sx = fp.sx;
-    s.sy = fp.sy;
-    s.scale_e = sc.scale_e;
-    s.scale_h = sc.scale_h;
-    for (int m = 0; m < n; ++m) {
-        const d2 *fields = ctx->fields.buf.as<d2>() + (size_t)(first + m) * 4 * t.nx * t.ny;
-        for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch)   // the current spectra of every tile, once per set
-            ML_TRY(grid_tile_currents(ctx, fields, sc.Z, cur + (size_t)tile0 * GRID_CURRENTS * ps, tile0,
-                                      std::min(t.batch, t.tiles - tile0), rows_fwd));
-        s.result = pp.result.as<d2>() + (size_t)m * nc * T;
-        for (int l0 = 0; l0 < layers; l0 += GRID_FINE_PAIR) {
-            const int nl = std::min(GRID_FINE_PAIR, layers - l0);
-            if (fp.cache_kernels) {
-                ML_TRY(grid_fine_contract(ctx, nl, blocks, true, K + (size_t)l0 * k_layer, k_layer, cur, out, ps, t.tiles));
-            } else {
-                for (int tile0 = 0; tile0 < t.tiles; tile0 += t.batch) {
-                    const int nt = std::min(t.batch, t.tiles - tile0);
-                    ML_TRY(stack_kernels(ctx, l0, nl, tile0, nt, K, k_layer));
-                    ML_TRY(grid_fine_contract(ctx, nl, blocks, tile0 == 0, K, k_layer, cur + (size_t)tile0 * GRID_CURRENTS * ps, out,
-                                              ps, nt));
-                }
-            }
-            ML_TRY(grid_fft_cols(ctx, out, nl * nc, true));
-            ML_TRY(grid_fft_rows(ctx, out, nl * nc, fp.m_cx, true));
-            s.layers = pp.stack_layers.as<GridStackLayerRow>() + l0;
-            hipLaunchKernelGGL(grid_stack_scatter_kernel, dim3((fp.m_cx * fp.m_cy + 255) / 256, nc, nl), dim3(256), 0, ctx->stream, s);
-            ML_HIP(hipGetLastError());
-        }
-    }
-    pp.have_result = true;
-    pp.result_sets = n;
+    const GridStackScatterArgs s = {out, result, p.ps, (size_t)p.T, pp.stack_layers.as<GridStackLayerRow>() + l0, p.nc, pp.grid.Ly,
+                                    fp.m_cx, fp.m_cy, fp.mx, fp.my, fp.sx, fp.sy, p.sc.scale_e, p.sc.scale_h};
+    hipLaunchKernelGGL(grid_stack_scatter_kernel, dim3((fp.m_cx * fp.m_cy + 255) / 256, p.nc, nl), dim3(256), 0, ctx->stream, s);
+    ML_HIP(hipGetLastError());
     return ML_OK;
 }
+
+static void stack_no_memory(ml_ctx *ctx, int64_t workspace_bytes) {
+    const PropagatePlan &pp = ctx->prop;
+    const GridFinePlan &p = pp.fine;
+    const GridTilePlan &t = p.tile;
+    const int nz = (int)pp.stack_z.size();
+    if (p.cache_kernels) {
+        char why[480];
+        GridStackPlan streamed;
+        grid_stack_plan(t.nx, t.ny, p.mx, p.my, p.sx, p.sy, pp.want_h, pp.tile_lx, pp.tile_ly, 0, grid_tile_batch_bytes(),
+                        pp.stack_z.data(), nz, &streamed, why, sizeof why);
+        set_error("the stack FFT form keeps the kernel spectra of %d planes x %d x %d lattices and %d tiles: the device did not "
+                  "give the %lld bytes of its workspace; cache_kernels=0 fills them in every pass and takes %lld bytes",
+                  nz, p.ax, p.ay, t.tiles, (long long)workspace_bytes, (long long)streamed.workspace_bytes);
+    } else {
+        set_error("the stack FFT form: the device did not give the %lld bytes of its workspace (%d tiles; the current spectra "
+                  "of all tiles are kept for a pass)", (long long)workspace_bytes, t.tiles);
+    }
+}
+
+static int stack_prepare(ml_ctx *ctx);
+static GridLayeredOps stack_ops(const PropagatePlan &pp) {
+    return {(int)pp.stack_z.size() * pp.fine.ax * pp.fine.ay, GRID_FINE_PAIR, stack_prepare, stack_fill, stack_scatter, stack_no_memory};
+}
+
+// the plan and the workspace for the resident field's shape and, with cache_kernels, every layer's kernel spectra (kept
+// while the shape stays)
+static int stack_prepare(ml_ctx *ctx) {
+    const PropagatePlan &pp = ctx->prop;
+    if (grid_spectra_kept(ctx)) return ML_OK;
+    char why[480];
+    GridStackPlan s;
+    if (grid_stack_plan(ctx->fields.nx, ctx->fields.ny, pp.fine.mx, pp.fine.my, pp.fine.sx, pp.fine.sy, pp.want_h, pp.tile_lx,
+                        pp.tile_ly, pp.fine.cache_kernels, grid_tile_batch_bytes(), pp.stack_z.data(), (int)pp.stack_z.size(), &s, why,
+                        sizeof why) != 0) {
+        set_error("%s", why);
+        return ML_EINVAL;
+    }
+    return grid_layered_prepare(ctx, stack_ops(pp), s.fine, s.workspace_bytes);
+}
+
+int propagate_stack_sets(ml_ctx *ctx, double Z0, int first, int n) { return grid_layered_sets(ctx, Z0, first, n, stack_ops(ctx->prop)); }
 
 }  // namespace ml

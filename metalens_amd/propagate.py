@@ -18,7 +18,7 @@ GPU-resident near field; for ``R -> infinity`` it reduces to the amplitudes behi
 
 ``method='fft'``: for a tensor grid of targets on the aperture's own pitch every factor of a (sample, target) pair
 depends on the lag ``(i_t - i_s, j_t - j_s)`` alone, and the same sum runs as a zero-padded circular convolution
-(csrc/propagate_grid.hip): ``O(L^2 log L)`` with ``L >= n + m - 1`` per axis instead of ``n^2 m^2`` pairs.
+(csrc/propagate_grid.hip, propagate_grid_fft.hip): ``O(L^2 log L)`` with ``L >= n + m - 1`` per axis instead of ``n^2 m^2`` pairs.
 ``method='fft-long'`` is the same with padded axes of up to 16384 instead of 8192 - apertures of 4097 ... 8192 samples a
 side - and a workspace of up to 77 GB.  ``method='fft-tiled'`` cuts the aperture into tiles, convolves each at a short
 padded length ``L >= m`` and adds the tiles' products in the spectral domain (overlap-add): for ``m << n``.
@@ -327,7 +327,7 @@ class PlanePropagator:
     touched.  A context that belongs to a multi-rank communicator is refused.
 
     ``method='direct'`` (default) is the pair sum.  ``method='fft'`` computes the same sum as an FFT convolution
-    (csrc/propagate_grid.hip).  It takes a tensor grid only, both of whose axes lie on the aperture's pitch as the C
+    (csrc/propagate_grid*.hip).  It takes a tensor grid only, both of whose axes lie on the aperture's pitch as the C
     ABI defines it (``xp_list[1] - xp_list[0]``, likewise y): ``|x[i] - (x[0] + i dxp)| <= 4 spacing(max |x|)``; one
     target along an axis is accepted, and the origin ``x[0] - xp_list[0]`` is arbitrary (no multiple of the pitch).
     Each axis is padded to ``L`` = the smallest power of two ``>= max(16, n + m - 1)``, at most 8192; the workspace is

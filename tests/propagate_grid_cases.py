@@ -1,4 +1,4 @@
-"""The cases of the FFT form of the finite-distance propagator (csrc/propagate_grid.hip with propagate_grid.h; methods
+"""The cases of the FFT form of the finite-distance propagator (csrc/propagate_grid*.hip with propagate_grid.h; methods
 'fft', 'fft-long', 'fft-tiled', 'fft-fine') that the suite runs against a high-precision reference, in one table, and the
 launch variants of the product build that the table has to reach.  Plain data and pure functions, no test collects
 from here: test_propagate_grid_cases.py holds every row's ``expect`` against the plan the host tools print and the
@@ -15,8 +15,8 @@ which comes from running every row as EH and as E.
 module that owns the case (``geometry_of``).  ``ROWS`` are the cases of this table, with fields from
 ``propagate_grid_ref.random_fields(nx, ny, nx + ny)`` on ``propagate_grid_ref.axis``.
 
-How a row's plan facts give its contraction variants (propagate_grid.hip: propagate_grid_sets, propagate_tile_sets,
-propagate_fine_sets):
+How a row's plan facts give its contraction variants (propagate_grid.hip propagate_grid_sets, propagate_grid_tiled.hip
+propagate_tile_sets, propagate_grid_fine.hip propagate_fine_sets):
     'fft', 'fft-long':   grid_contract_kernel<H>.
     'fft-tiled':         grid_tile_contract_kernel<H, FIRST>; the first batch of a pass is FIRST = true, always; every later
                          batch is FIRST = false, so that one runs if and only if tiles > batch.
@@ -33,7 +33,8 @@ it.  Every row runs each of them forward and back.  The padding is ``grid_pad_ke
 The product build ignores the ML_GRID_* knobs (they exist under -DML_DIAG only): sizes alone reach everything here.
 ``grid_rows_top_kernel<1>`` is launched only with the diagnostic build's ML_GRID_ROW_BLOCK knob and is no part of the
 inventory.  The kernels without variants (grid_fill_kernel, grid_tile_fill_kernel, grid_crop_kernel,
-grid_fine_scatter_kernel) run in every row of their method.
+grid_fine_scatter_kernel) run in every row of their method; grid_stack_fill_kernel and grid_stack_scatter_kernel are those of
+'fft-stack' (propagate_stack.hip), which has no row here: tests/test_gpu_propagate_grid_stack.py runs them.
 
 The long-double sum of a row of ``ROWS`` is taken on a subset of its targets: the four corners and targets drawn from a
 fixed seed, 32 in all - 16 where the aperture holds more than 50 000 samples (the sum is 1.5 us per pair).  The NumPy
@@ -68,7 +69,8 @@ def _plain(Lx, Ly, rows, cols):
     return Expect((Lx, Ly), rows, cols, None, None, None, PLAIN)
 
 
-# ---- the launch variants of the product build, written out from propagate_grid.hip ----------------------------------
+# ---- the launch variants of the product build, written out from propagate_grid_fft.hip (the transform) and
+# propagate_grid.hip, propagate_grid_tiled.hip, propagate_grid_fine.hip (the contractions and the padding) -------------
 INVENTORY = frozenset([
     # fft_rows: one launch of grid_rows_kernel for Ly <= 8192 - max(1, 2048 / Ly) rows per workgroup - and fft_rows_long above
     'grid_rows_kernel/16', 'grid_rows_kernel/32', 'grid_rows_kernel/64', 'grid_rows_kernel/128', 'grid_rows_kernel/256',
@@ -89,8 +91,10 @@ INVENTORY = frozenset([
     # the padding: row_first null (an uploaded field) or the row extents of a synthesised one
     'grid_pad_kernel/uploaded', 'grid_pad_kernel/row-extents', 'grid_tile_pad_kernel/uploaded', 'grid_tile_pad_kernel/row-extents',
 ])
-# the kernel templates of propagate_grid.hip that have no variant of their own, and the launch of the diagnostic build
-NO_VARIANTS = frozenset(['grid_fill_kernel', 'grid_tile_fill_kernel', 'grid_crop_kernel', 'grid_fine_scatter_kernel'])
+# the kernels of propagate_grid*.hip and propagate_stack.hip that have no variant of their own, and the launch of the
+# diagnostic build
+NO_VARIANTS = frozenset(['grid_fill_kernel', 'grid_tile_fill_kernel', 'grid_crop_kernel', 'grid_fine_scatter_kernel',
+                         'grid_stack_fill_kernel', 'grid_stack_scatter_kernel'])
 DIAGNOSTIC = frozenset(['grid_rows_top_kernel<1>'])
 
 # the padding with row extents: the resident (synthesised) near field of a 512^2 lens against the same arrays uploaded, by

@@ -1,5 +1,5 @@
 """NumPy restatement of the fine FFT form of the finite-distance propagator (csrc/propagate_grid.h GridFinePlan,
-propagate_grid.hip grid_fine_*; ``PlanePropagator(method='fft-fine')``), its plan, and the cases the tests share.  Test
+propagate_grid_fine.hip; ``PlanePropagator(method='fft-fine')``), its plan, and the cases the tests share.  Test
 infrastructure beside tests/propagate_grid_tiled_ref.py, whose tiled sum it calls; nothing under metalens_amd/ imports it.
 
 Targets on the aperture's pitch divided by an integer s per axis: m fine targets ``t[i] = t[0] + i dxp / s``.  The targets

@@ -1,5 +1,5 @@
 """The cases and NumPy restatements for ``PlanePropagator(method='fft-long')`` (csrc/propagate_grid.h grid_axis_route,
-propagate_grid.hip; ml_propagate_plan_grid_long): padded axes of 16384.  Test infrastructure beside
+propagate_grid.hip, propagate_grid_fft.hip; ml_propagate_plan_grid_long): padded axes of 16384.  Test infrastructure beside
 tests/propagate_grid_ref.py, whose kernel planes, axes, fields and error measure it uses; nothing under metalens_amd/
 imports it.
 

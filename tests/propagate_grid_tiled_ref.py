@@ -1,5 +1,5 @@
 """NumPy restatement of the tiled FFT form of the finite-distance propagator (csrc/propagate_grid.h GridTilePlan,
-propagate_grid.hip grid_tile_*; ``PlanePropagator(method='fft-tiled')``), its plan, and the cases the tests share.  Test
+propagate_grid_tiled.hip; ``PlanePropagator(method='fft-tiled')``), its plan, and the cases the tests share.  Test
 infrastructure beside tests/propagate_grid_ref.py, whose axes, fields and error measure it uses; nothing under
 metalens_amd/ imports it.
 

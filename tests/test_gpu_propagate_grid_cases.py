@@ -1,4 +1,4 @@
-"""The rows of tests/propagate_grid_cases.py on the GPU: the launches of csrc/propagate_grid.hip that no case of
+"""The rows of tests/propagate_grid_cases.py on the GPU: the launches of csrc/propagate_grid*.hip that no case of
 tests/test_gpu_propagate_grid.py, _long, _tiled or _fine reached - columns of 256 and of 4096 (two streaming stages
 above blocks of 1024), rows of 512, 1024 and 4096, both axes of 'fft' mid-size at once, its shortest axes, and the
 streamed fine plan across more than one batch of tiles - every row as EH and as E.  Needs an MI355X.

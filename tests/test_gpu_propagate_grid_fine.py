@@ -1,4 +1,4 @@
-"""``PlanePropagator(method='fft-fine')`` on the GPU (csrc/propagate_grid.hip grid_fine_*, ml_propagate_plan_grid_fine):
+"""``PlanePropagator(method='fft-fine')`` on the GPU (csrc/propagate_grid_fine.hip, ml_propagate_plan_grid_fine):
 the FFT form of the finite-distance propagator for a patch of targets on the aperture's pitch divided by integers - the
 interleave of lattices on the pitch, each a tiled convolution of the same current spectra.  Needs an MI355X.
 

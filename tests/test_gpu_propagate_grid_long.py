@@ -1,4 +1,4 @@
-"""``PlanePropagator(method='fft-long')`` on the GPU (csrc/propagate_grid.hip, ml_propagate_plan_grid_long): the FFT form of
+"""``PlanePropagator(method='fft-long')`` on the GPU (csrc/propagate_grid.hip, propagate_grid_fft.hip; ml_propagate_plan_grid_long): the FFT form of
 the finite-distance propagator with padded axes of 16384.  Needs an MI355X.
 
 Errors and bounds are those of tests/test_gpu_propagate_grid.py: max |difference| over components and targets / max

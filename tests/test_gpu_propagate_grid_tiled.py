@@ -1,4 +1,4 @@
-"""``PlanePropagator(method='fft-tiled')`` on the GPU (csrc/propagate_grid.hip grid_tile_*, ml_propagate_plan_grid_tiled):
+"""``PlanePropagator(method='fft-tiled')`` on the GPU (csrc/propagate_grid_tiled.hip, ml_propagate_plan_grid_tiled):
 the FFT form of the finite-distance propagator by overlap-add over tiles of the aperture.  Needs an MI355X.
 
 Errors and bounds are those of tests/test_gpu_propagate_grid.py: max |difference| over components and targets / max

@@ -1,5 +1,5 @@
 """The table of cases of the FFT form of the finite-distance propagator (tests/propagate_grid_cases.py) against the plan
-arithmetic itself and against the launches of csrc/propagate_grid.hip: every case's ``expect`` equals what
+arithmetic itself and against the launches of csrc/propagate_grid*.hip and propagate_stack.hip: every case's ``expect`` equals what
 tools/propagate_grid, propagate_grid_tiled and propagate_grid_fine print for its sizes (csrc/propagate_grid.h: the
 functions the launchers call), the table reaches every launch variant of ``INVENTORY``, the inventory names every kernel
 the source launches, every row of this table reaches something no earlier case reached, and the NumPy restatement of
@@ -20,7 +20,10 @@ import propagate_grid_ref as gref
 import propagate_grid_tiled_ref as tref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIP = os.path.join(ROOT, 'metalens_amd', 'csrc', 'propagate_grid.hip')
+CSRC = os.path.join(ROOT, 'metalens_amd', 'csrc')
+# the files of the FFT form, one per job: the transform, the plain, the tiled and the fine pass, the plans, the stack pass
+HIP = [os.path.join(CSRC, name + '.hip') for name in ('propagate_grid_fft', 'propagate_grid', 'propagate_grid_tiled', 'propagate_grid_fine',
+                                                     'propagate_grid_plan', 'propagate_stack')]
 TESTS = os.path.join(ROOT, 'tests')
 
 
@@ -157,8 +160,13 @@ def test_table_and_inventory_agree():
 
 
 def test_the_inventory_names_what_the_source_launches():
-    with open(HIP) as f:
-        text = f.read()
+    texts = []
+    for path in HIP:
+        with open(path) as f:
+            texts.append(f.read())
+    text = '\n'.join(texts)
+    defined = [name for t in texts for name in re.findall(r'__global__[^\n]*void (grid_\w+)\(', t)]
+    assert len(defined) == len(set(defined)), sorted(defined)                            # every kernel in exactly one file
     launches = re.findall(r'hipLaunchKernelGGL\(\(?(grid_\w+)(?:<([^<>]*)>)?', text)
     kernels = {name for name, _ in launches}
     assert kernels == set(re.findall(r'__global__[^\n]*void (grid_\w+)\(', text))      # every kernel of the file is launched

@@ -22,7 +22,7 @@ count covers NS = 1, 2, 3: per (sample, target) pair, all sets of the pass toget
 
     python tools/propagate_bench.py --method fft [--quick] >> profiles/propagate_bench.txt     (needs an MI355X)
 
---method fft: ``PlanePropagator(method='fft')`` (csrc/propagate_grid.hip) against the direct sum on the SAME targets - an
+--method fft: ``PlanePropagator(method='fft')`` (csrc/propagate_grid.hip, propagate_grid_fft.hip) against the direct sum on the SAME targets - an
 m x m patch on the aperture's pitch around the focus, off its lattice by 0.3 / 0.6 pitch - for 2048^2 -> 64^2, 4096^2 ->
 64^2 and 4096^2 -> 256^2, E + H and E only: ms of a pass on cached kernel spectra (timed as above), ms_first = plan +
 first pass (workspace, kernel fill and its transform, once), the direct pass, max |E_fft - E_direct| / max |E|, and crossover_targets = the target count
