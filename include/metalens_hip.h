@@ -642,6 +642,41 @@ int ml_propagate_otf(ml_ctx *ctx, int source, int mx, int my, int planes, const 
 int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, int nx, const double *y2, int ny,
                     const double *e2, int n_edges, int ref_mode, const double *ra, const double *rb, double ref_c,
                     double k, double *records, int record_doubles);
+/* Zernike moments of the resident near field's wavefront, reduced on the GPU (csrc/fields_wavefront.hip): over a circular
+ * pupil of radius R about a centre, and for n_sets field sets in one pass, the members, the sums of Sz, |Ex|^2, |Ey|^2
+ * and the complex moments sum Ex conj(w) Z_j, sum Ey conj(w) Z_j of the aperture field against a reference wave
+ * w = exp(i phi), for the Zernike terms up to radial order n_max - what the aberrations are (tilt, defocus, astigmatism,
+ * coma, spherical ...), without the fields crossing PCIe.
+ *   first_set, n_sets : as for ml_fields_zones
+ *   x2, xi, nx        : X2[i] = (x[i] - xc)^2 and xi[i] = (x[i] - xc) / R as the host formed them; nx, ny must be the
+ *   y2, eta, ny         resident shape; x2, y2 finite and >= 0, xi, eta finite, and y2 must fall to its minimum and rise again
+ *   r2                : R R, finite and > 0.  Sample (i, j) is a member iff X2[i] + Y2[j] <= r2 (one rounded addition; a
+ *                       sample on the rim is inside): the rule of ml_fields_zones
+ *   n_max             : 0 <= n_max <= ML_ZERNIKE_ORDER_MAX.  J = (n_max + 1)(n_max + 2) / 2 terms in OSA/ANSI order,
+ *                       j = (n (n + 2) + m) / 2, m = -n, -n + 2, ... n, m < 0 the sine term, Noll-normalised (sqrt(n + 1) for
+ *                       m = 0, sqrt(2 (n + 1)) otherwise): (1 / pi) int Z_j Z_k d^2 rho = delta_jk on the unit disc
+ *   ref_mode, ra, rb, ref_c, k : the reference phase, as for ml_fields_zones (ML_ZONES_REF_PLANE, ML_ZONES_REF_FOCUS)
+ *   records           : HOST, [n_sets][record_doubles], record_doubles >= ML_ZERNIKE_RECORD(n_max) = 4 + 4 J.  A record:
+ *                       [0] the members  [1] sum S  [2] sum |Ex|^2  [3] sum |Ey|^2 (the terms of ml_fields_zones), then per
+ *                       term j at 4 + 4 j: Re, Im of sum Cx Z_j and Re, Im of sum Cy Z_j, Cx = Ex conj(w), without dA
+ * The method fixes the bits (csrc/fields_wavefront.h): Z_j / N_j is a polynomial in (xi, eta) with integer coefficients
+ * A_j,pq, so sum C Z_j = N_j sum_pq A_j,pq M_pq with the separable monomial moments M_pq = sum_i xi[i]^p sum_j C(i, j) eta[j]^q.
+ * A wave walks a line in blocks of 64 and leaves sum_j C eta^q, q <= n_max, per line; a second launch adds xi^p times the
+ * lines' sums in a fixed order; the host adds A M in ascending (p, then q) order and multiplies by N_j.  fp64, no
+ * atomics: a record is repeatable bit for bit, does not depend on the other sets of the call, and its terms up to order
+ * n' do not depend on n_max >= n'.  Undoes ml_nearfield_premodulate first, as ml_fields_download does.  Scratch:
+ * n_sets nx (4 + 4 (n_max + 1)) doubles, reserved on first use.
+ * ML_ESTATE if no field set is resident; ML_EINVAL with the numbers in ml_last_error for a context of more than one rank,
+ * n_sets outside [1, 3], sets that are not resident, axes that differ from the resident shape, n_max outside [0, 8], r2
+ * not finite or <= 0, an entry of x2, y2 that is negative or not finite, of xi, eta that is not finite, a y2 with more
+ * than one valley, an unknown ref_mode, ra or rb not finite (focus: or negative), ref_c = 0 or k <= 0 for a focus, a
+ * reference phase beyond 1e9 rad on the grid (the value is named), record_doubles < 4 + 4 J, a NULL pointer.  A refused
+ * call changes nothing.  Synchronises.  Replaces no reference lines.                         */
+#define ML_ZERNIKE_ORDER_MAX 8
+#define ML_ZERNIKE_RECORD(n_max) (4 + 2 * ((n_max) + 1) * ((n_max) + 2))
+int ml_fields_zernike(ml_ctx *ctx, int first_set, int n_sets, const double *x2, const double *xi, int nx,
+                      const double *y2, const double *eta, int ny, double r2, int n_max, int ref_mode, const double *ra,
+                      const double *rb, double ref_c, double k, double *records, int record_doubles);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
  * (csrc/propagate_grid_plan.hip; the pass: csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the

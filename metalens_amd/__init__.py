@@ -4,7 +4,7 @@ transform for the sbyrnes321/metalens design flow.
 Host code in Python (mirroring the reference's function and class names), compute
 in hand-written HIP for gfx950 behind the C ABI of include/metalens_hip.h.
 """
-from . import constants, grating, interp, layout, lens_center, postprocess, synthetic, zones  # noqa: F401
+from . import constants, grating, interp, layout, lens_center, postprocess, synthetic, wavefront, zones  # noqa: F401
 from .grating import Grating, GratingCollection  # noqa: F401
 from .lens_center import HexGridSet  # noqa: F401
 from .nearfield import build_nearfield, build_nearfield_big, good_fft_number  # noqa: F401
@@ -16,3 +16,4 @@ from .nearfield_farfield import (FarfieldTransform, farfield_direct,  # noqa: F4
                                  fft_direction_cosines)
 from .propagate import PlanePropagator, field_at_plane  # noqa: F401
 from .zones import ApertureZones, aperture_zones, zone_edges  # noqa: F401
+from .wavefront import ApertureWavefront, aperture_wavefront, zernike, zernike_terms  # noqa: F401

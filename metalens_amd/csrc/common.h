@@ -510,6 +510,9 @@ struct ml_ctx {
     // per-zone sums of the resident near field (fields_zones.hip, ml_fields_zones): the call's axis arrays and edges, the
     // lines' run lists with their counts, and the device copy of the records
     ml::DevBuf zones_in, zones_runs, zones_records;
+    // Zernike moments of the resident near field's wavefront (fields_wavefront.hip, ml_fields_zernike): the call's axis
+    // arrays, the line records, and the sets' monomial moments
+    ml::DevBuf wavefront_in, wavefront_lines, wavefront_records;
     ml::DevBuf lattice_in;  // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only

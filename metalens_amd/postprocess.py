@@ -339,3 +339,170 @@ def zone_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, edges, centre=(0.0, 
         for q, t in enumerate(terms):
             rec[m, :, 1 + q] = np.bincount(zi, weights=t, minlength=K)
     return _zones_dict(rec, z['dA'], shape[0] * shape[1])
+
+
+ZERNIKE_ORDER_MAX = 8   # csrc/fields_wavefront.h WF_ORDER_MAX, ML_ZERNIKE_ORDER_MAX
+# the record of ml_fields_zernike per field set (csrc/fields_wavefront.h WF_*): the header sums, then four doubles per term
+_WF_N, _WF_S, _WF_IX, _WF_IY, _WF_HEAD = 0, 1, 2, 3, 4
+
+
+def zernike_terms(n_max):
+    """the ``(J, 2)`` array of ``(n, m)`` of the Zernike terms up to radial order ``n_max`` in OSA/ANSI order, ``j = (n (n + 2) +
+    m) / 2`` with ``m = -n, -n + 2, ... n``; ``m < 0`` is the sine term"""
+    if isinstance(n_max, bool) or int(n_max) != n_max or not 0 <= n_max <= ZERNIKE_ORDER_MAX:
+        raise ValueError('n_max must be a radial order from 0 to %d, got %r' % (ZERNIKE_ORDER_MAX, n_max))
+    return np.array([(n, m) for n in range(int(n_max) + 1) for m in range(-n, n + 1, 2)], dtype=np.int64).reshape(-1, 2)
+
+
+def wavefront_record(n_max):
+    """the doubles of a record of ml_fields_zernike: ``4 + 4 J`` (ML_ZERNIKE_RECORD)"""
+    return _WF_HEAD + 4 * len(zernike_terms(n_max))
+
+
+def _zernike_coefficients(n, m):
+    """the integer coefficients ``{(p, q): A}`` of ``Z_n^m / N`` as a polynomial in ``xi = rho cos(phi)``, ``eta = rho sin(phi)``,
+    from the factorial formula of the radial polynomial and the binomial expansions of ``(xi^2 + eta^2)^t`` and ``(xi + i
+    eta)^|m|`` in Python integers (csrc/fields_wavefront.h wf_coefficients)"""
+    from math import comb, factorial
+    a = abs(m)
+    A = {}
+    for s in range((n - a) // 2 + 1):
+        t = (n - a) // 2 - s
+        rad = (-1) ** s * factorial(n - s) // (factorial(s) * factorial((n + a) // 2 - s) * factorial(t))
+        for i in range(t + 1):
+            for k in range(1 if m < 0 else 0, a + 1, 2):
+                key = (2 * i + a - k, 2 * (t - i) + k)
+                A[key] = A.get(key, 0) + rad * comb(t, i) * (-1) ** (k // 2) * comb(a, k)
+    return {key: v for key, v in sorted(A.items()) if v != 0}
+
+
+def _zernike_norm(n, m):
+    return np.sqrt(float(n + 1) if m == 0 else 2.0 * (n + 1))
+
+
+def _zernike_check_term(n, m):
+    if int(n) != n or int(m) != m or not 0 <= n <= ZERNIKE_ORDER_MAX or abs(m) > n or (n - m) % 2:
+        raise ValueError('a Zernike term needs 0 <= n <= %d and m = -n, -n + 2, ... n, got (%r, %r)' % (ZERNIKE_ORDER_MAX, n, m))
+    return int(n), int(m)
+
+
+def zernike(n, m, xi, eta):
+    """The Zernike term ``Z_n^m`` at the pupil coordinates ``xi = (x - xc) / R``, ``eta = (y - yc) / R`` (broadcast against
+    each other), Noll-normalised: ``sqrt(n + 1) R_n^0(rho)`` for ``m = 0``, ``sqrt(2 (n + 1)) R_n^|m|(rho) cos(m phi)`` for ``m > 0``
+    and ``... sin(|m| phi)`` for ``m < 0``, so that ``(1 / pi) int Z_j Z_k = delta_jk`` over the unit disc.  Evaluated as the
+    polynomial in ``(xi, eta)`` the moments are formed with; a wavefront map is ``sum_j wavefront[j] zernike(n_j, m_j, xi, eta)``."""
+    n, m = _zernike_check_term(n, m)
+    xi, eta = np.asarray(xi, dtype=float), np.asarray(eta, dtype=float)
+    out = np.zeros(np.broadcast(xi, eta).shape)
+    for (p, q), A in _zernike_coefficients(n, m).items():
+        out = out + float(A) * (xi ** p * eta ** q)
+    return _zernike_norm(n, m) * out
+
+
+def _check_wavefront(x, y, wavelength, n_glass, radius, n_max, centre=(0.0, 0.0), reference=('plane', 0.0, 0.0)):
+    """the argument checks of ``ApertureWavefront``, ``aperture_wavefront`` and ``wavefront_metrics``, before any device call:
+    those of ``_check_zones`` with the pupil's radius as the single edge, and what the host forms for ml_fields_zernike
+    beside: ``r2 = R R``, ``xi = (x - xc) / R``, ``eta = (y - yc) / R``, ``terms``"""
+    try:
+        R = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError('radius must be one number, got %r' % (radius,)) from None
+    if not (np.isfinite(R) and R > 0):
+        raise ValueError('the radius of the pupil must be finite and > 0, got %r' % (radius,))
+    terms = zernike_terms(n_max)
+    z = _check_zones(x, y, wavelength, n_glass, [R], centre, reference)
+    x, y, c = np.asarray(x, dtype=float), np.asarray(y, dtype=float), np.asarray(centre, dtype=float)
+    z.update(R=R, r2=float(z.pop('e2')[0]), xi=(x - c[0]) / R, eta=(y - c[1]) / R, n_max=int(n_max), terms=terms)
+    return z
+
+
+def _wavefront_convert(head, M, n_max):
+    """header sums ``(sets, 4)`` and monomial moments ``M[p][q]`` -> ``(sets, 4)`` -> the records of ml_fields_zernike: per term
+    ``A M`` over the non-zero coefficients in ascending (p, then q) order onto +0.0, then one multiplication by ``N_j``"""
+    terms = zernike_terms(n_max)
+    rec = np.zeros((head.shape[0], _WF_HEAD + 4 * len(terms)))
+    rec[:, :_WF_HEAD] = head
+    for j, (n, m) in enumerate(terms):
+        acc = np.zeros((head.shape[0], 4))
+        for (p, q), A in _zernike_coefficients(int(n), int(m)).items():
+            acc = acc + float(A) * M[p][q]
+        rec[:, _WF_HEAD + 4 * j:_WF_HEAD + 4 * j + 4] = _zernike_norm(int(n), int(m)) * acc
+    return rec
+
+
+def _wavefront_dict(rec, dA, total, R, n_max):
+    """records of ml_fields_zernike, shape ``(sets, 4 + 4 J)`` -> the dict of ``ApertureWavefront.analyse``; ``total``: the samples
+    of the aperture"""
+    rec = np.asarray(rec, dtype=float)
+    terms = zernike_terms(n_max)
+    n = rec[0, _WF_N]
+    out = {'terms': terms, 'samples': np.int64(n), 'area': n * dA, 'outside': int(total - n)}
+    out['P'] = rec[:, _WF_S] * dA
+    raw_I = rec[:, _WF_IX:_WF_IY + 1]
+    out['I'] = raw_I * dA
+    t = rec[:, _WF_HEAD:].reshape(rec.shape[0], len(terms), 4)
+    raw = np.stack([t[:, :, 0] + 1j * t[:, :, 1], t[:, :, 2] + 1j * t[:, :, 3]], axis=1)      # (sets, 2, J)
+    out['moments'] = raw * dA / (np.pi * R * R)
+    out['piston'] = np.angle(out['moments'][..., 0])
+    den = n * raw_I
+    c0 = raw[..., 0]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        out['coherence'] = np.where(den != 0, (c0.real ** 2 + c0.imag ** 2) / den, np.nan)
+        w = np.where(c0[..., None] != 0, (out['moments'] / out['moments'][..., :1]).imag, np.nan)
+    out['wavefront'] = w
+    out['rms'] = np.sqrt((w[..., 1:] ** 2).sum(axis=-1))
+    return out
+
+
+def wavefront_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, radius, n_max=4, centre=(0.0, 0.0), reference=('plane', 0.0, 0.0)):
+    """Zernike moments of a near field's wavefront on the host: what ``ApertureWavefront.analyse`` reduces on the GPU
+    (``ml_fields_zernike``), for host arrays in NumPy, by the same separable route with every operation rounded on its own.
+    ``Ex, Ey, Hx, Hy``: complex, shape ``(len(x), len(y))`` or ``(sets, len(x), len(y))``; the pupil is the disc of ``radius``
+    about ``centre = (xc, yc)``: sample ``(i, j)`` is a member iff ``(x[i] - xc)**2 + (y[j] - yc)**2 <= radius * radius``, a sample
+    on the rim is inside; ``reference`` as for ``zone_metrics``; ``n_max``: the highest radial order, 0 to 8.
+
+    With ``C = E conj(w)`` of a member, ``xi = (x - xc) / R`` and ``eta = (y - yc) / R``, the moments of the Noll-normalised
+    terms ``Z_j`` (``zernike_terms``, ``zernike``) come from the monomial moments ``sum_i xi^p sum_j C eta^q`` and the terms'
+    integer coefficients.  -> dict, the leading axis of every entry but ``terms``, ``samples``, ``area`` and ``outside`` the
+    sets: ``terms`` ``(J, 2)``, the ``(n, m)``; ``samples``, the members; ``area = samples dx dy``; ``outside``; ``P = sum S dA``;
+    ``I`` ``(sets, 2)``, ``sum |Ex|^2 dA`` and ``sum |Ey|^2 dA``; ``moments`` ``(sets, 2, J)`` complex, ``sum C Z_j dA / (pi R^2)`` of Ex
+    and Ey; ``piston = angle(moments[..., 0])``; ``coherence = |sum C|^2 / (n sum |E|^2)``, in [0, 1], the Strehl ratio of the
+    wavefront against the reference, NaN where ``n sum |E|^2`` is 0; ``wavefront = Im(moments / moments[..., :1])``, radians
+    per term, NaN where the piston moment is 0; ``rms = sqrt(sum_{j >= 1} wavefront^2)``.
+
+    ``wavefront`` is the small-aberration reading of the complex moments: for a field ``exp(i W)`` with ``W = sum a_j Z_j``
+    small it returns ``a_j`` to first order in ``W``.  There is no phase unwrapping and no least-squares fit; and on a
+    sampled disc the terms are orthogonal only to O(pitch / R), so a term leaks into the others at that level."""
+    z = _check_wavefront(x, y, wavelength, n_glass, radius, n_max, centre, reference)
+    F = [np.asarray(a, dtype=np.complex128) for a in (Ex, Ey, Hx, Hy)]
+    F = [a[None] if a.ndim == 2 else a for a in F]
+    shape = (z['x2'].size, z['y2'].size)
+    for name, a in zip(('Ex', 'Ey', 'Hx', 'Hy'), F):
+        if a.ndim != 3 or a.shape[1:] != shape or a.shape[0] != F[0].shape[0]:
+            raise ValueError('%s has shape %s, the axes give %s' % (name, a.shape[-2:] if a.ndim == 3 else a.shape, shape))
+    sets, n_max = F[0].shape[0], z['n_max']
+    member = z['x2'][:, None] + z['y2'][None, :] <= z['r2']
+    phi = np.where(member, _zones_phase(z), 0.0)
+    c, s = np.cos(phi), np.sin(phi)
+    held = member.any(axis=1)                                   # the lines that hold members
+    xi = np.where(held, z['xi'], 0.0)
+    head, T = np.zeros((sets, 4)), np.zeros((sets, 4, shape[0], n_max + 1))
+    head[:, _WF_N] = member.sum()
+    for m in range(sets):
+        ex, ey, hx, hy = (np.where(member, a[m], 0.0) for a in F)
+        head[m, _WF_S] = (0.5 * ((ex.real * hy.real + ex.imag * hy.imag) - (ey.real * hx.real + ey.imag * hx.imag))).sum()
+        head[m, _WF_IX] = (ex.real * ex.real + ex.imag * ex.imag).sum()
+        head[m, _WF_IY] = (ey.real * ey.real + ey.imag * ey.imag).sum()
+        C = (ex.real * c + ex.imag * s, ex.imag * c - ex.real * s, ey.real * c + ey.imag * s, ey.imag * c - ey.real * s)
+        e = np.where(member, 1.0, 0.0)                          # eta^q by repeated multiplication
+        for q in range(n_max + 1):
+            for comp in range(4):
+                T[m, comp, :, q] = (C[comp] * e).sum(axis=1)
+            e = e * np.where(member, z['eta'][None, :], 0.0)
+    M = [[None] * (n_max + 1) for _ in range(n_max + 1)]
+    pw = np.ones(shape[0])                                      # xi^p by repeated multiplication
+    for p in range(n_max + 1):
+        for q in range(n_max + 1 - p):
+            M[p][q] = (pw[None, None, :] * T[:, :, :, q]).sum(axis=2)
+        pw = pw * xi
+    return _wavefront_dict(_wavefront_convert(head, M, n_max), z['dA'], shape[0] * shape[1], z['R'], n_max)
