@@ -677,6 +677,43 @@ int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, in
 int ml_fields_zernike(ml_ctx *ctx, int first_set, int n_sets, const double *x2, const double *xi, int nx,
                       const double *y2, const double *eta, int ny, double r2, int n_max, int ref_mode, const double *ra,
                       const double *rb, double ref_c, double k, double *records, int record_doubles);
+/* A pupil function multiplied into the resident near field where it lies (csrc/fields_pupil.hip): an aperture stop, one
+ * complex factor per zone and a Zernike phase plate.  Everything that reads the resident sets afterwards - the transform,
+ * ml_propagate*, ml_fields_zones, ml_fields_zernike, a download - sees the modified aperture.  Two entries: the plan
+ * checks the call and uploads its arrays once, the pass queues ONE launch and returns.
+ * ml_fields_pupil_plan:
+ *   x2, xi, nx, y2, eta, ny, r2 : the pupil, as for ml_fields_zernike (the shape is held against the resident sets by the
+ *                       pass, not here: a plan does not depend on the fields).  Sample (i, j) has r2' = X2[i] + Y2[j], one
+ *                       rounded addition, and is a member iff r2' <= r2; a sample on the rim is inside
+ *   stop              : 1: all four fields of a non-member become +0.0 + 0.0i; 0: a non-member takes its zone factor only
+ *   n_max, c          : c = NULL for no phase; else J = (n_max + 1)(n_max + 2) / 2 coefficients in radians in the order of
+ *                       ml_fields_zernike's terms, 0 <= n_max <= ML_ZERNIKE_ORDER_MAX: a member takes exp(+i psi),
+ *                       psi = sum_j c_j Z_j(xi, eta) - the pupil ADDS the aberration c, so c = -wavefront flattens what
+ *                       ml_fields_zernike measured.  A non-member takes no phase
+ *   e2, n_edges, g    : 0 <= n_edges = K <= ML_ZONES_EDGES_MAX ascending squared edges (NULL for K = 0) and K complex factors
+ *                       g[z] = (re, im): a sample in zone z = searchsorted(e2, r2', 'left') < K - the rule of ml_fields_zones -
+ *                       takes g[z]; outside every edge, and without edges, the zone factor is exactly 1
+ * The values are fixed by the method (csrc/fields_pupil.h): the host forms B_pq = sum_j (c_j N_j) A_j,pq, j ascending onto
+ * +0.0, and per line b_q(i) = sum_p B_pq xi^p by Horner, p descending; a member's psi is Horner in eta, q descending;
+ * (cs, sn) = sincos_cw(psi); f = g (cs + i sn) = (g.r cs - g.i sn) + i (g.r sn + g.i cs), f = g without a phase; every
+ * field becomes (E.r f.r - E.i f.i) + i (E.r f.i + E.i f.r), every operation rounded on its own.  A sample whose factor
+ * is exactly 1 - no phase applies to it and no zone factor is given for it - is neither read nor written.
+ * ML_EINVAL with the numbers in ml_last_error, before any device work, for a context of more than one rank, stop other than
+ * 0 or 1, n_max outside [0, 8], n_edges outside [0, 4096], an empty axis, a NULL pointer, r2 not finite or <= 0, an entry of
+ * x2, y2, e2 that is negative or not finite, of xi, eta, c, g that is not finite, a y2 with more than one valley, edges that
+ * decrease, sum_pq |B_pq| - what |psi| can reach on the unit disc - beyond 1e9 rad.  A refused call changes nothing.  May
+ * synchronise.  The plan stays until the next plan or ml_ctx_destroy.
+ * ml_fields_pupil_apply: the planned pupil on the field sets first_set ... first_set + n_sets - 1, 1 <= n_sets <= 3, in one
+ * launch; membership, zone, psi and its sincos are computed once per sample for all sets, and every set has the bits of
+ * the set taken alone.  Undoes ml_nearfield_premodulate first, as ml_fields_download does.  Queued on the context's stream:
+ * no host synchronisation, no download, no atomics.  Afterwards the fields count as supplied by the caller, as after
+ * ml_fields_upload.  ML_ESTATE without a plan, without a resident field set, or when the plan's shape is not the resident
+ * one; ML_EINVAL for n_sets outside [1, 3], sets that are not resident, a context of more than one rank.  Replaces no
+ * reference lines.                                                                     */
+int ml_fields_pupil_plan(ml_ctx *ctx, const double *x2, const double *xi, int nx, const double *y2, const double *eta,
+                         int ny, double r2, int stop, int n_max, const double *c, const double *e2, int n_edges,
+                         const double *g);
+int ml_fields_pupil_apply(ml_ctx *ctx, int first_set, int n_sets);
 
 /* The same fields for a tensor grid of targets ON THE APERTURE'S PITCH, by FFT convolution
  * (csrc/propagate_grid_plan.hip; the pass: csrc/propagate_grid.hip): targets (tx0 + i dxp, ty0 + j dyp, z), i < mx, j < my, target t = i my + j; the

@@ -53,7 +53,7 @@ SYMBOLS = (
     'ml_propagate_plan_grid_fine', 'ml_propagate_plan_lattices', 'ml_math_probe',
     'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes', 'ml_propagate_focus',
     'ml_propagate_otf', 'ml_nearfield_synth_info', 'ml_farfield_beam', 'ml_farfield_beams',
-    'ml_fields_zones', 'ml_fields_zernike', 'ml_geometry_probe',
+    'ml_fields_zones', 'ml_fields_zernike', 'ml_geometry_probe', 'ml_fields_pupil_plan', 'ml_fields_pupil_apply',
 )
 
 
@@ -199,6 +199,9 @@ def load():
     if hasattr(lib, 'ml_fields_zernike'):
         lib.ml_fields_zernike.argtypes = [c_void_p, c_int, c_int, _dp, _dp, c_int, _dp, _dp, c_int, c_double, c_int, c_int, _dp, _dp,
                                           c_double, c_double, _dp, c_int]
+    if hasattr(lib, 'ml_fields_pupil_plan'):
+        lib.ml_fields_pupil_plan.argtypes = [c_void_p, _dp, _dp, c_int, _dp, _dp, c_int, c_double, c_int, c_int, _dp, _dp, c_int, _dp]
+        lib.ml_fields_pupil_apply.argtypes = [c_void_p, c_int, c_int]
     if hasattr(lib, 'ml_math_probe'):   # (test surface: tests/test_gpu_device_math.py)
         lib.ml_math_probe.argtypes = [c_void_p, c_int, _dp, _ip, c_int, _dp, _dp, _ip]
     if hasattr(lib, 'ml_geometry_probe'):   # (test surface: tests/test_gpu_geometry_cases.py)
@@ -331,6 +334,8 @@ class Context:
         self.fields_owner = None
         # ... and which PlanePropagator made the active propagation plan (its targets and result)
         self.propagate_owner = None
+        # ... and which AperturePupil made the active pupil plan (ml_fields_pupil_plan)
+        self.pupil_owner = None
 
     def close(self):
         if getattr(self, '_h', None):

@@ -19,6 +19,7 @@
 #include "synth_caches.h"
 #include "transform_route.h"
 #include "propagate_grid.h"
+#include "fields_pupil.h"
 
 namespace ml {
 
@@ -513,6 +514,10 @@ struct ml_ctx {
     // Zernike moments of the resident near field's wavefront (fields_wavefront.hip, ml_fields_zernike): the call's axis
     // arrays, the line records, and the sets' monomial moments
     ml::DevBuf wavefront_in, wavefront_lines, wavefront_records;
+    // the pupil function applied to the resident near field (fields_pupil.hip, ml_fields_pupil_plan / _apply): the plan's
+    // axis arrays, line table, edges and factors, and what the plan was made for; it stays until the next plan
+    ml::DevBuf pupil_in;
+    ml::PupilPlan pupil;
     ml::DevBuf lattice_in;  // staging for ml_farfield_lattice_power
     int gemm_f32 = 0;   // ml_farfield_set_precision: folded GEMMs on the fp32 matrix cores
     int ff_method = 0;  // ml_farfield_set_method: 0 auto (FFT on lattice grids), 1 GEMMs only

@@ -1,0 +1,273 @@
+// A pupil function applied to the resident near field where it lies (ml_fields_pupil_plan, ml_fields_pupil_apply): an
+// aperture stop, one complex factor per zone and a Zernike phase plate, multiplied into the field sets in place, so that
+// the transform, the propagator, the zone and wavefront analyses and a sweep see the modified aperture without a change of
+// their own.  Definitions, which samples change and how every value is formed: fields_pupil.h.  The reference has no
+// counterpart (SURVEY.md section 4 ends at "checked by eye").
+//
+// The plan does the host's share once: it checks the call, forms the monomial coefficients B_pq of the phase plate and the
+// per-line table b_q(i) = sum_p B_pq xi^p, and uploads axes, table, edges and factors into one buffer of the context.
+//
+// The pass, pupil_line_kernel<NS, NQ, EDGES>, is ONE launch: one wave per line, four lines per workgroup, as
+// wavefront_line_kernel; the squared edges lie in the LDS (8 K bytes) and a lane finds its zone there by bisection, the
+// zone's factor is a gather from global memory (K <= 4096 factors: they stay in the caches).  The wave takes the line in
+// blocks of 64 samples in ascending order.  Membership, zone, psi and its sincos are computed once per sample and serve all
+// NS sets of the call; per set the four fields of a sample are four 16-byte loads and four 16-byte stores past the
+// caches, coalesced over the wave, and the loads of block b + 1 are issued before the arithmetic of block b.  What a lane
+// does NOT do: a stopped non-member is stored as zeros and never loaded; a line whose vertex lies outside a stopped pupil
+// is stores only; a sample whose factor is exactly 1 - without stop and edges every non-member, and with them whatever
+// lies outside the last edge - is neither loaded nor stored.  No atomics, no reduction, nothing read back: the launch is
+// queued and the entry returns.
+#include "nearfield_math.h"
+#include "fields_pupil.h"
+
+#pragma clang fp contract(off)
+
+namespace ml {
+
+static_assert(PUPIL_PHASE_LIMIT == PHASE_LIMIT, "fields_pupil.h restates common.h PHASE_LIMIT");
+
+struct PupilArgs {
+    double2 *fields;         // [NS][4][nx][ny]: Ex, Ey, Hx, Hy of the first set of the call, the others behind it
+    const double *x2, *y2;   // [nx], [ny]
+    const double *eta;       // [ny]
+    const double *table;     // [nx][PUPIL_NQ]: b_q(i)
+    const double *e2;        // [K]
+    const double *g;         // [K][2]
+    int nx, ny, K, jv, stop;
+    double r2;
+};
+
+// one 16-byte store past the caches, as the synthesis stores its fields: at 4096^2 a set is 1 GB, nothing of it is still
+// cached when the transform reads it, and with the transform right behind the pass this was the faster of the two
+// (0.585 ms against 0.594 with plain stores)
+__device__ __forceinline__ void pupil_store(double2 *p, double re, double im) {
+    typedef double double2v __attribute__((ext_vector_type(2)));
+    __builtin_nontemporal_store((double2v){re, im}, reinterpret_cast<double2v *>(p));
+}
+
+// searchsorted(e2, r2, side = 'left'): the number of edges below r2 (fields_zones.hip zones_find)
+__device__ __forceinline__ int pupil_find(const double *e2, int K, double r2) {
+    int lo = 0, hi = K;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e2[mid] < r2)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// what a lane holds of a block: what becomes of its sample, then its pupil coordinate, its zone factor and the four
+// fields of every set
+template <int NS>
+struct PupilBlock {
+    bool member, touch, zero;   // touch: multiplied by a factor; zero: a stopped non-member
+    double eta;
+    double2 g;
+    double2 f[NS][4];
+};
+
+template <int NS, int NQ, bool EDGES>
+__device__ __forceinline__ void pupil_fetch(const PupilArgs &a, const double *s_e2, const double2 *row, size_t plane, double x2, int j,
+                                            PupilBlock<NS> &b) {
+    const bool in_line = j < a.ny;
+    const double r2 = in_line ? x2 + a.y2[j] : INFINITY;
+    b.member = r2 <= a.r2;
+    b.zero = in_line && !b.member && a.stop;
+    b.eta = 0.0;
+    b.g = make_double2(1.0, 0.0);
+    bool factor = false;   // a zone factor of its own
+    if (EDGES && in_line && !b.zero) {
+        const int z = pupil_find(s_e2, a.K, r2);
+        if (z < a.K) {   // (z < K: inside g)
+            factor = true;
+            b.g = make_double2(a.g[2 * z], a.g[2 * z + 1]);
+        }
+    }
+    b.touch = in_line && !b.zero && (factor || (NQ > 0 && b.member));
+#pragma unroll
+    for (int m = 0; m < NS; ++m)
+#pragma unroll
+        for (int f = 0; f < 4; ++f) b.f[m][f] = make_double2(0.0, 0.0);
+    if (b.touch) {   // (j < ny: inside the line)
+        if (NQ > 0 && b.member) b.eta = a.eta[j];
+#pragma unroll
+        for (int m = 0; m < NS; ++m)
+#pragma unroll
+            for (int f = 0; f < 4; ++f) b.f[m][f] = row[(size_t)(4 * m + f) * plane + j];
+    }
+}
+
+template <int NS, int NQ, bool EDGES>
+__global__ __launch_bounds__(PUPIL_LINE_THREADS) void pupil_line_kernel(const PupilArgs a) {
+    extern __shared__ double s_e2[];
+    if (EDGES) {
+        for (int k = threadIdx.x; k < a.K; k += PUPIL_LINE_THREADS) s_e2[k] = a.e2[k];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int line = __builtin_amdgcn_readfirstlane(blockIdx.x * (PUPIL_LINE_THREADS / 64) + (threadIdx.x >> 6));
+    if (line >= a.nx) return;
+    const double x2 = a.x2[line];
+    const size_t plane = (size_t)a.nx * a.ny;
+    double2 *row = a.fields + (size_t)line * a.ny;
+    if (!(x2 + a.y2[a.jv] <= a.r2)) {   // the vertex lies outside: so does the line
+        if (a.stop) {                   // stores only
+            for (int j = lane; j < a.ny; j += PUPIL_BLOCK)
+#pragma unroll
+                for (int q = 0; q < 4 * NS; ++q) pupil_store(row + (size_t)q * plane + j, 0.0, 0.0);
+            return;
+        }
+        if (!EDGES) return;             // every factor is exactly 1
+    }
+    double bq[NQ > 0 ? NQ : 1];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) bq[q] = a.table[(size_t)line * PUPIL_NQ + q];
+    const int blocks = (a.ny + PUPIL_BLOCK - 1) / PUPIL_BLOCK;
+    PupilBlock<NS> cur, nxt;
+    pupil_fetch<NS, NQ, EDGES>(a, s_e2, row, plane, x2, lane, cur);
+    for (int b = 0; b < blocks; ++b) {
+        const int j = b * PUPIL_BLOCK + lane;
+        if (b + 1 < blocks) pupil_fetch<NS, NQ, EDGES>(a, s_e2, row, plane, x2, j + PUPIL_BLOCK, nxt);   // (in flight over this block's arithmetic)
+        if (cur.zero) {   // (zero: j < ny)
+#pragma unroll
+            for (int q = 0; q < 4 * NS; ++q) pupil_store(row + (size_t)q * plane + j, 0.0, 0.0);
+        } else if (cur.touch) {   // (touch: j < ny)
+            double fr = cur.g.x, fi = cur.g.y;
+            if (NQ > 0 && cur.member) {
+                double psi = bq[NQ > 0 ? NQ - 1 : 0];   // Horner in eta, q descending
+#pragma unroll
+                for (int q = NQ - 2; q >= 0; --q) psi = psi * cur.eta + bq[q];
+                double sn, cs;
+                sincos_cw(psi, sn, cs);
+                fr = cur.g.x * cs - cur.g.y * sn;
+                fi = cur.g.x * sn + cur.g.y * cs;
+            }
+#pragma unroll
+            for (int m = 0; m < NS; ++m)
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    const double2 E = cur.f[m][f];
+                    pupil_store(row + (size_t)(4 * m + f) * plane + j, E.x * fr - E.y * fi, E.x * fi + E.y * fr);
+                }
+        }
+        if (b + 1 < blocks) cur = nxt;
+    }
+}
+
+template <int NS, int NQ>
+static void pupil_launch_edges(hipStream_t stream, dim3 grid, const PupilArgs &a) {
+    if (a.K > 0)
+        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, true>), grid, dim3(PUPIL_LINE_THREADS), (size_t)a.K * sizeof(double), stream, a);
+    else
+        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, false>), grid, dim3(PUPIL_LINE_THREADS), 0, stream, a);
+}
+
+template <int NS>
+static void pupil_launch_phase(hipStream_t stream, dim3 grid, const PupilArgs &a, int nq) {
+    if (nq == 0)
+        pupil_launch_edges<NS, 0>(stream, grid, a);
+    else if (nq == 5)
+        pupil_launch_edges<NS, 5>(stream, grid, a);
+    else
+        pupil_launch_edges<NS, PUPIL_NQ>(stream, grid, a);
+}
+
+}  // namespace ml
+
+using namespace ml;
+
+extern "C" {
+
+int ml_fields_pupil_plan(ml_ctx *ctx, const double *x2, const double *xi, int nx, const double *y2, const double *eta, int ny, double r2,
+                         int stop, int n_max, const double *c, const double *e2, int n_edges, const double *g) {
+    ML_REQUIRE(ctx, "NULL argument");
+    char why[400];
+    double B[PUPIL_NQ * PUPIL_NQ];
+    if (pupil_check(ctx->n_ranks, x2, xi, nx, y2, eta, ny, r2, stop, n_max, c, e2, n_edges, g, B, why, sizeof why) != 0) {
+        set_error("%s", why);
+        return ML_EINVAL;
+    }
+    ML_HIP(hipSetDevice(ctx->device));
+    const int K = n_edges;
+    // the plan's arrays in one upload: x2 [nx]; y2, eta [ny]; the line table [nx][PUPIL_NQ]; e2 [K]; g [K][2]
+    std::vector<double> h((size_t)pupil_plan_doubles(nx, ny, K));
+    double *at = h.data();
+    std::copy(x2, x2 + nx, at);
+    at += nx;
+    std::copy(y2, y2 + ny, at);
+    at += ny;
+    std::copy(eta, eta + ny, at);
+    at += ny;
+    pupil_line_table(n_max, B, xi, nx, at);
+    at += (size_t)nx * PUPIL_NQ;
+    if (K > 0) {
+        std::copy(e2, e2 + K, at);
+        std::copy(g, g + 2 * (size_t)K, at + K);
+    }
+    // a pass of the plan before may still read the buffer: the copy is queued behind it, and a larger buffer is
+    // allocated only once the stream has drained
+    if (h.size() * sizeof(double) > ctx->pupil_in.bytes) ML_HIP(hipStreamSynchronize(ctx->stream));
+    ML_TRY(ctx->pupil_in.reserve(h.size() * sizeof(double)));
+    ML_HIP(hipMemcpyAsync(ctx->pupil_in.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    PupilPlan &p = ctx->pupil;
+    p.valid = false;
+    ML_HIP(hipStreamSynchronize(ctx->stream));   // h leaves with this call
+    p.nx = nx;
+    p.ny = ny;
+    p.K = K;
+    p.jv = zones_vertex(y2, ny);
+    p.nq = !c ? 0 : n_max <= 4 ? 5 : PUPIL_NQ;
+    p.stop = stop;
+    p.r2 = r2;
+    p.valid = true;
+    return ML_OK;
+}
+
+int ml_fields_pupil_apply(ml_ctx *ctx, int first_set, int n_sets) {
+    ML_REQUIRE(ctx, "NULL argument");
+    ZonesState st;
+    st.n_ranks = ctx->n_ranks;
+    st.nx = ctx->fields.nx;
+    st.ny = ctx->fields.ny;
+    st.n_sets = ctx->fields.n_sets;
+    char why[400];
+    const int rc = pupil_apply_check(st, ctx->pupil, first_set, n_sets, why, sizeof why);
+    if (rc != 0) {
+        set_error("%s", why);
+        return rc == -2 ? ML_ESTATE : ML_EINVAL;
+    }
+    ML_HIP(hipSetDevice(ctx->device));
+    ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
+    const PupilPlan &p = ctx->pupil;
+    PupilArgs a;
+    a.fields = ctx->fields.buf.as<double2>() + (size_t)first_set * 4 * p.nx * p.ny;
+    a.x2 = ctx->pupil_in.as<double>();
+    a.y2 = a.x2 + p.nx;
+    a.eta = a.y2 + p.ny;
+    a.table = a.eta + p.ny;
+    a.e2 = a.table + (size_t)p.nx * PUPIL_NQ;
+    a.g = a.e2 + p.K;
+    a.nx = p.nx;
+    a.ny = p.ny;
+    a.K = p.K;
+    a.jv = p.jv;
+    a.stop = p.stop;
+    a.r2 = p.r2;
+    const int lines = PUPIL_LINE_THREADS / 64;
+    const dim3 grid((p.nx + lines - 1) / lines);
+    if (n_sets == 1)
+        pupil_launch_phase<1>(ctx->stream, grid, a, p.nq);
+    else if (n_sets == 2)
+        pupil_launch_phase<2>(ctx->stream, grid, a, p.nq);
+    else
+        pupil_launch_phase<3>(ctx->stream, grid, a, p.nq);
+    ML_HIP(hipGetLastError());
+    // the fields are no longer the synthesis's: nothing is assumed about the zeros outside the lens, and row_first is
+    // not theirs - the next synthesis writes every sample again
+    ctx->caches.fields_overwritten();
+    return ML_OK;
+}
+
+}  // extern "C"

@@ -506,3 +506,150 @@ def wavefront_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, radius, n_max=4
             M[p][q] = (pw[None, None, :] * T[:, :, :, q]).sum(axis=2)
         pw = pw * xi
     return _wavefront_dict(_wavefront_convert(head, M, n_max), z['dA'], shape[0] * shape[1], z['R'], n_max)
+
+
+PUPIL_NQ = ZERNIKE_ORDER_MAX + 1   # csrc/fields_pupil.h PUPIL_NQ: the entries of a line of the table
+PUPIL_PHASE_LIMIT = 1e9            # csrc/fields_pupil.h PUPIL_PHASE_LIMIT
+
+
+def _check_pupil(x, y, radius, centre=(0.0, 0.0), stop=True, phase=None, edges=None, zone_factors=None):
+    """the argument checks of ``AperturePupil``, ``apply_pupil``, ``pupil_factor`` and ``apply_pupil_host``, before any device call,
+    and what the host forms for ml_fields_pupil_plan -> dict: ``x2``, ``y2``, ``xi``, ``eta``, ``r2``, ``R`` as ``_check_wavefront``
+    forms them, ``stop`` (0 or 1), ``n_max`` and ``c`` (the phase coefficients, or None), ``e2`` and ``g`` (the squared edges and
+    the factors as ``(K, 2)`` doubles, or None)"""
+    try:
+        R = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError('radius must be one number, got %r' % (radius,)) from None
+    if not (np.isfinite(R) and R > 0):
+        raise ValueError('the radius of the pupil must be finite and > 0, got %r' % (radius,))
+    if not isinstance(stop, (bool, np.bool_)):
+        raise ValueError('stop must be True or False, got %r' % (stop,))
+    n_max, c = 0, None
+    if phase is not None:
+        try:
+            c = np.array(phase, dtype=float)
+        except (TypeError, ValueError):
+            raise ValueError('phase must be a sequence of Zernike coefficients in radians, got %r' % (phase,)) from None
+        orders = {(n + 1) * (n + 2) // 2: n for n in range(ZERNIKE_ORDER_MAX + 1)}
+        if c.ndim != 1 or c.size not in orders:
+            raise ValueError('phase must hold the (n_max + 1)(n_max + 2) / 2 coefficients of the terms up to a radial order n_max <= %d '
+                             '(zernike_terms): 1, 3, 6, ... 45 numbers, got an array of shape %s' % (ZERNIKE_ORDER_MAX, c.shape))
+        if not np.isfinite(c).all():
+            j = int(np.argmin(np.isfinite(c)))
+            raise ValueError('a phase coefficient must be finite: phase[%d] = %g' % (j, c[j]))
+        n_max = orders[c.size]
+    if (edges is None) != (zone_factors is None):
+        raise ValueError('edges and zone_factors go together: one factor per zone, got edges=%s and zone_factors=%s'
+                         % ('None' if edges is None else 'given', 'None' if zone_factors is None else 'given'))
+    e = [R] if edges is None else edges
+    z = _check_zones(x, y, 1.0, 1.0, e, centre)
+    g = None
+    if zone_factors is not None:
+        try:
+            gz = np.array(zone_factors, dtype=complex)
+        except (TypeError, ValueError):
+            raise ValueError('zone_factors must be a sequence of complex numbers, got %r' % (zone_factors,)) from None
+        if gz.shape != z['e2'].shape:
+            raise ValueError('zone_factors must hold one factor per edge: got shape %s for %d edges' % (gz.shape, z['e2'].size))
+        if not (np.isfinite(gz.real) & np.isfinite(gz.imag)).all():
+            k = int(np.argmin(np.isfinite(gz.real) & np.isfinite(gz.imag)))
+            raise ValueError('a zone factor must be finite: zone_factors[%d] = %r' % (k, complex(gz[k])))
+        g = np.ascontiguousarray(np.stack([gz.real, gz.imag], axis=-1))
+    x, y, ce = np.asarray(x, dtype=float), np.asarray(y, dtype=float), np.asarray(centre, dtype=float)
+    out = dict(x2=z['x2'], y2=z['y2'], xi=(x - ce[0]) / R, eta=(y - ce[1]) / R, R=R, r2=R * R, stop=int(bool(stop)), n_max=n_max, c=c,
+               e2=z['e2'] if edges is not None else None, g=g)
+    if c is not None:
+        reach = float(np.abs(_pupil_monomials(n_max, c)).sum())
+        if not reach <= PUPIL_PHASE_LIMIT:
+            raise ValueError('the phase plate can reach %.6g rad on the unit disc: the phase arithmetic covers up to %g'
+                             % (reach, PUPIL_PHASE_LIMIT))
+    return out
+
+
+def _pupil_monomials(n_max, c):
+    """``B[p, q] = sum_j (c_j N_j) A_j,pq`` over the terms whose coefficient is not 0, ``j`` ascending, onto +0.0: the phase plate
+    as a polynomial in ``(xi, eta)``, shape ``(9, 9)`` (csrc/fields_pupil.h pupil_monomials)"""
+    B = np.zeros((PUPIL_NQ, PUPIL_NQ))
+    for j, (n, m) in enumerate(zernike_terms(n_max)):
+        cn = float(c[j]) * _zernike_norm(int(n), int(m))
+        for (p, q), A in _zernike_coefficients(int(n), int(m)).items():
+            B[p, q] = B[p, q] + cn * float(A)
+    return B
+
+
+def _pupil_line_table(n_max, B, xi):
+    """``b[i, q] = sum_p B[p, q] xi[i]^p`` by Horner, ``p`` descending from ``n_max - q``; +0.0 beyond ``n_max`` (csrc/fields_pupil.h
+    pupil_line_table)"""
+    table = np.zeros((xi.size, PUPIL_NQ))
+    for q in range(n_max + 1):
+        b = np.full(xi.size, B[n_max - q, q])
+        for p in range(n_max - q - 1, -1, -1):
+            b = b * xi + B[p, q]
+        table[:, q] = b
+    return table
+
+
+def _pupil_parts(z):
+    """-> ``member``, ``zero`` (the stopped non-members), ``touch`` (the samples multiplied by a factor) and the factor's parts
+    ``fr``, ``fi``, each of shape ``(nx, ny)``, by the route of csrc/fields_pupil.h, every operation rounded on its own"""
+    r2 = z['x2'][:, None] + z['y2'][None, :]
+    member = r2 <= z['r2']
+    zero = ~member & bool(z['stop'])
+    gr, gi = np.ones(r2.shape), np.zeros(r2.shape)
+    factor = np.zeros(r2.shape, dtype=bool)
+    if z['e2'] is not None:
+        K = z['e2'].size
+        zone = np.searchsorted(z['e2'], r2, side='left')
+        factor = (zone < K) & ~zero
+        at = np.minimum(zone, K - 1)
+        gr, gi = np.where(factor, z['g'][at, 0], 1.0), np.where(factor, z['g'][at, 1], 0.0)
+    phased = member & (z['c'] is not None)
+    fr, fi = gr, gi
+    if z['c'] is not None:
+        n_max = z['n_max']
+        table = _pupil_line_table(n_max, _pupil_monomials(n_max, z['c']), z['xi'])
+        eta = np.where(member, z['eta'][None, :], 0.0)
+        psi = np.repeat(table[:, PUPIL_NQ - 1:], z['y2'].size, axis=1)
+        for q in range(PUPIL_NQ - 2, -1, -1):
+            psi = psi * eta + table[:, q:q + 1]
+        cs, sn = np.cos(psi), np.sin(psi)
+        fr = np.where(phased, gr * cs - gi * sn, gr)
+        fi = np.where(phased, gr * sn + gi * cs, gi)
+    return member, zero, ~zero & (factor | phased), fr, fi
+
+
+def pupil_factor(x, y, radius, centre=(0.0, 0.0), stop=True, phase=None, edges=None, zone_factors=None):
+    """The pupil function of ``AperturePupil`` on the host, by the same route with every operation rounded on its own
+    (csrc/fields_pupil.h): -> ``(member, f)``, each of shape ``(len(x), len(y))``.  ``member``: ``(x - xc)^2 + (y - yc)^2 <= radius^2``,
+    a sample on the rim is inside.  ``f``: the complex factor of every sample - ``g[zone] exp(+i psi)`` on a member, with
+    ``psi = sum_j phase[j] Z_j(xi, eta)`` (``zernike_terms`` gives the order) and ``g[zone] = zone_factors[searchsorted(edges^2,
+    r^2, 'left')]``, exactly 1 outside every edge and without edges; on a non-member 0 with ``stop`` and its zone factor alone
+    without."""
+    z = _check_pupil(x, y, radius, centre, stop, phase, edges, zone_factors)
+    member, zero, _touch, fr, fi = _pupil_parts(z)
+    f = np.empty(member.shape, dtype=np.complex128)
+    f.real, f.imag = np.where(zero, 0.0, fr), np.where(zero, 0.0, fi)
+    return member, f
+
+
+def apply_pupil_host(Ex, Ey, Hx, Hy, x, y, radius, centre=(0.0, 0.0), stop=True, phase=None, edges=None, zone_factors=None):
+    """What ``AperturePupil.apply`` does to the resident field sets, for host arrays in NumPy: ``Ex, Ey, Hx, Hy`` of shape
+    ``(len(x), len(y))`` or ``(sets, len(x), len(y))`` -> the four arrays multiplied by ``pupil_factor`` - ``(E.r f.r - E.i f.i) + i
+    (E.r f.i + E.i f.r)`` -, stopped non-members +0.0, and every sample whose factor is exactly 1 (no phase applies to it and
+    no zone factor is given for it) with the bytes it had."""
+    z = _check_pupil(x, y, radius, centre, stop, phase, edges, zone_factors)
+    F = [np.asarray(a, dtype=np.complex128) for a in (Ex, Ey, Hx, Hy)]
+    shape = (z['x2'].size, z['y2'].size)
+    for name, a in zip(('Ex', 'Ey', 'Hx', 'Hy'), F):
+        if a.ndim not in (2, 3) or a.shape[-2:] != shape or a.shape != F[0].shape:
+            raise ValueError('%s has shape %s, the axes give %s' % (name, a.shape[-2:] if a.ndim == 3 else a.shape, shape))
+    _member, zero, touch, fr, fi = _pupil_parts(z)
+    out = []
+    for a in F:
+        r = a.copy()
+        prod_r, prod_i = a.real * fr - a.imag * fi, a.real * fi + a.imag * fr
+        r.real = np.where(touch, prod_r, np.where(zero, 0.0, a.real))
+        r.imag = np.where(touch, prod_i, np.where(zero, 0.0, a.imag))
+        out.append(r)
+    return tuple(out)

@@ -96,7 +96,17 @@ class SourceSweep:
             raise ValueError('image= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
                              % (tuple(image.aperture_shape) + (self.x.size, self.y.size)))
 
-    def queue(self, sources, image=None, beam_cones=None, beam_centre='peak'):
+    def _check_pupil(self, pupil):
+        """argument errors of ``pupil=``, before any device call"""
+        if pupil is None:
+            return
+        if pupil.ctx is not self.ctx:
+            raise ValueError('pupil= must be an AperturePupil built on the context of this sweep (ctx=sweep.ctx)')
+        if tuple(pupil.shape) != (self.x.size, self.y.size):
+            raise ValueError('pupil= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
+                             % (tuple(pupil.shape) + (self.x.size, self.y.size)))
+
+    def queue(self, sources, image=None, beam_cones=None, beam_centre='peak', pupil=None):
         """queue the whole sweep on the GPU and return without synchronising (benchmarks);
         tie settlement and the downloads are ``run``'s business.
 
@@ -107,7 +117,8 @@ class SourceSweep:
         noticed (the context's tokens change) and triggers a full re-check.
 
         ``image``: as for ``run``; its sums stay on the GPU (``image.sums()``).  ``beam_cones``, ``beam_centre``: as for
-        ``run``; the records stay in the sources' slots (``ml_farfield_beams``)."""
+        ``run``; the records stay in the sources' slots (``ml_farfield_beams``).  ``pupil``: as for ``run``."""
+        self._check_pupil(pupil)
         beam = None
         if beam_cones is not None:
             beam_c, _back, beam_ce = _check_beam(beam_cones, beam_centre)
@@ -116,7 +127,7 @@ class SourceSweep:
         self.prepare(check_content=False)
         weights = np.ones(len(sources))
         for g in self._group(sources):
-            self._pass(g, None, (0.0, 0.0, 0.0), weights, image, beam)
+            self._pass(g, None, (0.0, 0.0, 0.0), weights, image, beam, pupil)
 
     def _group(self, sources):
         """consecutive sources at one position -> batches of up to MAX_BATCH polarisations (one
@@ -147,10 +158,11 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights, image=None, beam=None):
+    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None):
         """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
         group's field sets are then propagated to its targets in one pass and added to the image sums; with ``beam`` =
-        (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot"""
+        (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot; with
+        ``pupil`` the group's field sets are multiplied by it right after every synthesis, before anything reads them"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -160,6 +172,8 @@ class SourceSweep:
                                          self.dipole_moment, self.c0, self.Z0)
         _lib.check(lib.ml_nearfield_batch_async(ctx.handle, params, n, _lib.dptr(self.x), self.x.size,
                                                 _lib.dptr(self.y), self.y.size))
+        if pupil is not None:
+            pupil.queue(0, n)
         # member by member, each transform's second stage reading what its first stage has just
         # written (134 MB at 4096^2 -> 512^2: it is still in the 256 MB memory-side cache).  Stacking
         # the members' 4 S planes through one stage-1 launch was measured and taken out again: stage 1
@@ -183,6 +197,8 @@ class SourceSweep:
             if n > 1 and len(set(group['positions'])) == 1:
                 _lib.check(lib.ml_nearfield_members_async(ctx.handle, params, n, _lib.dptr(self.x), self.x.size,
                                                           _lib.dptr(self.y), self.y.size, 1))
+                if pupil is not None:
+                    pupil.queue(0, n)
             image.queue_sets(0, n)
             image.accumulate([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
         return n
@@ -215,7 +231,7 @@ class SourceSweep:
         return fx, fy
 
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
-            image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak'):
+            image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak', pupil=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -253,7 +269,13 @@ class SourceSweep:
         points), ``second_moments_u`` (how wide it is), ``cone_P`` of shape ``(len(sources), len(beam_cones))``, ... -,
         ``beam_sum``, the same of ``P_sum`` (no leading axis), and ``beam_efficiency = beam['cone_P'] / power_in[:, None]``.
         ``beam_centre``: ``'peak'`` (each map's own peak direction) or one ``(ux0, uy0)``.  Takes 1 to 4095 sources (one
-        slot is ``P_sum``'s)."""
+        slot is ``P_sum``'s).
+
+        ``pupil`` = an ``AperturePupil`` built on this sweep's context and axes: every source's field sets are multiplied by
+        it on the GPU right after their synthesis (``ml_fields_pupil_apply``, one launch per group, nothing synchronises),
+        so the maps, the sums, the beam records and the image are those of the modified aperture - the cone efficiency with
+        the coma removed, a ring re-phased, the outer zones stopped down.  ``power_in`` stays the incident power."""
+        self._check_pupil(pupil)
         beam = None
         if beam_cones is not None:
             beam_c, beam_back, beam_ce = _check_beam(beam_cones, beam_centre)
@@ -280,7 +302,7 @@ class SourceSweep:
         image_each = [None] * len(sources)
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights, image, beam)
+            n = self._pass(g, None, cone3, weights, image, beam, pupil)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -292,7 +314,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights, image, beam)
+                    n = self._pass(g, None, cone3, weights, image, beam, pupil)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:

@@ -36,6 +36,8 @@ class ApertureWavefront:
         self.n_max, self.terms, self.radius, self.dA = z['n_max'], z['terms'], z['R'], z['dA']
         self._mode, self._ref_c, self._k, self._r2 = z['mode'], z['ref_c'], z['k'], z['r2']
         self._x2, self._xi, self._y2, self._eta, self._ra, self._rb = (_lib.f64(z[key]) for key in ('x2', 'xi', 'y2', 'eta', 'ra', 'rb'))
+        # the pupil as given: what AperturePupil.from_wavefront builds the correcting pupil on
+        self._x, self._y, self._centre = np.array(xp_list, dtype=float), np.array(yp_list, dtype=float), (float(centre[0]), float(centre[1]))
         self.ctx = ctx or _lib.default_context()
 
     def records(self, first=0, n=None):

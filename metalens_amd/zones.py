@@ -46,6 +46,9 @@ class ApertureZones:
         self.dA = z['dA']
         self._mode, self._ref_c, self._k = z['mode'], z['ref_c'], z['k']
         self._x2, self._y2, self._e2, self._ra, self._rb = (_lib.f64(z[key]) for key in ('x2', 'y2', 'e2', 'ra', 'rb'))
+        # the zones as given: what AperturePupil.from_zones builds the re-phasing pupil on
+        self._x, self._y, self._centre = np.array(xp_list, dtype=float), np.array(yp_list, dtype=float), (float(centre[0]), float(centre[1]))
+        self._edges = np.array(edges, dtype=float)
         self.ctx = ctx or _lib.default_context()
 
     def records(self, first=0, n=None):
