@@ -4,7 +4,7 @@
 //
 // Pupil.  A disc of radius R > 0 about centre = (xc, yc), with X2, Y2, xi, eta and R2 = R R as fields_wavefront.h forms
 // them.  Sample (i, j) has r2 = X2[i] + Y2[j] - one rounded addition - and is a member iff r2 <= R2; a sample on the rim is
-// inside.  Y2 must fall to one minimum and rise again.
+// inside.  Y2 must fall to one minimum and rise again (fields_pass.h).
 //
 // The pupil function has three parts, each optional:
 //   stop     every field of a non-member becomes +0.0 + 0.0i.
@@ -30,7 +30,7 @@
 //   4. f = g (cs + i sn): fr = g.r cs - g.i sn, fi = g.r sn + g.i cs, with g = 1 + 0i where the zone factor is exactly 1;
 //      without a phase f = g.
 //   5. each of Ex, Ey, Hx, Hy becomes (E.r fr - E.i fi) + i (E.r fi + E.i fr).
-// |psi| <= sum_pq |B_pq| on the unit disc; a plan whose sum exceeds PUPIL_PHASE_LIMIT is refused.
+// |psi| <= sum_pq |B_pq| on the unit disc; a plan whose sum exceeds PASS_PHASE_LIMIT is refused.
 #pragma once
 
 #include "fields_wavefront.h"
@@ -40,10 +40,6 @@ namespace ml {
 constexpr int PUPIL_ORDER_MAX = WF_ORDER_MAX;
 constexpr int PUPIL_NQ = WF_ORDER_MAX + 1;     // entries of a line of the table
 constexpr int PUPIL_EDGES_MAX = ZONES_EDGES_MAX;
-constexpr int PUPIL_SETS_MAX = WF_SETS_MAX;    // field sets per launch (the members of a synthesis batch)
-constexpr int PUPIL_BLOCK = 64;                // samples of a block: one per lane of a wave
-constexpr int PUPIL_LINE_THREADS = 256;        // lanes of a workgroup: four lines
-constexpr double PUPIL_PHASE_LIMIT = WF_PHASE_LIMIT;
 
 // B[p * PUPIL_NQ + q] = B_pq; every entry is written (+0.0 where p + q > n_max).  c: wf_terms(n_max) coefficients, or
 // nullptr for no phase (all +0.0)
@@ -92,115 +88,51 @@ struct PupilPlan {
     int nq = 0;   // 0: no phase; 5: n_max <= 4; 9: the orders up to 8 - the instantiations of the kernel
     int stop = 0;
     double r2 = 0.0;
+    size_t x2 = 0, y2 = 0, eta = 0, table = 0, e2 = 0, g = 0;   // where the arrays begin in the upload, in doubles (PassPack)
 };
-
-static inline bool pupil_bad(const char *name, const double *v, int n, bool nonneg, const char *what, char *why, size_t why_len) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(v[i]) || (nonneg && v[i] < 0)) {
-            snprintf(why, why_len, "ml_fields_pupil_plan: %s[%d] = %g: %s", name, i, v[i], what);
-            return true;
-        }
-    return false;
-}
 
 // The argument checks of ml_fields_pupil_plan; B gets pupil_monomials of an accepted call.  -> 0, or -1 with `why` filled.
 inline int pupil_check(int n_ranks, const double *x2, const double *xi, int nx, const double *y2, const double *eta, int ny, double r2,
                        int stop, int n_max, const double *c, const double *e2, int n_edges, const double *g, double *B, char *why,
                        size_t why_len) {
-    if (n_ranks > 1) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: this context belongs to a communicator of %d ranks", n_ranks);
-        return -1;
-    }
-    if (stop != 0 && stop != 1) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: stop = %d: 0 to leave the samples outside the pupil standing or 1 to clear them", stop);
-        return -1;
-    }
-    if (n_max < 0 || n_max > PUPIL_ORDER_MAX) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: n_max = %d: radial orders 0 to %d are taken", n_max, PUPIL_ORDER_MAX);
-        return -1;
-    }
-    if (n_edges < 0 || n_edges > PUPIL_EDGES_MAX) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: %d edges: 0 to %d are taken", n_edges, PUPIL_EDGES_MAX);
-        return -1;
-    }
-    if (nx < 1 || ny < 1) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: the axes have %d x %d samples: at least one each", nx, ny);
-        return -1;
-    }
-    if (!x2 || !xi || !y2 || !eta || (n_edges > 0 && (!e2 || !g))) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: NULL argument");
-        return -1;
-    }
-    if (!(std::isfinite(r2) && r2 > 0)) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: r2 = %g: the squared radius of the pupil must be finite and > 0", r2);
-        return -1;
-    }
-    const char *sq = "a squared distance must be finite and >= 0";
-    if (pupil_bad("x2", x2, nx, true, sq, why, why_len) || pupil_bad("y2", y2, ny, true, sq, why, why_len)) return -1;
-    const char *co = "a pupil coordinate must be finite";
-    if (pupil_bad("xi", xi, nx, false, co, why, why_len) || pupil_bad("eta", eta, ny, false, co, why, why_len)) return -1;
-    const int jv = zones_vertex(y2, ny);
-    for (int j = 1; j < ny; ++j)
-        if (j <= jv ? y2[j] > y2[j - 1] : y2[j] < y2[j - 1]) {
-            snprintf(why, why_len, "ml_fields_pupil_plan: y2 must fall to its minimum y2[%d] = %g and rise again (a y axis in ascending or "
-                     "descending order): y2[%d] = %g follows y2[%d] = %g", jv, y2[jv], j, y2[j], j - 1, y2[j - 1]);
-            return -1;
-        }
-    if (n_edges > 0) {
-        if (pupil_bad("e2", e2, n_edges, true, "a squared edge must be finite and >= 0", why, why_len)) return -1;
-        for (int z = 1; z < n_edges; ++z)
-            if (e2[z] < e2[z - 1]) {
-                snprintf(why, why_len, "ml_fields_pupil_plan: the edges must not decrease: e2[%d] = %g < e2[%d] = %g", z, e2[z], z - 1,
-                         e2[z - 1]);
-                return -1;
-            }
-        for (int z = 0; z < n_edges; ++z)
-            if (!std::isfinite(g[2 * z]) || !std::isfinite(g[2 * z + 1])) {
-                snprintf(why, why_len, "ml_fields_pupil_plan: g[%d] = (%g, %g): a zone factor must be finite", z, g[2 * z], g[2 * z + 1]);
-                return -1;
-            }
-    }
-    if (c && pupil_bad("c", c, wf_terms(n_max), false, "a phase coefficient must be finite", why, why_len)) return -1;
+    const PassWhy w{"ml_fields_pupil_plan", why, why_len};
+    if (int rc = pass_check_comm(w, n_ranks)) return rc;
+    if (stop != 0 && stop != 1)
+        return pass_refuse(w, -1, "stop = %d: 0 to leave the samples outside the pupil standing or 1 to clear them", stop);
+    if (int rc = wf_check_order(w, n_max)) return rc;
+    if (int rc = pass_check_edge_count(w, n_edges, 0, PUPIL_EDGES_MAX)) return rc;
+    if (int rc = pass_check_axes(w, nx, ny)) return rc;
+    if (!x2 || !xi || !y2 || !eta || (n_edges > 0 && (!e2 || !g))) return pass_refuse(w, -1, "NULL argument");
+    if (int rc = pass_check_radius(w, r2)) return rc;
+    if (int rc = pass_check_squared_axes(w, x2, nx, y2, ny)) return rc;
+    if (int rc = pass_check_pupil_axes(w, xi, nx, eta, ny)) return rc;
+    if (int rc = pass_check_vertex(w, y2, ny)) return rc;
+    if (int rc = pass_check_edges(w, e2, n_edges)) return rc;
+    for (int z = 0; z < n_edges; ++z)
+        if (!std::isfinite(g[2 * z]) || !std::isfinite(g[2 * z + 1]))
+            return pass_refuse(w, -1, "g[%d] = (%g, %g): a zone factor must be finite", z, g[2 * z], g[2 * z + 1]);
+    if (c)
+        if (int rc = pass_check_range(w, "c", c, wf_terms(n_max), false, "a phase coefficient must be finite")) return rc;
     pupil_monomials(n_max, c, B);
     const double psi = pupil_phase_bound(B);
-    if (!(psi <= PUPIL_PHASE_LIMIT)) {
-        snprintf(why, why_len, "ml_fields_pupil_plan: the phase plate can reach %.6g rad on the unit disc: the phase arithmetic covers up "
-                 "to %g", psi, PUPIL_PHASE_LIMIT);
-        return -1;
-    }
+    if (!(psi <= PASS_PHASE_LIMIT))
+        return pass_refuse(w, -1, "the phase plate can reach %.6g rad on the unit disc: the phase arithmetic covers up to %g", psi,
+                           PASS_PHASE_LIMIT);
     return 0;
 }
 
-// The checks of ml_fields_pupil_apply against the plan and the resident field sets (fields_zones.h ZonesState).  -> 0; -1: an
-// argument error, -2: the state does not allow the call; `why` is filled then.
-inline int pupil_apply_check(const ZonesState &s, const PupilPlan &plan, int first_set, int n_sets, char *why, size_t why_len) {
-    if (s.n_ranks > 1) {
-        snprintf(why, why_len, "ml_fields_pupil_apply: this context belongs to a communicator of %d ranks", s.n_ranks);
-        return -1;
-    }
-    if (n_sets < 1 || n_sets > PUPIL_SETS_MAX) {
-        snprintf(why, why_len, "ml_fields_pupil_apply: a pass takes 1 to %d field sets, got %d", PUPIL_SETS_MAX, n_sets);
-        return -1;
-    }
-    if (!plan.valid) {
-        snprintf(why, why_len, "ml_fields_pupil_apply: no pupil has been planned on this context (ml_fields_pupil_plan)");
-        return -2;
-    }
-    if (s.nx == 0 || s.ny == 0) {
-        snprintf(why, why_len, "no resident field set");
-        return -2;
-    }
-    if (plan.nx != s.nx || plan.ny != s.ny) {
-        snprintf(why, why_len, "ml_fields_pupil_apply: the pupil was planned for %d x %d samples, the resident field sets have %d x %d",
-                 plan.nx, plan.ny, s.nx, s.ny);
-        return -2;
-    }
-    if (first_set < 0 || first_set + n_sets > s.n_sets) {
-        snprintf(why, why_len, "ml_fields_pupil_apply: field sets %d ... %d asked for, %d resident", first_set, first_set + n_sets - 1,
-                 s.n_sets);
-        return -1;
-    }
-    return 0;
+// The checks of ml_fields_pupil_apply against the plan and the resident field sets.  -> 0; -1: an argument error, -2: the
+// state does not allow the call; `why` is filled then.
+inline int pupil_apply_check(const PassState &s, const PupilPlan &plan, int first_set, int n_sets, char *why, size_t why_len) {
+    const PassWhy w{"ml_fields_pupil_apply", why, why_len};
+    if (int rc = pass_check_comm(w, s.n_ranks)) return rc;
+    if (int rc = pass_check_set_count(w, n_sets)) return rc;
+    if (!plan.valid) return pass_refuse(w, -2, "no pupil has been planned on this context (ml_fields_pupil_plan)");
+    if (int rc = pass_check_resident(w, s)) return rc;
+    if (plan.nx != s.nx || plan.ny != s.ny)
+        return pass_refuse(w, -2, "the pupil was planned for %d x %d samples, the resident field sets have %d x %d", plan.nx, plan.ny,
+                           s.nx, s.ny);
+    return pass_check_set_range(w, s, first_set, n_sets);
 }
 
 }  // namespace ml

@@ -18,13 +18,12 @@
 // lies outside the last edge - is neither loaded nor stored.  No atomics, no reduction, nothing read back: the launch is
 // queued and the entry returns.
 #include "nearfield_math.h"
-#include "fields_pupil.h"
 
 #pragma clang fp contract(off)
 
-namespace ml {
+#include "fields_dev.h"
 
-static_assert(PUPIL_PHASE_LIMIT == PHASE_LIMIT, "fields_pupil.h restates common.h PHASE_LIMIT");
+namespace ml {
 
 struct PupilArgs {
     double2 *fields;         // [NS][4][nx][ny]: Ex, Ey, Hx, Hy of the first set of the call, the others behind it
@@ -43,19 +42,6 @@ struct PupilArgs {
 __device__ __forceinline__ void pupil_store(double2 *p, double re, double im) {
     typedef double double2v __attribute__((ext_vector_type(2)));
     __builtin_nontemporal_store((double2v){re, im}, reinterpret_cast<double2v *>(p));
-}
-
-// searchsorted(e2, r2, side = 'left'): the number of edges below r2 (fields_zones.hip zones_find)
-__device__ __forceinline__ int pupil_find(const double *e2, int K, double r2) {
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e2[mid] < r2)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
 }
 
 // what a lane holds of a block: what becomes of its sample, then its pupil coordinate, its zone factor and the four
@@ -79,42 +65,36 @@ __device__ __forceinline__ void pupil_fetch(const PupilArgs &a, const double *s_
     b.g = make_double2(1.0, 0.0);
     bool factor = false;   // a zone factor of its own
     if (EDGES && in_line && !b.zero) {
-        const int z = pupil_find(s_e2, a.K, r2);
+        const int z = pass_find(s_e2, a.K, r2);
         if (z < a.K) {   // (z < K: inside g)
             factor = true;
             b.g = make_double2(a.g[2 * z], a.g[2 * z + 1]);
         }
     }
     b.touch = in_line && !b.zero && (factor || (NQ > 0 && b.member));
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-        for (int f = 0; f < 4; ++f) b.f[m][f] = make_double2(0.0, 0.0);
+    pass_zero<NS>(b.f);
     if (b.touch) {   // (j < ny: inside the line)
         if (NQ > 0 && b.member) b.eta = a.eta[j];
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b.f[m][f] = row[(size_t)(4 * m + f) * plane + j];
+        pass_load<NS>(b.f, row, plane, j);
     }
 }
 
 template <int NS, int NQ, bool EDGES>
-__global__ __launch_bounds__(PUPIL_LINE_THREADS) void pupil_line_kernel(const PupilArgs a) {
+__global__ __launch_bounds__(PASS_LINE_THREADS) void pupil_line_kernel(const PupilArgs a) {
     extern __shared__ double s_e2[];
     if (EDGES) {
-        for (int k = threadIdx.x; k < a.K; k += PUPIL_LINE_THREADS) s_e2[k] = a.e2[k];
+        for (int k = threadIdx.x; k < a.K; k += PASS_LINE_THREADS) s_e2[k] = a.e2[k];
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
-    const int line = __builtin_amdgcn_readfirstlane(blockIdx.x * (PUPIL_LINE_THREADS / 64) + (threadIdx.x >> 6));
+    const int line = __builtin_amdgcn_readfirstlane(blockIdx.x * (PASS_LINE_THREADS / 64) + (threadIdx.x >> 6));
     if (line >= a.nx) return;
     const double x2 = a.x2[line];
     const size_t plane = (size_t)a.nx * a.ny;
     double2 *row = a.fields + (size_t)line * a.ny;
     if (!(x2 + a.y2[a.jv] <= a.r2)) {   // the vertex lies outside: so does the line
         if (a.stop) {                   // stores only
-            for (int j = lane; j < a.ny; j += PUPIL_BLOCK)
+            for (int j = lane; j < a.ny; j += PASS_BLOCK)
 #pragma unroll
                 for (int q = 0; q < 4 * NS; ++q) pupil_store(row + (size_t)q * plane + j, 0.0, 0.0);
             return;
@@ -124,12 +104,12 @@ __global__ __launch_bounds__(PUPIL_LINE_THREADS) void pupil_line_kernel(const Pu
     double bq[NQ > 0 ? NQ : 1];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) bq[q] = a.table[(size_t)line * PUPIL_NQ + q];
-    const int blocks = (a.ny + PUPIL_BLOCK - 1) / PUPIL_BLOCK;
+    const int blocks = pass_blocks(a.ny);
     PupilBlock<NS> cur, nxt;
     pupil_fetch<NS, NQ, EDGES>(a, s_e2, row, plane, x2, lane, cur);
     for (int b = 0; b < blocks; ++b) {
-        const int j = b * PUPIL_BLOCK + lane;
-        if (b + 1 < blocks) pupil_fetch<NS, NQ, EDGES>(a, s_e2, row, plane, x2, j + PUPIL_BLOCK, nxt);   // (in flight over this block's arithmetic)
+        const int j = b * PASS_BLOCK + lane;
+        if (b + 1 < blocks) pupil_fetch<NS, NQ, EDGES>(a, s_e2, row, plane, x2, j + PASS_BLOCK, nxt);   // (in flight over this block's arithmetic)
         if (cur.zero) {   // (zero: j < ny)
 #pragma unroll
             for (int q = 0; q < 4 * NS; ++q) pupil_store(row + (size_t)q * plane + j, 0.0, 0.0);
@@ -159,9 +139,9 @@ __global__ __launch_bounds__(PUPIL_LINE_THREADS) void pupil_line_kernel(const Pu
 template <int NS, int NQ>
 static void pupil_launch_edges(hipStream_t stream, dim3 grid, const PupilArgs &a) {
     if (a.K > 0)
-        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, true>), grid, dim3(PUPIL_LINE_THREADS), (size_t)a.K * sizeof(double), stream, a);
+        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, true>), grid, dim3(PASS_LINE_THREADS), (size_t)a.K * sizeof(double), stream, a);
     else
-        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, false>), grid, dim3(PUPIL_LINE_THREADS), 0, stream, a);
+        hipLaunchKernelGGL((pupil_line_kernel<NS, NQ, false>), grid, dim3(PASS_LINE_THREADS), 0, stream, a);
 }
 
 template <int NS>
@@ -185,39 +165,32 @@ int ml_fields_pupil_plan(ml_ctx *ctx, const double *x2, const double *xi, int nx
     ML_REQUIRE(ctx, "NULL argument");
     char why[400];
     double B[PUPIL_NQ * PUPIL_NQ];
-    if (pupil_check(ctx->n_ranks, x2, xi, nx, y2, eta, ny, r2, stop, n_max, c, e2, n_edges, g, B, why, sizeof why) != 0) {
-        set_error("%s", why);
-        return ML_EINVAL;
-    }
+    ML_TRY(pass_checked(pupil_check(ctx->n_ranks, x2, xi, nx, y2, eta, ny, r2, stop, n_max, c, e2, n_edges, g, B, why, sizeof why), why));
     ML_HIP(hipSetDevice(ctx->device));
     const int K = n_edges;
-    // the plan's arrays in one upload: x2 [nx]; y2, eta [ny]; the line table [nx][PUPIL_NQ]; e2 [K]; g [K][2]
-    std::vector<double> h((size_t)pupil_plan_doubles(nx, ny, K));
-    double *at = h.data();
-    std::copy(x2, x2 + nx, at);
-    at += nx;
-    std::copy(y2, y2 + ny, at);
-    at += ny;
-    std::copy(eta, eta + ny, at);
-    at += ny;
-    pupil_line_table(n_max, B, xi, nx, at);
-    at += (size_t)nx * PUPIL_NQ;
-    if (K > 0) {
-        std::copy(e2, e2 + K, at);
-        std::copy(g, g + 2 * (size_t)K, at + K);
-    }
+    // the plan's arrays in one upload of pupil_plan_doubles(nx, ny, K) doubles; the plan keeps where each begins
+    PassPack in;
+    PupilPlan next;
+    next.x2 = in.add(x2, nx);
+    next.y2 = in.add(y2, ny);
+    next.eta = in.add(eta, ny);
+    next.table = in.add(nullptr, (size_t)nx * PUPIL_NQ);
+    pupil_line_table(n_max, B, xi, nx, in.h.data() + next.table);
+    next.e2 = in.add(e2, K);
+    next.g = in.add(g, 2 * (size_t)K);
     // a pass of the plan before may still read the buffer: the copy is queued behind it, and a larger buffer is
     // allocated only once the stream has drained
-    if (h.size() * sizeof(double) > ctx->pupil_in.bytes) ML_HIP(hipStreamSynchronize(ctx->stream));
-    ML_TRY(ctx->pupil_in.reserve(h.size() * sizeof(double)));
-    ML_HIP(hipMemcpyAsync(ctx->pupil_in.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (in.bytes() > ctx->pupil_in.bytes) ML_HIP(hipStreamSynchronize(ctx->stream));
+    ML_TRY(ctx->pupil_in.reserve(in.bytes()));
+    ML_HIP(hipMemcpyAsync(ctx->pupil_in.p, in.h.data(), in.bytes(), hipMemcpyHostToDevice, ctx->stream));
     PupilPlan &p = ctx->pupil;
     p.valid = false;
-    ML_HIP(hipStreamSynchronize(ctx->stream));   // h leaves with this call
+    ML_HIP(hipStreamSynchronize(ctx->stream));   // the host arrays leave with this call
+    p = next;
     p.nx = nx;
     p.ny = ny;
     p.K = K;
-    p.jv = zones_vertex(y2, ny);
+    p.jv = pass_vertex(y2, ny);
     p.nq = !c ? 0 : n_max <= 4 ? 5 : PUPIL_NQ;
     p.stop = stop;
     p.r2 = r2;
@@ -227,42 +200,29 @@ int ml_fields_pupil_plan(ml_ctx *ctx, const double *x2, const double *xi, int nx
 
 int ml_fields_pupil_apply(ml_ctx *ctx, int first_set, int n_sets) {
     ML_REQUIRE(ctx, "NULL argument");
-    ZonesState st;
-    st.n_ranks = ctx->n_ranks;
-    st.nx = ctx->fields.nx;
-    st.ny = ctx->fields.ny;
-    st.n_sets = ctx->fields.n_sets;
     char why[400];
-    const int rc = pupil_apply_check(st, ctx->pupil, first_set, n_sets, why, sizeof why);
-    if (rc != 0) {
-        set_error("%s", why);
-        return rc == -2 ? ML_ESTATE : ML_EINVAL;
-    }
+    ML_TRY(pass_checked(pupil_apply_check(pass_state(ctx), ctx->pupil, first_set, n_sets, why, sizeof why), why));
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     const PupilPlan &p = ctx->pupil;
     PupilArgs a;
     a.fields = ctx->fields.buf.as<double2>() + (size_t)first_set * 4 * p.nx * p.ny;
-    a.x2 = ctx->pupil_in.as<double>();
-    a.y2 = a.x2 + p.nx;
-    a.eta = a.y2 + p.ny;
-    a.table = a.eta + p.ny;
-    a.e2 = a.table + (size_t)p.nx * PUPIL_NQ;
-    a.g = a.e2 + p.K;
+    const double *d_in = ctx->pupil_in.as<double>();
+    a.x2 = d_in + p.x2;
+    a.y2 = d_in + p.y2;
+    a.eta = d_in + p.eta;
+    a.table = d_in + p.table;
+    a.e2 = d_in + p.e2;
+    a.g = d_in + p.g;
     a.nx = p.nx;
     a.ny = p.ny;
     a.K = p.K;
     a.jv = p.jv;
     a.stop = p.stop;
     a.r2 = p.r2;
-    const int lines = PUPIL_LINE_THREADS / 64;
+    const int lines = PASS_LINE_THREADS / 64;
     const dim3 grid((p.nx + lines - 1) / lines);
-    if (n_sets == 1)
-        pupil_launch_phase<1>(ctx->stream, grid, a, p.nq);
-    else if (n_sets == 2)
-        pupil_launch_phase<2>(ctx->stream, grid, a, p.nq);
-    else
-        pupil_launch_phase<3>(ctx->stream, grid, a, p.nq);
+    pass_for_sets(n_sets, [&](auto ns) { pupil_launch_phase<decltype(ns)::value>(ctx->stream, grid, a, p.nq); });
     ML_HIP(hipGetLastError());
     // the fields are no longer the synthesis's: nothing is assumed about the zeros outside the lens, and row_first is
     // not theirs - the next synthesis writes every sample again

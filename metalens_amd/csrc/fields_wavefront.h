@@ -4,13 +4,12 @@
 //
 // Pupil.  A disc of radius R > 0 about centre = (xc, yc).  The host hands over X2[i] = (x[i] - xc)^2, Y2[j] = (y[j] - yc)^2 and
 // R2 = R R, and xi[i] = (x[i] - xc) / R, eta[j] = (y[j] - yc) / R.  Sample (i, j) is a member iff X2[i] + Y2[j] <= R2 - one
-// rounded addition, a sample on the rim is inside: the rule of fields_zones.h.  Y2 must fall to one minimum and rise
-// again, so a line's members are one interval of j.
+// rounded addition, a sample on the rim is inside.  Y2 must fall to one minimum and rise again (fields_pass.h), so a line's
+// members are one interval of j.
 //
 // Terms of a member, per field set, every operation rounded on its own (nothing is contracted into an FMA): S, Ix, Iy,
-// Cx = Ex conj(w) and Cy exactly as in fields_zones.h, with the same two reference waves (WF_REF_PLANE: phi = ra[i] + rb[j];
-// WF_REF_FOCUS: phi = sk sqrt((ra[i] + rb[j]) + ref_c ref_c), sk = -sign(ref_c) k), the same ra, rb, ref_c, k and the same
-// refusal of a phase beyond WF_PHASE_LIMIT.
+// Cx = Ex conj(w) and Cy as fields_zones.h defines them (the device forms them by the same functions, fields_dev.h), with the
+// reference waves, ra, rb, ref_c, k and the refusal of a phase beyond PASS_PHASE_LIMIT of fields_pass.h.
 //
 // Zernike terms up to radial order n_max, 0 <= n_max <= WF_ORDER_MAX = 8: J = (n_max + 1)(n_max + 2) / 2 terms, 45 at the
 // most, in OSA/ANSI order, j = (n (n + 2) + m) / 2 with m = -n, -n + 2, ... n, m < 0 the sine term, with Noll normalisation
@@ -23,7 +22,7 @@
 // integer coefficients A_j,pq (wf_coefficients; all far below 2^53, exact in a double), so
 //   sum C Z_j = N_j sum_pq A_j,pq M_pq,   M_pq = sum_i xi[i]^p T_q(i),   T_q(i) = sum_j C(i, j) eta[j]^q :
 // per sample n_max + 1 multiply-adds per real component instead of J, no atan2 and no per-term trigonometry.
-//   1. Line i (fixed x, j contiguous) is taken by one wave in blocks of WF_BLOCK = 64 samples in ascending order; lane l
+//   1. Line i (fixed x, j contiguous) is taken by one wave in blocks of PASS_BLOCK = 64 samples in ascending order; lane l
 //      holds the samples l + 64 b.  Per member the powers eta^0 = 1, eta^q = eta^(q - 1) eta come by repeated multiplication,
 //      and the lane adds C eta^q (and S, Ix, Iy) onto accumulators that start at +0.0; a non-member adds nothing.
 //   2. At the line's end one butterfly per accumulator over the 64 lanes (lanes 32, 16, 8, 4, 2, 1 apart); the line record
@@ -40,35 +39,25 @@
 // the other sets are, and two calls agree to the bit.
 #pragma once
 
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <cstdio>
-
 #include "fields_zones.h"
 
 namespace ml {
 
 constexpr int WF_ORDER_MAX = 8;          // n_max at the most
 constexpr int WF_TERMS_MAX = 45;         // J at n_max = 8
-constexpr int WF_SETS_MAX = 3;           // field sets per call (the members of a synthesis batch)
-constexpr int WF_BLOCK = 64;             // samples of a block: one per lane of a wave
-constexpr int WF_LINE_THREADS = 256;     // lanes of a workgroup of the first launch: four lines
 constexpr int WF_SUM_THREADS = 256;      // lanes of a workgroup of the second launch
 constexpr int WF_N = 0, WF_S = 1, WF_IX = 2, WF_IY = 3;
 constexpr int WF_HEAD = 4;               // doubles of the header sums
-constexpr int WF_REF_PLANE = ZONES_REF_PLANE, WF_REF_FOCUS = ZONES_REF_FOCUS;
-constexpr double WF_PHASE_LIMIT = ZONES_PHASE_LIMIT;
 
 // terms up to radial order n_max, and the doubles of a record
-ML_ZONES_HD inline int wf_terms(int n_max) { return (n_max + 1) * (n_max + 2) / 2; }
+ML_PASS_HD inline int wf_terms(int n_max) { return (n_max + 1) * (n_max + 2) / 2; }
 inline int wf_record(int n_max) { return WF_HEAD + 4 * wf_terms(n_max); }
 
 // doubles of a line record of one set: the header sums and Re, Im of T_q of Cx and Cy for q = 0 ... n_max
-ML_ZONES_HD inline int wf_line_record(int n_max) { return WF_HEAD + 4 * (n_max + 1); }
+ML_PASS_HD inline int wf_line_record(int n_max) { return WF_HEAD + 4 * (n_max + 1); }
 
 // where the monomial moment M_pq, p + q <= n_max, lies among the wf_terms(n_max) moments of a set: ascending p, then q
-ML_ZONES_HD inline int wf_monomial(int n_max, int p, int q) { return p * (n_max + 1) - p * (p - 1) / 2 + q; }
+ML_PASS_HD inline int wf_monomial(int n_max, int p, int q) { return p * (n_max + 1) - p * (p - 1) / 2 + q; }
 
 // bytes of scratch of a call: the line records of every set
 inline long long wf_scratch_bytes(int sets, int nx, int n_max) { return (long long)sets * nx * wf_line_record(n_max) * 8; }
@@ -131,96 +120,33 @@ inline void wf_convert(const double *mono, int n_max, double *rec) {
     }
 }
 
-static inline bool wf_bad(const char *name, const double *v, int n, bool nonneg, const char *what, char *why, size_t why_len) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(v[i]) || (nonneg && v[i] < 0)) {
-            snprintf(why, why_len, "ml_fields_zernike: %s[%d] = %g: %s", name, i, v[i], what);
-            return true;
-        }
-    return false;
+static inline int wf_check_order(const PassWhy &w, int n_max) {
+    if (n_max < 0 || n_max > WF_ORDER_MAX) return pass_refuse(w, -1, "n_max = %d: radial orders 0 to %d are taken", n_max, WF_ORDER_MAX);
+    return 0;
 }
 
-// The argument checks of ml_fields_zernike (the state: fields_zones.h ZonesState).  -> 0; -1: an argument error, -2: the
-// state does not allow the call; `why` is filled then.
-inline int wf_check(const ZonesState &s, int first_set, int n_sets, const double *x2, const double *xi, int nx, const double *y2,
+// The argument checks of ml_fields_zernike.  -> 0; -1: an argument error, -2: the state does not allow the call; `why` is
+// filled then.
+inline int wf_check(const PassState &s, int first_set, int n_sets, const double *x2, const double *xi, int nx, const double *y2,
                     const double *eta, int ny, double r2, int n_max, int ref_mode, const double *ra, const double *rb, double ref_c,
                     double k, int record_doubles, char *why, size_t why_len) {
-    if (s.n_ranks > 1) {
-        snprintf(why, why_len, "ml_fields_zernike: this context belongs to a communicator of %d ranks", s.n_ranks);
-        return -1;
-    }
-    if (n_sets < 1 || n_sets > WF_SETS_MAX) {
-        snprintf(why, why_len, "ml_fields_zernike: a pass takes 1 to %d field sets, got %d", WF_SETS_MAX, n_sets);
-        return -1;
-    }
-    if (n_max < 0 || n_max > WF_ORDER_MAX) {
-        snprintf(why, why_len, "ml_fields_zernike: n_max = %d: radial orders 0 to %d are taken", n_max, WF_ORDER_MAX);
-        return -1;
-    }
-    if (ref_mode != WF_REF_PLANE && ref_mode != WF_REF_FOCUS) {
-        snprintf(why, why_len, "ml_fields_zernike: ref_mode %d: %d for a plane wave or %d for a focus", ref_mode, WF_REF_PLANE,
-                 WF_REF_FOCUS);
-        return -1;
-    }
-    if (record_doubles < wf_record(n_max)) {
-        snprintf(why, why_len, "ml_fields_zernike: record_doubles = %d: a record of order %d has %d doubles", record_doubles, n_max,
-                 wf_record(n_max));
-        return -1;
-    }
-    if (nx < 1 || ny < 1) {
-        snprintf(why, why_len, "ml_fields_zernike: the axes have %d x %d samples: at least one each", nx, ny);
-        return -1;
-    }
-    if (!x2 || !xi || !y2 || !eta || !ra || !rb) {
-        snprintf(why, why_len, "ml_fields_zernike: NULL argument");
-        return -1;
-    }
-    if (s.nx == 0 || s.ny == 0) {
-        snprintf(why, why_len, "no resident field set");
-        return -2;
-    }
-    if (nx != s.nx || ny != s.ny) {
-        snprintf(why, why_len, "ml_fields_zernike: the axes have %d x %d samples, the resident field sets %d x %d", nx, ny, s.nx, s.ny);
-        return -1;
-    }
-    if (first_set < 0 || first_set + n_sets > s.n_sets) {
-        snprintf(why, why_len, "ml_fields_zernike: field sets %d ... %d asked for, %d resident", first_set, first_set + n_sets - 1,
-                 s.n_sets);
-        return -1;
-    }
-    if (!(std::isfinite(r2) && r2 > 0)) {
-        snprintf(why, why_len, "ml_fields_zernike: r2 = %g: the squared radius of the pupil must be finite and > 0", r2);
-        return -1;
-    }
-    const char *sq = "a squared distance must be finite and >= 0";
-    if (wf_bad("x2", x2, nx, true, sq, why, why_len) || wf_bad("y2", y2, ny, true, sq, why, why_len)) return -1;
-    const char *co = "a pupil coordinate must be finite";
-    if (wf_bad("xi", xi, nx, false, co, why, why_len) || wf_bad("eta", eta, ny, false, co, why, why_len)) return -1;
-    const int jv = zones_vertex(y2, ny);
-    for (int j = 1; j < ny; ++j)
-        if (j <= jv ? y2[j] > y2[j - 1] : y2[j] < y2[j - 1]) {
-            snprintf(why, why_len, "ml_fields_zernike: y2 must fall to its minimum y2[%d] = %g and rise again (a y axis in ascending or "
-                     "descending order): y2[%d] = %g follows y2[%d] = %g", jv, y2[jv], j, y2[j], j - 1, y2[j - 1]);
-            return -1;
-        }
-    const bool focus = ref_mode == WF_REF_FOCUS;
-    const char *rw = focus ? "a squared distance to the focus must be finite and >= 0" : "a reference phase must be finite";
-    if (wf_bad("ra", ra, nx, focus, rw, why, why_len) || wf_bad("rb", rb, ny, focus, rw, why, why_len)) return -1;
-    if (focus && (!std::isfinite(ref_c) || ref_c == 0)) {
-        snprintf(why, why_len, "ml_fields_zernike: ref_c = %g: the focus lies at a finite distance zf != 0 from the aperture", ref_c);
-        return -1;
-    }
-    if (focus && !(std::isfinite(k) && k > 0)) {
-        snprintf(why, why_len, "ml_fields_zernike: k = %g: the wave number must be finite and > 0", k);
-        return -1;
-    }
-    const double phi = zones_phase_max(ref_mode, ra, nx, rb, ny, ref_c, k);
-    if (!(phi <= WF_PHASE_LIMIT)) {
-        snprintf(why, why_len, "ml_fields_zernike: the reference phase reaches %.6g rad on this grid: the phase arithmetic covers up to %g",
-                 phi, WF_PHASE_LIMIT);
-        return -1;
-    }
-    return 0;
+    const PassWhy w{"ml_fields_zernike", why, why_len};
+    if (int rc = pass_check_comm(w, s.n_ranks)) return rc;
+    if (int rc = pass_check_set_count(w, n_sets)) return rc;
+    if (int rc = wf_check_order(w, n_max)) return rc;
+    if (int rc = pass_check_ref_mode(w, ref_mode)) return rc;
+    if (record_doubles < wf_record(n_max))
+        return pass_refuse(w, -1, "record_doubles = %d: a record of order %d has %d doubles", record_doubles, n_max, wf_record(n_max));
+    if (int rc = pass_check_axes(w, nx, ny)) return rc;
+    if (!x2 || !xi || !y2 || !eta || !ra || !rb) return pass_refuse(w, -1, "NULL argument");
+    if (int rc = pass_check_resident(w, s)) return rc;
+    if (int rc = pass_check_shape(w, s, nx, ny)) return rc;
+    if (int rc = pass_check_set_range(w, s, first_set, n_sets)) return rc;
+    if (int rc = pass_check_radius(w, r2)) return rc;
+    if (int rc = pass_check_squared_axes(w, x2, nx, y2, ny)) return rc;
+    if (int rc = pass_check_pupil_axes(w, xi, nx, eta, ny)) return rc;
+    if (int rc = pass_check_vertex(w, y2, ny)) return rc;
+    return pass_check_ref_wave(w, ref_mode, ra, nx, rb, ny, ref_c, k);
 }
 
 }  // namespace ml

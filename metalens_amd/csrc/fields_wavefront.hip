@@ -23,13 +23,12 @@
 // to the bit, the record of a set does not depend on the other sets of the call, and the terms up to order n' have the
 // same bits whatever n_max >= n' the call asks for.
 #include "nearfield_math.h"
-#include "fields_wavefront.h"
 
 #pragma clang fp contract(off)
 
-namespace ml {
+#include "fields_dev.h"
 
-static_assert(WF_PHASE_LIMIT == PHASE_LIMIT, "fields_wavefront.h restates common.h PHASE_LIMIT");
+namespace ml {
 
 struct WavefrontArgs {
     const double2 *fields;   // [NS][4][nx][ny]: Ex, Ey, Hx, Hy of the first set of the call, the others behind it
@@ -41,12 +40,6 @@ struct WavefrontArgs {
     double r2;               // the squared radius of the pupil
     double zz, sk;           // focus: ref_c ref_c and -sign(ref_c) k
 };
-
-__device__ __forceinline__ double wavefront_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 // what a lane holds of a block: whether its sample is a member, and then its pupil coordinate, its share of the
 // reference phase and the four fields of every set
@@ -62,23 +55,17 @@ __device__ __forceinline__ void wavefront_fetch(const WavefrontArgs &a, const do
                                                 WavefrontBlock<NS> &b) {
     b.member = j < a.ny && x2 + a.y2[j] <= a.r2;
     b.rb = b.eta = 0.0;
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-        for (int f = 0; f < 4; ++f) b.f[m][f] = make_double2(0.0, 0.0);
+    pass_zero<NS>(b.f);
     if (b.member) {
         b.rb = a.rb[j];
         b.eta = a.eta[j];
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b.f[m][f] = row[(size_t)(4 * m + f) * plane + j];
+        pass_load<NS>(b.f, row, plane, j);
     }
 }
 
 template <int NS, int NQ>
-__global__ __launch_bounds__(WF_LINE_THREADS) void wavefront_line_kernel(const WavefrontArgs a) {
-    const int lane = threadIdx.x & 63, line = blockIdx.x * (WF_LINE_THREADS / 64) + (threadIdx.x >> 6);
+__global__ __launch_bounds__(PASS_LINE_THREADS) void wavefront_line_kernel(const WavefrontArgs a) {
+    const int lane = threadIdx.x & 63, line = blockIdx.x * (PASS_LINE_THREADS / 64) + (threadIdx.x >> 6);
     if (line >= a.nx) return;
     const double x2 = a.x2[line], ra = a.ra[line];
     double *out = a.lines + (size_t)line * a.lr;
@@ -101,28 +88,24 @@ __global__ __launch_bounds__(WF_LINE_THREADS) void wavefront_line_kernel(const W
 #pragma unroll
             for (int c = 0; c < 4; ++c) t[m][q][c] = 0.0;
     }
-    const int blocks = zones_blocks(a.ny);
+    const int blocks = pass_blocks(a.ny);
     WavefrontBlock<NS> cur, nxt;
     wavefront_fetch<NS>(a, row, plane, x2, lane, cur);
     for (int b = 0; b < blocks; ++b) {
-        if (b + 1 < blocks) wavefront_fetch<NS>(a, row, plane, x2, (b + 1) * WF_BLOCK + lane, nxt);   // (in flight over this block's arithmetic)
+        if (b + 1 < blocks) wavefront_fetch<NS>(a, row, plane, x2, (b + 1) * PASS_BLOCK + lane, nxt);   // (in flight over this block's arithmetic)
         if (__ballot(cur.member)) {
             if (cur.member) {
                 double sn, cs;
-                const double u = ra + cur.rb;
-                sincos_cw(a.focus ? a.sk * sqrt_exact(u + a.zz) : u, sn, cs);
+                pass_ref_sincos(a.focus, a.sk, a.zz, ra + cur.rb, sn, cs);
                 ++n;
                 double C[NS][4];
 #pragma unroll
                 for (int m = 0; m < NS; ++m) {
-                    const double2 Ex = cur.f[m][0], Ey = cur.f[m][1], Hx = cur.f[m][2], Hy = cur.f[m][3];
-                    h[m][0] += 0.5 * ((Ex.x * Hy.x + Ex.y * Hy.y) - (Ey.x * Hx.x + Ey.y * Hx.y));
-                    h[m][1] += Ex.x * Ex.x + Ex.y * Ex.y;
-                    h[m][2] += Ey.x * Ey.x + Ey.y * Ey.y;
-                    C[m][0] = Ex.x * cs + Ex.y * sn;
-                    C[m][1] = Ex.y * cs - Ex.x * sn;
-                    C[m][2] = Ey.x * cs + Ey.y * sn;
-                    C[m][3] = Ey.y * cs - Ey.x * sn;
+                    h[m][0] += pass_sz(cur.f[m]);
+                    h[m][1] += pass_abs2(cur.f[m][0]);
+                    h[m][2] += pass_abs2(cur.f[m][1]);
+                    pass_overlap(cur.f[m][0], sn, cs, C[m][0], C[m][1]);
+                    pass_overlap(cur.f[m][1], sn, cs, C[m][2], C[m][3]);
                 }
                 double e = 1.0;   // eta^q by repeated multiplication
 #pragma unroll
@@ -137,12 +120,12 @@ __global__ __launch_bounds__(WF_LINE_THREADS) void wavefront_line_kernel(const W
         }
         if (b + 1 < blocks) cur = nxt;
     }
-    const double members = wavefront_wave_sum((double)n);   // (integers: exact in any order)
+    const double members = pass_wave_sum((double)n);   // (integers: exact in any order)
 #pragma unroll
     for (int m = 0; m < NS; ++m) {
         double *rec = out + m * set_stride;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) h[m][c] = wavefront_wave_sum(h[m][c]);
+        for (int c = 0; c < 3; ++c) h[m][c] = pass_wave_sum(h[m][c]);
         if (lane == 0) {
             rec[WF_N] = members;
             rec[WF_S] = h[m][0];
@@ -152,7 +135,7 @@ __global__ __launch_bounds__(WF_LINE_THREADS) void wavefront_line_kernel(const W
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) t[m][q][c] = wavefront_wave_sum(t[m][q][c]);
+            for (int c = 0; c < 4; ++c) t[m][q][c] = pass_wave_sum(t[m][q][c]);
             if (lane == 0 && q < a.nq) {   // (q < nq: inside the line record)
 #pragma unroll
                 for (int c = 0; c < 4; ++c) rec[WF_HEAD + 4 * q + c] = t[m][q][c];
@@ -197,7 +180,7 @@ __global__ __launch_bounds__(WF_SUM_THREADS) void wavefront_sum_kernel(const dou
     for (int p = 0; p < NP; ++p)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const double v = wavefront_wave_sum(acc[p][c]);
+            const double v = pass_wave_sum(acc[p][c]);
             if ((tid & 63) == 0) s_red[tid >> 6][4 * p + c] = v;
         }
     __syncthreads();
@@ -210,13 +193,10 @@ __global__ __launch_bounds__(WF_SUM_THREADS) void wavefront_sum_kernel(const dou
 }
 
 template <int NQ>
-static void wavefront_launch(hipStream_t stream, dim3 grid, const WavefrontArgs &a, int ns) {
-    if (ns == 1)
-        hipLaunchKernelGGL((wavefront_line_kernel<1, NQ>), grid, dim3(WF_LINE_THREADS), 0, stream, a);
-    else if (ns == 2)
-        hipLaunchKernelGGL((wavefront_line_kernel<2, NQ>), grid, dim3(WF_LINE_THREADS), 0, stream, a);
-    else
-        hipLaunchKernelGGL((wavefront_line_kernel<3, NQ>), grid, dim3(WF_LINE_THREADS), 0, stream, a);
+static void wavefront_launch(hipStream_t stream, dim3 grid, const WavefrontArgs &a, int n_sets) {
+    pass_for_sets(n_sets, [&](auto ns) {
+        hipLaunchKernelGGL((wavefront_line_kernel<decltype(ns)::value, NQ>), grid, dim3(PASS_LINE_THREADS), 0, stream, a);
+    });
 }
 
 }  // namespace ml
@@ -229,52 +209,38 @@ int ml_fields_zernike(ml_ctx *ctx, int first_set, int n_sets, const double *x2, 
                       const double *eta, int ny, double r2, int n_max, int ref_mode, const double *ra, const double *rb, double ref_c,
                       double k, double *records, int record_doubles) {
     ML_REQUIRE(ctx && records, "NULL argument");
-    ZonesState st;
-    st.n_ranks = ctx->n_ranks;
-    st.nx = ctx->fields.nx;
-    st.ny = ctx->fields.ny;
-    st.n_sets = ctx->fields.n_sets;
     char why[400];
-    const int rc = wf_check(st, first_set, n_sets, x2, xi, nx, y2, eta, ny, r2, n_max, ref_mode, ra, rb, ref_c, k, record_doubles, why,
-                            sizeof why);
-    if (rc != 0) {
-        set_error("%s", why);
-        return rc == -2 ? ML_ESTATE : ML_EINVAL;
-    }
+    ML_TRY(pass_checked(wf_check(pass_state(ctx), first_set, n_sets, x2, xi, nx, y2, eta, ny, r2, n_max, ref_mode, ra, rb, ref_c, k,
+                                 record_doubles, why, sizeof why), why));
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     const int nq = n_max + 1, lr = wf_line_record(n_max), mono_doubles = WF_HEAD + 4 * wf_terms(n_max);
-    // the inputs in one upload: x2, xi, ra [nx]; y2, eta, rb [ny]
-    std::vector<double> h((size_t)3 * nx + 3 * ny);
-    std::copy(x2, x2 + nx, h.begin());
-    std::copy(xi, xi + nx, h.begin() + nx);
-    std::copy(ra, ra + nx, h.begin() + 2 * nx);
-    std::copy(y2, y2 + ny, h.begin() + 3 * nx);
-    std::copy(eta, eta + ny, h.begin() + 3 * nx + ny);
-    std::copy(rb, rb + ny, h.begin() + 3 * nx + 2 * ny);
-    ML_TRY(ctx->wavefront_in.reserve(h.size() * sizeof(double)));
+    PassPack in;   // the inputs in one upload: x2, xi, ra [nx]; y2, eta, rb [ny]
+    const size_t at_x2 = in.add(x2, nx), at_xi = in.add(xi, nx), at_ra = in.add(ra, nx);
+    const size_t at_y2 = in.add(y2, ny), at_eta = in.add(eta, ny), at_rb = in.add(rb, ny);
+    ML_TRY(ctx->wavefront_in.reserve(in.bytes()));
     ML_TRY(ctx->wavefront_lines.reserve((size_t)wf_scratch_bytes(n_sets, nx, n_max)));
     ML_TRY(ctx->wavefront_records.reserve((size_t)n_sets * mono_doubles * sizeof(double)));
-    ML_HIP(hipMemcpyAsync(ctx->wavefront_in.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ML_HIP(hipMemcpyAsync(ctx->wavefront_in.p, in.h.data(), in.bytes(), hipMemcpyHostToDevice, ctx->stream));
     WavefrontArgs a;
     a.fields = ctx->fields.buf.as<double2>() + (size_t)first_set * 4 * nx * ny;
-    a.x2 = ctx->wavefront_in.as<double>();
-    const double *d_xi = a.x2 + nx;
-    a.ra = a.x2 + 2 * nx;
-    a.y2 = a.x2 + 3 * nx;
-    a.eta = a.y2 + ny;
-    a.rb = a.y2 + 2 * ny;
+    const double *d_in = ctx->wavefront_in.as<double>();
+    a.x2 = d_in + at_x2;
+    a.ra = d_in + at_ra;
+    a.y2 = d_in + at_y2;
+    a.eta = d_in + at_eta;
+    a.rb = d_in + at_rb;
     a.lines = ctx->wavefront_lines.as<double>();
     a.nx = nx;
     a.ny = ny;
     a.nq = nq;
     a.lr = lr;
-    a.jv = zones_vertex(y2, ny);
-    a.focus = ref_mode == WF_REF_FOCUS;
+    a.jv = pass_vertex(y2, ny);
+    a.focus = ref_mode == PASS_REF_FOCUS;
     a.r2 = r2;
     a.zz = ref_c * ref_c;
     a.sk = ref_c > 0 ? -k : k;
-    const int lines = WF_LINE_THREADS / 64;
+    const int lines = PASS_LINE_THREADS / 64;
     const dim3 grid((nx + lines - 1) / lines);
     if (n_max <= 4)
         wavefront_launch<5>(ctx->stream, grid, a, n_sets);
@@ -282,7 +248,7 @@ int ml_fields_zernike(ml_ctx *ctx, int first_set, int n_sets, const double *x2, 
         wavefront_launch<WF_ORDER_MAX + 1>(ctx->stream, grid, a, n_sets);
     ML_HIP(hipGetLastError());
     double *mono = ctx->wavefront_records.as<double>();
-    hipLaunchKernelGGL(wavefront_sum_kernel, dim3(nq + 1, n_sets), dim3(WF_SUM_THREADS), 0, ctx->stream, a.lines, d_xi, mono, nx, nq, lr);
+    hipLaunchKernelGGL(wavefront_sum_kernel, dim3(nq + 1, n_sets), dim3(WF_SUM_THREADS), 0, ctx->stream, a.lines, d_in + at_xi, mono, nx, nq, lr);
     ML_HIP(hipGetLastError());
     std::vector<double> got((size_t)n_sets * mono_doubles);
     ML_HIP(hipMemcpyAsync(got.data(), mono, got.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

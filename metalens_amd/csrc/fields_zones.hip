@@ -26,13 +26,12 @@
 // lines and lanes that add nothing leave no trace: the record of zone (e_a, e_b] has the same bits whatever the other
 // edges are, the record of a set the same bits whatever the other sets of the call are, and two calls agree to the bit.
 #include "nearfield_math.h"
-#include "fields_zones.h"
 
 #pragma clang fp contract(off)
 
-namespace ml {
+#include "fields_dev.h"
 
-static_assert(ZONES_PHASE_LIMIT == PHASE_LIMIT, "fields_zones.h restates common.h PHASE_LIMIT");
+namespace ml {
 
 // a finished run: the members of one zone on one side of one line, 64 bytes
 struct alignas(ZONES_RUN_BYTES) ZoneRun {
@@ -52,25 +51,6 @@ struct ZonesArgs {
     double zz, sk;           // focus: ref_c ref_c and -sign(ref_c) k
 };
 
-__device__ __forceinline__ double zones_wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// searchsorted(e2, r2, side = 'left'): the number of edges below r2
-__device__ __forceinline__ int zones_find(const double *e2, int K, double r2) {
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (e2[mid] < r2)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // what a lane holds of a block: its sample's squared distance, whether it lies inside the largest edge, and then its
 // share of the reference phase and the four fields of every set
 template <int NS>
@@ -86,16 +66,10 @@ __device__ __forceinline__ void zones_fetch(const ZonesArgs &a, const double2 *r
     b.r2 = j < a.ny ? x2 + a.y2[j] : INFINITY;
     b.member = b.r2 <= e2_max;
     b.rb = 0.0;
-#pragma unroll
-    for (int m = 0; m < NS; ++m)
-#pragma unroll
-        for (int f = 0; f < 4; ++f) b.f[m][f] = make_double2(0.0, 0.0);
+    pass_zero<NS>(b.f);
     if (b.member) {
         b.rb = a.rb[j];
-#pragma unroll
-        for (int m = 0; m < NS; ++m)
-#pragma unroll
-            for (int f = 0; f < 4; ++f) b.f[m][f] = row[(size_t)(4 * m + f) * plane + j];
+        pass_load<NS>(b.f, row, plane, j);
     }
 }
 
@@ -146,17 +120,17 @@ __device__ __forceinline__ void zones_add(const ZonesArgs &a, ZoneRun *list, Zon
 #pragma unroll
         for (int m = 0; m < NS; ++m)
 #pragma unroll
-            for (int q = 0; q < ZONES_TERMS; ++q) w.v[m][q] += zones_wave_sum(mine ? t[m][q] : 0.0);
+            for (int q = 0; q < ZONES_TERMS; ++q) w.v[m][q] += pass_wave_sum(mine ? t[m][q] : 0.0);
         todo &= ~members;
     }
 }
 
 template <int NS>
-__global__ __launch_bounds__(ZONES_LINE_THREADS) void zones_line_kernel(const ZonesArgs a) {
+__global__ __launch_bounds__(PASS_LINE_THREADS) void zones_line_kernel(const ZonesArgs a) {
     extern __shared__ double s_e2[];
-    for (int k = threadIdx.x; k < a.K; k += ZONES_LINE_THREADS) s_e2[k] = a.e2[k];
+    for (int k = threadIdx.x; k < a.K; k += PASS_LINE_THREADS) s_e2[k] = a.e2[k];
     __syncthreads();
-    const int lane = threadIdx.x & 63, line = blockIdx.x * (ZONES_LINE_THREADS / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, line = blockIdx.x * (PASS_LINE_THREADS / 64) + (threadIdx.x >> 6);
     if (line >= a.nx) return;
     const double x2 = a.x2[line], ra = a.ra[line], e2_max = s_e2[a.K - 1];
     if (!(x2 + a.y2[a.jv] <= e2_max)) {   // the vertex lies outside: so does the line
@@ -170,34 +144,24 @@ __global__ __launch_bounds__(ZONES_LINE_THREADS) void zones_line_kernel(const Zo
     w.zone = -1;
     w.n = w.slot = 0;
     int runs_l = 0;
-    const int blocks = zones_blocks(a.ny);
+    const int blocks = pass_blocks(a.ny);
     ZoneBlock<NS> cur, nxt;
     zones_fetch<NS>(a, row, plane, x2, e2_max, lane, cur);
     for (int b = 0; b < blocks; ++b) {
-        const int j0 = b * ZONES_BLOCK, j = j0 + lane;
-        if (b + 1 < blocks) zones_fetch<NS>(a, row, plane, x2, e2_max, j + ZONES_BLOCK, nxt);   // (in flight over this block's arithmetic)
+        const int j0 = b * PASS_BLOCK, j = j0 + lane;
+        if (b + 1 < blocks) zones_fetch<NS>(a, row, plane, x2, e2_max, j + PASS_BLOCK, nxt);   // (in flight over this block's arithmetic)
         if (__ballot(cur.member)) {
             int zone = a.K;
             double t[NS][ZONES_TERMS];
             double sn = 0.0, cs = 1.0;
             if (cur.member) {
-                zone = zones_find(s_e2, a.K, cur.r2);
-                const double u = ra + cur.rb;
-                sincos_cw(a.focus ? a.sk * sqrt_exact(u + a.zz) : u, sn, cs);
+                zone = pass_find(s_e2, a.K, cur.r2);
+                pass_ref_sincos(a.focus, a.sk, a.zz, ra + cur.rb, sn, cs);
             }
 #pragma unroll
-            for (int m = 0; m < NS; ++m) {
-                const double2 Ex = cur.f[m][0], Ey = cur.f[m][1], Hx = cur.f[m][2], Hy = cur.f[m][3];
-                t[m][0] = 0.5 * ((Ex.x * Hy.x + Ex.y * Hy.y) - (Ey.x * Hx.x + Ey.y * Hx.y));
-                t[m][1] = Ex.x * Ex.x + Ex.y * Ex.y;
-                t[m][2] = Ey.x * Ey.x + Ey.y * Ey.y;
-                t[m][3] = Ex.x * cs + Ex.y * sn;
-                t[m][4] = Ex.y * cs - Ex.x * sn;
-                t[m][5] = Ey.x * cs + Ey.y * sn;
-                t[m][6] = Ey.y * cs - Ey.x * sn;
-            }
+            for (int m = 0; m < NS; ++m) pass_terms(cur.f[m], sn, cs, t[m]);
             zones_add<NS>(a, list, w, zone, j <= a.jv, t, lane);
-            if (j0 <= a.jv && a.jv < j0 + ZONES_BLOCK) {   // the vertex's block: side L ends here
+            if (j0 <= a.jv && a.jv < j0 + PASS_BLOCK) {   // the vertex's block: side L ends here
                 zones_flush<NS>(a, list, w, lane);
                 runs_l = w.slot;
             }
@@ -250,22 +214,13 @@ __global__ __launch_bounds__(ZONES_SUM_THREADS) void zones_sum_kernel(const Zone
     }
     acc[ZONES_N] = (double)n;   // (integers: exact in any order)
 #pragma unroll
-    for (int q = 0; q < ZONES_RECORD; ++q) acc[q] = zones_wave_sum(acc[q]);
+    for (int q = 0; q < ZONES_RECORD; ++q) acc[q] = pass_wave_sum(acc[q]);
     if ((tid & 63) == 0)
 #pragma unroll
         for (int q = 0; q < ZONES_RECORD; ++q) s_red[tid >> 6][q] = acc[q];
     __syncthreads();
     if (tid < ZONES_RECORD)
         records[((size_t)set * K + z) * ZONES_RECORD + tid] = ((s_red[0][tid] + s_red[1][tid]) + s_red[2][tid]) + s_red[3][tid];
-}
-
-static void zones_launch(hipStream_t stream, dim3 grid, size_t lds, const ZonesArgs &a, int ns) {
-    if (ns == 1)
-        hipLaunchKernelGGL((zones_line_kernel<1>), grid, dim3(ZONES_LINE_THREADS), lds, stream, a);
-    else if (ns == 2)
-        hipLaunchKernelGGL((zones_line_kernel<2>), grid, dim3(ZONES_LINE_THREADS), lds, stream, a);
-    else
-        hipLaunchKernelGGL((zones_line_kernel<3>), grid, dim3(ZONES_LINE_THREADS), lds, stream, a);
 }
 
 }  // namespace ml
@@ -278,51 +233,41 @@ int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, in
                     int n_edges, int ref_mode, const double *ra, const double *rb, double ref_c, double k, double *records,
                     int record_doubles) {
     ML_REQUIRE(ctx && records, "NULL argument");
-    ZonesState st;
-    st.n_ranks = ctx->n_ranks;
-    st.nx = ctx->fields.nx;
-    st.ny = ctx->fields.ny;
-    st.n_sets = ctx->fields.n_sets;
     char why[400];
-    const int rc = zones_check(st, first_set, n_sets, x2, nx, y2, ny, e2, n_edges, ref_mode, ra, rb, ref_c, k, record_doubles, why,
-                               sizeof why);
-    if (rc != 0) {
-        set_error("%s", why);
-        return rc == -2 ? ML_ESTATE : ML_EINVAL;
-    }
+    ML_TRY(pass_checked(zones_check(pass_state(ctx), first_set, n_sets, x2, nx, y2, ny, e2, n_edges, ref_mode, ra, rb, ref_c, k,
+                                    record_doubles, why, sizeof why), why));
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     const int K = n_edges, cap = (int)zones_run_capacity(ny, K);
-    // the inputs in one upload: x2, ra [nx]; y2, rb [ny]; e2 [K]
-    std::vector<double> h((size_t)2 * nx + 2 * ny + K);
-    std::copy(x2, x2 + nx, h.begin());
-    std::copy(ra, ra + nx, h.begin() + nx);
-    std::copy(y2, y2 + ny, h.begin() + 2 * nx);
-    std::copy(rb, rb + ny, h.begin() + 2 * nx + ny);
-    std::copy(e2, e2 + K, h.begin() + 2 * nx + 2 * ny);
-    ML_TRY(ctx->zones_in.reserve(h.size() * sizeof(double)));
+    PassPack in;   // the inputs in one upload: x2, ra [nx]; y2, rb [ny]; e2 [K]
+    const size_t at_x2 = in.add(x2, nx), at_ra = in.add(ra, nx), at_y2 = in.add(y2, ny), at_rb = in.add(rb, ny), at_e2 = in.add(e2, K);
+    ML_TRY(ctx->zones_in.reserve(in.bytes()));
     ML_TRY(ctx->zones_runs.reserve((size_t)zones_scratch_bytes(n_sets, nx, ny, K)));
     ML_TRY(ctx->zones_records.reserve((size_t)n_sets * K * ZONES_RECORD * sizeof(double)));
-    ML_HIP(hipMemcpyAsync(ctx->zones_in.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ML_HIP(hipMemcpyAsync(ctx->zones_in.p, in.h.data(), in.bytes(), hipMemcpyHostToDevice, ctx->stream));
     ZonesArgs a;
     a.fields = ctx->fields.buf.as<double2>() + (size_t)first_set * 4 * nx * ny;
-    a.x2 = ctx->zones_in.as<double>();
-    a.ra = a.x2 + nx;
-    a.y2 = a.x2 + 2 * nx;
-    a.rb = a.y2 + ny;
-    a.e2 = a.y2 + 2 * ny;
+    const double *d_in = ctx->zones_in.as<double>();
+    a.x2 = d_in + at_x2;
+    a.ra = d_in + at_ra;
+    a.y2 = d_in + at_y2;
+    a.rb = d_in + at_rb;
+    a.e2 = d_in + at_e2;
     a.runs = ctx->zones_runs.as<ZoneRun>();
     a.line_runs = reinterpret_cast<int2 *>(a.runs + (size_t)n_sets * nx * cap);   // behind the lists: 8-byte aligned
     a.nx = nx;
     a.ny = ny;
     a.K = K;
     a.cap = cap;
-    a.jv = zones_vertex(y2, ny);
-    a.focus = ref_mode == ZONES_REF_FOCUS;
+    a.jv = pass_vertex(y2, ny);
+    a.focus = ref_mode == PASS_REF_FOCUS;
     a.zz = ref_c * ref_c;
     a.sk = ref_c > 0 ? -k : k;
-    const int lines = ZONES_LINE_THREADS / 64;
-    zones_launch(ctx->stream, dim3((nx + lines - 1) / lines), (size_t)K * sizeof(double), a, n_sets);
+    const int lines = PASS_LINE_THREADS / 64;
+    pass_for_sets(n_sets, [&](auto ns) {
+        hipLaunchKernelGGL((zones_line_kernel<decltype(ns)::value>), dim3((nx + lines - 1) / lines), dim3(PASS_LINE_THREADS),
+                           (size_t)K * sizeof(double), ctx->stream, a);
+    });
     ML_HIP(hipGetLastError());
     double *rec = ctx->zones_records.as<double>();
     hipLaunchKernelGGL(zones_sum_kernel, dim3(K, n_sets), dim3(ZONES_SUM_THREADS), 0, ctx->stream, a.runs, a.line_runs, a.x2, a.e2, rec,

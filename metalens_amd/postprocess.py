@@ -509,7 +509,7 @@ def wavefront_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, radius, n_max=4
 
 
 PUPIL_NQ = ZERNIKE_ORDER_MAX + 1   # csrc/fields_pupil.h PUPIL_NQ: the entries of a line of the table
-PUPIL_PHASE_LIMIT = 1e9            # csrc/fields_pupil.h PUPIL_PHASE_LIMIT
+PUPIL_PHASE_LIMIT = 1e9            # csrc/fields_pass.h PASS_PHASE_LIMIT
 
 
 def _check_pupil(x, y, radius, centre=(0.0, 0.0), stop=True, phase=None, edges=None, zone_factors=None):

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from .postprocess import _check_pupil, apply_pupil_host, pupil_factor  # noqa: F401
-from .zones import SETS_MAX, _check_sets
+from .zones import SETS_MAX, _check_sets, _resolve_sets, _upload_fields
 
 
 class AperturePupil:
@@ -60,11 +60,7 @@ class AperturePupil:
         _check_sets(first, n)
         ctx = self.ctx
         self.plan()
-        if n is None:
-            have = _lib.c_int(0)
-            _lib.check(ctx.lib.ml_fields_sets(ctx.handle, _lib.byref(have)))
-            n = max(have.value - int(first), 1)
-        _lib.check(ctx.lib.ml_fields_pupil_apply(ctx.handle, int(first), int(n)))
+        _lib.check(ctx.lib.ml_fields_pupil_apply(ctx.handle, int(first), _resolve_sets(ctx, first, n)))
         ctx.fields_owner = None
 
     def apply(self, first=0, n=None):
@@ -119,11 +115,7 @@ def apply_pupil(Ex, Ey, Hx, Hy, xp_list, yp_list, radius, **kw):
     if Ex is None:
         a.apply(first, n)
         return None
-    arrs = [_lib.c128(v) for v in (Ex, Ey, Hx, Hy)]
-    if not all(v.shape == a.shape for v in arrs):
-        raise ValueError('the fields have shapes %s, the axes give %s' % ([v.shape for v in arrs], a.shape))
-    _lib.check(ctx.lib.ml_fields_upload(ctx.handle, a.shape[0], a.shape[1], *[_lib.dptr(v) for v in arrs]))
-    ctx.fields_owner = None
+    _upload_fields(ctx, a.shape, Ex, Ey, Hx, Hy)
     a.apply(0, 1)
     out = [np.empty(a.shape, dtype=np.complex128) for _ in range(4)]
     _lib.check(ctx.lib.ml_fields_download(ctx.handle, *[_lib.dptr(v) for v in out]))

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .postprocess import _check_wavefront, _wavefront_dict, wavefront_record, zernike, zernike_terms  # noqa: F401
-from .zones import SETS_MAX, _check_sets  # noqa: F401
+from .zones import SETS_MAX, _check_sets, _resolve_sets, _upload_fields  # noqa: F401
 
 
 class ApertureWavefront:
@@ -44,13 +44,10 @@ class ApertureWavefront:
         """the records of ml_fields_zernike as they come, shape ``(n, 4 + 4 J)`` (csrc/fields_wavefront.h WF_*)"""
         _check_sets(first, n)
         ctx = self.ctx
-        if n is None:
-            have = _lib.c_int(0)
-            _lib.check(ctx.lib.ml_fields_sets(ctx.handle, _lib.byref(have)))
-            n = max(have.value - int(first), 1)
+        n = _resolve_sets(ctx, first, n)
         doubles = wavefront_record(self.n_max)
-        rec = np.zeros((int(n), doubles))
-        _lib.check(ctx.lib.ml_fields_zernike(ctx.handle, int(first), int(n), _lib.dptr(self._x2), _lib.dptr(self._xi), self.shape[0],
+        rec = np.zeros((n, doubles))
+        _lib.check(ctx.lib.ml_fields_zernike(ctx.handle, int(first), n, _lib.dptr(self._x2), _lib.dptr(self._xi), self.shape[0],
                                              _lib.dptr(self._y2), _lib.dptr(self._eta), self.shape[1], self._r2, self.n_max, self._mode,
                                              _lib.dptr(self._ra), _lib.dptr(self._rb), self._ref_c, self._k, _lib.dptr(rec), doubles))
         return rec
@@ -66,11 +63,6 @@ def aperture_wavefront(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, ra
     first, n = kw.pop('first', 0), kw.pop('n', None)
     _check_sets(first, n)
     a = ApertureWavefront(xp_list, yp_list, wavelength, n_glass, radius, **kw)
-    ctx = a.ctx
     if Ex is not None:
-        arrs = [_lib.c128(v) for v in (Ex, Ey, Hx, Hy)]
-        if not all(v.shape == a.shape for v in arrs):
-            raise ValueError('the fields have shapes %s, the axes give %s' % ([v.shape for v in arrs], a.shape))
-        _lib.check(ctx.lib.ml_fields_upload(ctx.handle, a.shape[0], a.shape[1], *[_lib.dptr(v) for v in arrs]))
-        ctx.fields_owner = None
+        _upload_fields(a.ctx, a.shape, Ex, Ey, Hx, Hy)
     return a.analyse(first, n)

@@ -9,7 +9,7 @@ import numpy as np
 from . import _lib
 from .postprocess import ZONES_RECORD, _check_zones, _zones_dict
 
-SETS_MAX = 3   # csrc/fields_zones.h ZONES_SETS_MAX: the members of a synthesis batch
+SETS_MAX = 3   # csrc/fields_pass.h PASS_SETS_MAX: the members of a synthesis batch
 
 
 def zone_edges(lens_periphery_summary):
@@ -24,6 +24,24 @@ def _check_sets(first, n):
         raise ValueError('first must be a field set index >= 0, got %r' % (first,))
     if n is not None and (int(n) != n or not 1 <= n <= SETS_MAX):
         raise ValueError('analyse() takes 1 to %d field sets per call, got n = %r' % (SETS_MAX, n))
+
+
+def _resolve_sets(ctx, first, n):
+    """``n``, or for ``n=None`` the resident field sets from ``first`` on (at least one: the entry names what is missing)"""
+    if n is None:
+        have = _lib.c_int(0)
+        _lib.check(ctx.lib.ml_fields_sets(ctx.handle, _lib.byref(have)))
+        n = max(have.value - int(first), 1)
+    return int(n)
+
+
+def _upload_fields(ctx, shape, Ex, Ey, Hx, Hy):
+    """make the host arrays the one resident field set of ``ctx``; no object owns the fields then"""
+    arrs = [_lib.c128(v) for v in (Ex, Ey, Hx, Hy)]
+    if not all(v.shape == shape for v in arrs):
+        raise ValueError('the fields have shapes %s, the axes give %s' % ([v.shape for v in arrs], shape))
+    _lib.check(ctx.lib.ml_fields_upload(ctx.handle, shape[0], shape[1], *[_lib.dptr(v) for v in arrs]))
+    ctx.fields_owner = None
 
 
 class ApertureZones:
@@ -55,12 +73,9 @@ class ApertureZones:
         """the records of ml_fields_zones as they come, shape ``(n, K, 8)`` (csrc/fields_zones.h ZONES_*)"""
         _check_sets(first, n)
         ctx = self.ctx
-        if n is None:
-            have = _lib.c_int(0)
-            _lib.check(ctx.lib.ml_fields_sets(ctx.handle, _lib.byref(have)))
-            n = max(have.value - int(first), 1)
-        rec = np.zeros((int(n), self.n_zones, ZONES_RECORD))
-        _lib.check(ctx.lib.ml_fields_zones(ctx.handle, int(first), int(n), _lib.dptr(self._x2), self.shape[0], _lib.dptr(self._y2),
+        n = _resolve_sets(ctx, first, n)
+        rec = np.zeros((n, self.n_zones, ZONES_RECORD))
+        _lib.check(ctx.lib.ml_fields_zones(ctx.handle, int(first), n, _lib.dptr(self._x2), self.shape[0], _lib.dptr(self._y2),
                                            self.shape[1], _lib.dptr(self._e2), self.n_zones, self._mode, _lib.dptr(self._ra),
                                            _lib.dptr(self._rb), self._ref_c, self._k, _lib.dptr(rec), ZONES_RECORD))
         return rec
@@ -76,11 +91,6 @@ def aperture_zones(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, edges,
     first, n = kw.pop('first', 0), kw.pop('n', None)
     _check_sets(first, n)
     a = ApertureZones(xp_list, yp_list, wavelength, n_glass, edges, **kw)
-    ctx = a.ctx
     if Ex is not None:
-        arrs = [_lib.c128(v) for v in (Ex, Ey, Hx, Hy)]
-        if not all(v.shape == a.shape for v in arrs):
-            raise ValueError('the fields have shapes %s, the axes give %s' % ([v.shape for v in arrs], a.shape))
-        _lib.check(ctx.lib.ml_fields_upload(ctx.handle, a.shape[0], a.shape[1], *[_lib.dptr(v) for v in arrs]))
-        ctx.fields_owner = None
+        _upload_fields(a.ctx, a.shape, Ex, Ey, Hx, Hy)
     return a.analyse(first, n)

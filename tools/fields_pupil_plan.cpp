@@ -43,7 +43,7 @@ int main(int argc, char **argv) {
     using namespace ml;
     if (argc == 2 && !strcmp(argv[1], "layout")) {
         printf("order_max=%d nq=%d edges_max=%d sets_max=%d block=%d line_threads=%d phase_limit=%g\n", PUPIL_ORDER_MAX, PUPIL_NQ,
-               PUPIL_EDGES_MAX, PUPIL_SETS_MAX, PUPIL_BLOCK, PUPIL_LINE_THREADS, PUPIL_PHASE_LIMIT);
+               PUPIL_EDGES_MAX, PASS_SETS_MAX, PASS_BLOCK, PASS_LINE_THREADS, PASS_PHASE_LIMIT);
         return 0;
     }
     if ((argc == 4 && !strcmp(argv[1], "monomials")) || (argc == 5 && !strcmp(argv[1], "table"))) {
@@ -95,7 +95,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc == 11 && !strcmp(argv[1], "apply")) {
-        ZonesState s;
+        PassState s;
         s.n_ranks = atoi(argv[2]);
         s.nx = atoi(argv[3]);
         s.ny = atoi(argv[4]);

@@ -44,8 +44,8 @@ int main(int argc, char **argv) {
     using namespace ml;
     if (argc == 2 && !strcmp(argv[1], "layout")) {
         printf("n=%d s=%d ix=%d iy=%d head=%d order_max=%d terms_max=%d sets_max=%d block=%d line_threads=%d sum_threads=%d plane=%d focus=%d\n",
-               WF_N, WF_S, WF_IX, WF_IY, WF_HEAD, WF_ORDER_MAX, WF_TERMS_MAX, WF_SETS_MAX, WF_BLOCK, WF_LINE_THREADS, WF_SUM_THREADS,
-               WF_REF_PLANE, WF_REF_FOCUS);
+               WF_N, WF_S, WF_IX, WF_IY, WF_HEAD, WF_ORDER_MAX, WF_TERMS_MAX, PASS_SETS_MAX, PASS_BLOCK, PASS_LINE_THREADS, WF_SUM_THREADS,
+               PASS_REF_PLANE, PASS_REF_FOCUS);
         return 0;
     }
     if (argc == 3 && !strcmp(argv[1], "table")) {
@@ -91,7 +91,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     if (argc == 20 && !strcmp(argv[1], "check")) {
-        ZonesState s;
+        PassState s;
         s.n_ranks = atoi(argv[2]);
         s.nx = atoi(argv[3]);
         s.ny = atoi(argv[4]);
@@ -115,7 +115,7 @@ int main(int argc, char **argv) {
         if (rc != 0)
             printf("refused=%d\n%s\n", rc, why);
         else
-            printf("ok=1 phase=%.17g\n", zones_phase_max(mode, ptr[4], nx, ptr[5], ny, ref_c, k));
+            printf("ok=1 phase=%.17g\n", pass_phase_max(mode, ptr[4], nx, ptr[5], ny, ref_c, k));
         return 0;
     }
     if (argc < 4 || (argc - 1) % 3 != 0) {
@@ -125,8 +125,8 @@ int main(int argc, char **argv) {
     }
     for (int i = 1; i + 2 < argc; i += 3) {
         const int sets = atoi(argv[i]), nx = atoi(argv[i + 1]), n_max = atoi(argv[i + 2]);
-        if (sets < 1 || sets > WF_SETS_MAX || nx < 1 || !order_ok(n_max)) {
-            fprintf(stderr, "1 <= sets <= %d, nx >= 1\n", WF_SETS_MAX);
+        if (sets < 1 || sets > PASS_SETS_MAX || nx < 1 || !order_ok(n_max)) {
+            fprintf(stderr, "1 <= sets <= %d, nx >= 1\n", PASS_SETS_MAX);
             return 2;
         }
         printf("sets=%d nx=%d n_max=%d terms=%d record=%d line_record=%d scratch=%lld\n", sets, nx, n_max, wf_terms(n_max), wf_record(n_max),

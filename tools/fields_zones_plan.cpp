@@ -35,7 +35,7 @@ int main(int argc, char **argv) {
     if (argc == 2 && !strcmp(argv[1], "layout")) {
         printf("n=%d s=%d ix=%d iy=%d cx=%d cy=%d record=%d terms=%d run_bytes=%d edges_max=%d sets_max=%d block=%d plane=%d focus=%d\n",
                ZONES_N, ZONES_S, ZONES_IX, ZONES_IY, ZONES_CX, ZONES_CY, ZONES_RECORD, ZONES_TERMS, ZONES_RUN_BYTES, ZONES_EDGES_MAX,
-               ZONES_SETS_MAX, ZONES_BLOCK, ZONES_REF_PLANE, ZONES_REF_FOCUS);
+               PASS_SETS_MAX, PASS_BLOCK, PASS_REF_PLANE, PASS_REF_FOCUS);
         return 0;
     }
     if (argc == 3 && !strcmp(argv[1], "vertex")) {
@@ -44,11 +44,11 @@ int main(int argc, char **argv) {
             fprintf(stderr, "vertex: a list of numbers\n");
             return 2;
         }
-        printf("jv=%d\n", zones_vertex(y2.data(), (int)y2.size()));
+        printf("jv=%d\n", pass_vertex(y2.data(), (int)y2.size()));
         return 0;
     }
     if (argc == 17 && !strcmp(argv[1], "check")) {
-        ZonesState s;
+        PassState s;
         s.n_ranks = atoi(argv[2]);
         s.nx = atoi(argv[3]);
         s.ny = atoi(argv[4]);
@@ -70,7 +70,7 @@ int main(int argc, char **argv) {
         if (rc != 0)
             printf("refused=%d\n%s\n", rc, why);
         else
-            printf("ok=1 phase=%.17g\n", zones_phase_max(mode, ptr[3], nx, ptr[4], ny, ref_c, k));
+            printf("ok=1 phase=%.17g\n", pass_phase_max(mode, ptr[3], nx, ptr[4], ny, ref_c, k));
         return 0;
     }
     if (argc < 5 || (argc - 1) % 4 != 0) {
@@ -80,11 +80,11 @@ int main(int argc, char **argv) {
     }
     for (int i = 1; i + 3 < argc; i += 4) {
         const int sets = atoi(argv[i]), nx = atoi(argv[i + 1]), ny = atoi(argv[i + 2]), K = atoi(argv[i + 3]);
-        if (sets < 1 || sets > ZONES_SETS_MAX || nx < 1 || ny < 1 || K < 1 || K > ZONES_EDGES_MAX) {
-            fprintf(stderr, "1 <= sets <= %d, nx, ny >= 1, 1 <= K <= %d\n", ZONES_SETS_MAX, ZONES_EDGES_MAX);
+        if (sets < 1 || sets > PASS_SETS_MAX || nx < 1 || ny < 1 || K < 1 || K > ZONES_EDGES_MAX) {
+            fprintf(stderr, "1 <= sets <= %d, nx, ny >= 1, 1 <= K <= %d\n", PASS_SETS_MAX, ZONES_EDGES_MAX);
             return 2;
         }
-        printf("sets=%d nx=%d ny=%d k=%d blocks=%d capacity=%lld scratch=%lld bound=%lld\n", sets, nx, ny, K, zones_blocks(ny),
+        printf("sets=%d nx=%d ny=%d k=%d blocks=%d capacity=%lld scratch=%lld bound=%lld\n", sets, nx, ny, K, pass_blocks(ny),
                zones_run_capacity(ny, K), zones_scratch_bytes(sets, nx, ny, K), zones_scratch_bound(sets, nx, ny, K));
     }
     return 0;
