@@ -330,7 +330,7 @@ struct PropagatePlan {
     int result_sets = 0;   // field sets in `result`: 1 after ml_propagate, n after ml_propagate_sets
     double x0 = 0, y0 = 0, dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
     PropExtent extent;   // of the targets: every pass checks it against the shape it meets (prop_check_phase)
-    DevBuf targets;   // double [3][T]: x - x0, y - y0, z of every target
+    DevBuf targets;   // double [5][T]: x - x0, y - y0, z of every target, then the low parts of x - x0 and y - y0 (propagate_direct.h)
     DevBuf partial;   // double [splits][sets][12 or 6][T]: the aperture's row sets, summed by the second pass in their order
     DevBuf result;    // complex [sets][6 or 3][T]: Ex, Ey, Ez (, Hx, Hy, Hz) of every set of the last pass
     DevBuf sums;      // double [2][T]: weighted sums of |E|^2 and of Sz over the passes since the last reset (ml_propagate_accumulate)

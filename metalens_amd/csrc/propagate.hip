@@ -18,7 +18,7 @@
 // alike - each of which leaves a partial sum; a second pass adds the partials in their order.  No atomics:
 // the result is bit-for-bit repeatable, and `splits` depends on the sizes alone.
 // Several field sets in one pass (NS = 2, 3: the members of a synthesis batch, ml_propagate_sets).  Everything above
-// that depends on the pair alone - dy, R, 1 / R, Rhat, q, the sincos of k R, w, a, b: about 68 of the 176 vector
+// that depends on the pair alone - dy, R, 1 / R, Rhat, q, the sincos of k R, w, a, b: about 69 of the 177 vector
 // instructions of a pair - is computed once per pair and serves every set; a tile is staged as
 // [sample][set][current] (64 NS bytes per sample, 24 KiB at NS = 3) and pair_term runs once per set into that set's own
 // accumulators.  The per-pair expressions are the same inlined functions in the same order whatever NS is, nothing is
@@ -30,21 +30,22 @@
 // The phase k R (1.6e4 rad at 1 mm, 1e7 at 1 m) is the accuracy: R by a correctly rounded square root (nearfield_math.h
 // sqrt_exact: bit for bit np.sqrt over 1e-200 ... 1e200), sin / cos by the two-constant Cody-Waite reduction with FMA
 // (sincos_cw: within 2^-51 absolute for |k R| <= 1e9) - both held to that on the GPU by tests/test_gpu_device_math.py.
+// A target's coordinates against the aperture's origin, x - x0 and y - y0, are kept as two doubles each (propagate_direct.h
+// prop_two_diff) and the low part is added behind the fma that forms dx and dy: with the rounded difference alone the
+// distance to the sample under a target is off by up to u |x - x0| - a 1e-14 of the field 30 nm behind a sample, 28 x the
+// error of the plain NumPy sum (tests/propagate_direct_cases.py, row d-near).  One addition per pair, 0.5 % of a pass.
 // k R <= 1e9 is enforced: the plan keeps the targets' bounding box and the largest z, and a plan or a pass whose largest
 // possible k R over the aperture exceeds the limit is refused (common.h prop_check_phase; 1e9 is 92 m at 580 nm in glass).
 #include "nearfield_math.h"
+#include "propagate_direct.h"   // PROP_THREADS, PROP_TILE, PROP_MAX_SETS, PROP_BLOCKS; tiles, splits and buffer sizes of a pass
 
 namespace ml {
-
-constexpr int PROP_THREADS = 256;   // targets per workgroup
-constexpr int PROP_TILE = 128;      // aperture samples per LDS tile (8 KiB per field set)
-constexpr int PROP_MAX_SETS = 3;    // field sets per pass (the members of a synthesis batch, nearfield_dev.h MAX_POL)
-constexpr int PROP_BLOCKS = 2048;   // workgroups aimed at: eight per compute unit
 
 struct PropArgs {
     const double2 *fields;   // [NS][4][nx][ny]: Ex, Ey, Hx, Hy of the first field set of the pass, the others behind it
     const int *row_first;    // [nx] (row_extent_kernel) or nullptr: every sample is read
     const double *tx, *ty, *tz;   // [T]: x - x0, y - y0, z
+    const double *tx_lo, *ty_lo;  // [T]: what the rounding of x - x0 and y - y0 left behind (propagate_direct.h prop_two_diff)
     double *partial;         // [splits][NS][12 or 6][T]
     int nx, ny, T, splits;
     double dxp, dyp, k, inv_k, Z;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
     const int tid = threadIdx.x;
     const int t = blockIdx.x * PROP_THREADS + tid;
     const int tc = min(t, a.T - 1);   // (lanes past the last target work on a copy of it and store nothing)
-    const double tx = a.tx[tc], ty = a.ty[tc], z = a.tz[tc];
+    const double tx = a.tx[tc], ty = a.ty[tc], z = a.tz[tc], ty_lo = a.ty_lo[tc];
     const double zz = z * z;
     const bool wave_live = blockIdx.x * PROP_THREADS + (tid & ~63) < a.T;
     // staging: this thread converts field f of the columns c and c + 64 of a tile into current 3 - f, set by set:
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
         const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
         const int j_hi = a.ny - first;
         if (first >= j_hi) continue;
-        const double dx = fma(-(double)i, a.dxp, tx);
+        const double dx = fma(-(double)i, a.dxp, tx) + a.tx_lo[tc];   // (the low part: once per row, not kept in registers)
         const double s_row = fma(dx, dx, zz);
         const double2 *row = a.fields + ((size_t)f * a.nx + i) * a.ny;
         for (int j0 = first; j0 < j_hi; j0 += PROP_TILE) {
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
             __syncthreads();
             if (!wave_live) continue;
             for (int s = 0; s < n; ++s) {
-                const double dy = fma(-(double)(j0 + s), a.dyp, ty);
+                const double dy = fma(-(double)(j0 + s), a.dyp, ty) + ty_lo;
                 const double R = sqrt_exact(fma(dy, dy, s_row));
                 const double iR = recip(R);
                 const double ux = dx * iR, uy = dy * iR, uz = z * iR;
@@ -225,17 +226,19 @@ static int propagate_sets(ml_ctx *ctx, const char *who, double Z0, int first, in
     ML_HIP(hipSetDevice(ctx->device));
     ML_TRY(fields_unmodulate(ctx));   // as ml_fields_download: the plain near field
     if (pp.method != ML_PROPAGATE_DIRECT) return propagate_grid_sets(ctx, Z0, first, n);
-    const int T = pp.T, nq = pp.want_h ? 12 : 6, tiles = (T + PROP_THREADS - 1) / PROP_THREADS;
-    const int splits = std::max(1, std::min(ctx->fields.nx, (PROP_BLOCKS + tiles - 1) / tiles));   // (of T and nx alone)
+    const int T = pp.T, nq = prop_partial_doubles(pp.want_h), tiles = prop_tiles(T);
+    const int splits = prop_splits(T, ctx->fields.nx);   // (of T and nx alone)
     pp.have_result = false;
-    ML_TRY(pp.partial.reserve((size_t)splits * n * nq * T * sizeof(double)));
-    ML_TRY(pp.result.reserve((size_t)n * (nq / 2) * T * 2 * sizeof(double)));
+    ML_TRY(pp.partial.reserve(prop_partial_bytes(T, ctx->fields.nx, n, pp.want_h)));
+    ML_TRY(pp.result.reserve(prop_result_bytes(T, n, pp.want_h)));
     PropArgs a;
     a.fields = ctx->fields.buf.as<double2>() + (size_t)first * 4 * ctx->fields.nx * ctx->fields.ny;
     a.row_first = ctx->caches.rows_describe_fields ? ctx->grid.row_first.as<int>() : nullptr;
     a.tx = pp.targets.as<double>();
     a.ty = a.tx + T;
     a.tz = a.tx + 2 * (size_t)T;
+    a.tx_lo = a.tx + 3 * (size_t)T;
+    a.ty_lo = a.tx + 4 * (size_t)T;
     a.partial = pp.partial.as<double>();
     a.nx = ctx->fields.nx;
     a.ny = ctx->fields.ny;
@@ -299,11 +302,11 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
     pp.method = ML_PROPAGATE_DIRECT;
     pp.spectra_ready = false;
     pp.grid_work.release();   // (the spectra of an FFT plan live as long as that plan)
-    std::vector<double> h((size_t)3 * T);
+    std::vector<double> h((size_t)PROP_TARGET_ROWS * T);   // x - x0 and y - y0 as two doubles each: nothing of a target is lost
     for (long long t = 0; t < T; ++t) {
         const int ix = point_list ? (int)t : (int)(t / ny_t), iy = point_list ? (int)t : (int)(t % ny_t);
-        h[t] = x[ix] - x0;
-        h[T + t] = y[iy] - y0;
+        h[t] = prop_two_diff(x[ix], x0, &h[3 * T + t]);
+        h[T + t] = prop_two_diff(y[iy], y0, &h[4 * T + t]);
         h[2 * T + t] = z[point_list ? (int)t : 0];
     }
     ML_TRY(pp.targets.reserve(h.size() * sizeof(double)));

@@ -23,15 +23,23 @@ import numpy as np
 Z0_SI = 1.25663706212e-6 * 299792458.0
 
 
+def _pitches(xp_list, yp_list, pitch):
+    """(dx', dy') as the C ABI takes them: the axes' first steps, or ``pitch`` for an axis of one sample"""
+    if pitch is not None:
+        return float(pitch[0]), float(pitch[1])
+    return float(xp_list[1] - xp_list[0]), float(yp_list[1] - yp_list[0])
+
+
 def direct_sum(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, points, Z0=Z0_SI, *, real=np.float64,
-               want_h=True):
-    """E [3][T] (and H [3][T]) at ``points`` [T][3]; ``real`` = np.float64 or np.longdouble"""
+               want_h=True, pitch=None):
+    """E [3][T] (and H [3][T]) at ``points`` [T][3]; ``real`` = np.float64 or np.longdouble.  ``pitch`` = (dx', dy')
+    where an axis has one sample and no step of its own (the C ABI takes the pitches as numbers)"""
     cplx = np.complex128 if real is np.float64 else np.clongdouble
     k = real(2 * np.pi * n_glass / wavelength)
     Z = real(Z0 / n_glass)
     pi = 4 * np.arctan(real(1))
     x0, y0 = real(xp_list[0]), real(yp_list[0])
-    dxp, dyp = real(xp_list[1] - xp_list[0]), real(yp_list[1] - yp_list[0])
+    dxp, dyp = (real(v) for v in _pitches(xp_list, yp_list, pitch))
     X, Y = np.meshgrid(x0 + np.arange(len(xp_list)).astype(real) * dxp,
                        y0 + np.arange(len(yp_list)).astype(real) * dyp, indexing='ij')
     Ex, Ey, Hx, Hy = (np.asarray(F).astype(cplx) for F in (Ex, Ey, Hx, Hy))
@@ -76,6 +84,116 @@ def max_error(got, want):
     """max |got - want| over all components and targets / max |want| (`want` may be long double)"""
     want = np.asarray(want)
     return float(np.abs(np.asarray(got).astype(want.dtype) - want).max() / np.abs(want).max())
+
+
+# ---- a bound per target for the direct pair sum (csrc/propagate.hip propagate_kernel) -------------------------------------
+U = 2.0 ** -53
+BOUND_C0, BOUND_C1, BOUND_C2 = 104, 3, 6
+
+
+def term_sums(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, points, Z0=Z0_SI, *, pitch=None):
+    """-> A_E [T], A_H [T], Phi [T] in long double: per target the sum over the samples of the absolute values of a pair's
+    terms, the largest phase k R, and -> q_max [T], the largest 1 / (k R).
+
+    With q = 1 / (k R), |w| = q, a = 1 + i q - q^2, b = 1 + 3 i q - 3 q^2, m = M / Z and |V|_1 = |Vx| + |Vy| (moduli of the
+    complex currents), a pair adds w { i (a V - b Rhat (Rhat . V)) -+ (i - q) Rhat x U } to each component, which is at
+    most q { (|a| + |b|) |V|_1 + |i - q| |U|_1 } in modulus for every component (|Rhat components| <= 1):
+
+        A_E[t] = Z k^2 / (4 pi) dx' dy' sum q { (|a| + |b|) |J|_1 + |i - q| |m|_1 }
+        A_H[t] =   k^2 / (4 pi) dx' dy' sum q { (|a| + |b|) |m|_1 + |i - q| |J|_1 }
+
+    ``target_bound`` is (BOUND_C0 + BOUND_C1 n + BOUND_C2 Phi[t]) u A[t], u = 2^-53, n = the samples of the aperture, for the
+    modulus of the error of every complex component of E (with A_E) and H (with A_H) at target t, to first order in u.  The
+    constants, from the kernel's operations; "x u" stands for a relative error against the pair's share of A unless it says
+    otherwise:
+
+      coordinates    the plan stores x - x0 as two doubles, exactly (propagate_direct.h prop_two_diff); dx = fl(fma(-i, dx', hi) +
+                     lo): the fma rounds hi - i dx', the addition the sum - 2 u |dx| (and u^2 |x - x0|, second order).  Likewise
+                     dy.  Against the reference's x - (x0 + i dx') the squares dx^2 + dy^2 are off by 4 u (dx^2 + dy^2) <= 4 u R^2
+      R              z z, fma(dx, dx, zz), fma(dy, dy, s_row): 3 u of R^2, with the coordinates 7 u; the correctly rounded root
+                     halves it and adds at most u: e_R = 4.5 u
+      phase          fl(k R): u k R.  |d theta| <= 5.5 u k R <= 5.5 u Phi.  sincos_cw is within 2^-51 = 4 u absolute in sin and in
+                     cos: 5.66 u of the unit phasor
+      1 / R, q       recip: 2^-52 = 2 u; inv_k = fl(1 / k): u; the product: u.  e_q = 8.5 u
+      w a, w b,      w = (cos q, sin q): u.  As functions of ln R the products q a, q b, q (i - q) change by (1 + 2 q + 3 q^2) /
+      w (i - q)      |a| <= 6.1, (1 + 6 q + 9 q^2) / |b| <= 4.5 and (1 + 2 q) / |i - q| <= 2.3 times e_q relative to their moduli,
+                     whatever q is: 6.1 e_q = 51.85 u.  Their own roundings - q q, 1 - q2, fma(-3, q2, 1), 3 q - count against 1 + q +
+                     q^2 <= 3 |a| and twice 1 + 3 q + 3 q^2 <= 2.16 |b|: 6 u.  Together with the phase: 64.51 u + 5.5 u Phi
+      Rhat           ux = fl(dx iR): 2 u of dx, 6.5 u of iR, u of the product: 9.5 u.  b Rhat (Rhat . V) holds two such factors, the
+                     cross product one: 19 u
+      currents       sg v / den, one division where the reference divides M by Z: u
+      pair_term      along the longest path of a component: dot 2, cmulf 2, D 3, X 2, the two fma that join them 2 - 11 u,
+                     each against the absolute values of what it adds, which the pair's share of A holds
+      per pair       95.51 u + 5.5 u Phi
+      the n          cfma rounds each accumulator twice per pair, at a partial sum of at most A: 2 n u A
+      additions
+      reduce, scale  `splits` <= nx <= n additions of partials: n u A; the scale Z k^2 / (4 pi) dx' dy' formed in fp64 (six
+                     roundings) and its product with the sum: 7 u
+
+    c1 = 3;  c0 = 95.51 + 7 = 102.51 -> 104;  c2 = 5.5 -> 6.  Nothing here was fitted to a GPU's output.
+    The plain-fp64 NumPy sum (``direct_sum``) forms X = x0 + i dx' before it subtracts, an error of u |X| in dx that grows with
+    the aperture's distance from the ORIGIN, which no term above holds; tests/test_propagate_direct_cases.py asserts that it
+    stays within the bound all the same at every compared target of every row of tests/propagate_direct_cases.py."""
+    LD, CLD = np.longdouble, np.clongdouble
+    k, Z = LD(2 * np.pi * n_glass / wavelength), LD(Z0 / n_glass)
+    pi = 4 * np.arctan(LD(1))
+    x0, y0 = LD(xp_list[0]), LD(yp_list[0])
+    dxp, dyp = (LD(v) for v in _pitches(xp_list, yp_list, pitch))
+    Ex, Ey, Hx, Hy = (np.asarray(F).astype(CLD) for F in (Ex, Ey, Hx, Hy))
+    nx, ny = Ex.shape
+    X, Y = np.meshgrid(x0 + np.arange(nx).astype(LD) * dxp, y0 + np.arange(ny).astype(LD) * dyp, indexing='ij')
+    J1 = np.abs(Hy) + np.abs(Hx)
+    m1 = (np.abs(Ey) + np.abs(Ex)) / Z
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    A_E, A_H, Phi, q_max = (np.zeros(len(points), dtype=LD) for _ in range(4))
+    scale = k * k / (4 * pi) * dxp * dyp
+    for t, (x, y, z) in enumerate(points):
+        R = np.sqrt((LD(x) - X) ** 2 + (LD(y) - Y) ** 2 + LD(z) ** 2)
+        q = 1 / (k * R)
+        ab = np.sqrt((1 - q * q) ** 2 + q * q) + np.sqrt((1 - 3 * q * q) ** 2 + 9 * q * q)
+        iq = np.sqrt(1 + q * q)
+        A_E[t] = Z * scale * (q * (ab * J1 + iq * m1)).sum()
+        A_H[t] = scale * (q * (ab * m1 + iq * J1)).sum()
+        Phi[t] = (k * R).max()
+        q_max[t] = q.max()
+    return A_E, A_H, Phi, q_max
+
+
+def target_bound(n, Phi, A):
+    """the bound of ``term_sums`` on the modulus of the error of a component at every target"""
+    return (BOUND_C0 + BOUND_C1 * n + BOUND_C2 * Phi) * U * A
+
+
+def bound_ratio(got, want, bound):
+    """-> the largest |got - want| / bound over the components [3] and targets [T] (``want`` long double)"""
+    want = np.asarray(want)
+    return float((np.abs(np.asarray(got).astype(want.dtype) - want) / bound[None, :]).max())
+
+
+def one_pair(Ex, Ey, Hx, Hy, sample, wavelength, n_glass, point, pitch, Z0=Z0_SI):
+    """The field of ONE aperture sample at (x', y', 0) with the fields Ex ... Hy (four complex numbers) and the area dx' dy' = ``pitch[0] pitch[1]``, at
+    one point: the closed form written out component by component in long double - no arrays, no sums -> E [3], H [3]"""
+    LD, CLD = np.longdouble, np.clongdouble
+    k, Z = LD(2 * np.pi * n_glass / wavelength), LD(Z0 / n_glass)
+    pi = 4 * np.arctan(LD(1))
+    Jx, Jy, Mx, My = -CLD(Hy), CLD(Hx), CLD(Ey), -CLD(Ex)
+    Rx, Ry, Rz = LD(point[0]) - LD(sample[0]), LD(point[1]) - LD(sample[1]), LD(point[2])
+    R = np.sqrt(Rx * Rx + Ry * Ry + Rz * Rz)
+    ux, uy, uz = Rx / R, Ry / R, Rz / R
+    kr = k * R
+    g = (np.cos(kr) + CLD(1j) * np.sin(kr)) / (4 * pi * R) * (LD(pitch[0]) * LD(pitch[1]))
+    a = CLD(1 - 1 / kr ** 2 + 1j / kr)
+    b = CLD(1 - 3 / kr ** 2 + 3j / kr)
+    c = CLD(-1 / R + 1j * k)
+    uJ, uM = ux * Jx + uy * Jy, ux * Mx + uy * My
+    ikZ, ik_Z = CLD(1j) * k * Z, CLD(1j) * k / Z
+    E = [g * (ikZ * (a * Jx - b * ux * uJ) - c * (-uz * My)),
+         g * (ikZ * (a * Jy - b * uy * uJ) - c * (uz * Mx)),
+         g * (ikZ * (-b * uz * uJ) - c * (ux * My - uy * Mx))]
+    H = [g * (ik_Z * (a * Mx - b * ux * uM) + c * (-uz * Jy)),
+         g * (ik_Z * (a * My - b * uy * uM) + c * (uz * Jx)),
+         g * (ik_Z * (-b * uz * uM) + c * (ux * Jy - uy * Jx))]
+    return np.array(E, dtype=CLD), np.array(H, dtype=CLD)
 
 
 # ---- the cases the tests share ---------------------------------------------------------------------------
