@@ -871,7 +871,7 @@ int ml_math_probe(ml_ctx *ctx, int op, const double *x, const int *kq, int n,
                   double *out0, double *out1, int *outk);
 
 /* ---- test surface: the discrete decisions of the synthesis, one point per lane ---------------
- * Which ring a sample lies in, which sector of the ring, which centre cell: sample_geometry (csrc/nearfield_fast.hip)
+ * Which ring a sample lies in, which sector of the ring, which centre cell: sample_geometry (csrc/nearfield_geometry.hip)
  * decides them once per (grid, layout) and every synthesis reuses the records.  This entry runs the same function on n
  * points (x[i], y[i]) of the caller's against the layout now on the context (ml_upload_layout; no tables, grid or source
  * are needed), so that tests can place points on every edge of every decision (tests/test_gpu_geometry_cases.py).

@@ -441,12 +441,12 @@ struct SynthGrid {
     std::vector<double> h_x_pts, h_y_pts;   // what x_pts / y_pts hold (re-uploaded only on change)
     DevBuf row_first;                       // see row_extent_kernel
     int trim_rows[2] = {0, 0};              // rows of the local aperture that meet the lens circle, [lo, hi) - farfield.hip trim_rows_of
-    // per-sample geometry records and the four patch lists (nearfield_fast.hip; NfArgs::active_list)
+    // per-sample geometry records and the four patch lists (nearfield_geometry.hip; NfArgs::active_list)
     DevBuf geo_ix, active_list, active_count, active_flag;
     int n_active[4] = {0, 0, 0, 0};         // the lists' lengths, once SynthCaches::lengths == KNOWN
 };
 
-// exact nearest-cell ties (nearfield_dev.h settle_tie): samples the last synthesis could not settle, and the host's
+// exact nearest-cell ties (nearfield_geometry.hip settle_tie): samples the last synthesis could not settle, and the host's
 // answers for the current (grid, layout)
 struct Ties {
     DevBuf count, list, ovr_key, ovr_slot;

@@ -99,7 +99,7 @@ struct RingBucket {
     int first, pad;
 };
 
-// a centre cell as the fast kernel's lattice shortcut reads it (nearfield_dev.h lattice_pick)
+// a centre cell as the fast kernel's lattice shortcut reads it (nearfield_geometry.hip lattice_pick)
 struct CellRec {
     double x, y;          // cell centre (NaN for an empty lattice node)
     int which, index;     // grating type, original index in lens_center_summary
@@ -272,7 +272,7 @@ inline bool canon_orders(const HostTable &t, Canon &L) {   // false: not a simpl
 
 // PER TABLE: the collections (and the centre table) whose order sets are simple take the kernels of
 // nearfield_simple.hip, the others - an order with oy != 0 (grating.lua:406-423 searches (ox, oy) in [-5, 5]^2), a
-// list that is not ascending - the general kernel of nearfield_fast.hip, each over the patches that hold its
+// list that is not ascending - the general kernel of nearfield_general.hip, each over the patches that hold its
 // samples: one table with an order (ox, +-1) no longer sends the whole lens through the general kernel.
 struct LensClass {
     Canon canon[MAX_RING_COLLS], canon_center;
@@ -490,7 +490,7 @@ inline RingTables pack_ring_tables(const HostTable *const *colls, const TableDes
     for (int c = 0; c < n_colls; ++c) {
         const HostTable &t = *colls[c];
         const TableDesc &d = *desc[c];
-        // the field kernel addresses a ring's table with 24-bit products (nearfield_fast.hip)
+        // the field kernel addresses a ring's table with 24-bit products (nearfield_general.hip)
         ML_PACK_REQUIRE(out, (long long)t.n0 * t.n1 * 4 < (1ll << 24), "table of collection %d is too large (%d x %d nodes)",
                         coll_slot[c], t.n0, t.n1);
         CollDesc &C = out.coll[c];

@@ -1,6 +1,7 @@
-// Near-field synthesis on MI355X: launch code and the small helper kernels.  The synthesis
-// kernel itself is nearfield_fast.hip (one thread per aperture sample, reference
-// nearfield.py:117-477; oracle/nearfield_oracle.py is the NumPy statement of the same thing).
+// Near-field synthesis on MI355X: the steps of a synthesis, the choice of its kernels and the small helper
+// kernels.  The kernels themselves (one thread per aperture sample, reference nearfield.py:117-477;
+// oracle/nearfield_oracle.py is the NumPy statement of the same thing): nearfield_geometry.hip the per-sample
+// records and patch lists, nearfield_simple.hip the fields of a round lens' order sets, nearfield_general.hip of any other.
 // Compiled with -ffp-contract=off: the arguments of the large phases (k*distance ~ 1e4 rad) must
 // be rounded exactly like the reference's NumPy expressions, so no multiply-add may be fused.
 //
@@ -314,13 +315,21 @@ static int ensure_list_lengths(ml_ctx *ctx, const NfArgs &a) {
 static int launch_members(ml_ctx *ctx, const ml_nearfield_params *p, int n, bool members_alone, NfArgs &a,
                           int *n_partials) {
     const int nx = a.nx, ny = a.ny;
+    // one wave (= one workgroup) per 8 x 8 patch.  A wave that walks several patches so that its stores drain under the
+    // next patch's arithmetic costs registers the kernel does not have (spills): 25-40 % slower.
+    const dim3 full((ny + 7) / 8, (nx + 7) / 8);
+    *n_partials = (int)(full.x * full.y) * 4;   // four power partials per patch (wave_power)
+    // the kernels of a round lens' order sets, else the general one - over list 0 once the zeros are in place
+    auto launch = [&](const NfArgs &q) {
+        return q.simple_orders ? nearfield_simple_launch(ctx, q) : nearfield_general_launch(ctx, q, q.use_active ? dim3(q.n_active[0]) : full);
+    };
     if (!a.use_active) a.centre_patch_bound = centre_patch_bound(ctx, nx, ny);
     bool one_position = true;
     for (int m = 1; m < n; ++m)
         one_position = one_position && p[m].source_x == p[0].source_x && p[m].source_y == p[0].source_y &&
                        p[m].source_z == p[0].source_z;
     ProfScope scope(ctx, ML_K_NEARFIELD);
-    if (one_position && !members_alone) return nearfield_fast_launch(ctx, a, n_partials);
+    if (one_position && !members_alone) return launch(a);
     for (int m = 0; m < n; ++m) {
         NfArgs am;
         fill_nf_args(ctx, p + m, 1, nx, ny, am);
@@ -330,7 +339,7 @@ static int launch_members(ml_ctx *ctx, const ml_nearfield_params *p, int n, bool
         for (int k = 0; k < 4; ++k) am.n_active[k] = a.n_active[k];
         am.fields += (size_t)m * 4 * nx * ny * 2;
         am.partial_power += (size_t)m * a.n_partials;
-        ML_TRY(nearfield_fast_launch(ctx, am, n_partials));
+        ML_TRY(launch(am));
     }
     return ML_OK;
 }

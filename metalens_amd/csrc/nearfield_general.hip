@@ -1,5 +1,6 @@
-// Near-field synthesis kernel (reference nearfield.py:117-477 per aperture sample).
-//
+// Near-field synthesis for GENERAL order sets (reference nearfield.py:117-477 per aperture sample): the field kernel
+// of every table whose orders are not all (ox, 0) - nearfield_simple.hip takes those - from the per-sample records
+// of nearfield_geometry.hip.
 // Agrees with the reference's operation order (oracle/nearfield_oracle.py) to ~1e-15; only the
 // arithmetic that feeds LARGE phases is kept in the reference's exact order:
 //   * ring / sector / nearest-cell decisions (r, atan2, round)            -> exact
@@ -19,73 +20,10 @@
 //       Ex += Z0 g (kx ky U_fy + (ky^2+kz^2) U_fx) ph ; Ey += Z0 g (-(kx^2+kz^2) U_fy - kx ky U_fx) ph
 //     with g = 1/(k_glass kz n_glass)  (nearfield.py:313-327 rearranged);
 //   * use one reciprocal per sample and a branch-free Cody-Waite sin/cos.
-#include <algorithm>
-
-#include "nearfield_math.h"
+#include "nearfield_dev.h"
 #include "synth_staging.h"
 
 namespace ml {
-
-
-// arctan2(y, x) to ~2 ulp for finite (x, y) != (0, 0): atan(a) = a Q(a^2) on [0, 1] (degree-20
-// least-squares-at-Chebyshev-nodes fit, 2.6e-17 from atan with these rounded coefficients),
-// reciprocal by Newton steps, octant fix-ups by selects.  The device libm's atan2 costs ~160
-// vector instructions here (44 of them v_mov pairs for its coefficients, two divisions, class
-// tests); this is ~45.  Used for the sector decision only, whose near-ties are re-decided
-// exactly (sector_of_fast), so 2 ulp is 1e6 times finer than needed.
-__device__ __forceinline__ double atan2_fast(double y, double x) {
-    const double ax = fabs(x), ay = fabs(y);
-    const double mx = fmax(ax, ay), mn = fmin(ax, ay);
-    const double t = mn * recip(mx);
-    const double z = t * t;
-    double q = horner(z, 1.26311784304774261e-05, -1.46170881636250135e-04);
-    q = horner(z, q, 8.03360418162602668e-04);
-    q = horner(z, q, -2.80476555317013152e-03);
-    q = horner(z, q, 7.03864620298981329e-03);
-    q = horner(z, q, -1.36741392883994780e-02);
-    q = horner(z, q, 2.17402138307581337e-02);
-    q = horner(z, q, -2.97007177362342313e-02);
-    q = horner(z, q, 3.65108135272103479e-02);
-    q = horner(z, q, -4.21257239638553257e-02);
-    q = horner(z, q, 4.71972399232111206e-02);
-    q = horner(z, q, -5.25272555732257465e-02);
-    q = horner(z, q, 5.88034200240154306e-02);
-    q = horner(z, q, -6.66637118772109849e-02);
-    q = horner(z, q, 7.69227555520562989e-02);
-    q = horner(z, q, -9.09090660565689823e-02);
-    q = horner(z, q, 1.11111109820871259e-01);
-    q = horner(z, q, -1.42857142815926930e-01);
-    q = horner(z, q, 1.99999999999299460e-01);
-    q = horner(z, q, -3.33333333333328596e-01);
-    // atan(t) = t + t z q'  keeps the leading term exact
-    double r = fma(t * z, q, t);
-    r = ay > ax ? 1.57079632679489655800e+00 - r : r;
-    r = x < 0.0 ? 3.14159265358979311600e+00 - r : r;
-    // the sign as atan2 takes it: y = -0.0 with x < 0 is -pi, a different sector from +pi when num_around_circle is odd
-    return copysign(r, y);
-}
-
-// sector_of (nearfield_dev.h) with the ring's constants already in registers and the fast
-// arctangent; the near-tie branch is the same exact recomputation
-__device__ __forceinline__ int sector_of_fast(const NfArgs &a, int half, int rot_center, double x,
-                                              double y, double dphi, double inv_dphi, int *trace = nullptr) {
-    double q = atan2_fast(y, x) * inv_dphi;
-    const double fl = floor(q);
-    if (fabs((q - fl) - 0.5) < 1e-9) {
-        const int k = min(max((int)fl, -half - 1), half);
-        if (trace) *trace |= ML_GEO_SECTOR_EXACT | (k != (int)fl ? ML_GEO_SECTOR_CLAMPED : 0);
-        const double *e = a.tie_table + (size_t)(rot_center + k) * 6;
-        const double th_hi = e[0], th_lo = e[1], c_hi = e[2], c_lo = e[3], s_hi = e[4], s_lo = e[5];
-        const double p1 = y * c_hi, e1 = fma(y, c_hi, -p1);
-        const double p2 = x * s_hi, e2 = fma(x, s_hi, -p2);
-        const double num = (p1 - p2) + ((e1 - e2) + (y * c_lo - x * s_lo));
-        const double den = x * c_hi + y * s_hi;
-        const double phi = th_hi + (th_lo + num / den);
-        q = phi / dphi;
-    }
-    if (trace && ((int)rint(q) < -half || (int)rint(q) > half)) *trace |= ML_GEO_SECTOR_CLAMPED;
-    return min(max((int)rint(q), -half), half);
-}
 
 // cell of a short ascending axis: largest i with axis[i] <= x, clamped to [0, n-2]
 __device__ __forceinline__ void locate_fast(const double *axis, int n, double x, int &i,
@@ -227,160 +165,7 @@ __device__ __forceinline__ void order_apply(Acc &acc, const OrderCommon &oc, dou
     acc.Ey.i += fma(oc.cyy, vy_i, -oc.cxy * vx_i);
 }
 
-// ---- kernel 1 of 2: the source-INDEPENDENT decisions of every sample ---------------------------
-// Ring (nearfield.py:125-128), sector and rotated local coordinates (:169,200-201), nearest
-// centre cell (:363-367) depend on the sample grid and the layout only.  They are evaluated once
-// per (grid, layout, tie answers) into an 8-byte record per sample (stored patch by patch),
-//     geo_ix = (idx | collection << 20, index into the rotation table)     periphery, idx = ring + 1,
-//                  collection = dense number of the ring's grating collection (ml_upload_layout)
-//              (cell type << 20, slot of the nearest cell; -1: no cells) centre: the cell's type
-//                  rides in the bits above the ring index (rings < 2^19) - one gather fewer
-//                  behind the record in kernel 2
-//              (n_rings + 1, -)                           outside the lens
-// (the rotated coordinates and the cell centre follow from these with one table load each: a
-// 24-byte record that carried them cost 10 % more per extra 16 bytes - the kernel is sensitive
-// to the bytes it streams from HBM, not to arithmetic in the shadow of its loads)
-// and every synthesis on that geometry - a sweep over sources, the steps of a benchmark - starts
-// from the records (kernel 2).  Same thread -> sample map as kernel 2 (8 x 8 patch per wave).
-// the decisions of one sample (see the geometry kernel below): idx, aux
-__device__ __forceinline__ void sample_geometry(const NfArgs &a, double x, double y, long long sample_id,
-                                                int &idx, int &aux, int *trace = nullptr) {
-    const double r = sqrt(x * x + y * y);
-    idx = boundaries_below_fast(a, r, trace);
-    aux = -1;
-    if (idx >= 1 && idx <= a.n_rings) {
-        const int ring = idx - 1;
-        const double dphi = a.dphi[ring];
-        const int rot_half = a.rot_half[ring], rot_center = a.rot_center[ring];
-        // sector decision: exact (nearfield.py:169)
-        const int sector = sector_of_fast(a, rot_half, rot_center, x, y, dphi, recip(dphi), trace);
-        aux = rot_center + sector;
-    } else if (idx == 0 && a.n_cells > 0) {
-        // nearest cell: the lattice shortcut settles almost every sample from the node map (two
-        // loads); anything it cannot settle goes through nearest_cell_fast
-        bool have_cell = false;
-        if (a.lat_rec) {
-            int ia, ib;
-            const int node = lattice_pick(a, x, y, ia, ib);
-            if (node >= 0) {
-                typedef double rec_t __attribute__((ext_vector_type(4)));
-                const rec_t q = *reinterpret_cast<const rec_t *>(a.lat_rec + node);
-                const double ex = x - q.x, ey = y - q.y;
-                if (ex * ex + ey * ey <= a.lat_accept_r2) {   // false for a NaN (empty) node
-                    aux = a.lat_map[node];
-                    have_cell = true;
-                    if (trace) *trace |= ML_GEO_CELL_NODE;
-                }
-            }
-        }
-        if (!have_cell) aux = nearest_cell_fast(a, x, y, sample_id, trace);
-        aux = max(aux, 0);   // a (never produced) negative slot would read as "no cells"
-    }
-}
-
-
-#ifndef ML_GEO_OCC
-#define ML_GEO_OCC 8   // (8: 64 registers, the spills sit in nearest_cell_fast's cold search; 102 us against 117 at 4 on 4096^2)
-#endif
-__global__ __launch_bounds__(64, ML_GEO_OCC) void nearfield_geometry_kernel(const NfArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.y * 8 + (lane >> 3);
-    const int j = blockIdx.x * 8 + (lane & 7);
-    int idx = a.n_rings + 1, aux = -1;
-    if (j < a.ny && i < a.nx) {
-        const size_t at = (size_t)i * a.ny + j;
-        sample_geometry(a, a.x_pts[i], a.y_pts[j], (long long)at, idx, aux);
-        // patch-major: the 64 records of a wave are 512 contiguous bytes
-        const size_t rec = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 64 + lane;
-        const int type = (idx == 0 && aux >= 0) ? a.cwhich[aux] : (idx >= 1 && idx <= a.n_rings) ? a.ring_coll[idx - 1] : 0;
-        a.geo_ix[rec] = make_int2(idx | (type << REC_TYPE_SHIFT), aux);
-    }
-    // patches with at least one sample inside the lens: the field kernels visit only these once
-    // the zeros of the others are in place.  Flags per patch here - bit 0 any lens sample, bit 1 any
-    // ring sample of a narrow collection, bit 2 any centre sample, bit 3 any ring sample of a wide
-    // collection - compacted into lists by active_compact_kernel (190 k
-    // waves adding to ONE counter took 2 ms)
-    // (ring samples by the instantiation of nearfield_simple.hip that takes their collection: NfArgs::wide_mask)
-    // (bit 4: any sample of a table that is NOT simple while others are - the general kernel's patches of a mixed
-    // lens, NfArgs::general_mask / centre_general; such samples count for neither ring instantiation nor the centre kernel)
-    const bool ring = idx >= 1 && idx <= a.n_rings;
-    const int coll = a.ring_coll[min(max(idx, 1), a.n_rings) - 1];
-    const bool gen = a.simple_orders && ((ring && ((a.general_mask >> coll) & 1)) || (idx == 0 && a.centre_general));
-    const bool wide = ring && !gen && ((a.wide_mask >> coll) & 1);
-    const int any_ring = __any(ring), any_centre = __any(idx == 0);   // all lanes vote
-    const int any_narrow = __any(ring && !wide && !gen), any_wide = __any(wide), any_gen = __any(gen);
-    const int any_simple_centre = __any(idx == 0 && !gen);
-    if (lane == 0)
-        a.active_flag[(size_t)blockIdx.y * gridDim.x + blockIdx.x] =
-            ((any_ring | any_centre) ? 1 : 0) | (any_narrow ? 2 : 0) | (any_simple_centre ? 4 : 0) | (any_wide ? 8 : 0) |
-            (any_gen ? 16 : 0);
-}
-
-// flags -> list of (bx, by) of the patches whose flags meet `mask`, in patch order.  Two small
-// kernels over chunks of 1024 patches: listed patches per chunk, then (per chunk) the sum of the
-// chunks before it + a scan of its own flags + the writes.  count[0] = total, count[1 + c] = chunk c.
-constexpr int COMPACT_CHUNK = 1024;
-
-__device__ __forceinline__ int chunk_scan(int mine, int *s_wave, int &total) {
-    // exclusive prefix of `mine` (0 / 1) over the 1024 threads of the workgroup
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long votes = __ballot(mine);
-    const int before = __popcll(votes & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(votes);
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < COMPACT_CHUNK / 64; ++w) {
-        const int v = s_wave[w];
-        base += w < wave ? v : 0;
-        total += v;
-    }
-    return base + before;
-}
-
-// blockIdx.y = which list: mask = masks[y] (0: a list nobody launches from - its count is written as 0),
-// count / list = the y-th of arrays count_stride / list_stride apart
-struct CompactLists {
-    int mask[4], first, n;   // lists first ... first + n - 1
-};
-
-__global__ __launch_bounds__(COMPACT_CHUNK) void active_count_kernel(const int *flag, CompactLists L, int n_patches, int *count,
-                                                                     int count_stride) {
-    __shared__ int s_wave[COMPACT_CHUNK / 64];
-    const int mask = L.mask[blockIdx.y];
-    count += (size_t)(L.first + blockIdx.y) * count_stride;
-    const int k = blockIdx.x * COMPACT_CHUNK + threadIdx.x;
-    int total;
-    chunk_scan(k < n_patches ? (flag[k] & mask) != 0 : 0, s_wave, total);
-    if (threadIdx.x == 0) count[1 + blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(COMPACT_CHUNK) void active_compact_kernel(const int *flag, CompactLists L, int n_patches,
-                                                                       int patches_x, int2 *list, int list_stride,
-                                                                       int *count, int count_stride) {
-    __shared__ int s_wave[COMPACT_CHUNK / 64];
-    __shared__ int s_before[COMPACT_CHUNK / 64];
-    const int mask = L.mask[blockIdx.y];
-    count += (size_t)(L.first + blockIdx.y) * count_stride;
-    list += (size_t)(L.first + blockIdx.y) * list_stride;
-    // lens patches in the chunks before this one (a few hundred chunks at most)
-    int part = 0;
-    for (int c = threadIdx.x; c < (int)blockIdx.x; c += COMPACT_CHUNK) part += count[1 + c];
-    for (int off = 32; off; off >>= 1) part += __shfl_down(part, off);
-    if ((threadIdx.x & 63) == 0) s_before[threadIdx.x >> 6] = part;
-    const int k = blockIdx.x * COMPACT_CHUNK + threadIdx.x;
-    const int mine = k < n_patches ? (flag[k] & mask) != 0 : 0;
-    int total;
-    const int at = chunk_scan(mine, s_wave, total);   // (its barrier also covers s_before)
-    int before = 0;
-#pragma unroll
-    for (int w = 0; w < COMPACT_CHUNK / 64; ++w) before += s_before[w];
-    if (mine) list[before + at] = make_int2(k % patches_x, k / patches_x);
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) count[0] = before + total;
-}
-
-// ---- kernel 2 of 2: fields from the records ----------------------------------------------------
+// ---- fields from the records ----------------------------------------------------
 // Periphery tables through LDS.  A sample needs, per diffraction order, the 4 table nodes around
 // (uxp, uyp) x 4 amplitudes = 16 complex of its ring's table: gathered per lane that is 48
 // wave-wide 16-byte loads per sample (3 orders), and the vector memory path moves 64 B per clock
@@ -813,58 +598,9 @@ __global__ __launch_bounds__(64, NP == 1 ? ML_NF_WAVES : 3) void nearfield_field
     }
 }
 
-int nearfield_geometry_launch(ml_ctx *ctx, const NfArgs &a) {
-    const dim3 grid((a.ny + 7) / 8, (a.nx + 7) / 8);
-    hipLaunchKernelGGL(nearfield_geometry_kernel, grid, dim3(64), 0, ctx->stream, a);
-    ML_HIP(hipGetLastError());
-    // the lists the field kernels of this lens launch from (NfArgs::active_list): every lens patch
-    // for the general kernels; ring patches and centre patches for the two kernels of nearfield_simple.hip
-    const int n_patches = (int)(grid.x * grid.y), chunks = (n_patches + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
-    // (all the lists of the lens in ONE launch of each of the two kernels: blockIdx.y = list.  A list nobody
-    // launches from - narrow ring patches of a lens without narrow collections, wide ones of a lens without
-    // wide collections - gets the mask 0: nothing listed, count 0)
-    const bool mixed = a.simple_orders && (a.general_mask || a.centre_general);
-    CompactLists L;
-    L.first = a.simple_orders && !mixed ? 1 : 0;
-    L.n = mixed ? 4 : a.simple_orders ? 3 : 1;
-    for (int y = 0; y < 4; ++y) L.mask[y] = 0;
-    for (int y = 0; y < L.n; ++y) {
-        const int k = L.first + y;
-        L.mask[y] = ((k == 1 && !a.narrow_exists) || (k == 3 && !a.wide_mask)) ? 0 : 1 << k;
-        if (k == 0 && mixed) L.mask[y] = 16;   // (list 0 of a mixed lens: the patches with samples of general tables)
-        if (k == 2 && a.simple_orders && a.centre_general) L.mask[y] = 0;   // (no centre kernel: the centre table is general)
-    }
-    hipLaunchKernelGGL(active_count_kernel, dim3(chunks, L.n), dim3(COMPACT_CHUNK), 0, ctx->stream, a.active_flag, L, n_patches,
-                       a.active_count, a.count_stride);
-    ML_HIP(hipGetLastError());
-    hipLaunchKernelGGL(active_compact_kernel, dim3(chunks, L.n), dim3(COMPACT_CHUNK), 0, ctx->stream, a.active_flag, L,
-                       n_patches, (int)grid.x, a.active_list, a.list_stride, a.active_count, a.count_stride);
-    ML_HIP(hipGetLastError());
-    return ML_OK;
-}
-
-// the general kernel over list 0 of a MIXED lens (nearfield_simple.hip launch_parts): the samples of the tables whose
-// order sets are not simple; a.use_active = 1, a.list_count set on the first pass (the list's length is on the device)
-int nearfield_general_listed_launch(ml_ctx *ctx, const NfArgs &a, int grid) {
-    if (grid <= 0) return ML_OK;
-    if (a.n_pol == 1)
-        hipLaunchKernelGGL((nearfield_field_kernel<1>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    else if (a.n_pol == 2)
-        hipLaunchKernelGGL((nearfield_field_kernel<2>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((nearfield_field_kernel<3>), dim3(grid), dim3(64), 0, ctx->stream, a);
-    ML_HIP(hipGetLastError());
-    return ML_OK;
-}
-
-int nearfield_fast_launch(ml_ctx *ctx, const NfArgs &a, int *n_partials) {
-    // one wave (= one workgroup) per 8 x 8 patch.  A wave that walks several patches so that its
-    // stores drain under the next patch's arithmetic was tried: the loop costs registers the
-    // kernel does not have (spills) and ran 25-40 % slower.
-    const dim3 full((a.ny + 7) / 8, (a.nx + 7) / 8);
-    *n_partials = (int)(full.x * full.y) * 4;   // four power partials per patch (wave_power)
-    if (a.simple_orders) return nearfield_simple_launch(ctx, a);
-    const dim3 grid = a.use_active ? dim3(a.n_active[0]) : full;
+// `grid`: every patch, or (a.use_active) the length of list 0 - of a MIXED lens (nearfield_simple.hip launch_parts) the
+// patches with samples of general tables; a.list_count set on its first pass (the list's length is on the device)
+int nearfield_general_launch(ml_ctx *ctx, const NfArgs &a, dim3 grid) {
     if (a.n_pol == 1)
         hipLaunchKernelGGL((nearfield_field_kernel<1>), grid, dim3(64), 0, ctx->stream, a);
     else if (a.n_pol == 2)
@@ -875,64 +611,4 @@ int nearfield_fast_launch(ml_ctx *ctx, const NfArgs &a, int *n_partials) {
     return ML_OK;
 }
 
-// ---- test surface (ml_geometry_probe): the decisions of sample_geometry at points of the caller's ------------------
-// One lane per point, against the layout on the context, with the trace the product's instantiation compiles out.
-// Down here so that no product kernel of this file moves.  No product code launches it.
-constexpr int GEO_PROBE_MAX_N = 1 << 20;
-constexpr int GEO_PROBE_TIES = 4096;   // entries of the probe's own tie list (the count goes on beyond it)
-
-__global__ __launch_bounds__(64) void geometry_probe_kernel(const NfArgs a, const double *x, const double *y, int n, int *ring,
-                                                            int *pick, int *path) {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    int idx, aux, trace = 0;
-    sample_geometry(a, x[i], y[i], (long long)i, idx, aux, &trace);
-    int p = -1;
-    if (idx >= 1 && idx <= a.n_rings)
-        p = aux - a.rot_center[idx - 1];
-    else if (idx == 0 && a.n_cells > 0)
-        p = a.cindex[aux];
-    ring[i] = idx;
-    pick[i] = p;
-    path[i] = trace;
-}
-
 }  // namespace ml
-
-using namespace ml;
-
-extern "C" int ml_geometry_probe(ml_ctx *ctx, const double *x, const double *y, int n, int32_t *ring, int32_t *pick,
-                                 int32_t *path) {
-    ML_REQUIRE(ctx && x && y && ring && pick && path, "ml_geometry_probe: NULL argument");
-    ML_REQUIRE(n >= 1 && n <= GEO_PROBE_MAX_N, "ml_geometry_probe: n = %d points, 1 ... 2^20 are taken", n);
-    for (int i = 0; i < n; ++i)
-        ML_REQUIRE(std::isfinite(x[i]) && std::isfinite(y[i]), "ml_geometry_probe: point %d is not finite (%g, %g)", i, x[i], y[i]);
-    if (!ctx->lens.have_layout) {
-        set_error("ml_geometry_probe: ml_upload_layout has not been called");
-        return ML_ESTATE;
-    }
-    ML_HIP(hipSetDevice(ctx->device));
-    const size_t nd = (size_t)n * sizeof(double), ni = (size_t)n * sizeof(int32_t);
-    // [x][y] doubles, [tie list] 64-bit integers, [ring][pick][path][tie count] integers - all the probe's own
-    DevBuf buf;
-    ML_TRY(buf.reserve(2 * nd + GEO_PROBE_TIES * sizeof(long long) + 3 * ni + sizeof(int)));
-    double *dx = buf.as<double>(), *dy = dx + n;
-    long long *tie_list = reinterpret_cast<long long *>(dy + n);
-    int *dring = reinterpret_cast<int *>(tie_list + GEO_PROBE_TIES), *dpick = dring + n, *dpath = dpick + n, *tie_count = dpath + n;
-    NfArgs a{};
-    fill_layout_args(ctx, a);
-    a.tie_count = tie_count;
-    a.tie_list = tie_list;
-    a.tie_cap = GEO_PROBE_TIES;
-    a.n_ovr = 0;   // no answers: every tie keeps the lowest original index
-    ML_HIP(hipMemcpyAsync(dx, x, nd, hipMemcpyHostToDevice, ctx->stream));
-    ML_HIP(hipMemcpyAsync(dy, y, nd, hipMemcpyHostToDevice, ctx->stream));
-    ML_HIP(hipMemsetAsync(tie_count, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(geometry_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, a, dx, dy, n, dring, dpick, dpath);
-    ML_HIP(hipGetLastError());
-    ML_HIP(hipMemcpyAsync(ring, dring, ni, hipMemcpyDeviceToHost, ctx->stream));
-    ML_HIP(hipMemcpyAsync(pick, dpick, ni, hipMemcpyDeviceToHost, ctx->stream));
-    ML_HIP(hipMemcpyAsync(path, dpath, ni, hipMemcpyDeviceToHost, ctx->stream));
-    ML_HIP(hipStreamSynchronize(ctx->stream));
-    return ML_OK;
-}

@@ -1,6 +1,7 @@
-// Device arithmetic shared by the near-field kernels (nearfield_fast.hip: geometry + general order
-// sets; nearfield_simple.hip: the round-lens order set) and the propagators (propagate.hip,
-// propagate_grid*.hip): Cody-Waite sin / cos with scalar-register
+// Device arithmetic shared by the near-field kernels (nearfield_geometry.hip: the decisions of a sample;
+// nearfield_general.hip: general order sets; nearfield_simple.hip: the round-lens order set), the passes over the
+// resident field (fields_*.hip) and the propagators (propagate.hip, propagate_grid*.hip): the complex pair c2 and
+// its products, a DPP lane sum, Cody-Waite sin / cos with scalar-register
 // coefficients, reciprocal and reciprocal root by one third-order step, an exact square root
 // without range scaling.  Amplitude-type accuracy (a few ulp) unless said otherwise.
 // Every function here is run alone on the GPU over the range its comment states (math_probe.hip,
@@ -8,9 +9,33 @@
 // operation for the host in tools/device_math.cpp, which tests/test_device_math_host.py holds against
 // 200-bit arithmetic and the GPU must match bit for bit.  Measured figures: DESIGN.md appendix.
 #pragma once
-#include "nearfield_dev.h"
+#include "common.h"
 
 namespace ml {
+
+struct c2 {
+    double r, i;
+};
+__device__ __forceinline__ c2 operator+(c2 a, c2 b) { return {a.r + b.r, a.i + b.i}; }
+__device__ __forceinline__ c2 cmul(c2 a, c2 b) {
+    return {a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r};
+}
+__device__ __forceinline__ c2 scale(c2 a, double s) { return {a.r * s, a.i * s}; }
+
+// v + (v of the lane the DPP control names; 0 where there is none or the row is masked off)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_add(double v) {
+    const long long b = __double_as_longlong(v);
+    int lo, hi;
+    if (ROW_MASK == 0xf) {   // every row takes part: lanes without a source read 0 (bound_ctrl), nothing to preset
+        lo = __builtin_amdgcn_mov_dpp((int)b, CTRL, 0xf, 0xf, true);
+        hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xf, 0xf, true);
+    } else {
+        lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xf, false);
+        hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    }
+    return v + __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
 
 // sin and cos of x for |x| <= 1e9, each within 2^-51 absolute: Cody-Waite reduction by the first two
 // of three constants of pi/2 with FMA (each step rounds once, relative to the already small

@@ -6,7 +6,7 @@
 // (1 + ox)^2 u_x^2 < 1 - (-1, 0) the design order, (0, 0) and (-2, 0) always, (+1, 0) and (-3, 0)
 // inside 30 degrees, and so on inwards - while oy != 0 needs a lateral period above a wavelength,
 // which a lens that is to diffract into one order along y does not have.  Any other order set
-// (oy != 0) runs the general kernels of nearfield_fast.hip; the source-independent decisions of a
+// (oy != 0) runs the general kernels of nearfield_general.hip; the source-independent decisions of a
 // sample (ring, sector, nearest cell) come from the records of nearfield_geometry_kernel either way.
 //
 // What the restricted order sets buy (the kernel is bound by fp64 vector ISSUE: every vector
@@ -46,9 +46,8 @@
 // - x', y', the propagation distance and k * distance - follows the reference operation by
 // operation (this file is compiled with -ffp-contract=off; every fma() here is deliberate).
 #include <algorithm>
-#include <type_traits>
 
-#include "nearfield_math.h"
+#include "nearfield_dev.h"
 #include "synth_staging.h"
 
 namespace ml {
@@ -153,7 +152,7 @@ struct OrderShared {
     c2 E0, X;
 };
 
-// E-from-H factors of one order (nearfield.py:313-327 rearranged, nearfield_fast.hip header):
+// E-from-H factors of one order (nearfield.py:313-327 rearranged, nearfield_general.hip header):
 //   Ex += Z0 g (kx ky U_fy + (ky^2 + kz^2) U_fx) ph,  Ey += Z0 g (-(kx^2 + kz^2) U_fy - kx ky U_fx) ph,
 //   g = 1 / (k_glass kz n_glass), with ky^2 + kz^2 = k_glass^2 - kx^2 and kx^2 + kz^2 = k_glass^2 - ky^2
 struct OrderFactors {
@@ -393,39 +392,30 @@ __device__ unsigned long long g_phase[(size_t)PHASE_SLOTS * PHASE_WAVES];
     do {                                                  \
         asm volatile("" ::"v"(dep));                      \
         __builtin_amdgcn_sched_barrier(0);                \
-        stamp[k] = __builtin_amdgcn_s_memtime();          \
+        s.stamp[k] = __builtin_amdgcn_s_memtime();        \
         __builtin_amdgcn_sched_barrier(0);                \
     } while (0)
 #else
 #define ML_MARK(k, dep)
 #endif
 
-// Two kernels share the samples of a lens: nearfield_ring_kernel takes the RING samples of the
-// patches that hold any (96 registers and 4.7 KB of LDS: five waves per SIMD), nearfield_centre_kernel
-// the CENTRE samples of the patches that hold any (two 5 KB block buffers, 112 registers: four).  A
-// patch that straddles the switch radius is visited by both, each storing its own samples.  The
-// incident power of a patch and - on the first synthesis into a buffer - the zeros outside the lens
-// are the ring kernel's where the patch has ring samples (and on its full-grid launch), the centre
-// kernel's otherwise.
-enum { PART_RING = 1, PART_CENTRE = 2 };
-// Wave priority along a ring wave's life.  Among waves of equal priority a SIMD issues the OLDEST first, so a young
-// wave's short instruction runs between its three dependent loads (record -> ring record + rotation -> blocks) queue
-// behind the long vector streams of its elders' order loops.  A ring wave of a single-source listed launch therefore
-// starts at priority 3 and drops to 0 once its round's blocks are requested (ML_PRIO_AT(2, 0)): near field 0.250 ->
-// 0.243 ms at 4096^2, 1.26 -> 1.20 at 8192^2 NA 0.94 (same-box A/B, profiles/r06_ab_runs.txt).  Also measured: high
-// only until the ring record is requested (-1.5 %), high again from the rotation back to the stores (as this), a
-// constant priority per wave slot (nothing).  ML_NF_PRIO = 0: off.
-#ifndef ML_NF_PRIO
-#define ML_NF_PRIO 1
+// Two kernels share the samples of a lens: nearfield_ring_kernel takes the RING samples of the patches that hold any
+// (96 registers and 4.7 KB of LDS: five waves per SIMD), nearfield_centre_kernel the CENTRE samples of the patches that
+// hold any (two 5 KB block buffers, 112 registers: four).  A patch that straddles the switch radius is visited by both,
+// each storing its own samples.  The incident power of a patch and - on the first synthesis into a buffer - the zeros
+// outside the lens are the ring kernel's where the patch has ring samples (and on its full-grid launch), the centre
+// kernel's otherwise.  Both start with patch_prologue, which leaves a lane's sample in a Sample.
+template <int NP>
+struct Sample {
+    int i, j;                      // x index, y index (fastest in memory)
+    double x, y, ux, uy, uz;       // coordinates, direction of incidence
+    double Hx_i[NP], Hy_i[NP];     // incident field per member
+    int idx, aux, cell_type;       // the record: ring + 1 (0: centre, n_rings + 1: outside), rotation / cell slot, collection / cell type
+    bool lens, peri_any, peri;     // inside the lens, a ring sample, a ring sample of THIS instantiation (centre kernel: any)
+#ifdef ML_PHASE_TIMERS
+    unsigned long long stamp[PHASE_SLOTS] = {0};
 #endif
-#define ML_PRIO_AT(point, level)                                                                                          \
-    do {                                                                                                                  \
-        if (PART == PART_RING && NP == 1 && LISTED && ML_NF_PRIO == 1 && ((point) == 0 || (point) == 2))                  \
-            __builtin_amdgcn_s_setprio(level);                                                                            \
-    } while (0)
-#ifndef ML_NF_KEEP_ROT
-#define ML_NF_KEEP_ROT 0
-#endif
+};
 
 // FIXED3: the FIXED-SHAPE form of the listed single-source kernels for what the flagship lens and the outer, narrow
 // collections of a real lens hold - every narrow collection (ring kernel), the centre table (centre kernel) exactly
@@ -436,114 +426,143 @@ enum { PART_RING = 1, PART_CENTRE = 2 };
 constexpr int FIXED3_SLOTS = 3, FIXED3_PRESENT = 7;
 static_assert(narrow_pitch(FIXED3_SLOTS) == 49 && narrow_cap(narrow_pitch(FIXED3_SLOTS)) == SK_SLOTS_NARROW && FIXED3_SLOTS * UNIT == 48,
               "the fixed-shape ring kernel's pitch, capacity and staging lanes");
-template <int NP, int PART, bool LISTED, bool WIDE, bool FIXED3 = false>
-__device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab, double2 *s_tab1, int bx, int by) {
+
+// What both kernels do first: pinned constants, coordinates, record load, incidence and incident field, record decode,
+// the patch's incident power and zeros.  RING / WIDE: which kernel asks - they decide which ring samples are its own
+// and whether the power and the zeros are.
+template <int NP, bool RING, bool LISTED, bool WIDE, bool FIXED3>
+__device__ __forceinline__ void patch_prologue(const NfArgs &a, Consts &K, int bx, int by, Sample<NP> &s) {
     static_assert(!FIXED3 || (NP == 1 && LISTED && !WIDE), "fixed-shape kernels: one source, from the lists, narrow");
     const int lane = threadIdx.x;
-    const unsigned lane_off = (unsigned)lane * 16u;
-    ML_PRIO_AT(0, 3);
-    Consts K;
     load_consts<FIXED3>(a, K);
-    const int i = by * 8 + (lane >> 3);   // x index
-    const int j = bx * 8 + (lane & 7);    // y index (fastest in memory)
-    const bool inb = j < K.ny && i < K.nx;
+    s.i = by * 8 + (lane >> 3);
+    s.j = bx * 8 + (lane & 7);
+    const bool inb = s.j < K.ny && s.i < K.nx;
     // the sample's coordinates do not wait for its record
-    const double x = a.x_pts[min(i, K.nx - 1)], y = a.y_pts[min(j, K.ny - 1)];
+    s.x = a.x_pts[min(s.i, K.nx - 1)], s.y = a.y_pts[min(s.j, K.ny - 1)];
     // (every patch has 64 records, whether or not all its samples exist: the load needs no branch - a
     // branch would make the wave wait for the record right here, in front of the arithmetic below)
     const int2v ix = reinterpret_cast<const int2v *>(K.geo_ix + ((size_t)by * K.patches_x + bx) * 64)[lane];   // patch-major
 #ifdef ML_PHASE_TIMERS
-    unsigned long long stamp[PHASE_SLOTS] = {0};
-    stamp[0] = __builtin_amdgcn_s_memtime();
-    struct StampOut {   // written on every way out of the patch
-        unsigned long long *st;
-        size_t wid;
-        __device__ ~StampOut() {
-            st[7] = __builtin_amdgcn_s_memtime();
-            __builtin_amdgcn_s_waitcnt(0);   // the stores have left the wave
-            st[8] = __builtin_amdgcn_s_memtime();
-            if (threadIdx.x == 0 && wid < PHASE_WAVES && PART == PART_RING)
-                for (int k = 0; k < PHASE_SLOTS; ++k) g_phase[wid * PHASE_SLOTS + k] = st[k];
-        }
-    } stamp_out{stamp, (size_t)by * K.patches_x + bx};
+    s.stamp[0] = __builtin_amdgcn_s_memtime();
 #endif
-    // ---- incidence direction (shared) and incident field per polarisation (nearfield.py:172-228;
-    // amplitude-type arithmetic).  They need the sample's coordinates and the source only, so they
-    // are worked out for every lane while the record is on its way and masked by it afterwards.
-    // Incident power density (:474-477): Ex Hy - Ey Hx with E = Z0 H x u and H = (u x p) amp is
-    // Z0 u_z |H|^2 = (Z0 H_coef^2) (u_z / d)^2 |u x p|^2  (amp = H_coef sqrt(u_z) / d, the Lambert factor).
-    double ux = 0.0, uy = 0.0, uz = 1.0;
-    double Hx_i[NP], Hy_i[NP], power_in[NP];
+    // ---- incidence direction (shared) and incident field per polarisation (nearfield.py:172-228; amplitude-type
+    // arithmetic).  They need the sample's coordinates and the source only, so they are worked out for every lane while
+    // the record is on its way and masked by it afterwards.
+    // Incident power density (:474-477): Ex Hy - Ey Hx with E = Z0 H x u and H = (u x p) amp is Z0 u_z |H|^2 = (Z0
+    // H_coef^2) (u_z / d)^2 |u x p|^2  (amp = H_coef sqrt(u_z) / d, the Lambert factor).
+    s.ux = 0.0, s.uy = 0.0, s.uz = 1.0;
+    double power_in[NP];
     if (K.plane_wave) {
 #pragma unroll
         for (int m = 0; m < NP; ++m) {
-            Hx_i[m] = a.pw_Hx[m];
-            Hy_i[m] = a.pw_Hy[m];
+            s.Hx_i[m] = a.pw_Hx[m];
+            s.Hy_i[m] = a.pw_Hy[m];
             power_in[m] = a.pw_power[m];
         }
     } else {
         double inv;
-        incidence(K, x, y, ux, uy, uz, inv);
-        const double t = uz * inv, rs = rsqrt_fast(uz);   // uz > 0
+        incidence(K, s.x, s.y, s.ux, s.uy, s.uz, inv);
+        const double t = s.uz * inv, rs = rsqrt_fast(s.uz);   // uz > 0
         const double t2 = t * t;
 #pragma unroll
         for (int m = 0; m < NP; ++m) {
             const double *pol = NP == 1 ? K.pol : a.pol[m];
             const double amp = ((NP == 1 ? K.hcoef : a.hcoef[m]) * rs) * t;   // H_coef sqrt(uz) / d
-            const double hx = fma(uy, pol[2], -(uz * pol[1]));
-            const double hy = fma(uz, pol[0], -(ux * pol[2]));
-            const double hz = fma(ux, pol[1], -(uy * pol[0]));
-            Hx_i[m] = hx * amp;
-            Hy_i[m] = hy * amp;
+            const double hx = fma(s.uy, pol[2], -(s.uz * pol[1]));
+            const double hy = fma(s.uz, pol[0], -(s.ux * pol[2]));
+            const double hz = fma(s.ux, pol[1], -(s.uy * pol[0]));
+            s.Hx_i[m] = hx * amp;
+            s.Hy_i[m] = hy * amp;
             power_in[m] = ((NP == 1 ? K.pcoef : a.pcoef[m]) * t2) * fma(hx, hx, fma(hy, hy, hz * hz));
         }
     }
-    int idx = inb ? ix.x : K.n_rings + 1;   // cell type / collection above bit 20, split off below
-    const int aux = inb ? ix.y : -1;
-    ML_MARK(1, idx + aux);   // the record has arrived
-    const int cell_type = idx >> REC_TYPE_SHIFT;   // (ring samples: the collection)
-    idx &= (1 << REC_TYPE_SHIFT) - 1;
-    const bool lens = idx <= K.n_rings;
-    const bool peri_any = lens && idx >= 1;   // a ring sample
-    // ... of THIS instantiation: the collections of a lens are dealt to the two ring instantiations by their
-    // order count (NfArgs::wide_mask: bit per dense collection number), each launched over the patches
-    // that hold samples of its collections - a patch on the border between a narrow and a wide collection
-    // is visited by both, each storing its own samples
+    s.idx = inb ? ix.x : K.n_rings + 1;   // cell type / collection above bit 20, split off below
+    s.aux = inb ? ix.y : -1;
+    ML_MARK(1, s.idx + s.aux);   // the record has arrived
+    s.cell_type = s.idx >> REC_TYPE_SHIFT;   // (ring samples: the collection)
+    s.idx &= (1 << REC_TYPE_SHIFT) - 1;
+    s.lens = s.idx <= K.n_rings;
+    s.peri_any = s.lens && s.idx >= 1;
+    // a ring sample of THIS instantiation: the collections of a lens are dealt to the two ring instantiations by their
+    // order count (NfArgs::wide_mask: bit per dense collection number), each launched over the patches that hold
+    // samples of its collections - a patch on the border between a narrow and a wide collection is visited by both,
+    // each storing its own samples
     // (of a MIXED lens - NfArgs::general_mask: some collections' order sets are not simple - the ring samples of those
-    // collections are neither instantiation's: the general kernel of nearfield_fast.hip takes them from its own list)
-    // (hence ONE mask per instantiation: the collections that are its own)
-    const bool peri = PART == PART_RING ? peri_any && (((WIDE ? a.wide_mask : a.narrow_mask) >> cell_type) & 1) != 0 : peri_any;
-    // who sums the patch's incident power and stores its zeros: see above
-    // (the full-grid launch - the first synthesis into a buffer - visits every patch with the ring kernel)
-    // (ring samples of a narrow collection: the narrow instantiation's patch; else of a wide one: the wide
-    // instantiation's; else the centre kernel's.  On the first synthesis into a buffer one ring instantiation
-    // - the narrow one if the lens has narrow collections - runs over the whole grid and does it for every patch)
+    // collections are neither's: nearfield_general.hip takes them from its own list; hence ONE mask per instantiation)
+    s.peri = RING ? s.peri_any && (((WIDE ? a.wide_mask : a.narrow_mask) >> s.cell_type) & 1) != 0 : s.peri_any;
+    // who sums the patch's incident power and stores its zeros (ring samples of a narrow collection: the narrow instantiation's patch; else of a wide one: the wide
+    // instantiation's; else the centre kernel's.  On the first synthesis into a buffer one ring instantiation - the
+    // narrow one if the lens has narrow collections - runs over the whole grid and does it for every patch)
     // (mixed lens: ... else the general kernel's where it has samples of a general table, else the centre kernel's)
-    const bool mine_too = PART == PART_RING ? (!WIDE || !a.narrow_exists || (LISTED && !a.first_pass && !__ballot(peri_any && ((a.narrow_mask >> cell_type) & 1))))
-                                            : (LISTED && (FIXED3 || !a.first_pass) && !__ballot(peri_any));   // wave-uniform
+    const bool mine_too = RING ? (!WIDE || !a.narrow_exists || (LISTED && !a.first_pass && !__ballot(s.peri_any && ((a.narrow_mask >> s.cell_type) & 1))))
+                               : (LISTED && (FIXED3 || !a.first_pass) && !__ballot(s.peri_any));   // wave-uniform
     if (mine_too) {
 #pragma unroll
-        for (int m = 0; m < NP; ++m) wave_power_k(a, K, lens ? power_in[m] : 0.0, bx, by, m);
-        if (!LISTED && inb && !lens && !K.outside_is_zero) {   // (a listed launch follows one that stored them)
+        for (int m = 0; m < NP; ++m) wave_power_k(a, K, s.lens ? power_in[m] : 0.0, bx, by, m);
+        if (!LISTED && inb && !s.lens && !K.outside_is_zero) {   // (a listed launch follows one that stored them)
             const c2 zero = {0.0, 0.0};
 #pragma unroll
-            for (int m = 0; m < NP; ++m) store_fields_k(K, m, i, j, zero, zero, zero, zero);
+            for (int m = 0; m < NP; ++m) store_fields_k(K, m, s.i, s.j, zero, zero, zero, zero);
         }
     }
-    ML_MARK(2, Hx_i[0]);   // incident field and power done
+    ML_MARK(2, s.Hx_i[0]);   // incident field and power done
+}
 
-    if (PART == PART_CENTRE) {
-        if (!__ballot(lens && !peri_any)) return;   // (wave-uniform; only on the full-grid launch)
-    // ================= centre: the record holds the nearest hexagonal cell =================
-    // The lanes of a patch sit in ~50 cells of up to K types, and (the direction of incidence
-    // hardly changes over 2 um) almost always in ONE (ux, uy) cell of the centre table.  Per
-    // order the wave stages that cell's block - four nodes x four amplitudes x a group of
-    // SK_TYPES types, contiguous in the centre table's cell-block form (common.h) - through LDS
-    // and every lane picks its type's sixteen values from there; order o + 1's block is on its
-    // way into the other buffer while order o is evaluated.  A round serves the lanes of one
-    // (table cell, group of types); a wave that straddles a table cell, or a table of more
-    // types, takes more rounds.
-    const bool cen = lens && !peri_any && aux >= 0;
+// What the orders of a sample share (S), for a sample at (px, py) from its grating's (cell's) centre in the grating's
+// frame, lit from direction cosines (u, v) there.  E0 = order (0, 0)'s phasor (its argument in the reference's own
+// operation order, nearfield.py:268-269,291 / :391-409 with ox = oy = 0) times the phase-critical propagation phasor
+// from the grating centre (:337-341 / :453-461, exact argument), through ONE sincos: the large angle k |r| is reduced
+// to [-pi/4, pi/4] + quadrants first and the small one added to the remainder.  X = exp(i G x'), G = 2 pi / period.
+// `centre()`: the grating centre in the lab frame, asked for under a dipole only.
+template <class Centre>
+__device__ __forceinline__ void order_shared(OrderShared &S, const Consts &K, double u, double v, double px, double py, double G,
+                                             const Centre &centre) {
+    S.kx0 = K.kvac * u;
+    S.ky = K.kvac * v;
+    double a0 = S.kx0 * px + S.ky * py;
+    int kq = 0;
+    if (!K.plane_wave) {
+        const double2 g = centre();
+        const double gx = g.x - K.sx, gy = g.y - K.sy;
+        const double air = sqrt_exact(gx * gx + gy * gy + K.z2);
+        double r;
+        reduce_pio2(K.kvac * air, r, kq);
+        a0 = r + a0;
+    }
+    sincos_cw_q(a0, kq, S.E0.i, S.E0.r);
+    S.G = G;
+    sincos_cw(S.G * px, S.X.i, S.X.r);
+    S.ky2 = S.ky * S.ky;
+}
+
+// the bilinear interpolation weights of the four nodes c = 2 (i0 step) + (i1 step) around a sample at (t0, t1) in its cell
+__device__ __forceinline__ void node_weights(double t0, double t1, double *w) {
+    w[0] = (1 - t0) * (1 - t1), w[1] = (1 - t0) * t1, w[2] = t0 * (1 - t1), w[3] = t0 * t1;
+}
+
+// input modulation of the far-field plan's stage 1, applied here for free (NfArgs::premod)
+__device__ __forceinline__ void modulate(AccS &q, c2 e) {
+    const c2 Ex = cmulf({q.Exr, q.Exi}, e), Ey = cmulf({q.Eyr, q.Eyi}, e);
+    const c2 Hx = cmulf({q.Hxr, q.Hxi}, e), Hy = cmulf({q.Hyr, q.Hyi}, e);
+    q = {Ex.r, Ex.i, Ey.r, Ey.i, Hx.r, Hx.i, Hy.r, Hy.i};
+}
+
+// ================= centre: the record holds the nearest hexagonal cell =================
+// The lanes of a patch sit in ~50 cells of up to K types, and (the direction of incidence hardly changes over 2 um)
+// almost always in ONE (ux, uy) cell of the centre table.  Per order the wave stages that cell's block - four nodes x
+// four amplitudes x a group of SK_TYPES types, contiguous in the centre table's cell-block form (common.h) - through
+// LDS and every lane picks its type's sixteen values from there; order o + 1's block is on its way into the other
+// buffer while order o is evaluated.  A round serves the lanes of one
+// (table cell, group of types); a wave that straddles a table cell, or a table of more types, takes more rounds.
+template <int NP, bool LISTED, bool FIXED3>
+__device__ __forceinline__ void synthesize_centre(const NfArgs &a, double2 *s_tab, double2 *s_tab1, int bx, int by) {
+    const unsigned lane_off = threadIdx.x * 16u;
+    Consts K;
+    Sample<NP> s;
+    patch_prologue<NP, false, LISTED, false, FIXED3>(a, K, bx, by, s);
+    if (!__ballot(s.lens && !s.peri_any)) return;   // (wave-uniform; only on the full-grid launch)
+    const bool cen = s.lens && !s.peri_any && s.aux >= 0;
     AccS acc[NP];
 #pragma unroll
     for (int m = 0; m < NP; ++m) acc[m] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -551,15 +570,15 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     int i0, i1;
     double t0, t1;
     if (FIXED3 || T.uniform) {   // (every lane: ux, uy are defined for all of them)
-        locate_uniform(T.uni_ax, (double)(T.n0 - 2), (double)(T.n1 - 2), ux, uy, i0, t0, i1, t1);
+        locate_uniform(T.uni_ax, (double)(T.n0 - 2), (double)(T.n1 - 2), s.ux, s.uy, i0, t0, i1, t1);
     } else {
-        locate_axis(T.axis0, T.n0, ux, i0, t0);
-        locate_axis(T.axis1, T.n1, uy, i1, t1);
+        locate_axis(T.axis0, T.n0, s.ux, i0, t0);
+        locate_axis(T.axis1, T.n1, s.uy, i1, t1);
     }
-    const bool out_c = (int)(ux < T.bounds[0]) | (int)(ux > T.bounds[1]) | (int)(uy < T.bounds[2]) |
-                       (int)(uy > T.bounds[3]);
+    const bool out_c = (int)(s.ux < T.bounds[0]) | (int)(s.ux > T.bounds[1]) | (int)(s.uy < T.bounds[2]) |
+                       (int)(s.uy > T.bounds[3]);
     const int n2 = T.n2, groups = (n2 + SK_TYPES - 1) / SK_TYPES;
-    const int which = min(cell_type, n2 - 1);
+    const int which = min(s.cell_type, n2 - 1);
     const int grp = which / SK_TYPES;
     const int cblk = (i0 * (T.n1 - 1) + i1) * groups + grp;   // the sample's block of order 0
     const size_t order_blocks = (size_t)(T.n0 - 1) * (T.n1 - 1) * groups;
@@ -567,35 +586,17 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     OrderShared S;   // (centre samples only; no defaults: each costs a move and a select)
     double wa[4], wb[4];
     if (cen) {
-        // the record holds the cell's slot in the bin-sorted arrays
-        const double2 cc = a.cxy[aux];
-        // phase-critical: offset from the cell centre (nearfield.py:408-409)
-        const double ox_ = x - cc.x, oy_ = y - cc.y;
-        // E0 = order (0, 0)'s phasor (its argument in the reference's own operation order,
-        // :391-409 with ox = oy = 0) times the propagation phasor from the cell centre
-        // (:453-461, exact argument), through ONE sincos: the large angle k |r| is reduced
-        // to [-pi/4, pi/4] + quadrants first, the small one added to the remainder
-        S.kx0 = K.kvac * ux;
-        S.ky = K.kvac * uy;
-        double a0 = S.kx0 * ox_ + S.ky * oy_;
-        int kq = 0;
-        if (!K.plane_wave) {
-            const double gx = cc.x - K.sx, gy = cc.y - K.sy;
-            const double air = sqrt_exact(gx * gx + gy * gy + K.z2);
-            double r;
-            reduce_pio2(K.kvac * air, r, kq);
-            a0 = r + a0;
-        }
-        sincos_cw_q(a0, kq, S.E0.i, S.E0.r);
-        S.G = T.center_g[0];
-        sincos_cw(S.G * ox_, S.X.i, S.X.r);
-        S.ky2 = S.ky * S.ky;
-        const double w[4] = {(1 - t0) * (1 - t1), (1 - t0) * t1, t0 * (1 - t1), t0 * t1};
+        // the record holds the cell's slot in the bin-sorted arrays; phase-critical: the offset from the cell
+        // centre (nearfield.py:408-409)
+        const double2 cc = a.cxy[s.aux];
+        order_shared(S, K, s.ux, s.uy, s.x - cc.x, s.y - cc.y, T.center_g[0], [&] { return cc; });
+        double w[4];
+        node_weights(t0, t1, w);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             // un-rotated weights: x table <-> H along y (nearfield.py:375-376)
-            wa[c] = NP == 1 ? w[c] * Hy_i[0] : w[c];
-            wb[c] = NP == 1 ? w[c] * Hx_i[0] : 0.0;
+            wa[c] = NP == 1 ? w[c] * s.Hy_i[0] : w[c];
+            wb[c] = NP == 1 ? w[c] * s.Hx_i[0] : 0.0;
         }
     }
     const int mine_off = which - grp * SK_TYPES;
@@ -623,7 +624,7 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
                 } else {
                     staged_wait<0>();
                 }
-                order_simple<NP, SK_TYPES>(acc, cur + mine_off, wa, wb, Hy_i, Hx_i, R, K, W, mine);
+                order_simple<NP, SK_TYPES>(acc, cur + mine_off, wa, wb, s.Hy_i, s.Hx_i, R, K, W, mine);
                 if (oc + 1 < FIXED3_SLOTS) walk_step(W, R);
                 __builtin_amdgcn_sched_barrier(0);   // (as below)
             }
@@ -638,7 +639,7 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
             } else {
                 staged_wait<0>();
             }
-            if ((a.center_present >> oc) & 1) order_simple<NP, SK_TYPES>(acc, cur + mine_off, wa, wb, Hy_i, Hx_i, R, K, W, mine);
+            if ((a.center_present >> oc) & 1) order_simple<NP, SK_TYPES>(acc, cur + mine_off, wa, wb, s.Hy_i, s.Hx_i, R, K, W, mine);
             walk_step(W, R);
             // (every LDS read of this order has come back - its values were used - before the
             // load that overwrites its buffer is issued, one iteration on)
@@ -647,145 +648,70 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
     }
     if (__ballot(cen && out_c)) {
         if (cen && out_c)
-            report_orders<false>(a, K.kvac2, K.kvac * ux, T.center_g[0], K.kvac * uy, a.center_n_slots, a.center_lo,
-                                 (unsigned)a.center_present, MAX_SLOTS, ux, uy, 0.0);
+            report_orders<false>(a, K.kvac2, K.kvac * s.ux, T.center_g[0], K.kvac * s.uy, a.center_n_slots, a.center_lo,
+                                 (unsigned)a.center_present, MAX_SLOTS, s.ux, s.uy, 0.0);
     }
     if (cen && K.premod) {
-        // input modulation of the far-field plan's stage 1, applied here for free (NfArgs)
-        const double2 t2 = K.premod[j];
-        const c2 e = {t2.x, t2.y};
+        const double2 t2 = K.premod[s.j];
 #pragma unroll
-        for (int m = 0; m < NP; ++m) {
-            AccS &q = acc[m];
-            const c2 Ex = cmulf({q.Exr, q.Exi}, e), Ey = cmulf({q.Eyr, q.Eyi}, e);
-            const c2 Hx = cmulf({q.Hxr, q.Hxi}, e), Hy = cmulf({q.Hyr, q.Hyi}, e);
-            q = {Ex.r, Ex.i, Ey.r, Ey.i, Hx.r, Hx.i, Hy.r, Hy.i};
-        }
+        for (int m = 0; m < NP; ++m) modulate(acc[m], {t2.x, t2.y});
     }
-
-        if (lens && !peri_any) {
+    if (s.lens && !s.peri_any) {
 #pragma unroll
-            for (int m = 0; m < NP; ++m)
-                store_fields_k(K, m, i, j, {acc[m].Exr, acc[m].Exi}, {acc[m].Eyr, acc[m].Eyi},
-                             {acc[m].Hxr, acc[m].Hxi}, {acc[m].Hyr, acc[m].Hyi});
-        }
-        return;
+        for (int m = 0; m < NP; ++m)
+            store_fields_k(K, m, s.i, s.j, {acc[m].Exr, acc[m].Exi}, {acc[m].Eyr, acc[m].Eyi},
+                           {acc[m].Hxr, acc[m].Hxi}, {acc[m].Hyr, acc[m].Hyi});
     }
-    if (!__ballot(peri)) return;   // (wave-uniform; only on the full-grid launch)
+}
 
-    // ================= periphery =================
-    // the ring's record (common.h ring_rec) and rotation, requested as soon as the geometry record is
-    // there.  State of ring samples only, deliberately without defaults.
-    double2 r0, r1, cs;
-    if (peri) {
-        const double2 *rr = K.ring_rec + (size_t)(idx - 1) * 2;
-        r0 = rr[0];
-        r1 = rr[1];
-        cs = K.rot_table[aux];
-    }
-    double uxp, uyp, t0, t1, xp, yp;
-    int cell = 0;
+// ================= periphery =================
+// Wave priority along a ring wave's life.  Among waves of equal priority a SIMD issues the OLDEST first, so a young
+// wave's short instruction runs between its three dependent loads (record -> ring record + rotation -> blocks) queue
+// behind the long vector streams of its elders' order loops.  A ring wave of a single-source listed launch therefore
+// starts at priority 3 and drops to 0 once its round's blocks are requested: near field 0.250 -> 0.243 ms at 4096^2,
+// 1.26 -> 1.20 at 8192^2 NA 0.94 (same-box A/B, profiles/r06_ab_runs.txt).  Also measured: high only until the ring
+// record is requested (-1.5 %), high again from the rotation back to the stores (as this), a constant priority per wave
+// slot (nothing).  ML_NF_PRIO = 0: off.
+#ifndef ML_NF_PRIO
+#define ML_NF_PRIO 1
+#endif
+#define ML_PRIO_AT(level) do { if (NP == 1 && LISTED && ML_NF_PRIO == 1) __builtin_amdgcn_s_setprio(level); } while (0)
+#ifndef ML_NF_KEEP_ROT
+#define ML_NF_KEEP_ROT 0
+#endif
+
+// ---- LDS-staged cell blocks.  The 64 samples of a patch fall into 2-4 rings and almost always one table cell: the
+// wave finds its distinct blocks and fetches each ONCE - block number from the lead lane -> scalar base, lane l loads
+// element l straight into LDS - and every lane reads its block from there (equal addresses broadcast: a wave-wide
+// 16-byte read costs 4 cycles instead of the 16 of a gather through the vector memory path).
+// A ROUND serves up to SK_SLOTS distinct blocks of ONE collection (one round unless a wave spans many rings or
+// straddles two collections).  The buffer holds RING_LDS complex: a round of n blocks of a collection with more orders
+// than fit at once goes through it in PASSES of `upp` order slots per block - all blocks, some orders - so that every
+// order is evaluated once per round however many blocks there are (staging all orders of as many blocks as fit would
+// evaluate the whole order list again for every further group of blocks: eleven orders, three rings = twenty-two for
+// eleven).
+// Collections of up to SIMPLE_NARROW_SLOTS orders - the three-order tables of SURVEY.md 8(d), the outer collections of
+// a real lens - always fit with six blocks at a FIXED pitch, in one pass: that case is compiled on its own (!WIDE:
+// constant LDS addresses, one staging load per block, the order loop unrolled over its four possible slots), so that it
+// pays nothing for the generality of the other.
+template <int NP, bool WIDE, bool FIXED3>
+struct RingRounds {
+    static constexpr int NSLOT = WIDE ? SK_SLOTS : SK_SLOTS_NARROW;
+    const Consts &K;
+    double2 *s_tab;
+    unsigned lane_off;
+    int blk;                      // the sample's (ring, table cell) block, by its first unit: what the lanes are matched by; -1: none
+    int small_pitch, small_cap;   // !WIDE: complex between staged blocks, blocks per round (see RING_LDS_NARROW)
     // the grating collection being worked on and its order list, in scalar registers: slot count,
     // lowest order, which slots its data holds (CollDesc)
-    int c_cur = -1, ns = 1, lo = 0;
-    unsigned present = 0;
-    bool several = false;   // the wave's ring samples belong to more than one collection (wave-uniform)
-    if (peri) {
-        ML_MARK(3, cs.x + r0.x + r1.x);   // (ring waves: the ring's record and rotation have arrived)
-        // phase-critical: local coordinates, exact operation order (nearfield.py:200-201)
-        xp = x * cs.x + y * cs.y - r0.x;
-        yp = -x * cs.y + y * cs.x;
-        rotate_dir(ux, uy, cs, uxp, uyp);
-    }
-    // what depends on the ring's grating COLLECTION (table shape and axes): one round per collection
-    // among the wave's ring samples - one, except on the few waves that straddle two collections -
-    // with the descriptor read by scalar loads from the kernel arguments
-    for (unsigned long long pm = __ballot(peri); pm;) {
-        const int c0 = __builtin_amdgcn_readlane(cell_type, __ffsll((long long)pm) - 1);
-        const bool mc = peri && cell_type == c0;
-        pm &= ~__ballot(mc);
-        const CollDesc &C = a.coll[c0];   // wave-uniform index: scalar loads
-        // (the whole descriptor in ONE round of scalar loads, pinned: fetched where it is used, the flag
-        // test, the axes and the order list each wait for a round trip of their own)
-        double ax0 = C.uni_ax[0], ax2 = C.uni_ax[2], ax3 = C.uni_ax[3], ax5 = C.uni_ax[5], lim0 = C.lim0, lim1 = C.lim1;
-        int flags = 1, n1m1 = C.n1 - 1, c_ns = FIXED3_SLOTS, c_lo = C.ox_lo, c_present = FIXED3_PRESENT;
-        if constexpr (FIXED3) {   // (uniform axes, three slots, all present: three scalars fewer)
-            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(n1m1), "+s"(c_lo));
-        } else {
-            flags = C.flags, c_ns = C.n_slots, c_present = C.present;
-            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(flags), "+s"(n1m1),
-                         "+s"(c_ns), "+s"(c_lo), "+s"(c_present));
-        }
-        if (c_cur < 0) {
-            c_cur = c0;
-            ns = c_ns;
-            lo = c_lo;
-            present = (unsigned)c_present;
-        } else {
-            several = true;
-        }
-        if (mc) {
-            int i0, i1;
-            if (flags & 1) {
-                const double uni[6] = {ax0, 0.0, ax2, ax3, 0.0, ax5};
-                locate_uniform(uni, lim0, lim1, uxp, uyp, i0, t0, i1, t1);
-            } else {
-                const TableDesc &T = a.tables[a.gc[idx - 1]];
-                locate_axis(T.axis0, T.n0, uxp, i0, t0);
-                locate_axis(T.axis1, T.n1, uyp, i1, t1);
-            }
-            // (i0 (n1 - 1) + i1) n_slots, in units of 16 complex; 24-bit products (full rate): tables of
-            // up to 4096 x 4096 cells
-            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(cell) : "v"(i0), "s"(n1m1), "v"(i1));
-            if constexpr (FIXED3)
-                cell *= FIXED3_SLOTS;   // (the same 24-bit product, exact; a shift-and-add)
-            else
-                asm("v_mul_u32_u24 %0, %1, %2" : "=v"(cell) : "v"(cell), "s"(c_ns));
-        }
-    }
-    // the sample's (ring, table cell) block, by its first unit: what the lanes of the wave are matched by
-    const int blk = peri ? (int)(__double_as_longlong(r1.y) & 0x7fffffffll) + cell : -1;
-    // the table-bound tests do not depend on the order: evaluated once; only a failure takes the
-    // reporting path (per order, in the reference's check order).  A sample inside the range
-    // EVERY ring table covers, on a ring whose period its table covers (bit 32 of the ring record),
-    // cannot fail; only the others read their table's bounds.  (In front of the block matching: the four
-    // bounds leave their scalar registers before the matching needs its own.)
-    bool outside = false;
-    if (peri) {
-        outside = (int)(uxp < K.b0) | (int)(uxp > K.b1) | (int)(uyp < K.b2) | (int)(uyp > K.b3) |
-                  (int)((__double_as_longlong(r1.y) >> 32) & 1);
-        if (outside) {
-            const double *b = a.tables[a.gc[idx - 1]].bounds;
-            const double period = r0.y;
-            outside = (int)(uxp < b[0]) | (int)(uxp > b[1]) | (int)(uyp < b[2]) | (int)(uyp > b[3]) |
-                      (int)(period < b[4]) | (int)(period > b[5]);
-        }
-    }
-    // ---- LDS-staged cell blocks.  The 64 samples of a patch fall into 2-4 rings and almost always
-    // one table cell: the wave finds its distinct blocks and fetches each ONCE - block number from
-    // the lead lane -> scalar base, lane l loads element l straight into LDS - and every lane reads
-    // its block from there (equal addresses broadcast: a wave-wide 16-byte read costs 4 cycles
-    // instead of the 16 of a gather through the vector memory path).
-    // A ROUND serves up to SK_SLOTS distinct blocks of ONE collection (one round unless a wave spans
-    // many rings or straddles two collections).  The buffer holds RING_LDS complex: a round of n blocks
-    // of a collection with more orders than fit at once goes through it in PASSES of `upp` order slots
-    // per block - all blocks, some orders - so that every order is evaluated once per round however
-    // many blocks there are (staging all orders of as many blocks as fit would evaluate the whole order
-    // list again for every further group of blocks: eleven orders, three rings = twenty-two for eleven).
-    // Collections of up to SMALL_SLOTS orders - the three-order tables of SURVEY.md 8(d), the outer collections
-    // of a real lens - always fit with six blocks at a FIXED pitch, in one pass: that case is compiled on
-    // its own (begin_round / finish_round with SMALL = true: constant LDS addresses, one staging load per
-    // block, the order loop unrolled over its four possible slots), so that it pays nothing for the
-    // generality of the other.
-    unsigned long long todo = __ballot(peri && cell_type == c_cur);      // lanes of the current collection not served yet
-    unsigned coll_done = 1u << (c_cur & 31);   // collections whose lanes have been (or are being) served: bit per dense number
-    int myslot, n_blocks, upp, pitch;
-    constexpr int NSLOT = WIDE ? SK_SLOTS : SK_SLOTS_NARROW;
-    int lead[NSLOT];
-    constexpr int SMALL_SLOTS = SIMPLE_NARROW_SLOTS;
-    // (narrow instantiation: see RING_LDS_NARROW; fixed-shape: three slots in every narrow collection)
-    const int small_pitch = FIXED3 ? narrow_pitch(FIXED3_SLOTS) : a.narrow_pitch, small_cap = FIXED3 ? SK_SLOTS_NARROW : a.narrow_cap;
-    auto match = [&]() {
+    int ns, lo;
+    unsigned present;
+    unsigned long long todo;      // lanes of the current collection not served yet
+    int lead[NSLOT], myslot, n_blocks, upp, pitch;
+    // (the state of a collection and a round deliberately without defaults)
+    __device__ __forceinline__ RingRounds(const Consts &K, double2 *s_tab) : K(K), s_tab(s_tab), lane_off(threadIdx.x * 16u) {}
+
+    __device__ __forceinline__ void match() {
         myslot = -1;
         n_blocks = 0;
         unsigned long long rest = todo;
@@ -804,9 +730,10 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
             }
         }
         todo = rest;
-    };
+    }
     // one pass' loads: order slots [s0, s0 + min(upp, ns - s0)) of every block of the round
-    auto stage = [&](int s0) {
+    __device__ __forceinline__ void stage(int s0) {
+        const int lane = threadIdx.x;
         const int len = min(upp, ns - s0) * UNIT;   // complex per block in this pass (wave-uniform)
 #pragma unroll
         for (int m = 0; m * 64 < UNIT * SIMPLE_MAX_SLOTS; ++m)
@@ -817,11 +744,12 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
                         stage_block<1>(K.ring_tab + (size_t)(unsigned)(lead[s] + s0) * UNIT + m * 64,
                                        s_tab + s * pitch + m * 64, lane_off);
             }
-    };
+    }
     // a round's blocks matched and its (first) loads issued
-    auto begin_round = [&](auto small) {
+    __device__ __forceinline__ void begin() {
         match();
-        if constexpr (decltype(small)::value) {
+        if constexpr (!WIDE) {
+            const int lane = threadIdx.x;
             if (lane < (FIXED3 ? FIXED3_SLOTS : ns) * UNIT) {
 #pragma unroll
                 for (int s = 0; s < NSLOT; ++s)
@@ -835,54 +763,10 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
             pitch = upp * UNIT + 1;   // (+1: blocks start in different 16-byte bank slots)
             stage(0);
         }
-    };
-    ML_MARK(9, blk);     // (ring waves: table cell located, block matching next)
-    begin_round(std::integral_constant<bool, !WIDE>());   // the first pass' blocks are on their way during the arithmetic below
-    ML_MARK(6, myslot);  // (ring waves: blocks matched, loads issued)
-    ML_PRIO_AT(2, 0);
-    OrderShared S;
-    double wa[4], wb[4], Hw_x[NP], Hw_y[NP];
-    if (peri) {
-        // E0 = order (0, 0)'s phasor (its argument in the reference's own operation order,
-        // nearfield.py:268-269,291 with ox = oy = 0) times the phase-critical propagation phasor
-        // from the grating centre (:337-341, exact argument), through ONE sincos: the large angle
-        // k |r| is reduced to [-pi/4, pi/4] + quadrants first and the small one added to the
-        // remainder.  X = exp(i G x').
-        S.kx0 = K.kvac * uxp;
-        S.ky = K.kvac * uyp;
-        double a0 = S.kx0 * xp + S.ky * yp;
-        int kq = 0;
-        if (!K.plane_wave) {
-            const double rcen = r0.x;
-            const double gx = rcen * cs.x - K.sx, gy = rcen * cs.y - K.sy;
-            const double air = sqrt_exact(gx * gx + gy * gy + K.z2);
-            double r;
-            reduce_pio2(K.kvac * air, r, kq);
-            a0 = r + a0;
-        }
-        sincos_cw_q(a0, kq, S.E0.i, S.E0.r);
-        S.G = r1.x;   // 2 pi / period
-        sincos_cw(S.G * xp, S.X.i, S.X.r);
-        S.ky2 = S.ky * S.ky;
-        // interpolation weights; one source: times the two polarisation weights
-        const double w[4] = {(1 - t0) * (1 - t1), (1 - t0) * t1, t0 * (1 - t1), t0 * t1};
-#pragma unroll
-        for (int m = 0; m < NP; ++m) {
-            Hw_y[m] = fma(Hx_i[m], cs.x, Hy_i[m] * cs.y);      // H along x' <-> y table
-            Hw_x[m] = fma(Hy_i[m], cs.x, -(Hx_i[m] * cs.y));   // H along y' <-> x table
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            wa[c] = NP == 1 ? w[c] * Hw_x[0] : w[c];
-            wb[c] = NP == 1 ? w[c] * Hw_y[0] : 0.0;
-        }
     }
-    AccS pr[NP];
-#pragma unroll
-    for (int m = 0; m < NP; ++m) pr[m] = {0, 0, 0, 0, 0, 0, 0, 0};
-    ML_MARK(4, wa[0] + pr[0].Exr);   // (ring waves: phasors and weights done)
     // the orders of a round's lanes
-    auto finish_round = [&](auto small) {
+    __device__ __forceinline__ void finish(AccS *pr, const OrderShared &S, const double *wa, const double *wb, const double *Hw_x,
+                                           const double *Hw_y) {
         // (nothing below changes from round to round, and the compiler would hoist the orders'
         // factors in front of the loop - sixty live registers - if it knew)
         OrderShared R = S;
@@ -903,13 +787,13 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
                 order_simple<NP, 1>(pr, b + sl * UNIT, wa, wb, Hw_x, Hw_y, R, K, W, mine);
                 __builtin_amdgcn_sched_barrier(0);   // (as below)
             }
-        } else if constexpr (decltype(small)::value) {
+        } else if constexpr (!WIDE) {
             int boff;   // the lane's block in the buffer (complex)
             asm("v_mul_u32_u24 %0, %1, %2" : "=v"(boff) : "v"(max(myslot, 0)), "s"(small_pitch));
             const double2 *b = s_tab + boff;
             staged_wait<0>();
 #pragma unroll
-            for (int sl = 0; sl < SMALL_SLOTS; ++sl) {
+            for (int sl = 0; sl < SIMPLE_NARROW_SLOTS; ++sl) {
                 if (sl < ns) {   // wave-uniform
                     if (sl) {
                         walk_step(W, R);
@@ -941,67 +825,206 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
                 stage(s0);             // (this pass' LDS reads are done: the sched_barrier above)
             }
         }
-    };
-    while (true) {   // rounds
-        finish_round(std::integral_constant<bool, !WIDE>());
-        if (!todo) {   // wave-uniform
+    }
+};
+
+template <int NP, bool LISTED, bool WIDE, bool FIXED3>
+__device__ __forceinline__ void synthesize_ring(const NfArgs &a, double2 *s_tab, int bx, int by) {
+    ML_PRIO_AT(3);
+    Consts K;
+    Sample<NP> s;
+    patch_prologue<NP, true, LISTED, WIDE, FIXED3>(a, K, bx, by, s);
+#ifdef ML_PHASE_TIMERS
+    struct StampOut {   // written on every way out of the patch
+        unsigned long long *st;
+        size_t wid;
+        __device__ ~StampOut() {
+            st[7] = __builtin_amdgcn_s_memtime();
+            __builtin_amdgcn_s_waitcnt(0);   // the stores have left the wave
+            st[8] = __builtin_amdgcn_s_memtime();
+            if (threadIdx.x == 0 && wid < PHASE_WAVES)
+                for (int k = 0; k < PHASE_SLOTS; ++k) g_phase[wid * PHASE_SLOTS + k] = st[k];
+        }
+    } stamp_out{s.stamp, (size_t)by * K.patches_x + bx};
+#endif
+    const bool peri = s.peri;
+    if (!__ballot(peri)) return;   // (wave-uniform; only on the full-grid launch)
+
+    // ---- the ring's record (common.h ring_rec) and rotation, requested as soon as the geometry record is
+    // there, and the local frame.  State of ring samples only, deliberately without defaults.
+    double2 r0, r1, cs;
+    if (peri) {
+        const double2 *rr = K.ring_rec + (size_t)(s.idx - 1) * 2;
+        r0 = rr[0];
+        r1 = rr[1];
+        cs = K.rot_table[s.aux];
+    }
+    double uxp, uyp, t0, t1, xp, yp;
+    int cell = 0;
+    int c_cur = -1;   // the collection being worked on (RingRounds: its order list)
+    bool several = false;   // the wave's ring samples belong to more than one collection (wave-uniform)
+    RingRounds<NP, WIDE, FIXED3> rounds(K, s_tab);
+    rounds.ns = 1, rounds.lo = 0, rounds.present = 0;
+    if (peri) {
+        ML_MARK(3, cs.x + r0.x + r1.x);   // (ring waves: the ring's record and rotation have arrived)
+        // phase-critical: local coordinates, exact operation order (nearfield.py:200-201)
+        xp = s.x * cs.x + s.y * cs.y - r0.x;
+        yp = -s.x * cs.y + s.y * cs.x;
+        rotate_dir(s.ux, s.uy, cs, uxp, uyp);
+    }
+    // ---- what depends on the ring's grating COLLECTION (table shape and axes): one round per collection among the
+    // wave's ring samples - one, except on the few waves that straddle two collections - with the descriptor read by
+    // scalar loads from the kernel arguments; it locates the sample's table cell
+    for (unsigned long long pm = __ballot(peri); pm;) {
+        const int c0 = __builtin_amdgcn_readlane(s.cell_type, __ffsll((long long)pm) - 1);
+        const bool mc = peri && s.cell_type == c0;
+        pm &= ~__ballot(mc);
+        const CollDesc &C = a.coll[c0];   // wave-uniform index: scalar loads
+        // (the whole descriptor in ONE round of scalar loads, pinned: fetched where it is used, the flag
+        // test, the axes and the order list each wait for a round trip of their own)
+        double ax0 = C.uni_ax[0], ax2 = C.uni_ax[2], ax3 = C.uni_ax[3], ax5 = C.uni_ax[5], lim0 = C.lim0, lim1 = C.lim1;
+        int flags = 1, n1m1 = C.n1 - 1, c_ns = FIXED3_SLOTS, c_lo = C.ox_lo, c_present = FIXED3_PRESENT;
+        if constexpr (FIXED3) {   // (uniform axes, three slots, all present: three scalars fewer)
+            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(n1m1), "+s"(c_lo));
+        } else {
+            flags = C.flags, c_ns = C.n_slots, c_present = C.present;
+            asm volatile("" : "+s"(ax0), "+s"(ax2), "+s"(ax3), "+s"(ax5), "+s"(lim0), "+s"(lim1), "+s"(flags), "+s"(n1m1),
+                         "+s"(c_ns), "+s"(c_lo), "+s"(c_present));
+        }
+        if (c_cur < 0) {
+            c_cur = c0;
+            rounds.ns = c_ns;
+            rounds.lo = c_lo;
+            rounds.present = (unsigned)c_present;
+        } else {
+            several = true;
+        }
+        if (mc) {
+            int i0, i1;
+            if (flags & 1) {
+                const double uni[6] = {ax0, 0.0, ax2, ax3, 0.0, ax5};
+                locate_uniform(uni, lim0, lim1, uxp, uyp, i0, t0, i1, t1);
+            } else {
+                const TableDesc &T = a.tables[a.gc[s.idx - 1]];
+                locate_axis(T.axis0, T.n0, uxp, i0, t0);
+                locate_axis(T.axis1, T.n1, uyp, i1, t1);
+            }
+            // (i0 (n1 - 1) + i1) n_slots, in units of 16 complex; 24-bit products (full rate): tables of
+            // up to 4096 x 4096 cells
+            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(cell) : "v"(i0), "s"(n1m1), "v"(i1));
+            if constexpr (FIXED3)
+                cell *= FIXED3_SLOTS;   // (the same 24-bit product, exact; a shift-and-add)
+            else
+                asm("v_mul_u32_u24 %0, %1, %2" : "=v"(cell) : "v"(cell), "s"(c_ns));
+        }
+    }
+    rounds.blk = peri ? (int)(__double_as_longlong(r1.y) & 0x7fffffffll) + cell : -1;
+    // ---- the table-bound tests do not depend on the order: evaluated once; only a failure takes the reporting path
+    // (per order, in the reference's check order).  A sample inside the range EVERY ring table covers, on a ring whose
+    // period its table covers (bit 32 of the ring record), cannot fail; only the others read their table's bounds.  (In
+    // front of the block matching: the four bounds leave their scalar registers before the matching needs its own.)
+    bool outside = false;
+    if (peri) {
+        outside = (int)(uxp < K.b0) | (int)(uxp > K.b1) | (int)(uyp < K.b2) | (int)(uyp > K.b3) |
+                  (int)((__double_as_longlong(r1.y) >> 32) & 1);
+        if (outside) {
+            const double *b = a.tables[a.gc[s.idx - 1]].bounds;
+            const double period = r0.y;
+            outside = (int)(uxp < b[0]) | (int)(uxp > b[1]) | (int)(uyp < b[2]) | (int)(uyp > b[3]) |
+                      (int)(period < b[4]) | (int)(period > b[5]);
+        }
+    }
+    // ---- block matching and staging (RingRounds)
+    rounds.todo = __ballot(peri && s.cell_type == c_cur);
+    unsigned coll_done = 1u << (c_cur & 31);   // collections whose lanes have been (or are being) served: bit per dense number
+    // (narrow instantiation: see RING_LDS_NARROW; fixed-shape: three slots in every narrow collection)
+    rounds.small_pitch = FIXED3 ? narrow_pitch(FIXED3_SLOTS) : a.narrow_pitch;
+    rounds.small_cap = FIXED3 ? SK_SLOTS_NARROW : a.narrow_cap;
+    ML_MARK(9, rounds.blk);     // (ring waves: table cell located, block matching next)
+    rounds.begin();   // the first pass' blocks are on their way during the arithmetic below
+    ML_MARK(6, rounds.myslot);  // (ring waves: blocks matched, loads issued)
+    ML_PRIO_AT(0);
+    // ---- phasors (order_shared, about the grating centre r_center (cos, sin)) and weights
+    OrderShared S;
+    double wa[4], wb[4], Hw_x[NP], Hw_y[NP];
+    if (peri) {
+        order_shared(S, K, uxp, uyp, xp, yp, r1.x, [&] { return make_double2(r0.x * cs.x, r0.x * cs.y); });
+        // interpolation weights; one source: times the two polarisation weights
+        double w[4];
+        node_weights(t0, t1, w);
+#pragma unroll
+        for (int m = 0; m < NP; ++m) {
+            Hw_y[m] = fma(s.Hx_i[m], cs.x, s.Hy_i[m] * cs.y);      // H along x' <-> y table
+            Hw_x[m] = fma(s.Hy_i[m], cs.x, -(s.Hx_i[m] * cs.y));   // H along y' <-> x table
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wa[c] = NP == 1 ? w[c] * Hw_x[0] : w[c];
+            wb[c] = NP == 1 ? w[c] * Hw_y[0] : 0.0;
+        }
+    }
+    AccS pr[NP];
+#pragma unroll
+    for (int m = 0; m < NP; ++m) pr[m] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ML_MARK(4, wa[0] + pr[0].Exr);   // (ring waves: phasors and weights done)
+    // ---- the rounds
+    while (true) {
+        rounds.finish(pr, S, wa, wb, Hw_x, Hw_y);
+        if (!rounds.todo) {   // wave-uniform
             if (!several) break;
-            const unsigned long long later = __ballot(peri && !((coll_done >> cell_type) & 1u));
+            const unsigned long long later = __ballot(peri && !((coll_done >> s.cell_type) & 1u));
             if (!later) break;
             // the next collection among the wave's lanes: its list by scalar loads
-            c_cur = __builtin_amdgcn_readlane(cell_type, __ffsll((long long)later) - 1);
+            c_cur = __builtin_amdgcn_readlane(s.cell_type, __ffsll((long long)later) - 1);
             coll_done |= 1u << c_cur;
-            if (!FIXED3) ns = a.coll[c_cur].n_slots;   // (fixed-shape: three slots, all present, in every collection)
-            lo = a.coll[c_cur].ox_lo;
-            if (!FIXED3) present = (unsigned)a.coll[c_cur].present;
-            todo = __ballot(peri && cell_type == c_cur);
+            if (!FIXED3) rounds.ns = a.coll[c_cur].n_slots;   // (fixed-shape: three slots, all present, in every collection)
+            rounds.lo = a.coll[c_cur].ox_lo;
+            if (!FIXED3) rounds.present = (unsigned)a.coll[c_cur].present;
+            rounds.todo = __ballot(peri && s.cell_type == c_cur);
         }
         __builtin_amdgcn_sched_barrier(0);   // (this round's LDS reads are done before the next round's loads go out)
-        begin_round(std::integral_constant<bool, !WIDE>());
+        rounds.begin();
     }
     ML_MARK(5, pr[0].Exr + pr[0].Hyi);   // orders done
+    // ---- rare path, the bound reports: everything it reports is worked out again (nothing kept live for it)
     if (__ballot(outside)) {
         if (outside) {
-            // rare path: everything it reports is worked out again (nothing kept live for it)
-            const int2v ix = reinterpret_cast<const int2v *>(K.geo_ix + ((size_t)by * K.patches_x + bx) * 64)[lane];
+            const int2v ix = reinterpret_cast<const int2v *>(K.geo_ix + ((size_t)by * K.patches_x + bx) * 64)[threadIdx.x];
             const int ring = (ix.x & ((1 << REC_TYPE_SHIFT) - 1)) - 1;
             const CollDesc *C = a.coll + (ix.x >> REC_TYPE_SHIFT);   // (per-lane index: ordinary loads from the kernel arguments)
             double vx = 0.0, vy = 0.0, vz, vinv, vxp, vyp;
-            if (!K.plane_wave) incidence(K, a.x_pts[i], a.y_pts[j], vx, vy, vz, vinv);
+            if (!K.plane_wave) incidence(K, a.x_pts[s.i], a.y_pts[s.j], vx, vy, vz, vinv);
             rotate_dir(vx, vy, K.rot_table[ix.y], vxp, vyp);
             const double2 *rr = K.ring_rec + (size_t)ring * 2;
             report_orders<true>(a, K.kvac2, K.kvac * vxp, rr[1].x, K.kvac * vyp, C->n_slots, C->ox_lo, (unsigned)C->present,
                                 a.gc[ring], vxp, vyp, rr[0].y);
         }
     }
+    // ---- rotation back and store
     if (peri) {
         // (the rotation is needed again only here and is re-read, an L1 hit: four registers that are not
         // live across the order loop, which is what fits five waves per SIMD.  Parking it in LDS instead
         // measured +1 %, keeping it in registers at four waves per SIMD +6 % (ML_NF_KEEP_ROT = 1))
         double2 cs2 = cs;
-        if (!(ML_NF_KEEP_ROT && NP == 1)) cs2 = K.rot_table[aux];
+        if (!(ML_NF_KEEP_ROT && NP == 1)) cs2 = K.rot_table[s.aux];
         const double cosr = cs2.x, sinr = cs2.y;
         // (the propagation phasor already rides in every order's phasor; what is left is the
         // far-field plan's input modulation, if the plan has one: re-read here, an L2 hit)
         c2 e = {1.0, 0.0};
         if (K.premod) {
-            const double2 t2 = K.premod[j];
+            const double2 t2 = K.premod[s.j];
             e = {t2.x, t2.y};
         }
 #pragma unroll
         for (int m = 0; m < NP; ++m) {
             AccS q = pr[m];
-            if (K.premod) {
-                const c2 Ex = cmulf({q.Exr, q.Exi}, e), Ey = cmulf({q.Eyr, q.Eyi}, e);
-                const c2 Hx = cmulf({q.Hxr, q.Hxi}, e), Hy = cmulf({q.Hyr, q.Hyi}, e);
-                q = {Ex.r, Ex.i, Ey.r, Ey.i, Hx.r, Hx.i, Hy.r, Hy.i};
-            }
+            if (K.premod) modulate(q, e);
             // back to the lab frame (nearfield.py:351-354)
             const c2 Ex = {fma(q.Exr, cosr, -(q.Eyr * sinr)), fma(q.Exi, cosr, -(q.Eyi * sinr))};
             const c2 Ey = {fma(q.Exr, sinr, q.Eyr * cosr), fma(q.Exi, sinr, q.Eyi * cosr)};
             const c2 Hx = {fma(q.Hxr, cosr, -(q.Hyr * sinr)), fma(q.Hxi, cosr, -(q.Hyi * sinr))};
             const c2 Hy = {fma(q.Hxr, sinr, q.Hyr * cosr), fma(q.Hxi, sinr, q.Hyi * cosr)};
-            store_fields_k(K, m, i, j, Ex, Ey, Hx, Hy);
+            store_fields_k(K, m, s.i, s.j, Ex, Ey, Hx, Hy);
         }
     }
 }
@@ -1012,9 +1035,10 @@ __device__ __forceinline__ void synthesize_patch(const NfArgs &a, double2 *s_tab
 
 // LISTED: the launch is a list of patches (`list`, a leading kernel argument of its own so that the
 // pointer can arrive in scalar registers with the wave - kernarg preload, see the Makefile - and the
-// list entry is the FIRST load of the wave, not the third of a dependent chain); else the whole grid
+// list entry is the FIRST load of the wave, not the third of a dependent chain); else the whole grid.
+// (The list-entry preamble stands in both kernels: as a shared function it cost the two-source centre kernel a scalar register.)
 // WIDE: the instantiation for the ring collections of more than SIMPLE_NARROW_SLOTS = 4 orders (NfArgs::wide_mask)
-// FIXED3: the fixed-shape form (synthesize_patch) - of <1, true, false> and of the centre kernel's <1, true> only
+// FIXED3: the fixed-shape form - of <1, true, false> and of the centre kernel's <1, true> only
 template <int NP, bool LISTED, bool WIDE, bool FIXED3 = false>
 __global__ __launch_bounds__(64, NP == 1 ? ML_NF_RING_MINW : 3) void nearfield_ring_kernel(const int2 *list, const NfArgs a) {
     __shared__ double2 s_tab[WIDE ? RING_LDS : RING_LDS_NARROW];
@@ -1027,7 +1051,7 @@ __global__ __launch_bounds__(64, NP == 1 ? ML_NF_RING_MINW : 3) void nearfield_r
         bx = pb.x;
         by = pb.y;
     }
-    synthesize_patch<NP, PART_RING, LISTED, WIDE, FIXED3>(a, s_tab, s_tab, bx, by);
+    synthesize_ring<NP, LISTED, WIDE, FIXED3>(a, s_tab, bx, by);
 }
 
 template <int NP, bool LISTED, bool FIXED3 = false>
@@ -1036,13 +1060,12 @@ __global__ __launch_bounds__(64, 3) void nearfield_centre_kernel(const int2 *lis
     __shared__ double2 s_tab[CB], s_tab1[CB];
     int bx = blockIdx.x, by = blockIdx.y;
     if (LISTED) {
-        // (first pass: the launch covers every patch number, the list's length is on the device)
         if (!FIXED3 && a.list_count && (int)blockIdx.x >= *a.list_count) return;
         const int2 pb = list[blockIdx.x];
         bx = pb.x;
         by = pb.y;
     }
-    synthesize_patch<NP, PART_CENTRE, LISTED, false, FIXED3>(a, s_tab, s_tab1, bx, by);
+    synthesize_centre<NP, LISTED, FIXED3>(a, s_tab, s_tab1, bx, by);
 }
 
 #ifdef ML_PHASE_TIMERS
@@ -1090,7 +1113,7 @@ static int launch_parts(ml_ctx *ctx, const NfArgs &a) {
         if (a.general_mask || a.centre_general) {
             c.list_count = a.active_count;
             c.use_active = 1;
-            ML_TRY(nearfield_general_listed_launch(ctx, c, (int)(full.x * full.y)));
+            ML_TRY(nearfield_general_launch(ctx, c, dim3(full.x * full.y)));
         }
     } else {
         // (resident workgroups walking the lists with the launch's stride - as many as the chip holds at once, to
@@ -1101,39 +1124,22 @@ static int launch_parts(ml_ctx *ctx, const NfArgs &a) {
         // noise, 5120 resident workgroups 0.265-0.27 against 0.25.  The empty wave slots are not what the kernel waits for.)
         // three-order tables lit by one dipole: the fixed-shape kernels (NfArgs::fixed3, from lens_pack.h fixed3_takes;
         // this branch is the listed steady-state launch that predicate asks for)
-        const bool listed = a.use_active && !a.first_pass;
-        bool ring_fixed = false, centre_fixed = false;
-        if constexpr (NP == 1) {
-            ring_fixed = listed && (a.fixed3 & 1) != 0;
-            centre_fixed = listed && (a.fixed3 & 2) != 0;
-        }
-        if (a.n_active[1] > 0) {
-            if constexpr (NP == 1) {
-                if (ring_fixed)
-                    hipLaunchKernelGGL((nearfield_ring_kernel<1, true, false, true>), dim3(a.n_active[1]), dim3(64), 0, ctx->stream,
-                                       a.active_list + (size_t)1 * a.list_stride, a);
-            }
-            if (!ring_fixed)
-                hipLaunchKernelGGL((nearfield_ring_kernel<NP, true, false>), dim3(a.n_active[1]), dim3(64), 0, ctx->stream,
-                                   a.active_list + (size_t)1 * a.list_stride, a);
-        }
+        // (the fixed-shape kernels exist for one source only: for NP > 1 the flag is false and the name unused)
+        const bool listed = NP == 1 && a.use_active && !a.first_pass;
+        const bool ring_fixed = listed && (a.fixed3 & 1) != 0, centre_fixed = listed && (a.fixed3 & 2) != 0;
+        if (a.n_active[1] > 0)
+            hipLaunchKernelGGL((ring_fixed ? nearfield_ring_kernel<1, true, false, true> : nearfield_ring_kernel<NP, true, false>),
+                               dim3(a.n_active[1]), dim3(64), 0, ctx->stream, a.active_list + (size_t)1 * a.list_stride, a);
         if (a.n_active[3] > 0)
             hipLaunchKernelGGL((nearfield_ring_kernel<NP, true, true>), dim3(a.n_active[3]), dim3(64), 0, ctx->stream,
                                a.active_list + (size_t)3 * a.list_stride, a);
-        if (a.n_active[2] > 0) {
-            if constexpr (NP == 1) {
-                if (centre_fixed)
-                    hipLaunchKernelGGL((nearfield_centre_kernel<1, true, true>), dim3(a.n_active[2]), dim3(64), 0, ctx->stream,
-                                       a.active_list + (size_t)2 * a.list_stride, a);
-            }
-            if (!centre_fixed)
-                hipLaunchKernelGGL((nearfield_centre_kernel<NP, true>), dim3(a.n_active[2]), dim3(64), 0, ctx->stream,
-                                   a.active_list + (size_t)2 * a.list_stride, a);
-        }
+        if (a.n_active[2] > 0)
+            hipLaunchKernelGGL((centre_fixed ? nearfield_centre_kernel<1, true, true> : nearfield_centre_kernel<NP, true>),
+                               dim3(a.n_active[2]), dim3(64), 0, ctx->stream, a.active_list + (size_t)2 * a.list_stride, a);
         ctx->out.ring_form = a.n_active[1] > 0 ? (ring_fixed ? 2 : 1) : 0;
         ctx->out.centre_form = a.n_active[2] > 0 ? (centre_fixed ? 2 : 1) : 0;
         if ((a.general_mask || a.centre_general) && a.n_active[0] > 0)
-            ML_TRY(nearfield_general_listed_launch(ctx, a, a.n_active[0]));
+            ML_TRY(nearfield_general_launch(ctx, a, dim3(a.n_active[0])));
     }
     ML_HIP(hipGetLastError());
     return ML_OK;

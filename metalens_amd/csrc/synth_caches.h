@@ -43,7 +43,7 @@ struct SynthCaches {
 
     Stamp<2> row_extents;   // SynthGrid::row_first (nearfield.hip row_extent_kernel)
     Stamp<2> trim;          // SynthGrid::trim_rows (farfield.hip trim_rows_of)
-    Stamp<5> geometry;      // the geometry records and the four patch lists (nearfield_fast.hip)
+    Stamp<5> geometry;      // the geometry records and the four patch lists (nearfield_geometry.hip)
     Stamp<6> zeros;         // the zeros outside the lens in the resident field sets
     Stamp<2> answers;       // the (grid, layout) the tie answers were given for; nothing while there are none
     // the lengths of the four patch lists on the host: not known, on their way (queued behind the scans that make

@@ -1,4 +1,4 @@
-// The staging rules of the synthesis kernels (nearfield_simple.hip, nearfield_fast.hip): how many distinct
+// The staging rules of the synthesis kernels (nearfield_simple.hip, nearfield_general.hip): how many distinct
 // (ring, table cell) blocks a wave takes through LDS per ROUND, and in how many PASSES of order slots the wide
 // ring instantiation takes a round's blocks through its buffer.  Constants and pure functions, so that the
 // kernels, the launch code (nearfield.hip fill_nf_args) and the host - tools/synth_staging.cpp prints them, the
@@ -40,7 +40,7 @@ static_assert(slots_per_pass(SK_SLOTS) >= 1, "block buffer too small");
 constexpr int SK_TYPES = 20;                    // centre: cell types per staged block (the reference's default K, lens_center.py:28)
 static_assert(SK_TYPES == CENTER_GROUP, "the centre table's cell blocks hold groups of SK_TYPES types");
 
-// the general kernel (nearfield_fast.hip nearfield_field_kernel)
+// the general kernel (nearfield_general.hip nearfield_field_kernel)
 constexpr int NF_SLOTS = 6;                  // distinct (ring, cell) blocks staged per round
 constexpr int NF_CHUNK = 4;                  // orders per staging pass (64 lanes = 4 x 4 x 4)
 

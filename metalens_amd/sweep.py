@@ -8,7 +8,7 @@ i.e. many runs of near field -> far field whose POWERS are added, and whose effi
 What a sweep shares:
 
 * tables, layout, far-field plan and the per-sample geometry records (ring, sector, rotated
-  coordinates, nearest cell: csrc/nearfield_fast.hip) - they depend on grid and lens only;
+  coordinates, nearest cell: csrc/nearfield_geometry.hip) - they depend on grid and lens only;
 * within a group of sources at ONE position that differ in polarisation (the x, y, z triple): the
   whole per-sample evaluation except the two weights the incident H enters with - such a group
   is ONE synthesis pass (``ml_nearfield_batch_async``) that leaves one resident field set per

@@ -29,7 +29,7 @@ import geometry_ref as ref
 WL = 580e-9
 PITCH = 320e-9                     # of small's hexagonal cells
 OFFS = (0.0, 1e-16, 3e-16, 1e-15, 1e-14, 1e-12, 0.99e-9, 1.01e-9, 1e-6)   # |off| in sectors; every one but 0 with both signs
-TIE_WINDOW = 1e-9                  # nearfield_fast.hip sector_of_fast
+TIE_WINDOW = 1e-9                  # nearfield_geometry.hip sector_of_fast
 ODD_NUMS = {1: 45, 3: 7001, 5: 36, 7: 44}
 MP_POINT_CAP, CASE_POINT_CAP = 40000, 1 << 18
 

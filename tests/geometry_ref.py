@@ -1,4 +1,4 @@
-"""The exact statements of the three discrete decisions of the synthesis (csrc/nearfield_fast.hip sample_geometry), in
+"""The exact statements of the three discrete decisions of the synthesis (csrc/nearfield_geometry.hip sample_geometry), in
 NumPy, mpmath and scipy, for tests/geometry_cases.py.  Everything here is a statement of integers: nothing has a tolerance.
 
 ring    np.searchsorted(B, np.sqrt(x*x + y*y), 'left'), the reference's expression (nearfield.py:125-128).  The library is

@@ -1,7 +1,7 @@
 """The cases of the synthesis kernels' staging rounds and passes that the suite runs, in one table, and the census
 that says which of those paths an input reaches.
 
-The ring kernels of csrc/nearfield_simple.hip and the general kernel of csrc/nearfield_fast.hip serve the 64 samples
+The ring kernels of csrc/nearfield_simple.hip and the general kernel of csrc/nearfield_general.hip serve the 64 samples
 of an 8 x 8 patch in ROUNDS of up to a capacity of distinct (ring, table cell) blocks staged through LDS, the wide
 ring instantiation a round in PASSES of as many order slots as fit its buffer (csrc/synth_staging.h).  Which of
 these paths run depends on the data: how many rings and table cells a patch spans.  The census counts, on the host,
@@ -264,7 +264,7 @@ def census(args, rules):
                      <= kvac ** 2 for o, oy in order_lists[c]]
         grid = gc_list[c].interpolators[(wl_nm, order_lists[c][0], 'x', 'ampfy')].grid
         if colls[c].kernel == 'general':
-            # (the general kernel shares blocks among lanes for axes of up to 64 nodes only - nearfield_fast.hip
+            # (the general kernel shares blocks among lanes for axes of up to 64 nodes only - nearfield_general.hip
             # `key` - so the table keeps its general collections at or below that)
             assert len(grid[0]) <= 64 and len(grid[1]) <= 64, 'general collection %d: axes beyond 64 nodes' % c
         i0[here] = _locate(grid[0], dec['uxp'][here])

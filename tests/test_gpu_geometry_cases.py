@@ -1,4 +1,4 @@
-"""The three discrete decisions of the synthesis on the GPU - ring, sector, nearest centre cell (csrc/nearfield_fast.hip
+"""The three discrete decisions of the synthesis on the GPU - ring, sector, nearest centre cell (csrc/nearfield_geometry.hip
 sample_geometry) - one point per lane through ml_geometry_probe, against the exact statements of tests/geometry_ref.py at
 EVERY point of the case table (tests/geometry_cases.py).  Needs an MI355X.
 

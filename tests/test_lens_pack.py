@@ -388,7 +388,7 @@ def test_small_tables(tool):
 
 # ---- ring search ---------------------------------------------------------------------------
 def boundaries_below(B, got, r):
-    """nearfield_dev.h boundaries_below_fast: the bucket record where it settles the search, else the walk from the
+    """nearfield_geometry.hip boundaries_below_fast: the bucket record where it settles the search, else the walk from the
     uniform table's entry"""
     n_rings = B.size - 1
     if r > got['r_outer'][0]:

@@ -117,8 +117,8 @@ def test_the_source_uses_the_header():
 
 
 def propagate_direct_h_in_makefile():
-    rule = [line for line in _text(os.path.join(CSRC, 'Makefile')).splitlines() if line.startswith('$(BUILD)/%.o:')]
-    return len(rule) == 1 and ' propagate_direct.h ' in rule[0]
+    import makefile_deps
+    return makefile_deps.header_is_prerequisite('propagate_direct.h', 'propagate')
 
 
 def test_table_and_inventory_agree():

@@ -1,5 +1,5 @@
 // Prints the staging rules of the synthesis kernels (metalens_amd/csrc/synth_staging.h): what the ring kernels of
-// nearfield_simple.hip and the general kernel of nearfield_fast.hip are compiled with, and what nearfield.hip
+// nearfield_simple.hip and the general kernel of nearfield_general.hip are compiled with, and what nearfield.hip
 // fill_nf_args hands the narrow ring instantiation.  Runs without a GPU.
 //
 //   synth_staging
