@@ -600,6 +600,46 @@ int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, doub
 #define ML_OTF_FREQ_MAX 64
 int ml_propagate_otf(ml_ctx *ctx, int source, int mx, int my, int planes, const double *u, int nu, const double *v,
                      int nv, double *otf);
+/* The overlap of the resident image with separable modes, contracted on the GPU (csrc/propagate_modes.hip): per plane and
+ * per component F (0: Ex, 1: Ey, 2: Hx, 3: Hy) of one member of the last pass
+ *     O_F[p][a][b] = sum_i sum_j conj(mode_x[a][i]) conj(mode_y[b][j]) F(p, i, j),   a < nu, b < nv
+ * - the amplitude with which the field enters the mode psi_ab(x, y) = mode_x[a](x) mode_y[b](y): a fibre mode, a Gaussian
+ * beam, a Hermite-Gauss order -, without the image crossing PCIe.  The sums of ml_propagate_accumulate carry no phase and
+ * have no overlap.  Three entries, on the pattern of ml_farfield_beam / ml_farfield_beams, so that a sweep queues one call per
+ * source and reads every slot at its end:
+ * ml_propagate_modes_plan: checks, conjugates the tables on the host (a sign: exact), uploads them index-major (Tx[mx][nu],
+ * Ty[my][nv]) and reserves the row sums and n_slots output slots of planes 4 nu nv complex each, all of them zeros.
+ *   mx, my, planes   : as for ml_propagate_focus; mx my planes must be the plan's targets
+ *   mode_x, nu       : HOST, complex128 [nu][mx] as (re, im) pairs, finite; 1 <= nu <= ML_MODES_MAX; likewise mode_y [nv][my].
+ *                      In any order, repeats allowed; the arrays are not read after the call returns
+ *   n_slots          : 1 <= n_slots <= ML_MAX_SWEEP_SLOTS
+ * The tables belong to the active propagation plan: every ml_propagate_plan* entry that plans drops them; a pass
+ * (ml_propagate, ml_propagate_sets) does not.  Caps: mx nu + my nv <= 2^24 table entries, planes mx nv <= 2^25 row sums per
+ * component, n_slots planes 4 nu nv <= 2^24 output entries, planes <= 65535.  Synchronises.
+ * ml_propagate_modes_queue: member source >= 0 of the last pass into slot `slot`: two launches, no synchronisation, no
+ * download.  It writes its own slot and nothing else; for a plan with want_h == 0 the blocks of Hx and Hy are zeros.
+ * ml_propagate_modes_fetch: out = HOST, complex128 [n_slots][planes][4][nu][nv] as (re, im) pairs, the slots first_slot ...
+ * first_slot + n_slots - 1; a slot never written since the plan reads zeros.  Synchronises.
+ * fp64, no atomics: rows, then columns, each in segments of 32 indices added in ascending order; a complex product x t is
+ * re = x.r t.r - x.i t.i, im = x.r t.i + x.i t.r, every operation rounded on its own.  The order depends on (mx, my) alone,
+ * so an entry is repeatable bit for bit, plane p of a stack has the bits of that plane planned alone, and an entry does
+ * not depend on nu, nv, the other modes, their order, the slot or the member index; a mode that is 1 at one index and 0
+ * elsewhere on either axis returns the field at that target as it is stored (csrc/propagate_modes.h).
+ * ML_EINVAL with the numbers in ml_last_error for mx my planes != targets, more than 65535 planes, nu or nv outside
+ * [1, 64], a NULL pointer, a table entry that is not finite (axis, mode, index and value), n_slots outside [1,
+ * ML_MAX_SWEEP_SLOTS], a total above the caps, a member the last pass does not hold, source < 0, a slot out of the planned
+ * range, a context of more than one rank.  ML_ESTATE with the wording of ml_propagate_download if no pass has run on the
+ * active plan (queue), with "ml_propagate_modes_plan has not run on the active propagation plan" if no tables are planned
+ * on it (queue, fetch).  A refused call leaves result, sums, focus records, transfer function, the slots and the plan as they
+ * were; so does an accepted one, apart from its own slot (the plan entry: the tables and all slots).  The one exception: a plan call that fails with ML_ENOMEM
+ * or a HIP error while a buffer grows or the tables are uploaded has given up the earlier tables and slots (queue and fetch
+ * then answer ML_ESTATE); with buffers that are large enough already nothing is given up before the upload.  Replaces no reference
+ * lines; the aperture's counterparts are ml_fields_zones and ml_fields_zernike.  */
+#define ML_MODES_MAX 64
+int ml_propagate_modes_plan(ml_ctx *ctx, int mx, int my, int planes, const double *mode_x, int nu, const double *mode_y,
+                            int nv, int n_slots);
+int ml_propagate_modes_queue(ml_ctx *ctx, int source, int slot);
+int ml_propagate_modes_fetch(ml_ctx *ctx, int first_slot, int n_slots, double *out);
 /* Per-zone power and wavefront overlap of the resident near field, reduced on the GPU (csrc/fields_zones.hip): for every
  * zone of a list of ring edges about a centre - with the edges of a lens layout, zone 0 is the centre and zone z ring
  * z - 1 - and for n_sets field sets in one pass the members, the sums of Sz, |Ex|^2, |Ey|^2 and the overlaps sum Ex conj(w),

@@ -54,6 +54,7 @@ SYMBOLS = (
     'ml_propagate_plan_grid_stack', 'ml_propagate_plan_planes', 'ml_propagate_focus',
     'ml_propagate_otf', 'ml_nearfield_synth_info', 'ml_farfield_beam', 'ml_farfield_beams',
     'ml_fields_zones', 'ml_fields_zernike', 'ml_geometry_probe', 'ml_fields_pupil_plan', 'ml_fields_pupil_apply',
+    'ml_propagate_modes_plan', 'ml_propagate_modes_queue', 'ml_propagate_modes_fetch',
 )
 
 
@@ -190,6 +191,10 @@ def load():
         lib.ml_propagate_focus.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, _dp, _dp, c_int, _dp, c_int]
     if hasattr(lib, 'ml_propagate_otf'):
         lib.ml_propagate_otf.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp]
+    if hasattr(lib, 'ml_propagate_modes_plan'):
+        lib.ml_propagate_modes_plan.argtypes = [c_void_p, c_int, c_int, c_int, _dp, c_int, _dp, c_int, c_int]
+        lib.ml_propagate_modes_queue.argtypes = [c_void_p, c_int, c_int]
+        lib.ml_propagate_modes_fetch.argtypes = [c_void_p, c_int, c_int, _dp]
     if hasattr(lib, 'ml_farfield_beam'):
         lib.ml_farfield_beam.argtypes = [c_void_p, c_int, _dp, _dp, c_int, c_int]
         lib.ml_farfield_beams.argtypes = [c_void_p, c_int, c_int, _dp]

@@ -20,6 +20,7 @@
 #include "transform_route.h"
 #include "propagate_grid.h"
 #include "fields_pupil.h"
+#include "propagate_modes.h"
 
 namespace ml {
 
@@ -366,6 +367,12 @@ struct PropagatePlan {
     // the transfer function (propagate_otf.hip, ml_propagate_otf): the phasor tables Tx[mx][nu], Ty[my][nv], the row sums
     // R[2][planes][mx][nv] and the device copy of the output [planes][2][nu][nv]; it reads result and sums and changes neither
     DevBuf otf_tables, otf_rows, otf_out;
+    // the mode overlaps (propagate_modes.hip, ml_propagate_modes_plan / _queue / _fetch): what is planned, the conjugated
+    // tables Tx[mx][nu], Ty[my][nv], the row sums R[4 or 2][planes][mx][nv] and the output slots [n_slots][planes][4][nu][nv].
+    // The tables belong to the plan: every ml_propagate_plan* entry drops them (modes.planned).  They read the result and
+    // change nothing but their own slots
+    ModesState modes;
+    DevBuf modes_tables, modes_rows, modes_out;
 };
 
 // The parts of PropagatePlan::grid_work in planes of ps = grid.Lx grid.Ly elements, one function per layout: what a

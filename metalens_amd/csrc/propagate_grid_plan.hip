@@ -123,6 +123,7 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
     }
     // nothing below refuses: the new state, in one place
     pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
+    pp.modes.planned = false;                           // and its mode tables (propagate_modes.hip)
     pp.spectra_ready = false;
     pp.method = method;
     pp.extent = ext;

@@ -653,3 +653,66 @@ def apply_pupil_host(Ex, Ey, Hx, Hy, x, y, radius, centre=(0.0, 0.0), stop=True,
         r.imag = np.where(touch, prod_i, np.where(zero, 0.0, a.imag))
         out.append(r)
     return tuple(out)
+
+
+# ---- overlaps of an image with separable modes: the NumPy twin of PlanePropagator.overlap ---------------------------
+def mode_norm(mode_x, mode_y, dx, dy):
+    """-> ``(sum_i |mode_x[a, i]|^2 dx) (sum_j |mode_y[b, j]|^2 dy)``, shape ``(nu, nv)``: the integral of ``|psi_ab|^2`` over the
+    patch"""
+    mode_x, mode_y = np.atleast_2d(mode_x), np.atleast_2d(mode_y)
+    return ((np.abs(mode_x) ** 2).sum(axis=1) * dx)[:, None] * ((np.abs(mode_y) ** 2).sum(axis=1) * dy)[None, :]
+
+
+def mode_coupling(overlaps, norm, Z, power=None, I_dA=None):
+    """The power coupled into the x- and the y-polarised mode ``psi_ab`` over a reference power: the one place where
+    ``PlanePropagator.overlap``, ``SourceSweep.run(image_modes=...)`` and ``mode_overlaps`` form it.
+
+    ``overlaps``: ``{'Ex', 'Ey'}`` or ``{'Ex', 'Ey', 'Hx', 'Hy'}``, complex ``(..., nu, nv)``, ``sum conj(psi_ab) F dx dy``;
+    ``norm`` ``(nu, nv)``; ``Z = Z0 / n_glass``; ``power`` and ``I_dA``: arrays of the leading shape ``(...)``.  The mode is
+    paraxial, ``h = z^ x e / Z``, and carries ``norm / (2 Z)``.  With H: ``|O_Ex / Z + O_Hy|^2 Z / (8 norm power)`` and ``|O_Ey /
+    Z - O_Hx|^2 Z / (8 norm power)``.  Without H: ``|O_Ex|^2 / (2 Z norm power)`` with a power, ``|O_Ex|^2 / (norm I_dA)``
+    without one.  NaN where ``norm`` or the reference is 0.  -> ``(coupling_x, coupling_y)``"""
+    if 'Hx' in overlaps:
+        if power is None:
+            raise ValueError('mode_coupling with H needs a power')
+        ax, ay = overlaps['Ex'] / Z + overlaps['Hy'], overlaps['Ey'] / Z - overlaps['Hx']
+        scale, ref = Z / 8.0, power
+    else:
+        ax, ay = overlaps['Ex'], overlaps['Ey']
+        if power is None:
+            if I_dA is None:
+                raise ValueError('mode_coupling without H needs a power or I_dA')
+            scale, ref = 1.0, I_dA
+        else:
+            scale, ref = 1.0 / (2.0 * Z), power
+    den = norm * np.asarray(ref, dtype=float)[..., None, None]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return tuple(np.where(den != 0, (a.real * a.real + a.imag * a.imag) * scale / den, np.nan) for a in (ax, ay))
+
+
+def mode_overlaps(fields, x, y, mode_x, mode_y, Z, power=None):
+    """The dict of ``PlanePropagator.overlap`` from a DOWNLOADED result dict (``propagate()``, ``propagate_sets()``): ``Ex``,
+    ``Ey`` and, for the forms with H, ``Hx``, ``Hy`` of shape ``(len(x), len(y))`` or ``(planes, len(x), len(y))`` on uniform
+    axes ``x``, ``y``.  ``mode_x`` ``(nu, len(x))`` or ``(len(x),)``, ``mode_y`` likewise; ``Z = Z0 / n_glass``; ``power``: None
+    (with H: ``sum Sz dx dy``; without: the Cauchy-Schwarz form over ``sum |E|^2 dx dy``), a number or ``(planes,)``."""
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    dx, dy = (x[-1] - x[0]) / (x.size - 1), (y[-1] - y[0]) / (y.size - 1)
+    mode_x, mode_y = np.atleast_2d(np.asarray(mode_x, dtype=complex)), np.atleast_2d(np.asarray(mode_y, dtype=complex))
+    want_h = 'Hx' in fields and 'Hy' in fields
+    F = {k: np.asarray(fields[k], dtype=complex).reshape((-1, x.size, y.size)) for k in ('Ex', 'Ey', 'Hx', 'Hy')[:4 if want_h else 2]}
+    # separable, as on the GPU: rows first, then columns - two matrix products per plane and component
+    O = {k: np.matmul(mode_x.conj()[None], np.matmul(v, mode_y.conj().T[None])) * (dx * dy) for k, v in F.items()}
+    planes = F['Ex'].shape[0]
+    out = {'overlap_' + k: v for k, v in O.items()}
+    out['norm'] = mode_norm(mode_x, mode_y, dx, dy)
+    I_dA = None
+    if power is not None:
+        power = np.broadcast_to(np.asarray(power, dtype=float), (planes,)).copy()
+    elif want_h:
+        power = (0.5 * np.real(F['Ex'] * F['Hy'].conj() - F['Ey'] * F['Hx'].conj())).sum(axis=(1, 2)) * (dx * dy)
+    else:
+        E2 = sum(np.abs(np.asarray(fields[k]).reshape((-1, x.size, y.size))) ** 2 for k in ('Ex', 'Ey', 'Ez') if k in fields)
+        I_dA = E2.sum(axis=(1, 2)) * (dx * dy)
+    out['power'] = I_dA if power is None else power
+    out['coupling_x'], out['coupling_y'] = mode_coupling(O, out['norm'], Z, power=power, I_dA=I_dA)
+    return out

@@ -281,6 +281,72 @@ def _check_otf(p, fx, fy, centre, of):
     return ax, ay, centre, planes, dx, dy
 
 
+MODES_MAX = 64                 # csrc/propagate_modes.h, ML_MODES_MAX
+MODES_OUT_MAX = 1 << 24        # output entries of all slots of a plan (csrc/propagate_modes.h MODES_OUT_MAX)
+_MODE_COMPONENTS = ('Ex', 'Ey', 'Hx', 'Hy')   # the blocks of an output slot
+
+
+def _mode_table(name, m, n):
+    """one axis of ``overlap()``: -> complex128 (modes, n), contiguous; a 1-D array is one mode"""
+    try:
+        t = np.array(m, dtype=np.complex128)
+    except (TypeError, ValueError):
+        raise ValueError('mode_%s must be an array of numbers of shape (modes, %d) or (%d,)' % (name, n, n)) from None
+    if t.ndim == 1:
+        t = t[None, :]
+    if t.ndim != 2 or t.shape[1] != n or t.shape[0] < 1:
+        raise ValueError('mode_%s must have shape (modes, %d) or (%d,) - one axis factor per mode on the %d targets along %s -, '
+                         'got %s' % (name, n, n, n, name, np.shape(m)))
+    if t.shape[0] > MODES_MAX:
+        raise ValueError('overlap() takes at most %d modes per axis: mode_%s has %d' % (MODES_MAX, name, t.shape[0]))
+    bad = ~np.isfinite(t)
+    if bad.any():
+        a, i = np.argwhere(bad)[0]
+        raise ValueError('a mode must be finite: mode_%s[%d][%d] = %r' % (name, a, i, complex(t[a, i])))
+    return _lib.c128(t)
+
+
+def _check_overlap(p, mode_x, mode_y, n_slots=1):
+    """the argument checks of ``PlanePropagator.overlap`` (and of ``SourceSweep.run(image_modes=...)``), before any device call
+    -> (mode_x (nu, len(x)), mode_y (nv, len(y)), planes, dx, dy)"""
+    if p.point_list:
+        raise ValueError('overlap() takes a tensor grid of targets, not a point list: separable modes need the lattice')
+    dx, _ = _focus_axis('x', p.x)
+    dy, _ = _focus_axis('y', p.y)
+    planes = p.z.size if p.method == 'fft-stack' else 1
+    tx, ty = _mode_table('x', mode_x, p.x.size), _mode_table('y', mode_y, p.y.size)
+    entries = n_slots * planes * len(_MODE_COMPONENTS) * tx.shape[0] * ty.shape[0]
+    if entries > MODES_OUT_MAX:
+        raise ValueError('%d sources x %d planes x 4 x %d x %d modes are %d overlaps, at most 2^24 = %d are held on the GPU'
+                         % (n_slots, planes, tx.shape[0], ty.shape[0], entries, MODES_OUT_MAX))
+    return tx, ty, planes, dx, dy
+
+
+def _check_overlap_power(power, planes):
+    """``power=`` of ``overlap()``: None, a number or an array (planes,) -> None or a float array (planes,)"""
+    if power is None:
+        return None
+    try:
+        w = np.asarray(power, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('power must be None, a number or an array (%d,) - one per plane -, got %r' % (planes, power)) from None
+    if w.shape not in ((), (planes,)):
+        raise ValueError('power must be None, a number or an array (%d,) - one per plane -, got shape %s' % (planes, w.shape))
+    return np.broadcast_to(w, (planes,)).copy()
+
+
+def _overlap_dict(raw, tx, ty, dx, dy, want_h, Z, power, I_dA=None):
+    """the numbers of ``ml_propagate_modes_fetch``, complex (..., planes, 4, nu, nv), -> the dict of ``overlap()``; ``power``
+    and ``I_dA``: arrays of shape ``raw.shape[:-3]`` (``I_dA`` is read without H and without a power only)"""
+    from .postprocess import mode_coupling, mode_norm
+    out = {'overlap_' + name: raw[..., c, :, :] * (dx * dy) for c, name in enumerate(_MODE_COMPONENTS[:4 if want_h else 2])}
+    out['norm'] = mode_norm(tx, ty, dx, dy)
+    out['power'] = I_dA if (power is None and not want_h) else power
+    out['coupling_x'], out['coupling_y'] = mode_coupling({k[8:]: v for k, v in out.items() if k.startswith('overlap_')}, out['norm'],
+                                                         Z, power=power, I_dA=I_dA)
+    return out
+
+
 def plan_info(ctx):
     """-> ``{'method', 'Lx', 'Ly', 'workspace_bytes'}`` of the context's active propagation plan
     (ml_propagate_plan_info): the padded lengths are 0 for the direct method.  For ``'fft-tiled'`` they are the tile
@@ -318,7 +384,9 @@ class PlanePropagator:
     ``propagate_sets()`` does the same for all field sets of a synthesis batch (the x, y, z dipoles of an emitter)
     in one pass and ``accumulate()`` keeps their weighted intensity sums on the GPU (``SourceSweep.run(image=...)``).
     ``focus()`` reduces the resident image - a field set or the sums - to its focus metrics on the GPU: peak, moments,
-    the power inside up to 32 radii, per plane (csrc/propagate_focus.hip).
+    the power inside up to 32 radii, per plane (csrc/propagate_focus.hip).  ``otf()`` contracts it with Fourier phasors and
+    ``overlap()`` with the caller's separable modes - the coupling into a fibre mode or a Gaussian beam
+    (csrc/propagate_otf.hip, csrc/propagate_modes.hip).
 
     ``propagate()`` sums the field set resident on the GPU (the selected one of a batch) and returns a dict
     with ``Ex, Ey, Ez, Hx, Hy, Hz`` (complex128, shape ``(len(x), len(y))`` or ``(len(x),)``) and
@@ -628,6 +696,61 @@ class PlanePropagator:
             out['otf_' + name] = (raw[:, w] * turn)[:, iu][:, :, iv] * (dx * dy)
         out['fx'], out['fy'] = np.array(fx, dtype=float), np.array(fy, dtype=float)
         return out
+
+    def overlap(self, mode_x, mode_y, member=0, power=None):
+        """The overlap of the image that is resident on the GPU with separable modes ``psi_ab(x, y) = mode_x[a](x)
+        mode_y[b](y)`` - how much of the light enters a single-mode fibre, a Gaussian beam of a given waist, a Hermite-Gauss
+        order -, contracted there (``ml_propagate_modes_plan`` / ``_queue`` / ``_fetch``, csrc/propagate_modes.hip): ``4 nu nv``
+        complex numbers per plane cross PCIe, not the image.
+
+        ``mode_x``: complex array ``(nu, len(x))`` - the axis factors sampled on the targets' x axis (``metalens_amd.modes``
+        has Gaussian and Hermite-Gauss factors) - or ``(len(x),)`` for one mode; likewise ``mode_y`` with ``(nv, len(y))``;
+        finite, at most 64 per axis, in any order, repeats allowed.  The tensor product serves Hermite-Gauss orders ``m x
+        n``, a grid of lateral fibre offsets, or a scan of waists taken from the diagonal; a mode that is a sum of separable
+        terms (LP01) is served by one call with the terms as modes, whose overlaps add.  Their normalisation is immaterial:
+        ``norm`` divides it out.  ``member``: of the last ``propagate()`` / ``queue_sets()`` / ``propagate_sets()`` pass (the
+        sums of ``accumulate()`` carry no phase).  The targets must be a tensor grid with uniform ascending axes, as for
+        ``focus()``.
+
+        The mode model is paraxial: an x-polarised mode has ``e = psi x^``, ``h = z^ x e / Z = psi y^ / Z`` with ``Z = Z0 /
+        n_glass``, a y-polarised one ``e = psi y^``, ``h = -psi x^ / Z``; its power is ``norm / (2 Z)``.  The patch of
+        targets must hold the mode: what of ``psi`` lies outside it is missing from the overlap and from ``norm`` alike.
+
+        -> dict of arrays whose leading axis is the planes (1 unless ``method='fft-stack'``): ``overlap_Ex``, ``overlap_Ey`` and
+        with ``want_h`` ``overlap_Hx``, ``overlap_Hy``, complex ``(planes, nu, nv)``, ``sum_ij conj(psi_ab) F dx dy``; ``norm``
+        ``(nu, nv)``, ``(sum_i |mode_x[a, i]|^2 dx) (sum_j |mode_y[b, j]|^2 dy)``; ``power`` ``(planes,)``; ``coupling_x`` and
+        ``coupling_y`` ``(planes, nu, nv)``, the power coupled into the x- or y-polarised mode over ``power`` (NaN where
+        ``norm`` or ``power`` is 0).  With ``want_h``
+            ``coupling_x = |O_Ex / Z + O_Hy|^2 Z / (8 norm power)``,  ``coupling_y = |O_Ey / Z - O_Hx|^2 Z / (8 norm power)``
+        and ``power=None`` means ``focus(member=member)['P']``, the power through the patch.  Without H and with
+        ``power=None``: ``|O_Ex|^2 / (norm I_dA)``, the Cauchy-Schwarz share of ``I_dA = sum |E|^2 dx dy`` (returned as
+        ``power``), at most 1; with a power given ``|O_Ex|^2 / (2 Z norm power)``.  ``power``: a number or an array
+        ``(planes,)``, e.g. the incident power.  Repeatable bit for bit; plane ``p`` of a stack has the numbers of that plane
+        planned alone; an entry does not depend on the other modes of the call.  Synchronises."""
+        tx, ty, planes, dx, dy = _check_overlap(self, mode_x, mode_y)
+        power = _check_overlap_power(power, planes)
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        self._modes_plan(tx, ty, planes, 1)
+        _lib.check(ctx.lib.ml_propagate_modes_queue(ctx.handle, int(member), 0))
+        raw = self._modes_fetch(1, planes, tx.shape[0], ty.shape[0])[0]
+        I_dA = None
+        if power is None:
+            foc = self.focus(member=member)
+            power, I_dA = (foc['P'], None) if self.want_h else (None, foc['I_dA'])
+        return _overlap_dict(raw, tx, ty, dx, dy, self.want_h, self.Z0 / self._geometry[5], power, I_dA)
+
+    def _modes_plan(self, tx, ty, planes, n_slots):
+        """upload the mode tables of ``_check_overlap`` and reserve ``n_slots`` output slots on the active plan"""
+        _lib.check(self.ctx.lib.ml_propagate_modes_plan(self.ctx.handle, self.x.size, self.y.size, planes, _lib.dptr(tx), tx.shape[0],
+                                                        _lib.dptr(ty), ty.shape[0], int(n_slots)))
+
+    def _modes_fetch(self, n_slots, planes, nu, nv):
+        """-> complex (n_slots, planes, 4, nu, nv): the slots 0 ... n_slots - 1"""
+        raw = np.empty((n_slots, planes, len(_MODE_COMPONENTS), nu, nv), dtype=np.complex128)
+        _lib.check(self.ctx.lib.ml_propagate_modes_fetch(self.ctx.handle, 0, int(n_slots), _lib.dptr(raw)))
+        return raw
 
 
 def field_at_plane(Ex, Ey, Hx, Hy, xp_list, yp_list, wavelength, n_glass, x, y, z, *, point_list=False,

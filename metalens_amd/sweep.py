@@ -158,11 +158,13 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None):
+    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None, modes=None):
         """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
         group's field sets are then propagated to its targets in one pass and added to the image sums; with ``beam`` =
         (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot; with
-        ``pupil`` the group's field sets are multiplied by it right after every synthesis, before anything reads them"""
+        ``pupil`` the group's field sets are multiplied by it right after every synthesis, before anything reads them; with
+        ``modes`` (the tables of ``_check_image_modes``) every member's image is contracted with them into the slot of its
+        source right behind the image pass (``ml_propagate_modes_queue``: two launches, nothing synchronises)"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -201,6 +203,12 @@ class SourceSweep:
                     pupil.queue(0, n)
             image.queue_sets(0, n)
             image.accumulate([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
+            if modes is not None:
+                if not modes['planned']:   # once per run, behind the first image pass: the image's plan is the active one now
+                    image._modes_plan(modes['tx'], modes['ty'], modes['planes'], modes['n_slots'])
+                    modes['planned'] = True
+                for m, (k, pol) in enumerate(group['members']):
+                    _lib.check(lib.ml_propagate_modes_queue(ctx.handle, m, k))
         return n
 
     def _check_image_focus(self, image, image_radii, image_centre):
@@ -230,8 +238,23 @@ class SourceSweep:
         _check_otf(image, fx, fy, image_centre, 'sums')
         return fx, fy
 
+    def _check_image_modes(self, image, image_modes, n_sources):
+        """argument errors of ``image_modes=``, before any device call -> the state ``_pass`` carries, or None"""
+        if image_modes is None:
+            return None
+        if image is None:
+            raise ValueError('image_modes= needs image=, the PlanePropagator whose images are contracted with the modes')
+        try:
+            mode_x, mode_y = image_modes
+        except (TypeError, ValueError):
+            raise ValueError('image_modes must be a pair (mode_x, mode_y) of mode tables, got %r' % (image_modes,)) from None
+        from .propagate import _check_overlap
+        tx, ty, planes, dx, dy = _check_overlap(image, mode_x, mode_y, n_slots=max(1, n_sources))
+        return dict(tx=tx, ty=ty, planes=planes, dx=dx, dy=dy, n_slots=n_sources, planned=False)
+
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
-            image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak', pupil=None):
+            image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak', pupil=None,
+            image_modes=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -271,6 +294,14 @@ class SourceSweep:
         ``beam_centre``: ``'peak'`` (each map's own peak direction) or one ``(ux0, uy0)``.  Takes 1 to 4095 sources (one
         slot is ``P_sum``'s).
 
+        ``image_modes`` = ``(mode_x, mode_y)``, the tables of ``PlanePropagator.overlap`` (needs ``image``): every source's image
+        is contracted with the modes on the GPU right behind its pass (``ml_propagate_modes_queue``, one asynchronous call per
+        source into the source's slot; the tables are planned once, the slots are fetched at the end).  The result gains
+        ``image_coupling``, the dict of ``overlap()`` with a leading axis over the sources: ``overlap_*`` of shape ``(len(sources),
+        planes, nu, nv)`` - source k's have the bits of ``image.overlap()`` on that source's pass -, ``norm``, ``power`` =
+        ``power_in`` per source and plane, and ``coupling_x``, ``coupling_y`` taken over each source's ``power_in``: the share of
+        the emitted power that enters the mode.
+
         ``pupil`` = an ``AperturePupil`` built on this sweep's context and axes: every source's field sets are multiplied by
         it on the GPU right after their synthesis (``ml_fields_pupil_apply``, one launch per group, nothing synchronises),
         so the maps, the sums, the beam records and the image are those of the modified aperture - the cone efficiency with
@@ -284,6 +315,7 @@ class SourceSweep:
         self._check_image_focus(image, image_radii, image_centre)
         image_freqs = self._check_image_otf(image, image_freqs, image_centre)
         sources = list(sources)
+        modes = self._check_image_modes(image, image_modes, len(sources))
         if not 1 <= len(sources) <= MAX_SLOTS:
             raise ValueError('a sweep takes 1 to %d sources, got %d' % (MAX_SLOTS, len(sources)))
         if beam is not None and len(sources) > MAX_SLOTS - 1:
@@ -302,7 +334,7 @@ class SourceSweep:
         image_each = [None] * len(sources)
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights, image, beam, pupil)
+            n = self._pass(g, None, cone3, weights, image, beam, pupil, modes)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -314,7 +346,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights, image, beam, pupil)
+                    n = self._pass(g, None, cone3, weights, image, beam, pupil, modes)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:
@@ -373,6 +405,12 @@ class SourceSweep:
                 out['focus_efficiency'] = enc / incident if incident else np.full(enc.shape, np.nan)
             if image_freqs is not None:
                 out['image_otf'] = image.otf(*image_freqs, of='sums', centre=image_centre)
+            if modes is not None:
+                from .propagate import _overlap_dict
+                raw = image._modes_fetch(len(sources), modes['planes'], modes['tx'].shape[0], modes['ty'].shape[0])
+                reference = np.repeat(power_in[:, None], modes['planes'], axis=1)
+                out['image_coupling'] = _overlap_dict(raw, modes['tx'], modes['ty'], modes['dx'], modes['dy'], image.want_h,
+                                                      image.Z0 / image._geometry[5], reference)
         return out
 
 
