@@ -575,6 +575,45 @@ int ml_propagate_sums(ml_ctx *ctx, double *I, double *Sz);
  * ml_farfield_beam. */
 int ml_propagate_focus(ml_ctx *ctx, int source, int mx, int my, int planes, double dx, double dy,
                        const double *centre, const double *radii, int n_radii, double *records, int record_doubles);
+/* Stokes records of the resident image, reduced on the GPU (csrc/propagate_stokes.hip): per plane the peak of I = |E|^2 and
+ * its place, and the sums of the Stokes parameters and of the longitudinal intensity over the plane and inside n_radii radii
+ * about a centre - the polarisation purity of a spot, its cross-polarised share, the |Ez|^2 share of a high-NA focus, the
+ * degree of polarisation of an unpolarised emitter's image - without the vector field crossing PCIe.  Per target, every
+ * operation rounded on its own, from Ex, Ey, Ez alone (H is never read; plans with and without H are served):
+ *     a = Ex.r Ex.r + Ex.i Ex.i,  b = Ey.r Ey.r + Ey.i Ey.i,  Iz = Ez.r Ez.r + Ez.i Ez.i,   S0 = a + b,   S1 = a - b,
+ *     S2 = 2 (Ex.r Ey.r + Ex.i Ey.i) = 2 Re(Ex conj Ey),   S3 = 2 (Ex.r Ey.i - Ex.i Ey.r) = 2 Im(conj(Ex) Ey),   I = S0 + Iz
+ * (I has the bits of ml_propagate_focus's).  Sign of S3: S3 = +S0 for E proportional to x^ + i y^.  Under the project's
+ * exp(-i omega t), for a wave travelling to +z, that is the field rotating counter-clockwise seen looking towards the
+ * source (positive helicity).
+ *   source           : >= 0: member `source` of the last pass (ml_propagate: 0); -1: the Stokes sums of
+ *                      ml_propagate_accumulate_stokes, the stored doubles taken as they are, the peak that of stored
+ *                      S0_sum + Iz_sum
+ *   mx, my, planes, dx, dy : as for ml_propagate_focus
+ *   centre           : [planes][2], (ci, cj) in INDEX units, fractions allowed; may be NULL only when n_radii == 0 (the
+ *                      record then names the peak's (i, j) as its centre)
+ *   radii, n_radii   : as for ml_propagate_focus, with its membership rule
+ *   record           : HOST, [planes][record_doubles], record_doubles >= 9 + 5 n_radii.  A record:
+ *                      [0] peak I  [1] its flat index i my + j, the lowest of equals
+ *                      [2 + q] the plane's sum of component q = 0 ... 4 for S0, S1, S2, S3, Iz
+ *                      [7] ci [8] cj, the centre  [9 + 5 r + q] the sum of component q inside radii[r]
+ *                      (csrc/propagate_stokes.h STOKES_*)
+ * States and refusals as ml_propagate_focus (ML_ESTATE for source = -1 before ml_propagate_accumulate_stokes), and ML_EINVAL
+ * for centre == NULL with n_radii > 0.  Reads the result (or the Stokes sums) and changes neither.  fp64, no atomics, the
+ * cut of a plane into chunks and the two launches of ml_propagate_focus: a record is repeatable bit for bit, plane p of a
+ * stack has the record of that plane planned alone, and the sum inside a radius does not depend on the other radii of the
+ * call.  Synchronises.  Replaces no reference lines. */
+int ml_propagate_stokes(ml_ctx *ctx, int source, int mx, int my, int planes, double dx, double dy,
+                        const double *centre, const double *radii, int n_radii, double *record, int record_doubles);
+/* Stokes maps kept on the GPU, double [5][targets] of the active propagation plan - S0, S1, S2, S3, Iz as
+ * ml_propagate_stokes forms them per target: map q += weights[0] S_q of member 0 + ... of the last pass, the pass's own
+ * sum formed in member order and then added ONCE to the running sum (reset != 0: to zero), as ml_propagate_accumulate.  The
+ * incoherent sum over an unpolarised emitter's dipoles.  The first call on a plan needs reset != 0 (ML_ESTATE otherwise);
+ * every ml_propagate_plan* entry drops the maps.  The sums of ml_propagate_accumulate are not touched.  Asynchronous, no
+ * atomics.  Replaces no reference lines. */
+int ml_propagate_accumulate_stokes(ml_ctx *ctx, const double *weights, int n, int reset);
+/* The maps of ml_propagate_accumulate_stokes: out double [5][targets].  ML_ESTATE if none has run on the active
+ * propagation plan.  Synchronises.  Replaces no reference lines. */
+int ml_propagate_stokes_sums(ml_ctx *ctx, double *out);
 /* The transfer function of the resident image, contracted on the GPU (csrc/propagate_otf.hip): per plane and per weight
  * w (0: I = |E|^2, 1: Sz, formed as ml_propagate_focus forms them)
  *     O_w[p][a][b] = sum_i sum_j w(p, i, j) exp(-2 pi i (u[a] i + v[b] j)),   a < nu, b < nv

@@ -19,4 +19,5 @@ from .zones import ApertureZones, aperture_zones, zone_edges  # noqa: F401
 from .wavefront import ApertureWavefront, aperture_wavefront, zernike, zernike_terms  # noqa: F401
 from .pupil import AperturePupil, apply_pupil  # noqa: F401
 from .postprocess import apply_pupil_host, pupil_factor, mode_overlaps  # noqa: F401
+from .postprocess import stokes_maps, stokes_metrics, analyser_power  # noqa: F401
 from .modes import gaussian_axis, hermite_gauss_axis  # noqa: F401

@@ -55,6 +55,7 @@ SYMBOLS = (
     'ml_propagate_otf', 'ml_nearfield_synth_info', 'ml_farfield_beam', 'ml_farfield_beams',
     'ml_fields_zones', 'ml_fields_zernike', 'ml_geometry_probe', 'ml_fields_pupil_plan', 'ml_fields_pupil_apply',
     'ml_propagate_modes_plan', 'ml_propagate_modes_queue', 'ml_propagate_modes_fetch',
+    'ml_propagate_stokes', 'ml_propagate_accumulate_stokes', 'ml_propagate_stokes_sums',
 )
 
 
@@ -189,6 +190,10 @@ def load():
         lib.ml_propagate_plan_planes.argtypes = [c_void_p, POINTER(c_int)]
     if hasattr(lib, 'ml_propagate_focus'):
         lib.ml_propagate_focus.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, _dp, _dp, c_int, _dp, c_int]
+    if hasattr(lib, 'ml_propagate_stokes'):
+        lib.ml_propagate_stokes.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, _dp, _dp, c_int, _dp, c_int]
+        lib.ml_propagate_accumulate_stokes.argtypes = [c_void_p, _dp, c_int, c_int]
+        lib.ml_propagate_stokes_sums.argtypes = [c_void_p, _dp]
     if hasattr(lib, 'ml_propagate_otf'):
         lib.ml_propagate_otf.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _dp, c_int, _dp, c_int, _dp]
     if hasattr(lib, 'ml_propagate_modes_plan'):

@@ -327,6 +327,7 @@ inline int prop_check_phase(const char *who, const PropExtent &e, int nx, int ny
 // far-field plan, the radiation vectors or the sweep sums.
 struct PropagatePlan {
     bool ready = false, have_result = false, have_sums = false;
+    bool have_stokes = false;   // stokes_sums hold a pass (ml_propagate_accumulate_stokes); cleared with have_sums by every plan
     int T = 0, want_h = 1;
     int result_sets = 0;   // field sets in `result`: 1 after ml_propagate, n after ml_propagate_sets
     double x0 = 0, y0 = 0, dxp = 0, dyp = 0, wavelength = 0, n_glass = 0;
@@ -364,6 +365,10 @@ struct PropagatePlan {
     // the focus metrics (propagate_focus.hip, ml_propagate_focus): the chunks' partial records [planes][chunks][FOCUS_PARTIAL],
     // the planes' records and the centres [planes][2] the radii are taken about; they read result and sums and change neither
     DevBuf focus_partial, focus_records, focus_centre;
+    // the Stokes records (propagate_stokes.hip, ml_propagate_stokes): the weighted sums [5][T] of S0, S1, S2, S3 and |Ez|^2 over
+    // the passes since the last reset (ml_propagate_accumulate_stokes), the chunks' partial records [planes][chunks][STOKES_PARTIAL],
+    // the planes' records and the centres [planes][2]; they read the result and change nothing but their own sums
+    DevBuf stokes_sums, stokes_partial, stokes_records, stokes_centre;
     // the transfer function (propagate_otf.hip, ml_propagate_otf): the phasor tables Tx[mx][nu], Ty[my][nv], the row sums
     // R[2][planes][mx][nv] and the device copy of the output [planes][2][nu][nv]; it reads result and sums and changes neither
     DevBuf otf_tables, otf_rows, otf_out;

@@ -298,7 +298,7 @@ int ml_propagate_plan(ml_ctx *ctx, double x0, double y0, double dxp, double dyp,
         ML_TRY(prop_check_phase("ml_propagate_plan", ext, ctx->fields.nx, ctx->fields.ny, dxp, dyp, wavelength, n_glass));
     ML_HIP(hipSetDevice(ctx->device));
     PropagatePlan &pp = ctx->prop;
-    pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
+    pp.ready = pp.have_result = pp.have_sums = pp.have_stokes = false;   // results and sums of the previous plan are gone
     pp.modes.planned = false;                           // and its mode tables (propagate_modes.hip)
     pp.method = ML_PROPAGATE_DIRECT;
     pp.spectra_ready = false;

@@ -122,7 +122,7 @@ static int plan_grid(ml_ctx *ctx, const char *entry, int method, double x0, doub
         ML_HIP(hipStreamSynchronize(ctx->stream));   // (`layers` goes away)
     }
     // nothing below refuses: the new state, in one place
-    pp.ready = pp.have_result = pp.have_sums = false;   // results and sums of the previous plan are gone
+    pp.ready = pp.have_result = pp.have_sums = pp.have_stokes = false;   // results and sums of the previous plan are gone
     pp.modes.planned = false;                           // and its mode tables (propagate_modes.hip)
     pp.spectra_ready = false;
     pp.method = method;

@@ -716,3 +716,94 @@ def mode_overlaps(fields, x, y, mode_x, mode_y, Z, power=None):
     out['power'] = I_dA if power is None else power
     out['coupling_x'], out['coupling_y'] = mode_coupling(O, out['norm'], Z, power=power, I_dA=I_dA)
     return out
+
+
+# ---- Stokes records of an image: the NumPy twin of PlanePropagator.stokes -------------------------------------------
+def stokes_maps(Ex, Ey, Ez):
+    """-> ``(S0, S1, S2, S3, Iz)`` per target, array ``(5,) + Ex.shape``: the formulas of csrc/propagate_stokes.h line by line,
+    every operation rounded on its own, so that the GPU's numbers are these to the bit.  ``S3 = 2 Im(conj(Ex) Ey) = +S0`` for
+    ``E`` proportional to ``x^ + i y^``: under the project's ``exp(-i omega t)``, for a wave travelling to +z, that is the field
+    rotating counter-clockwise seen looking towards the source (positive helicity)."""
+    Ex, Ey, Ez = (np.asarray(v, dtype=complex) for v in (Ex, Ey, Ez))
+    a = Ex.real * Ex.real + Ex.imag * Ex.imag
+    b = Ey.real * Ey.real + Ey.imag * Ey.imag
+    Iz = Ez.real * Ez.real + Ez.imag * Ez.imag
+    S0 = a + b
+    S1 = a - b
+    S2 = 2 * (Ex.real * Ey.real + Ex.imag * Ey.imag)
+    S3 = 2 * (Ex.real * Ey.imag - Ex.imag * Ey.real)
+    return np.stack([S0, S1, S2, S3, Iz])
+
+
+def _stokes_state(S, Iz):
+    """integrated ``S`` ``(..., 4)`` and ``Iz`` ``(...)`` -> ``(longitudinal_share, dop, orientation, ellipticity)``: the one place
+    where ``PlanePropagator.stokes`` and ``stokes_metrics`` form them (NaN where the denominator is 0)"""
+    S0, S1, S2, S3 = (S[..., q] for q in range(4))
+    pol = np.sqrt(S1 * S1 + S2 * S2 + S3 * S3)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        share = np.where(S0 + Iz != 0, Iz / (S0 + Iz), np.nan)
+        dop = np.where(S0 != 0, pol / S0, np.nan)
+        ellipticity = np.where(pol != 0, 0.5 * np.arcsin(np.clip(S3 / pol, -1.0, 1.0)), np.nan)
+    return share, dop, 0.5 * np.arctan2(S2, S1), ellipticity
+
+
+def stokes_metrics(fields_or_maps, x, y, radii=(), centre='peak'):
+    """The dict of ``PlanePropagator.stokes`` from a DOWNLOADED result dict (``Ex``, ``Ey``, ``Ez`` of shape ``(len(x), len(y))`` or
+    ``(planes, len(x), len(y))``) or from the five maps of ``stokes_maps`` / ``PlanePropagator.stokes_sums()`` (``(5, ...)``), on
+    uniform axes ``x``, ``y``.  ``radii`` in any order; ``centre``: ``'peak'`` (every plane's peak of ``S0 + Iz``, the lowest index
+    of equals), one ``(xc, yc)`` or ``(planes, 2)``.  Membership of a radius as on the GPU: ``(dx (i - ci))^2 + (dy (j - cj))^2
+    <= R^2``."""
+    x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    dx, dy = (x[-1] - x[0]) / (x.size - 1), (y[-1] - y[0]) / (y.size - 1)
+    M = stokes_maps(*(fields_or_maps[k] for k in ('Ex', 'Ey', 'Ez'))) if isinstance(fields_or_maps, dict) else np.asarray(fields_or_maps, dtype=float)
+    M = M.reshape((5, -1, x.size, y.size))
+    planes = M.shape[1]
+    I = M[0] + M[4]
+    flat = I.reshape(planes, -1).argmax(axis=1)
+    peak = np.stack([flat // y.size, flat % y.size], axis=1)
+    if isinstance(centre, str):
+        if centre != 'peak':
+            raise ValueError("centre must be 'peak', one (xc, yc) or an array (planes, 2), got %r" % (centre,))
+        c = peak.astype(float)
+    else:
+        c = np.broadcast_to(np.asarray(centre, dtype=float), (planes, 2))
+        c = np.stack([(c[:, 0] - x[0]) / dx, (c[:, 1] - y[0]) / dy], axis=1)
+    radii = np.asarray(radii, dtype=float)
+    fi, fj = np.meshgrid(np.arange(x.size, dtype=float), np.arange(y.size, dtype=float), indexing='ij')
+    enc = np.zeros((planes, radii.size, 5))
+    for p in range(planes):
+        fx = dx * (fi - c[p, 0])
+        fy = dy * (fj - c[p, 1])
+        r2 = fx * fx + fy * fy
+        for r, R in enumerate(radii):
+            enc[p, r] = M[:, p][:, r2 <= R * R].sum(axis=1)
+    sums = M.sum(axis=(2, 3)).T * (dx * dy)
+    enc *= dx * dy
+    out = {'peak_I': I.reshape(planes, -1)[np.arange(planes), flat], 'peak_index': peak,
+           'peak_xy': np.stack([x[peak[:, 0]], y[peak[:, 1]]], axis=1), 'centre_index': c.copy(),
+           'centre_xy': np.stack([x[0] + dx * c[:, 0], y[0] + dy * c[:, 1]], axis=1), 'S': sums[:, :4], 'Iz_dA': sums[:, 4]}
+    out['longitudinal_share'], out['dop'], out['orientation'], out['ellipticity'] = _stokes_state(out['S'], out['Iz_dA'])
+    out['encircled_S'], out['encircled_Iz'] = enc[:, :, :4], enc[:, :, 4]
+    out['encircled_dop'] = _stokes_state(out['encircled_S'], out['encircled_Iz'])[1]
+    return out
+
+
+def analyser_power(S, jones):
+    """The power behind an analyser with Jones vector ``jones = (ax, ay)`` (any normalisation, complex allowed), from Stokes
+    parameters ``S`` of shape ``(..., 4)`` - a record of ``PlanePropagator.stokes`` -: ``(S0 + q1 S1 + q2 S2 + q3 S3) / 2`` with the
+    analyser's normalised Stokes vector ``q = (|ax|^2 - |ay|^2, 2 Re(ax conj ay), 2 Im(conj(ax) ay)) / (|ax|^2 + |ay|^2)``.
+    ``(1, 0)`` passes x, ``(0, 1)`` y - the cross-polarised share of an x-polarised emitter's image is ``analyser_power(S, (0, 1))
+    / S[..., 0]`` -, ``(1, 1)`` +45 degrees, ``(1, 1j)`` the circular state of ``S3 = +S0`` (positive helicity in the convention of
+    ``stokes_maps``).  Pure host code."""
+    S = np.asarray(S, dtype=float)
+    try:
+        ax, ay = (complex(v) for v in jones)
+    except (TypeError, ValueError):
+        raise ValueError('jones must be the two components (ax, ay) of a Jones vector, got %r' % (jones,)) from None
+    n = abs(ax) ** 2 + abs(ay) ** 2
+    if S.shape[-1:] != (4,):
+        raise ValueError('S must have the four Stokes parameters as its last axis, got shape %s' % (S.shape,))
+    if not (np.isfinite(n) and n > 0):
+        raise ValueError('jones must be a finite Jones vector other than (0, 0), got %r' % (jones,))
+    q1, q2, q3 = (abs(ax) ** 2 - abs(ay) ** 2) / n, 2 * (ax * ay.conjugate()).real / n, 2 * (ax.conjugate() * ay).imag / n
+    return 0.5 * (S[..., 0] + q1 * S[..., 1] + q2 * S[..., 2] + q3 * S[..., 3])

@@ -165,41 +165,43 @@ def _check_fine(name, n, m, s, L, method='fft-fine'):
 FOCUS_RADII_MAX = 32   # csrc/propagate_focus.h
 # the record of a plane (csrc/propagate_focus.h FOCUS_*): peak, its index, the moments of I and of Sz, the centre, the radii's sums
 _FOCUS_MOM_I, _FOCUS_MOM_SZ, _FOCUS_CENTRE, _FOCUS_ENC = 2, 8, 14, 16
+# the Stokes record of a plane (csrc/propagate_stokes.h STOKES_*): peak, its index, the five sums, the centre, [radius][component]
+_STOKES_SUMS, _STOKES_CENTRE, _STOKES_ENC = 2, 7, 9
 
 
-def _focus_axis(name, t):
+def _focus_axis(name, t, who='focus()'):
     """-> (pitch, tolerance in index units) of a target axis of ``focus()``: ``(t[-1] - t[0]) / (len(t) - 1)``, with every
     target within ``4 spacing(max |t|)`` of ``t[0] + i pitch`` (the rule of ``_on_pitch``)"""
     if t.size < 2:
-        raise ValueError('focus() needs at least 2 targets along %s to know their pitch, the axis has %d' % (name, t.size))
+        raise ValueError('%s needs at least 2 targets along %s to know their pitch, the axis has %d' % (who, name, t.size))
     pitch = (t[-1] - t[0]) / (t.size - 1)
     if not (np.isfinite(pitch) and pitch > 0):
-        raise ValueError('focus() needs an ascending target axis: %s runs from %.17g to %.17g' % (name, t[0], t[-1]))
+        raise ValueError('%s needs an ascending target axis: %s runs from %.17g to %.17g' % (who, name, t[0], t[-1]))
     tol = 4 * np.spacing(np.abs(t).max())
     off = np.abs(t - (t[0] + np.arange(t.size) * pitch)) > tol
     if off.any():
         i = int(np.argmax(off))
-        raise ValueError('focus() needs uniform target axes: %s[%d] = %.17g is not %s[0] + %d x %.17g (the moments and the '
-                         'radii are taken on the lattice of the targets)' % (name, i, t[i], name, i, pitch))
+        raise ValueError('%s needs uniform target axes: %s[%d] = %.17g is not %s[0] + %d x %.17g (the moments and the '
+                         'radii are taken on the lattice of the targets)' % (who, name, i, t[i], name, i, pitch))
     return float(pitch), tol / pitch
 
 
-def _check_focus(p, radii, centre, of):
+def _check_focus(p, radii, centre, of, who='focus()'):
     """the argument checks of ``PlanePropagator.focus`` (and of ``SourceSweep.run(image_radii=...)``), before any device
     call -> (radii ascending, the caller's order as indices into them, centres (planes, 2) in index units or None for
     ``'peak'``, planes, dx, dy)"""
     if of not in ('fields', 'sums'):
         raise ValueError("of must be 'fields' or 'sums', got %r" % (of,))
     if p.point_list:
-        raise ValueError('focus() takes a tensor grid of targets, not a point list: moments and radii need the lattice')
-    dx, tol_i = _focus_axis('x', p.x)
-    dy, tol_j = _focus_axis('y', p.y)
+        raise ValueError('%s takes a tensor grid of targets, not a point list: moments and radii need the lattice' % who)
+    dx, tol_i = _focus_axis('x', p.x, who)
+    dy, tol_j = _focus_axis('y', p.y, who)
     planes = p.z.size if p.method == 'fft-stack' else 1
     r = np.asarray(radii, dtype=float)
     if r.ndim != 1:
         raise ValueError('radii must be a sequence of numbers, got an array of shape %s' % (r.shape,))
     if r.size > FOCUS_RADII_MAX:
-        raise ValueError('focus() takes at most %d radii, got %d' % (FOCUS_RADII_MAX, r.size))
+        raise ValueError('%s takes at most %d radii, got %d' % (who, FOCUS_RADII_MAX, r.size))
     bad = ~(np.isfinite(r) & (r >= 0))
     if bad.any():
         raise ValueError('a radius must be finite and >= 0: radii[%d] = %g' % (int(np.argmax(bad)), r[np.argmax(bad)]))
@@ -386,7 +388,9 @@ class PlanePropagator:
     ``focus()`` reduces the resident image - a field set or the sums - to its focus metrics on the GPU: peak, moments,
     the power inside up to 32 radii, per plane (csrc/propagate_focus.hip).  ``otf()`` contracts it with Fourier phasors and
     ``overlap()`` with the caller's separable modes - the coupling into a fibre mode or a Gaussian beam
-    (csrc/propagate_otf.hip, csrc/propagate_modes.hip).
+    (csrc/propagate_otf.hip, csrc/propagate_modes.hip).  ``stokes()`` reduces it to its polarisation state - the Stokes sums, the
+    degree of polarisation, the longitudinal share, per plane and inside radii - and ``accumulate_stokes()`` keeps the Stokes
+    maps of a sweep (csrc/propagate_stokes.hip).
 
     ``propagate()`` sums the field set resident on the GPU (the selected one of a batch) and returns a dict
     with ``Ex, Ey, Ez, Hx, Hy, Hz`` (complex128, shape ``(len(x), len(y))`` or ``(len(x),)``) and
@@ -657,6 +661,74 @@ class PlanePropagator:
             out[total] = s * dx * dy
             out['centroid_' + name] = np.stack([self.x[0] + dx * mi, self.y[0] + dy * mj], axis=1)
             out[enc] = rec[:, e_at:e_at + K][:, back] * dx * dy
+        return out
+
+    def stokes(self, radii=(), centre='peak', member=0, of='fields'):
+        """The polarisation state of the image that is resident on the GPU, reduced there (``ml_propagate_stokes``,
+        csrc/propagate_stokes.hip): a record of ``9 + 5 len(radii)`` doubles per plane crosses PCIe, not three complex maps.
+
+        Per target, from ``Ex, Ey, Ez`` alone (``postprocess.stokes_maps`` is the same arithmetic, to the bit): ``S0 = |Ex|^2 +
+        |Ey|^2``, ``S1 = |Ex|^2 - |Ey|^2``, ``S2 = 2 Re(Ex conj Ey)``, ``S3 = 2 Im(conj(Ex) Ey)`` and the longitudinal ``Iz =
+        |Ez|^2``.  ``S3 = +S0`` for ``E`` proportional to ``x^ + i y^``: under the project's ``exp(-i omega t)``, for a wave
+        travelling to +z, that is the field rotating counter-clockwise seen looking towards the source (positive helicity).
+
+        ``of='fields'``: of member ``member`` of the last pass; ``of='sums'``: of the maps of ``accumulate_stokes()`` as they
+        are stored (``member`` is ignored) - the incoherent image of an unpolarised emitter.  ``radii``, ``centre``, the
+        membership rule and the conditions on the targets are those of ``focus()``; ``centre='peak'`` reads every plane's peak
+        with a first call and takes the radii about it with a second.
+
+        -> dict of arrays whose leading axis is the planes (1 unless ``method='fft-stack'``): ``peak_I``, ``peak_index``,
+        ``peak_xy``, ``centre_index``, ``centre_xy`` as ``focus()`` gives them (of a member, ``peak_I`` and ``peak_index`` to the
+        bit); ``S`` of shape ``(planes, 4)``, ``sum S_q dx dy``; ``Iz_dA``; ``longitudinal_share = Iz / (S0 + Iz)``; ``dop =
+        sqrt(S1^2 + S2^2 + S3^2) / S0`` of the integrated values (NaN where ``S0`` is 0); ``orientation = atan2(S2, S1) / 2``;
+        ``ellipticity = asin(S3 / sqrt(S1^2 + S2^2 + S3^2)) / 2``; ``encircled_S`` of shape ``(planes, len(radii), 4)``,
+        ``encircled_Iz`` and ``encircled_dop`` of shape ``(planes, len(radii))``, in the caller's order.  Repeatable bit for bit;
+        plane ``p`` of a stack has the numbers of that plane planned alone, and a radius those it has alone.  ``postprocess.
+        analyser_power(out['S'], (ax, ay))`` is the power behind an analyser.  Synchronises."""
+        from .postprocess import _stokes_state
+        r, back, c, planes, dx, dy = _check_focus(self, radii, centre, of, 'stokes()')
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        K, mx, my = r.size, self.x.size, self.y.size
+        source = -1 if of == 'sums' else int(member)
+
+        def call(centres, k):
+            rec = np.empty((planes, _STOKES_ENC + 5 * k))
+            _lib.check(ctx.lib.ml_propagate_stokes(ctx.handle, source, mx, my, planes, dx, dy, _lib.dptr(centres),
+                                                   _lib.dptr(r) if k else None, k, _lib.dptr(rec), rec.shape[1]))
+            return rec
+        if c is None and K:   # about the peak: read it first
+            c = _lib.f64(call(None, 0)[:, _STOKES_CENTRE:_STOKES_CENTRE + 2])
+        rec = call(c, K)
+        flat = rec[:, 1].astype(np.int64)
+        out = {'peak_I': rec[:, 0].copy(), 'peak_index': np.stack([flat // my, flat % my], axis=1)}
+        out['peak_xy'] = np.stack([self.x[out['peak_index'][:, 0]], self.y[out['peak_index'][:, 1]]], axis=1)
+        out['centre_index'] = rec[:, _STOKES_CENTRE:_STOKES_CENTRE + 2].copy()
+        out['centre_xy'] = np.stack([self.x[0] + dx * rec[:, _STOKES_CENTRE], self.y[0] + dy * rec[:, _STOKES_CENTRE + 1]], axis=1)
+        out['S'] = rec[:, _STOKES_SUMS:_STOKES_SUMS + 4] * dx * dy
+        out['Iz_dA'] = rec[:, _STOKES_SUMS + 4] * dx * dy
+        out['longitudinal_share'], out['dop'], out['orientation'], out['ellipticity'] = _stokes_state(out['S'], out['Iz_dA'])
+        enc = rec[:, _STOKES_ENC:].reshape(planes, K, 5)[:, back] * dx * dy
+        out['encircled_S'], out['encircled_Iz'] = enc[:, :, :4], enc[:, :, 4]
+        out['encircled_dop'] = _stokes_state(out['encircled_S'], out['encircled_Iz'])[1]
+        return out
+
+    def accumulate_stokes(self, weights, reset=False):
+        """add the sets of the last ``queue_sets`` / ``propagate_sets`` pass into the five Stokes maps kept on the GPU:
+        ``S_q += sum_m weights[m] S_q of set m`` for ``S0, S1, S2, S3`` and ``Iz`` (``reset``: the maps start from zero; the
+        first call needs it).  Beside ``accumulate()``, whose sums it does not touch.  Asynchronous."""
+        ctx = self.ctx
+        if ctx.propagate_owner != self.owner:
+            raise RuntimeError('another propagator has planned on the context since this one propagated')
+        w = _lib.f64(np.ravel(np.asarray(weights, dtype=float)))
+        _lib.check(ctx.lib.ml_propagate_accumulate_stokes(ctx.handle, _lib.dptr(w), w.size, int(bool(reset))))
+
+    def stokes_sums(self):
+        """-> the maps of ``accumulate_stokes``, ``(S0, S1, S2, S3, Iz)``, of shape ``(5,) + self.shape``"""
+        ctx = self.ctx
+        out = np.empty((5,) + self.shape)
+        _lib.check(ctx.lib.ml_propagate_stokes_sums(ctx.handle, _lib.dptr(out)))
         return out
 
     def otf(self, fx, fy, member=0, of='fields', centre=None):

@@ -158,13 +158,14 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None, modes=None):
+    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None, modes=None, stokes=False):
         """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
         group's field sets are then propagated to its targets in one pass and added to the image sums; with ``beam`` =
         (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot; with
         ``pupil`` the group's field sets are multiplied by it right after every synthesis, before anything reads them; with
         ``modes`` (the tables of ``_check_image_modes``) every member's image is contracted with them into the slot of its
-        source right behind the image pass (``ml_propagate_modes_queue``: two launches, nothing synchronises)"""
+        source right behind the image pass (``ml_propagate_modes_queue``: two launches, nothing synchronises); with ``stokes``
+        the group's images are added to the image's Stokes maps as well, with the same weights"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -203,6 +204,8 @@ class SourceSweep:
                     pupil.queue(0, n)
             image.queue_sets(0, n)
             image.accumulate([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
+            if stokes:
+                image.accumulate_stokes([weights[k] for k, pol in group['members']], reset=group['members'][0][0] == 0)
             if modes is not None:
                 if not modes['planned']:   # once per run, behind the first image pass: the image's plan is the active one now
                     image._modes_plan(modes['tx'], modes['ty'], modes['planes'], modes['n_slots'])
@@ -222,6 +225,17 @@ class SourceSweep:
                              'inside a radius over the incident power')
         from .propagate import _check_focus
         _check_focus(image, image_radii, image_centre, 'sums')
+
+    def _check_image_stokes(self, image, image_stokes, image_centre):
+        """argument errors of ``image_stokes=``, before any device call -> the radii (``()`` for ``True``), or None"""
+        if image_stokes is None or image_stokes is False:
+            return None
+        if image is None:
+            raise ValueError('image_stokes= needs image=, the PlanePropagator whose images\' Stokes maps are summed')
+        radii = () if image_stokes is True else image_stokes
+        from .propagate import _check_focus
+        _check_focus(image, radii, image_centre, 'sums', 'stokes()')
+        return radii
 
     def _check_image_otf(self, image, image_freqs, image_centre):
         """argument errors of ``image_freqs=``, before any device call -> (fx, fy) as arrays, or None"""
@@ -254,7 +268,7 @@ class SourceSweep:
 
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
             image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak', pupil=None,
-            image_modes=None):
+            image_modes=None, image_stokes=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -302,6 +316,12 @@ class SourceSweep:
         ``power_in`` per source and plane, and ``coupling_x``, ``coupling_y`` taken over each source's ``power_in``: the share of
         the emitted power that enters the mode.
 
+        ``image_stokes`` = ``True`` or up to 32 radii in the image (needs ``image``; H is not needed): every group's images are
+        added to the image's five Stokes maps beside the sums, with the same weights (``image.accumulate_stokes``).  The
+        result gains ``image_stokes`` = ``image.stokes(radii, image_centre, of='sums')`` - the polarisation state of the summed
+        image, its degree of polarisation for an unpolarised emitter's x, y and z dipoles - and ``image_stokes_maps`` =
+        ``image.stokes_sums()``, shape ``(5,) + image.shape``.  Without it the sweep issues no call more than before.
+
         ``pupil`` = an ``AperturePupil`` built on this sweep's context and axes: every source's field sets are multiplied by
         it on the GPU right after their synthesis (``ml_fields_pupil_apply``, one launch per group, nothing synchronises),
         so the maps, the sums, the beam records and the image are those of the modified aperture - the cone efficiency with
@@ -314,6 +334,8 @@ class SourceSweep:
         self._check_image(image)
         self._check_image_focus(image, image_radii, image_centre)
         image_freqs = self._check_image_otf(image, image_freqs, image_centre)
+        stokes_radii = self._check_image_stokes(image, image_stokes, image_centre)
+        stokes = stokes_radii is not None
         sources = list(sources)
         modes = self._check_image_modes(image, image_modes, len(sources))
         if not 1 <= len(sources) <= MAX_SLOTS:
@@ -334,7 +356,7 @@ class SourceSweep:
         image_each = [None] * len(sources)
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights, image, beam, pupil, modes)
+            n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -346,7 +368,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights, image, beam, pupil, modes)
+                    n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:
@@ -403,6 +425,9 @@ class SourceSweep:
                 incident = float((weights * power_in).sum())
                 enc = out['image_focus']['encircled_P']
                 out['focus_efficiency'] = enc / incident if incident else np.full(enc.shape, np.nan)
+            if stokes:
+                out['image_stokes'] = image.stokes(stokes_radii, image_centre, of='sums')
+                out['image_stokes_maps'] = image.stokes_sums()
             if image_freqs is not None:
                 out['image_otf'] = image.otf(*image_freqs, of='sums', centre=image_centre)
             if modes is not None:
