@@ -721,6 +721,40 @@ int ml_propagate_modes_fetch(ml_ctx *ctx, int first_slot, int n_slots, double *o
 int ml_fields_zones(ml_ctx *ctx, int first_set, int n_sets, const double *x2, int nx, const double *y2, int ny,
                     const double *e2, int n_edges, int ref_mode, const double *ra, const double *rb, double ref_c,
                     double k, double *records, int record_doubles);
+/* Per-zone contributions to the field at points behind the aperture (csrc/fields_zone_fields.hip): the direct pair sum of
+ * ml_propagate left un-added across the zones of ml_fields_zones.  For every slot z - the n_edges zones and, as slot
+ * n_edges, everything beyond the last edge -, every target t and n_sets field sets
+ *     E_z(t) = Z k^2 / (4 pi) dx' dy' sum over the samples of slot z of w { i D(J) - (i - q) Rhat x m }
+ * and H_z(t) likewise, so that E(t) = sum_z E_z(t): how much each ring adds at a focus and with which phase - the phasor
+ * diagram of the focus, the exact re-phasing pupil, the gradient of the focal intensity with respect to every ring's
+ * phase - in one pass over the aperture per four targets instead of one pupil and one propagation per zone.
+ *   first_set, n_sets : as for ml_fields_zones; the sets are walked one after the other
+ *   x0, y0, dxp, dyp, wavelength, n_glass : the aperture, as for ml_propagate_plan: sample [i][j] lies at (x0 + i dxp,
+ *                       y0 + j dyp, 0); k = 2 pi n_glass / wavelength, Z = Z0 / n_glass; all finite, all but x0, y0 > 0
+ *   x2, nx, y2, ny, e2, n_edges : the zones, as for ml_fields_zones - the same membership to the letter
+ *   tx, ty, tz, n_targets : HOST, 1 <= n_targets <= ML_ZONE_FIELDS_TARGETS_MAX points (x, y, z), finite, z > 0
+ *   want_h            : 0: E only, 6 doubles per record; else E and H, 12 doubles
+ *   records           : HOST, [n_sets][n_edges + 1][n_targets][6 or 12]: Re, Im of Ex, Ey, Ez (then of Hx, Hy, Hz)
+ *   samples           : HOST, [n_edges + 1]: the members of every slot
+ * A pair's term is formed by the inlined functions of the propagator's kernel in its order (csrc/propagate_pair.h), the
+ * currents from the fields as that kernel forms them, and the two scales multiply a finished sum once.  Undoes
+ * ml_nearfield_premodulate first, as ml_fields_download does.  fp64, no atomics; the sums run in the order of
+ * ml_fields_zones (csrc/fields_zone_fields.h): runs of one slot on one side of a line's vertex, then the runs of a slot
+ * over the lines.  A record is repeatable bit for bit and depends neither on the other sets of the call, nor on the other
+ * edges, nor on the other targets, and the E records do not depend on want_h.  Scratch: at most
+ * nx min(ny + 2, 2 n_edges + 4) (8 + 32 (12 or 6)) bytes whatever n_sets and n_targets are, reserved on first use.  Fields,
+ * plans, results and sums of the context are left as they are.
+ * ML_ESTATE if no field set is resident; ML_EINVAL with the numbers in ml_last_error for a context of more than one rank,
+ * n_sets outside [1, 3], sets that are not resident, axes that differ from the resident shape, n_edges outside [1, 4096],
+ * n_targets outside [1, 64], an entry of x2, y2, e2 that is negative or not finite, edges that decrease, a y2 with more than
+ * one valley, a target that is not finite or has z <= 0, a geometry that is not finite and > 0, a pair whose k R can
+ * exceed 1e9 (the wording of ml_propagate_plan), a NULL pointer.  A refused call changes nothing.  Synchronises.  Replaces
+ * no reference lines.                                                                      */
+#define ML_ZONE_FIELDS_TARGETS_MAX 64
+int ml_fields_zone_fields(ml_ctx *ctx, int first_set, int n_sets, double x0, double y0, double dxp, double dyp,
+                          double wavelength, double n_glass, double Z0, const double *x2, int nx, const double *y2, int ny,
+                          const double *e2, int n_edges, const double *tx, const double *ty, const double *tz,
+                          int n_targets, int want_h, double *records, long long *samples);
 /* Zernike moments of the resident near field's wavefront, reduced on the GPU (csrc/fields_wavefront.hip): over a circular
  * pupil of radius R about a centre, and for n_sets field sets in one pass, the members, the sums of Sz, |Ex|^2, |Ey|^2
  * and the complex moments sum Ex conj(w) Z_j, sum Ey conj(w) Z_j of the aperture field against a reference wave

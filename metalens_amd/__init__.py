@@ -16,6 +16,8 @@ from .nearfield_farfield import (FarfieldTransform, farfield_direct,  # noqa: F4
                                  fft_direction_cosines)
 from .propagate import PlanePropagator, field_at_plane  # noqa: F401
 from .zones import ApertureZones, aperture_zones, zone_edges  # noqa: F401
+from . import zone_fields  # noqa: F401
+from .zone_fields import ApertureZoneFields, aperture_zone_fields  # noqa: F401
 from .wavefront import ApertureWavefront, aperture_wavefront, zernike, zernike_terms  # noqa: F401
 from .pupil import AperturePupil, apply_pupil  # noqa: F401
 from .postprocess import apply_pupil_host, pupil_factor, mode_overlaps  # noqa: F401

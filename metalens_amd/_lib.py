@@ -56,6 +56,7 @@ SYMBOLS = (
     'ml_fields_zones', 'ml_fields_zernike', 'ml_geometry_probe', 'ml_fields_pupil_plan', 'ml_fields_pupil_apply',
     'ml_propagate_modes_plan', 'ml_propagate_modes_queue', 'ml_propagate_modes_fetch',
     'ml_propagate_stokes', 'ml_propagate_accumulate_stokes', 'ml_propagate_stokes_sums',
+    'ml_fields_zone_fields',
 )
 
 
@@ -206,6 +207,9 @@ def load():
     if hasattr(lib, 'ml_fields_zones'):
         lib.ml_fields_zones.argtypes = [c_void_p, c_int, c_int, _dp, c_int, _dp, c_int, _dp, c_int, c_int, _dp, _dp, c_double,
                                         c_double, _dp, c_int]
+    if hasattr(lib, 'ml_fields_zone_fields'):
+        lib.ml_fields_zone_fields.argtypes = [c_void_p, c_int, c_int] + [c_double] * 7 + [_dp, c_int, _dp, c_int, _dp, c_int,
+                                                                                      _dp, _dp, _dp, c_int, c_int, _dp, POINTER(c_int64)]
     if hasattr(lib, 'ml_fields_zernike'):
         lib.ml_fields_zernike.argtypes = [c_void_p, c_int, c_int, _dp, _dp, c_int, _dp, _dp, c_int, c_double, c_int, c_int, _dp, _dp,
                                           c_double, c_double, _dp, c_int]

@@ -523,6 +523,9 @@ struct ml_ctx {
     // per-zone sums of the resident near field (fields_zones.hip, ml_fields_zones): the call's axis arrays and edges, the
     // lines' run lists with their counts, and the device copy of the records
     ml::DevBuf zones_in, zones_runs, zones_records;
+    // per-zone contributions to the field at points behind the aperture (fields_zone_fields.hip, ml_fields_zone_fields): the
+    // call's axis arrays, edges and targets, the run lists of one walk with their counts, and a set's records and members
+    ml::DevBuf zf_in, zf_runs, zf_records;
     // Zernike moments of the resident near field's wavefront (fields_wavefront.hip, ml_fields_zernike): the call's axis
     // arrays, the line records, and the sets' monomial moments
     ml::DevBuf wavefront_in, wavefront_lines, wavefront_records;

@@ -38,6 +38,7 @@
 // possible k R over the aperture exceeds the limit is refused (common.h prop_check_phase; 1e9 is 92 m at 580 nm in glass).
 #include "nearfield_math.h"
 #include "propagate_direct.h"   // PROP_THREADS, PROP_TILE, PROP_MAX_SETS, PROP_BLOCKS; tiles, splits and buffer sizes of a pass
+#include "propagate_pair.h"     // cfma, pair_term and the per-pair prologue: shared with fields_zone_fields.hip
 
 namespace ml {
 
@@ -51,31 +52,6 @@ struct PropArgs {
     double dxp, dyp, k, inv_k, Z;
 };
 
-// acc += w t
-__device__ __forceinline__ void cfma(c2 &acc, c2 w, double tr, double ti) {
-    acc.r = fma(-w.i, ti, fma(w.r, tr, acc.r));
-    acc.i = fma(w.i, tr, fma(w.r, ti, acc.i));
-}
-
-// acc[0..3) += w { i D(V) + sgn (i - q) Rhat x U },  D(V) = a V - b Rhat (Rhat . V);  V, U tangential
-template <int SGN>
-__device__ __forceinline__ void pair_term(c2 acc[3], c2 w, double q, c2 a, c2 b, double ux, double uy, double uz, c2 Vx,
-                                          c2 Vy, c2 Ux, c2 Uy) {
-    const c2 dot = {fma(ux, Vx.r, uy * Vy.r), fma(ux, Vx.i, uy * Vy.i)};
-    const c2 bd = cmulf(b, dot);
-    const c2 Dx = {fma(-ux, bd.r, fma(a.r, Vx.r, -(a.i * Vx.i))), fma(-ux, bd.i, fma(a.r, Vx.i, a.i * Vx.r))};
-    const c2 Dy = {fma(-uy, bd.r, fma(a.r, Vy.r, -(a.i * Vy.i))), fma(-uy, bd.i, fma(a.r, Vy.i, a.i * Vy.r))};
-    const c2 Dz = {-uz * bd.r, -uz * bd.i};
-    const c2 Xx = {-uz * Uy.r, -uz * Uy.i};
-    const c2 Xy = {uz * Ux.r, uz * Ux.i};
-    const c2 Xz = {fma(ux, Uy.r, -(uy * Ux.r)), fma(ux, Uy.i, -(uy * Ux.i))};
-    // i D = (-D.i, D.r);  (i - q) X = (-q X.r - X.i, X.r - q X.i)
-    const double s = (double)SGN;
-    cfma(acc[0], w, fma(s, fma(-q, Xx.r, -Xx.i), -Dx.i), fma(s, fma(-q, Xx.i, Xx.r), Dx.r));
-    cfma(acc[1], w, fma(s, fma(-q, Xy.r, -Xy.i), -Dy.i), fma(s, fma(-q, Xy.i, Xy.r), Dy.r));
-    cfma(acc[2], w, fma(s, fma(-q, Xz.r, -Xz.i), -Dz.i), fma(s, fma(-q, Xz.i, Xz.r), Dz.r));
-}
-
 template <bool WANT_H, int NS>
 __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs a) {
     __shared__ double2 s_cur[PROP_TILE][NS][4];   // per field set: Jx, Jy, Mx / Z, My / Z
@@ -85,8 +61,8 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
     const double tx = a.tx[tc], ty = a.ty[tc], z = a.tz[tc], ty_lo = a.ty_lo[tc];
     const double zz = z * z;
     const bool wave_live = blockIdx.x * PROP_THREADS + (tid & ~63) < a.T;
-    // staging: this thread converts field f of the columns c and c + 64 of a tile into current 3 - f, set by set:
-    // Ex -> My / Z = -Ex / Z, Ey -> Mx / Z, Hx -> Jy, Hy -> Jx = -Hy  (a division: exact for Z = 1, and x 2 commutes)
+    // staging: this thread converts field f of the columns c and c + 64 of a tile into current 3 - f, set by set
+    // (propagate_pair.h pair_current)
     const int f = tid >> 6, c = tid & 63;
     const double sg = (f == 0 || f == 3) ? -1.0 : 1.0, den = f < 2 ? a.Z : 1.0;
     const size_t set_stride = (size_t)4 * a.nx * a.ny;
@@ -99,6 +75,7 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
         const int first = a.row_first ? a.row_first[i] : 0;   // (0x7f7f7f7f: no sample of the row is inside)
         const int j_hi = a.ny - first;
         if (first >= j_hi) continue;
+        // (dx and dy: propagate_pair.h pair_offset, written out)
         const double dx = fma(-(double)i, a.dxp, tx) + a.tx_lo[tc];   // (the low part: once per row, not kept in registers)
         const double s_row = fma(dx, dx, zz);
         const double2 *row = a.fields + ((size_t)f * a.nx + i) * a.ny;
@@ -109,27 +86,20 @@ __global__ __launch_bounds__(PROP_THREADS) void propagate_kernel(const PropArgs 
 #pragma unroll
                 for (int m = 0; m < NS; ++m) {
                     const double2 v = (row + m * set_stride)[j0 + cc];
-                    s_cur[cc][m][3 - f] = make_double2(sg * v.x / den, sg * v.y / den);
+                    s_cur[cc][m][3 - f] = pair_current(sg, den, v);
                 }
             }
             __syncthreads();
             if (!wave_live) continue;
             for (int s = 0; s < n; ++s) {
                 const double dy = fma(-(double)(j0 + s), a.dyp, ty) + ty_lo;
-                const double R = sqrt_exact(fma(dy, dy, s_row));
-                const double iR = recip(R);
-                const double ux = dx * iR, uy = dy * iR, uz = z * iR;
-                const double q = iR * a.inv_k, q2 = q * q;
-                double sn, cs;
-                sincos_cw(a.k * R, sn, cs);
-                const c2 w = {cs * q, sn * q};
-                const c2 ca = {1.0 - q2, q}, cb = {fma(-3.0, q2, 1.0), 3.0 * q};
+                const PairGeom g = pair_geom(dx, dy, z, s_row, a.k, a.inv_k);
 #pragma unroll
                 for (int m = 0; m < NS; ++m) {
                     const double2 v0 = s_cur[s][m][0], v1 = s_cur[s][m][1], v2 = s_cur[s][m][2], v3 = s_cur[s][m][3];
                     const c2 Jx = {v0.x, v0.y}, Jy = {v1.x, v1.y}, Mx = {v2.x, v2.y}, My = {v3.x, v3.y};
-                    pair_term<-1>(E[m], w, q, ca, cb, ux, uy, uz, Jx, Jy, Mx, My);
-                    if (WANT_H) pair_term<1>(H[m], w, q, ca, cb, ux, uy, uz, Mx, My, Jx, Jy);
+                    pair_term<-1>(E[m], g.w, g.q, g.a, g.b, g.ux, g.uy, g.uz, Jx, Jy, Mx, My);
+                    if (WANT_H) pair_term<1>(H[m], g.w, g.q, g.a, g.b, g.ux, g.uy, g.uz, Mx, My, Jx, Jy);
                 }
             }
         }

@@ -341,6 +341,198 @@ def zone_metrics(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, edges, centre=(0.0, 
     return _zones_dict(rec, z['dA'], shape[0] * shape[1])
 
 
+ZONE_FIELDS_TARGETS_MAX = 64   # csrc/fields_zone_fields.h ZF_TARGETS_MAX, ML_ZONE_FIELDS_TARGETS_MAX
+ZONE_FIELDS_TG = 4             # csrc/fields_zone_fields.h ZF_TG: the targets of a walk
+
+
+def _zone_fields_axis(name, t, pitch):
+    """one aperture axis of the zone fields: ascending and uniform (the rule of ``PlanePropagator``: within 1e-9 of the
+    step) -> the step the C ABI is given: ``pitch`` where the caller names it, else the axis' first step; an axis of one
+    sample has no step of its own and needs ``pitch``"""
+    if pitch is not None and not (np.isfinite(pitch) and pitch > 0):
+        raise ValueError('pitch=(dx, dy) must give finite steps > 0, got %r for %s' % (pitch, name))
+    if t.size == 1:
+        if pitch is None:
+            raise ValueError('%s has one sample and no step of its own: pitch=(dx, dy) must give one > 0, got %r' % (name, pitch))
+        return float(pitch)
+    d = np.diff(t)
+    if not (d > 0).all():
+        i = int(np.argmin(d > 0)) + 1
+        raise ValueError('%s must ascend: %s[%d] = %.17g follows %s[%d] = %.17g' % (name, name, i, t[i], name, i - 1, t[i - 1]))
+    if d.max() - d.min() > 1e-9 * np.abs(d).max():
+        raise ValueError('%s must be uniform: its steps run from %.17g to %.17g' % (name, d.min(), d.max()))
+    return float(d[0]) if pitch is None else float(pitch)
+
+
+def _check_zone_fields(x, y, wavelength, n_glass, edges, points, centre=(0.0, 0.0), pitch=None, polarisation=None):
+    """the argument checks of ``ApertureZoneFields``, ``aperture_zone_fields`` and ``zone_fields``, before any device call
+    -> the dict of ``_check_zones`` with ``points`` (T, 3), ``x0``, ``y0``, ``dxp``, ``dyp`` and ``p`` (the unit polarisation or
+    None) added"""
+    z = _check_zones(x, y, wavelength, n_glass, edges, centre)
+    xa, ya = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+    if pitch is not None:
+        try:
+            pitch = (float(pitch[0]), float(pitch[1]))
+        except (TypeError, ValueError, IndexError):
+            raise ValueError('pitch must be None or (dx, dy), got %r' % (pitch,)) from None
+    z['dxp'] = _zone_fields_axis('xp_list', xa, None if pitch is None else pitch[0])
+    z['dyp'] = _zone_fields_axis('yp_list', ya, None if pitch is None else pitch[1])
+    z['x0'], z['y0'] = float(xa[0]), float(ya[0])
+    try:
+        p = np.asarray(points, dtype=float)
+    except (TypeError, ValueError):
+        raise ValueError('points must be an array of shape (T, 3), got %r' % (points,)) from None
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError('points must be an array of shape (T, 3), got shape %s' % (p.shape,))
+    if not 1 <= p.shape[0] <= ZONE_FIELDS_TARGETS_MAX:
+        raise ValueError('zone fields take 1 to %d points, got %d' % (ZONE_FIELDS_TARGETS_MAX, p.shape[0]))
+    if not np.isfinite(p).all():
+        t = int(np.argmax(~np.isfinite(p).all(axis=1)))
+        raise ValueError('a point must be finite: points[%d] = (%g, %g, %g)' % ((t,) + tuple(p[t])))
+    if not (p[:, 2] > 0).all():
+        t = int(np.argmax(~(p[:, 2] > 0)))
+        raise ValueError('every point needs z > 0 (the aperture is the plane z = 0): points[%d] has z = %g' % (t, p[t, 2]))
+    z['points'] = p
+    z['p'] = _zone_fields_polarisation(polarisation)
+    return z
+
+
+def _zone_fields_polarisation(polarisation):
+    """``polarisation=`` -> None or the unit vector (3,) complex"""
+    if polarisation is None:
+        return None
+    said = 'polarisation must be None or one (px, py, pz) that is finite and not zero, got %r' % (polarisation,)
+    try:
+        p = np.asarray(polarisation, dtype=complex)
+    except (TypeError, ValueError):
+        raise ValueError(said) from None
+    if p.shape != (3,) or not np.isfinite(p).all() or not np.abs(p).max() > 0:
+        raise ValueError(said)
+    return p / np.sqrt((np.abs(p) ** 2).sum())
+
+
+def _zone_fields_dict(rec, samples, want_h, p=None):
+    """records of ml_fields_zone_fields, shape ``(sets, K + 1, T, 6 or 12)``, and the members ``(K + 1,)`` -> the dict of
+    ``ApertureZoneFields.analyse``; ``p``: the unit polarisation (3,), or None for ``total_E / |total_E|`` per set and target"""
+    rec = np.asarray(rec)
+    K = rec.shape[1] - 1
+    out = {'samples': np.asarray(samples[:K]).astype(np.int64), 'outside': int(samples[K])}
+
+    def parts(c0):   # (sets, K + 1, 3, T) complex
+        c = rec[..., c0:c0 + 6:2] + 1j * rec[..., c0 + 1:c0 + 6:2]
+        return np.moveaxis(c, 2, 3)
+
+    def total(F):    # the zones in ascending order, then the outside
+        tot = F[:, 0].copy()
+        for zz in range(1, K + 1):
+            tot = tot + F[:, zz]
+        return tot
+    E = parts(0)
+    out['E'], out['outside_E'], out['total_E'] = E[:, :K], E[:, K], total(E)
+    if want_h:
+        H = parts(6)
+        out['H'], out['outside_H'], out['total_H'] = H[:, :K], H[:, K], total(H)
+    tE = out['total_E']
+    if p is None:
+        norm = np.sqrt((np.abs(tE) ** 2).sum(axis=1, keepdims=True))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            pol = np.where(norm > 0, tE / norm, 0)          # (sets, 3, T)
+    else:
+        pol = np.broadcast_to(np.asarray(p)[None, :, None], tE.shape)
+    out['polarisation'] = pol
+    out['projection'] = (np.conj(pol)[:, None] * out['E']).sum(axis=2)         # (sets, K, T)
+    out['outside_projection'] = (np.conj(pol) * out['outside_E']).sum(axis=1)
+    empty = (out['samples'] == 0)[None, :, None]
+    out['phase'] = np.where(empty, np.nan, np.angle(out['projection']).astype(float))
+    out['gradient'] = -2 * (np.conj(tE)[:, None] * out['E']).sum(axis=2).imag
+    out['aligned'] = np.abs(out['projection']).sum(axis=1)                     # (sets, T)
+    return out
+
+
+def zone_fields(Ex, Ey, Hx, Hy, x, y, wavelength, n_glass, edges, points, centre=(0.0, 0.0), want_h=True, units=None, Z0=None,
+                pitch=None, polarisation=None, real=np.float64):
+    """Per-zone contributions to the field at points behind the aperture, on the host: what ``ApertureZoneFields.analyse``
+    reduces on the GPU (``ml_fields_zone_fields``), for host arrays in NumPy.  ``Ex, Ey, Hx, Hy``: complex, shape ``(len(x),
+    len(y))`` or ``(sets, len(x), len(y))``; ``x``, ``y``: ascending uniform axes (``pitch=(dx, dy)``: their steps as numbers, needed for an axis of one sample);
+    ``edges``, ``centre``: the zones of ``zone_metrics``, the same membership; ``points`` ``(T, 3)``, ``z > 0``.
+
+    Sample ``(i, j)`` sits at ``(x[0] + i dx, y[0] + j dy, 0)`` and adds to the zone it lies in the term of the direct
+    Stratton-Chu sum of ``PlanePropagator`` (propagate.py): with ``J = (-Hy, Hx)``, ``M = (Ey, -Ex)``, ``R = r - r'``,
+    ``g = exp(ikR) / (4 pi R)``, ``a = 1 + i/(kR) - 1/(kR)^2``, ``b = 1 + 3i/(kR) - 3/(kR)^2``, ``c = ik - 1/R``
+
+        E_z(r) = dx dy sum_{zone z} g { i k Z   [a J - b Rhat (Rhat.J)] - c Rhat x M }
+        H_z(r) = dx dy sum_{zone z} g { i (k/Z) [a M - b Rhat (Rhat.M)] + c Rhat x J }
+
+    so that ``E = sum_z E_z`` over the zones and the samples outside every edge.  ``real=np.longdouble`` evaluates the sums in
+    long double from the same fp64 inputs.  -> dict, the leading axis the sets: ``E`` ``(sets, K, 3, T)`` (``H`` with
+    ``want_h``), ``outside_E`` ``(sets, 3, T)``, ``total_E``: the zones in ascending order, then the outside; ``samples`` ``(K,)``,
+    ``outside``; with ``p`` the unit vector ``polarisation`` (default, per set and target: ``total_E / |total_E|``, returned as
+    ``polarisation``) ``projection[s, z, t] = sum_d conj(p_d) E[s, z, d, t]``; ``phase = angle(projection)``, NaN for a zone
+    without samples; ``gradient[s, z, t] = -2 Im(conj(total_E) . E_z)``, the derivative of ``|E(t)|^2`` with respect to a phase
+    added to zone ``z``; ``aligned = sum_z |projection|`` over the K zones, what ``|p^H E|`` becomes when every zone is re-phased
+    and the outside is stopped; ``outside_projection``."""
+    from . import constants
+    z = _check_zone_fields(x, y, wavelength, n_glass, edges, points, centre, pitch, polarisation)
+    Z0 = constants.as_units(units).Z0 if Z0 is None else Z0
+    F = [np.asarray(a, dtype=np.complex128) for a in (Ex, Ey, Hx, Hy)]
+    F = [a[None] if a.ndim == 2 else a for a in F]
+    shape = (z['x2'].size, z['y2'].size)
+    for name, a in zip(('Ex', 'Ey', 'Hx', 'Hy'), F):
+        if a.ndim != 3 or a.shape[1:] != shape or a.shape[0] != F[0].shape[0]:
+            raise ValueError('%s has shape %s, the axes give %s' % (name, a.shape[-2:] if a.ndim == 3 else a.shape, shape))
+    K, T, sets = z['e2'].size, z['points'].shape[0], F[0].shape[0]
+    zi = np.searchsorted(z['e2'], z['x2'][:, None] + z['y2'][None, :], side='left').ravel()
+    counts = np.bincount(zi, minlength=K + 1)
+    order = np.argsort(zi, kind='stable')
+    held = counts > 0
+    starts = np.searchsorted(zi[order], np.arange(K + 1), side='left')[held]
+    cplx = np.complex128 if real is np.float64 else np.clongdouble
+
+    def by_zone(term):   # the sum of a term over the samples of every slot
+        out = np.zeros(K + 1, dtype=cplx)
+        out[held] = np.add.reduceat(term.ravel()[order], starts)
+        return out
+
+    k, Z = real(2 * np.pi * n_glass / wavelength), real(Z0 / n_glass)
+    pi = 4 * np.arctan(real(1))
+    dxp, dyp = real(z['dxp']), real(z['dyp'])
+    X, Y = np.meshgrid(real(z['x0']) + np.arange(shape[0]).astype(real) * dxp, real(z['y0']) + np.arange(shape[1]).astype(real) * dyp,
+                       indexing='ij')
+    i = cplx(1j)
+    nq = 12 if want_h else 6
+    rec = np.zeros((sets, K + 1, T, nq), dtype=real)
+
+    def dyad(a, b, ux, uy, uz, Vx, Vy):      # a V - b Rhat (Rhat . V), V tangential
+        dot = ux * Vx + uy * Vy
+        return a * Vx - b * ux * dot, a * Vy - b * uy * dot, -b * uz * dot
+
+    def cross(ux, uy, uz, Vx, Vy):           # Rhat x V
+        return -uz * Vy, uz * Vx, ux * Vy - uy * Vx
+
+    for m in range(sets):
+        ex, ey, hx, hy = (a[m].astype(cplx) for a in F)
+        Jx, Jy, Mx, My = -hy, hx, ey, -ex
+        for t, (px, py, pz) in enumerate(z['points']):
+            Rx, Ry, Rz = real(px) - X, real(py) - Y, real(pz)
+            R = np.sqrt(Rx ** 2 + Ry ** 2 + Rz ** 2)
+            ux, uy, uz = Rx / R, Ry / R, Rz / R
+            kr = k * R
+            g = np.exp(i * kr) / (4 * pi * R)
+            a = 1 + i / kr - 1 / kr ** 2
+            b = 1 + 3 * i / kr - 3 / kr ** 2
+            c = i * k - 1 / R
+            dJ, cM = dyad(a, b, ux, uy, uz, Jx, Jy), cross(ux, uy, uz, Mx, My)
+            for d in range(3):
+                v = by_zone(g * (i * k * Z * dJ[d] - c * cM[d])) * dxp * dyp
+                rec[m, :, t, 2 * d], rec[m, :, t, 2 * d + 1] = v.real, v.imag
+            if want_h:
+                dM, cJ = dyad(a, b, ux, uy, uz, Mx, My), cross(ux, uy, uz, Jx, Jy)
+                for d in range(3):
+                    v = by_zone(g * (i * (k / Z) * dM[d] + c * cJ[d])) * dxp * dyp
+                    rec[m, :, t, 6 + 2 * d], rec[m, :, t, 7 + 2 * d] = v.real, v.imag
+    return _zone_fields_dict(rec, counts, want_h, z['p'])
+
+
 ZERNIKE_ORDER_MAX = 8   # csrc/fields_wavefront.h WF_ORDER_MAX, ML_ZERNIKE_ORDER_MAX
 # the record of ml_fields_zernike per field set (csrc/fields_wavefront.h WF_*): the header sums, then four doubles per term
 _WF_N, _WF_S, _WF_IX, _WF_IY, _WF_HEAD = 0, 1, 2, 3, 4

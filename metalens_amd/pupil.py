@@ -102,6 +102,23 @@ class AperturePupil:
         radius = kw.pop('radius', az._edges[-1])
         return cls(az._x, az._y, radius, edges=az._edges, zone_factors=g, **kw)
 
+    @classmethod
+    def from_zone_fields(cls, azf, result, set=0, target=0, **kw):
+        """the pupil that aligns every zone's contribution at a point, as ``azf.analyse()`` measured it with the exact vector
+        kernel: ``zone_factors = exp(-i result['phase'][set, :, target])`` on the edges of the ``ApertureZoneFields`` ``azf``; a
+        zone whose phase is NaN (no samples) gets the factor 1.  ``radius`` defaults to the last edge; further keywords as for
+        ``AperturePupil`` (``ctx`` defaults to ``azf.ctx``)."""
+        ph = np.asarray(result['phase'], dtype=float)
+        if ph.ndim != 3 or ph.shape[1] != azf.n_zones or ph.shape[2] != azf.points.shape[0]:
+            raise ValueError('result must be the dict of analyse() of this ApertureZoneFields: phase has shape %s for %d zones and '
+                             '%d points' % (ph.shape, azf.n_zones, azf.points.shape[0]))
+        p = ph[set, :, target]
+        g = np.where(np.isnan(p), 1.0 + 0.0j, np.exp(-1j * np.where(np.isnan(p), 0.0, p)))
+        kw.setdefault('ctx', azf.ctx)
+        kw.setdefault('centre', azf._centre)
+        radius = kw.pop('radius', azf._edges[-1])
+        return cls(azf._x, azf._y, radius, edges=azf._edges, zone_factors=g, **kw)
+
 
 def apply_pupil(Ex, Ey, Hx, Hy, xp_list, yp_list, radius, **kw):
     """One-shot convenience, modelled on ``aperture_wavefront``: upload the host arrays ``Ex..Hy``, apply the pupil on the GPU

@@ -106,6 +106,16 @@ class SourceSweep:
             raise ValueError('pupil= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
                              % (tuple(pupil.shape) + (self.x.size, self.y.size)))
 
+    def _check_zone_fields(self, zone_fields):
+        """argument errors of ``zone_fields=``, before any device call"""
+        if zone_fields is None:
+            return
+        if zone_fields.ctx is not self.ctx:
+            raise ValueError('zone_fields= must be an ApertureZoneFields built on the context of this sweep (ctx=sweep.ctx)')
+        if tuple(zone_fields.shape) != (self.x.size, self.y.size):
+            raise ValueError('zone_fields= was built for an aperture of %d x %d samples, the sweep\'s grid has %d x %d'
+                             % (tuple(zone_fields.shape) + (self.x.size, self.y.size)))
+
     def queue(self, sources, image=None, beam_cones=None, beam_centre='peak', pupil=None):
         """queue the whole sweep on the GPU and return without synchronising (benchmarks);
         tie settlement and the downloads are ``run``'s business.
@@ -158,14 +168,16 @@ class SourceSweep:
                 merged.append(g)
         return merged
 
-    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None, modes=None, stokes=False):
+    def _pass(self, group, slots_done, cone, weights, image=None, beam=None, pupil=None, modes=None, stokes=False, zone_fields=None):
         """queue one group: batched synthesis, then per member transform -> projection -> sums; with ``image`` the
         group's field sets are then propagated to its targets in one pass and added to the image sums; with ``beam`` =
         (cones ascending, centre or None) the beam record of each member's map is queued into the member's slot; with
         ``pupil`` the group's field sets are multiplied by it right after every synthesis, before anything reads them; with
         ``modes`` (the tables of ``_check_image_modes``) every member's image is contracted with them into the slot of its
         source right behind the image pass (``ml_propagate_modes_queue``: two launches, nothing synchronises); with ``stokes``
-        the group's images are added to the image's Stokes maps as well, with the same weights"""
+        the group's images are added to the image's Stokes maps as well, with the same weights; with ``zone_fields`` = (the
+        ``ApertureZoneFields``, a dict) the zone contributions of the group's field sets, as they are resident at the end of the
+        pass, are stored in the dict under their sources (``ml_fields_zone_fields``: this synchronises)"""
         ctx, lib = self.ctx, self.ctx.lib
         n = len(group['members'])
         params = (_lib.NearfieldParams * n)()
@@ -212,6 +224,10 @@ class SourceSweep:
                     modes['planned'] = True
                 for m, (k, pol) in enumerate(group['members']):
                     _lib.check(lib.ml_propagate_modes_queue(ctx.handle, m, k))
+        if zone_fields is not None:
+            rec = zone_fields[0].records(0, n)
+            for m, (k, pol) in enumerate(group['members']):
+                zone_fields[1][k] = rec[m]
         return n
 
     def _check_image_focus(self, image, image_radii, image_centre):
@@ -268,7 +284,7 @@ class SourceSweep:
 
     def run(self, sources, weights=None, cone=None, cone_center=(0.0, 0.0), keep_each=False, image=None,
             image_radii=None, image_centre='peak', image_freqs=None, beam_cones=None, beam_centre='peak', pupil=None,
-            image_modes=None, image_stokes=None):
+            image_modes=None, image_stokes=None, zone_fields=None):
         """``sources`` = iterable of ``(source_x, source_y, source_z, source_pol)``; sources at the
         same position that follow each other (the x, y, z dipoles of one emitter) are synthesised
         together.  ``weights[k]`` scales source k in ``P_sum`` (default 1); ``cone`` = sine of the
@@ -325,8 +341,14 @@ class SourceSweep:
         ``pupil`` = an ``AperturePupil`` built on this sweep's context and axes: every source's field sets are multiplied by
         it on the GPU right after their synthesis (``ml_fields_pupil_apply``, one launch per group, nothing synchronises),
         so the maps, the sums, the beam records and the image are those of the modified aperture - the cone efficiency with
-        the coma removed, a ring re-phased, the outer zones stopped down.  ``power_in`` stays the incident power."""
+        the coma removed, a ring re-phased, the outer zones stopped down.  ``power_in`` stays the incident power.
+
+        ``zone_fields`` = an ``ApertureZoneFields`` built on this sweep's context and axes: the result gains ``zone_E``, shape
+        ``(len(sources), K, 3, T)`` - every source's field at the object's points, zone by zone (``ml_fields_zone_fields`` on each
+        synthesis batch's resident field sets, after the pupil if one is given; one synchronising call per batch) -, ``zone_H``
+        if it has ``want_h``, and ``zone_outside_E`` / ``zone_outside_H``, shape ``(len(sources), 3, T)``."""
         self._check_pupil(pupil)
+        self._check_zone_fields(zone_fields)
         beam = None
         if beam_cones is not None:
             beam_c, beam_back, beam_ce = _check_beam(beam_cones, beam_centre)
@@ -354,9 +376,10 @@ class SourceSweep:
         power_in = np.zeros(len(sources))
         each = [None] * len(sources)
         image_each = [None] * len(sources)
+        zf = None if zone_fields is None else (zone_fields, {})
         first = True
         for g in groups:
-            n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes)
+            n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes, zf)
             if first:
                 # exact nearest-cell ties are a property of grid and cells: settled once, by
                 # asking cKDTree like the reference (ties.py), then the pass is repeated
@@ -368,7 +391,7 @@ class SourceSweep:
                     known = ties.settle(ctx, self._cells, self.x, self.y, known=known)
                     if known is None:
                         break
-                    n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes)
+                    n = self._pass(g, None, cone3, weights, image, beam, pupil, modes, stokes, zf)
                     ctx.sync()
                 else:
                     if ties.pending(ctx).size:
@@ -414,6 +437,13 @@ class SourceSweep:
             out['beam_sum'] = _beam_single(_beam_dict(rec[S], self.ux, self.uy, False, beam_back), False)
             with np.errstate(divide='ignore', invalid='ignore'):
                 out['beam_efficiency'] = np.where(power_in[:, None] != 0, out['beam']['cone_P'] / power_in[:, None], np.nan)
+        if zf is not None:
+            from .postprocess import _zone_fields_dict
+            rec = np.stack([zf[1][k] for k in range(len(sources))])
+            d = _zone_fields_dict(rec, np.zeros(rec.shape[1], dtype=np.int64), zone_fields.want_h)
+            out['zone_E'], out['zone_outside_E'] = d['E'], d['outside_E']
+            if zone_fields.want_h:
+                out['zone_H'], out['zone_outside_H'] = d['H'], d['outside_H']
         if image is not None:
             out['I_sum'], Sz_sum = image.sums()
             if image.want_h:
